@@ -9,10 +9,15 @@ Workload at N=1: SynthWorld v1 config 3 (256x256 sectors, 15 props + ground slab
 the path, the broadphase's border boxes, is issued by the library itself (its own RCCL communicator: one group of
 ncclSend / ncclRecv per step).  This script's N>1 duties are the rendezvous of the communicator id and the timing.
 
-Parity gate IN THE RUN: after the timed region the oracle (liboracle.so, CPU) is brought to the same frame
--- the same number of producer steps on the same world -- and the visible list, every world matrix and the pair set are
-compared with what the GPU holds.  A mismatch exits non-zero; no number is printed.  The oracle is used for that and
-for the cpu_baseline leg only, never inside the timed region.
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes the outputs of the last
+timed step if --dump-outputs DIR is given, and prints the headline line.  Everything else moves behind --full:
+
+Parity gate IN THE RUN (--full): after the timed region the oracle (liboracle.so, CPU) is brought to the same
+frame -- the same number of producer steps on the same world -- and the visible list, every world matrix and the pair set
+are compared with what the GPU holds.  A mismatch exits non-zero; no number is printed.  The oracle is used for that and
+for the cpu_baseline leg only, never inside the timed region.  --full also runs the every-launch pass (roofline), the
+end-to-end leg, the copy rate and read-back figures, the CPU baseline, the config3dyn / config 5 legs and, at N > 1, the
+assembled visible list and the per-rank diagnostics.
 
 Prints ONE JSON line (rank 0).
 """
@@ -309,6 +314,43 @@ def end_of_tick_line(w, workload, SX, SZ, counts, kp_ms, stages, kind):
     return eot_ms, eot_bytes, eot_achieved
 
 
+DUMP_SEED = 20240607
+DUMP_MATRIX_ROWS = 1 << 17         # world matrices sampled (8 MB); the whole of them is 64 MB at 1M entities
+DUMP_MAX_VISIBLE = 1 << 20         # 8 MB as float64
+DUMP_MAX_PAIRS = 1 << 19           # 8 MB as float64
+
+
+def dump_outputs(out_dir, t, stages, rank, world_size):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of scTickRun reads it back, written as
+    float32 / float64 .npy files (indices and counts are exact in float64), at most ~25 MB over all ranks:
+      world_matrices    (R, 16) f32  the world matrices of R rows drawn with a fixed seed (all rows when the world is small)
+      world_matrix_rows (R,)    f64  the dense indices of those rows
+      visible           (V,)    f64  the visible list in the library's order (its first DUMP_MAX_VISIBLE entries)
+      pairs             (P, 2)  f64  the pair set, sorted (the device lists pairs in no fixed order; broadphase only)
+      counts            (16,)   f64  ScTickCounts, fields in capi.Counts order
+    An array with no entries is not written (config 3's pair set: all bodies static); counts holds every list's length.
+    At N > 1 every rank writes its own tile's arrays with the suffix _rank<r>, and the caps are divided by N."""
+    from sc_gameengine_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world_size > 1 else ""
+    n = t.n
+    k = max(DUMP_MATRIX_ROWS // world_size, 1)
+    rows = np.arange(n) if n <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    arrays = {"world_matrices": t.world_matrices_indexed(rows), "world_matrix_rows": rows.astype(np.float64)}
+    if "broadphase" in stages:
+        got, _ = t.pairs()
+        key = np.sort(got[:, 0].astype(np.uint64) << np.uint64(32) | got[:, 1].astype(np.uint64))[:DUMP_MAX_PAIRS // world_size]
+        arrays["pairs"] = np.stack([key >> np.uint64(32), key & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64).reshape(-1, 2)
+    if "cull" in stages:
+        arrays["visible"] = t.visible()[:DUMP_MAX_VISIBLE // world_size].astype(np.float64)
+    c = t.counts()
+    arrays["counts"] = np.array([getattr(c, f) for f, _ in capi.Counts._fields_], np.float64)
+    for name, a in arrays.items():
+        if a.size == 0:
+            continue
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a))
+
+
 DEVICE_WAKE_MS = float(os.environ.get("SC_BENCH_WAKE_MS", "20"))
 
 
@@ -397,9 +439,14 @@ def main():
                          "config3dyn: the same with one prop per sector a dynamic body (every bin holds pair work); "
                          "config5: 16 static + 12 vehicles + 4 peds per sector, agents advanced on device each step")
     ap.add_argument("--sample", type=int, default=0, help="record HIP events on every n-th step (0 = every step up to 64 steps, else every 8th)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity gate (profiling sessions only; the line then says so)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config3dyn / config 5 legs of the default line (N = 1, config 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity gate, every-launch pass (roofline), end-to-end leg, copy rate, CPU baseline, the "
+                         "config3dyn / config 5 legs and, at N > 1, the assembled visible list and per-rank diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs())")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the in-run parity gate (profiling sessions only; the line then says so)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the config3dyn / config 5 legs (N = 1, config 3)")
     ap.add_argument("--profile-run", action="store_true",
                     help="rocprofv3 sessions: warm-up + the timed steps and nothing else -- no event timing, no every-launch pass, no end-to-end "
                          "pass, no parity, no CPU leg -- so the profiler's per-kernel averages ARE the timed pass (profiles/README.md)")
@@ -408,6 +455,8 @@ def main():
                                                        "max-over-ranks timing); the data path is the library's own RCCL communicator either way")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on one GPU: every rank uses GPU 0 and the messages move by host staging (no RCCL)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.profile_run:
         args.no_parity = args.no_cpu_baseline = args.no_secondary = True
 
@@ -523,7 +572,7 @@ def main():
     # Kernel durations come from events that take the dispatch's own begin / end timestamps.  Timing a launch that way costs
     # about 12 us of extra gap per step (measured: 60.8 against 51.5 us per step with every step timed), so inside the timed
     # region only every n-th step is timed (default: every 8th, two launches in all for runs of 32 steps or fewer), and right after it -- same process,
-    # same resident world, the next frames -- a second pass of the same length times EVERY launch.  Both averages are
+    # same resident world, the next frames -- a second pass of the same length times EVERY launch (--full).  Both averages are
     # reported; the roofline uses the every-launch pass.
     sample = args.sample if args.sample > 0 else (8 if args.steps > 32 else max(args.steps // 2, 1))
     # (inside the timed region only the DOMINANT kernel is timed: every timed launch costs the queue ~6 us, and the end-of-tick kernel's
@@ -539,9 +588,12 @@ def main():
     learn_in_region = (t.learn_ticks() - learn_before) if (flags & capi.BROADPHASE) else 0
     k1_region = t.kernel_times_ms(capi.K_XFORM_CULL)
     kp_region = t.kernel_times_ms(capi.K_PAIRS)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, t, stages, rank, world_size)
+    every_launch_pass = args.full and not args.profile_run
     t.set_profiling_kernels(None)
-    t.set_profiling(0 if args.profile_run else 1)
-    for _ in range(0 if args.profile_run else min(args.steps, 64)):
+    t.set_profiling(1 if every_launch_pass else 0)
+    for _ in range(min(args.steps, 64) if every_launch_pass else 0):
         step()
     fence()
     k1 = t.kernel_times_ms(capi.K_XFORM_CULL)
@@ -556,7 +608,7 @@ def main():
     # 6000: src/sandbox/src/main.cpp:96) and reads back counts + visible list + draw items -- staged by a small kernel, ONE
     # device-to-host copy per frame on a copy stream under the next tick -- and the host consumes frame t-1 while tick t runs.
     end_to_end = None
-    if world_size == 1 and not args.graph and not args.profile_run:
+    if args.full and world_size == 1 and not args.graph and not args.profile_run:
         t.set_draw_budget(6000)
         t.set_frame_readback(8192, 6000)
         e2e_flags = flags | capi.DRAWS
@@ -596,8 +648,8 @@ def main():
 
     # ---- parity gate: every rank checks its own tile against the oracle on the same frame ----
     leg = None
-    parity = {"skipped": "--no-parity"}
-    if not args.no_parity:
+    parity = {"skipped": "--no-parity" if args.full else "plain run: the parity gate runs with --full"}
+    if args.full and not args.no_parity:
         leg = OracleLeg(w)
         parity = leg.parity(t, ticks_done[0], [s for s in stages if not (s == "broadphase" and world_size > 1)], view_proj)
         if world_size > 1:
@@ -625,7 +677,7 @@ def main():
     # the all-gathered counts (the library's own communicator: scTickGatherVisibleCounts; the host's control plane in the one-GPU
     # rehearsal).  Rank 0 checks the assembled list against the ranks' ORACLE lists assembled the same way.
     visible_assembly = None
-    if world_size > 1 and "cull" in stages:
+    if args.full and world_size > 1 and "cull" in stages:
         off, total, ids = tiles.global_visible(t, rank, w.n)
         mine_vis = {"rank": rank, "offset": off, "total": total, "ids": ids.tolist(),
                     "oracle_ids": (leg.ow.visible().astype(np.uint64) + np.uint64(rank * w.n)).tolist() if leg is not None else None}
@@ -653,7 +705,7 @@ def main():
 
     # ---- per-rank diagnostics (N > 1): what the first scaling curve will have to be read with ----
     per_rank = None
-    if world_size > 1:
+    if args.full and world_size > 1:
         ci = t.comm_info() if borders is None else {}
         mine = {"rank": rank, "border_lost": int(counts.border_lost), "vocabulary_violations": int(counts.vocabulary_violations),
                 "pairs": int(counts.pairs), "visible": int(counts.visible),
@@ -757,7 +809,12 @@ def main():
                                      "frame producer": float(np.mean(kn)) if len(kn) else "fused into the end-of-tick kernel (SC_TICK_PRODUCE_NEXT)"},
             },
         }
-        if world_size == 1:
+        out["config"]["full"] = bool(args.full)
+        if not args.full:
+            # a plain run: the headline and what it needs; every other figure and check is --full's
+            for key in ("visible_assembly", "per_rank", "end_to_end", "roofline"):
+                del out[key]
+        if args.full and world_size == 1:
             ceiling = copy_ceiling_gbs(torch, torch.device("cuda", local_rank))
             out["roofline"]["torch_copy_rate"] = ceiling
             out["roofline"]["torch_copy_rate_note"] = "torch D2D copy of 1 GiB on this box: a reference point, not the ceiling (DESIGN 5: plain streams of this kernel's traffic run at 5.7-6.9 TB/s)"
@@ -768,14 +825,14 @@ def main():
                 mats = t.world_matrices_indexed(vis[:65536])
                 out["config"]["readback_ms_visible_list_and_matrices"] = (time.perf_counter() - t0) * 1e3
             del mats
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             if leg is None:
                 leg = OracleLeg(w)
             out["cpu_baseline"] = leg.baseline()
             one = leg.baseline(ticks=5, warm=1, workers=0)
             out["cpu_baseline"]["single_thread_value"] = one["value"]
             out["cpu_baseline"]["single_thread_sample"] = one["sample"]
-        if world_size == 1 and args.workload == "config3" and args.sectors == TILE_SECTORS and not args.no_secondary and not args.graph:
+        if args.full and world_size == 1 and args.workload == "config3" and args.sectors == TILE_SECTORS and not args.no_secondary and not args.graph:
             # the pair search under the same clock: the headline world's pair pass is filter-skipped (all bodies static)
             sec = []
             for wl in ("config3dyn", "config5"):

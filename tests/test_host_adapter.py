@@ -25,9 +25,10 @@ def test_adapter_builds_against_the_api_mirror():
 
 
 def test_adapter_builds_against_the_real_engine_headers_when_present():
-    if not os.path.isdir("/root/reference/src/core/include"):
-        pytest.skip("reference tree not on this machine")
+    # the engine's headers are not part of this repository: oracle/Makefile (REF) says where they are, and whether they are there
     out = subprocess.check_output(["make", "-C", os.path.join(ROOT, "oracle"), "adapter-check"]).decode()
+    if "reference tree not present" in out:
+        pytest.skip("the engine's own headers (oracle/Makefile REF) are not on this machine")
     assert "adapter compiles against the real reference headers" in out
 
 

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/pmc_calib.hip -o $OUT/pmc_calib || exit 1
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/calib_$C -o calib -- $OUT/pmc_calib > $OUT/calib_$C.log 2>&1 || { tail -5 $OUT/calib_$C.log; exit 1; }
-  timeout -k 10 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/tick_$C -o tick -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --sample 0 > $OUT/tick_$C.log 2>&1 || { tail -5 $OUT/tick_$C.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/tick_$C -o tick -- python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --sample 0 > $OUT/tick_$C.log 2>&1 || { tail -5 $OUT/tick_$C.log; exit 1; }
   echo "pass $C done"
 done
 rm -f $OUT/pmc_calib

@@ -10,10 +10,10 @@ PART=${1:-A}; TAG=${2:-r04}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 if [ $PART = A ]; then
 (rocminfo | grep -E "Marketing Name|gfx|Compute Unit" | head -8; nproc; lscpu | grep "Model name") > $OUT/env.txt 2>&1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_config3_driver_20_steps.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
-timeout -k 10 500 python3 bench.py --steps 200 --warmup 20 > $OUT/bench_config3.json 2> $OUT/bench_config3.err || { tail -5 $OUT/bench_config3.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_config3_driver_20_steps.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --steps 200 --warmup 20 > $OUT/bench_config3.json 2> $OUT/bench_config3.err || { tail -5 $OUT/bench_config3.err; exit 1; }
 for W in config3dyn config5; do
-  timeout -k 10 400 python3 bench.py --workload $W --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$W.json 2> $OUT/bench_$W.err || { tail -5 $OUT/bench_$W.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --workload $W --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$W.json 2> $OUT/bench_$W.err || { tail -5 $OUT/bench_$W.err; exit 1; }
 done
 for W in config3 config3dyn config5; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$W -o tick -- python3 bench.py --workload $W --steps 400 --warmup 10 --profile-run > $OUT/prof_$W.log 2>&1 || { tail -5 $OUT/prof_$W.log; exit 1; }
@@ -21,7 +21,7 @@ for W in config3 config3dyn config5; do
   echo "== $W =="; python3 -c "import json; d=json.load(open('$OUT/bench_$W.json')); r=d['roofline']; e=r.get('end_of_tick_kernel',{}); print(round(d['value']/1e9,2), 'G ent/s', round(d['ms_per_step']*1e3,1), 'us/step', d['parity_in_run'].get('ok'), 'pairs', d['config']['pairs'], 'frac', round(r['frac'],3), 'k1 us', round(r['avg_launch_ms']*1e3,2), 'eot us', round(e.get('avg_launch_ms',0)*1e3,2), 'eot frac', round(e.get('frac',0),3))"
   head -5 $OUT/${W}_kernel_stats.csv | cut -c1-160
 done
-timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_full_config3 -o tick -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary > $OUT/trace_full_config3.log 2>&1 || { tail -5 $OUT/trace_full_config3.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_full_config3 -o tick -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary > $OUT/trace_full_config3.log 2>&1 || { tail -5 $OUT/trace_full_config3.log; exit 1; }
 python3 tools/trace_passes.py $OUT/trace_full_config3 --warmup 10 --steps 100 --bench-line $OUT/trace_full_config3.log > $OUT/config3_kernel_passes.json && head -30 $OUT/config3_kernel_passes.json
 rm -rf $OUT/prof_config3 $OUT/prof_config3dyn $OUT/prof_config5 $OUT/trace_full_config3
 fi

@@ -7,7 +7,7 @@ export TMPDIR=/tmp SC_TICK_LIB=$LIB SC_TICK_LAX_BIND=1
 P=0
 for C in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES" "SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_SMEM" "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH"; do
   P=$((P+1))
-  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$P -o sq -- python3 bench.py --workload $W --steps 40 --warmup 10 --no-cpu-baseline --no-parity > $OUT/pass$P.log 2>&1 || { tail -5 $OUT/pass$P.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$P -o sq -- python3 bench.py --full --workload $W --steps 40 --warmup 10 --no-cpu-baseline --no-parity > $OUT/pass$P.log 2>&1 || { tail -5 $OUT/pass$P.log; exit 1; }
 done
 python3 - $OUT <<'PY'
 import csv, glob, json, os, sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Per-pass kernel averages from a rocprofv3 --kernel-trace of `python bench.py`.
+"""Per-pass kernel averages from a rocprofv3 --kernel-trace of `python bench.py --full`.
 
-A default bench.py run launches the tick in four passes -- warm-up, the timed region (every n-th step also takes dispatch
+A `bench.py --full` run launches the tick in four passes -- warm-up, the timed region (every n-th step also takes dispatch
 timestamps), the every-launch-timed pass, the end-to-end pass (draw emission + overlapped read-back) -- and rocprofv3's
 --stats summary blends them.  This splits the trace by launch index of the fused kernel (the counts are known from the
 command line) and prints each kernel's average duration per pass, so that (the line's own bytes per entity) x N / (timed-region average)
