@@ -377,6 +377,7 @@ int flushLinks(ScTickContext* c)
   std::vector<std::vector<uint32_t>> deep;
   rebuildLinks(c, link, unreachBits, detached, deep);
   if (c->n) { if (!h2d(c, c->d.link, link.data(), (size_t)c->n * 4u)) return 0; }
+  launchRootMask(c->d, c->n, c->stream);
   if (!h2d(c, c->d.unreach, unreachBits.data(), unreachBits.size() * 4u)) return 0;
 
   c->levelOffsets.assign(1, 0);
@@ -731,7 +732,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
     d.meshId = reinterpret_cast<uint32_t*>(F(kMESH)); d.materialId = reinterpret_cast<uint32_t*>(F(kMATERIAL));
     d.w0 = rslab; d.w1 = rslab + N; d.w2 = rslab + 2 * N;
   }
-  ok = ok && dalloc(c, d.dirty, N / 32) && dalloc(c, d.unreach, N / 32)
+  ok = ok && dalloc(c, d.dirty, N / 32) && dalloc(c, d.unreach, N / 32) && dalloc(c, d.rootMask, N / 32)
           && dalloc(c, d.vis, N / 64) && dalloc(c, d.cand, N / 64) && dalloc(c, d.recomp, N / 64)
           && dalloc(c, d.blockVis, N / kTile) && dalloc(c, d.blockCand, N / kTile)
           && dalloc(c, d.visibleIdx, N) && dalloc(c, d.culledIdx, N) && dalloc(c, d.counters, kCounterWords)
@@ -1000,7 +1001,9 @@ int scTickAppendEntities(ScTickContext* c, uint32_t count, const float* pos3, co
   // roots only and the rest of the hierarchy untouched: write just the new link words
   std::vector<uint32_t> link(count);
   for (uint32_t i = 0; i < count; ++i) link[i] = linkWordOfRoot(c->hFlags[first + i]);
-  if (!h2d(c, c->d.link + first, link.data(), (size_t)count * 4u) || !sync(c)) { c->linksStale = true; return 0; }
+  if (!h2d(c, c->d.link + first, link.data(), (size_t)count * 4u)) { c->linksStale = true; return 0; }
+  launchRootMask(c->d, c->n, c->stream);
+  if (!sync(c)) { c->linksStale = true; return 0; }
   c->linksStale = false;
   c->topoEpoch++;
   return 1;
@@ -1132,6 +1135,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   if (movedFrom && movedTo) { std::copy(src.begin(), src.end(), movedFrom); std::copy(dst.begin(), dst.end(), movedTo); }
   if (movedCount) *movedCount = moves;
   if (relink) return flushLinks(c);
+  launchRootMask(c->d, c->n, c->stream);             // relocated link words, patched parents
   return sync(c) ? 1 : 0;
 }
 

@@ -77,6 +77,7 @@ struct DeviceState {
   uint32_t* link;
   uint32_t* dirty;          // 1 bit per entity (Transform::dirty), word i/32
   uint32_t* unreach;        // 1 bit per entity: depth == kUnreachable (dirty survives the tick there)
+  uint32_t* rootMask;       // 1 bit per entity: no parent and reachable (the root nudge's lanes); rebuilt from `link` wherever link words change
   // Bounds::localAabb (sc_world_partition.h:298-301)
   float *bminx, *bminy, *bminz, *bmaxx, *bmaxy, *bmaxz;
   // RenderMesh + collision layers
@@ -303,6 +304,7 @@ void launchCompactPack(const DeviceState& d, const TickParams& p, uint32_t grid,
 void launchBorderPack(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchBorderMerge(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchNudgeRootsX(const DeviceState& d, uint32_t n, float dx, hipStream_t s);
+void launchRootMask(const DeviceState& d, uint32_t n, hipStream_t s);
 void launchAdvanceMovers(const DeviceState& d, uint32_t n, float dt, float trafficSmooth, float trafficMult, hipStream_t s);
 struct TierParams { float px, pz, aEnter, aExit, bEnter, bExit; };
 void launchTrafficTiers(const DeviceState& d, uint32_t n, const TierParams& tp, hipStream_t s);

@@ -880,15 +880,25 @@ __device__ __forceinline__ bool producePosition(const DeviceState& d, const Tick
   return p.producerKind == 1u ? nudgePosition(d, i, p.n, p.producerParam) : moverPosition(d, i, p.n, p.producerParam, p.trafficSmooth, p.trafficMult);
 }
 
-__device__ __forceinline__ uint32_t blockSum(uint32_t v, uint32_t* scratch)
+// four sums over the workgroup behind one pair of barriers; `scratch`: kCompactScratch dwords of LDS
+constexpr uint32_t kCompactScratch = 4u * (kTile / 64u);
+__device__ __forceinline__ uint4 blockSum4(uint4 v, uint32_t* scratch)
 {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) {
+    v.x += __shfl_down(v.x, o, 64); v.y += __shfl_down(v.y, o, 64); v.z += __shfl_down(v.z, o, 64); v.w += __shfl_down(v.w, o, 64);
+  }
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   __syncthreads();
-  if (lane == 0) scratch[wave] = v;
+  if (lane == 0) reinterpret_cast<uint4*>(scratch)[wave] = v;
   __syncthreads();
-  return scratch[0] + scratch[1] + scratch[2] + scratch[3];
+  uint4 r = make_uint4(0, 0, 0, 0);
+#pragma unroll
+  for (uint32_t k = 0; k < kTile / 64u; ++k) {
+    const uint4 q = reinterpret_cast<const uint4*>(scratch)[k];
+    r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+  }
+  return r;
 }
 
 // `group`: how many of the fused kernel's spans one compaction workgroup takes (their counts are summed here; fewer,
@@ -900,6 +910,11 @@ __device__ __forceinline__ uint32_t blockSum(uint32_t v, uint32_t* scratch)
 // counts, and ONE visibility word per thread for the whole width (a word = one wave-tile of the fused kernel).  Then: block
 // scan of the words' popcounts -> (word, offset) pairs in LDS -> every thread scatters its own entities.  `words` is LDS
 // scratch of kCompactLdsWords dwords.
+// SC_DIAG_EOT (diagnostic builds only, results change): bit 0 = no producer, 1 = no scatter, 2 = span prefix taken as 0,
+// 3 = no pair-role workgroups.  Ablations of the end-of-tick kernel (profiles/r05/ab_eot_ablation.log).
+#ifndef SC_DIAG_EOT
+#define SC_DIAG_EOT 0
+#endif
 constexpr uint32_t kCompactWordsMax = kTile;                  // visibility words (64 entities each) one workgroup handles the fast way
 constexpr uint32_t kCompactLdsWords = kCompactWordsMax * 6u;  // per word: vis (2 dwords), culled (2), offsets (2)
 
@@ -938,44 +953,75 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
   const bool doCull = (p.flags & SC_TICK_CULL) != 0;
   const bool doCulled = (p.flags & SC_TICK_CULLED_LIST) != 0;
 
-  // ---- requests first
+  // ---- requests first.  Every load here is under uniform conditions only, from an index clamped into the workgroup's range, and what it
+  // returned is selected afterwards: a load under a divergent branch is waited for before that branch joins, which made
+  // these requests (dirty words, visibility words, each trip of the predecessors' counts) one dependent round trip each.
   const uint32_t wBegin = begin >> 5, wEnd = (end + 31u) >> 5;
-  uint32_t dirtyKeep = 0; const uint32_t dirtyWord = wBegin + threadIdx.x;
+  const uint32_t dirtyWord = wBegin + threadIdx.x;
   const bool clearDirty = (p.flags & SC_TICK_XFORM) && dirtyWord < wEnd;
-  if (clearDirty) dirtyKeep = d.dirty[dirtyWord] & d.unreach[dirtyWord];
+  const bool some = begin < end;                       // (uniform; false only for the one workgroup of an empty world)
+  const uint32_t dirtyAt = dirtyWord < wEnd ? dirtyWord : wEnd - 1u;
+  uint32_t rawDirty = 0u, rawUnreach = 0u;
+  if (some) { rawDirty = d.dirty[dirtyAt]; rawUnreach = d.unreach[dirtyAt]; }
 
   const uint32_t vBegin = begin >> 6, vEnd = (end + 63u) >> 6, vWords = vEnd - vBegin;
   const bool fast = doCull && vWords <= kCompactWordsMax;
-  unsigned long long myVis = 0ull, myCul = 0ull;
-  if (fast && threadIdx.x < vWords) {
-    myVis = d.vis[vBegin + threadIdx.x];
-    if (doCulled) myCul = d.cand[vBegin + threadIdx.x] & ~myVis;
+  unsigned long long rawVis = 0ull, rawCand = 0ull;
+  const uint32_t visAt = vBegin + (threadIdx.x < vWords ? threadIdx.x : vWords - 1u);
+  if (fast && some) {                                  // (uniform)
+    rawVis = d.vis[visAt];
+    if (doCulled) rawCand = d.cand[visAt];
   }
-  uint32_t pv = 0, pc = 0;
-  if (doCull) for (uint32_t j = threadIdx.x; j < bid * group; j += kTile) { pv += d.blockVis[j]; pc += d.blockCand[j]; }
+  // The predecessors' counts (spans [0, bid * group)), kPrefixBatch of them per thread and array in flight at once: one round
+  // trip up to kPrefixBatch * kTile spans.  The last workgroup takes its own spans in the same trip (CullingStats' totals).
+  constexpr uint32_t kPrefixBatch = 8;
+  const bool lastBlock = bid == nblocks - 1u;
+  const uint32_t pre = bid * group;
+  const uint32_t lim = lastBlock ? (p.n + p.span - 1u) / p.span : pre;
+  uint4 sums = make_uint4(0, 0, 0, 0);                 // predecessors' visible / candidates, own visible / candidates (last workgroup)
+  auto prefixBatch = [&](uint32_t j0) {
+    uint32_t bv[kPrefixBatch], bc[kPrefixBatch];
+#pragma unroll
+    for (uint32_t u = 0; u < kPrefixBatch; ++u) {
+      const uint32_t j = j0 + u * kTile + threadIdx.x;
+      const uint32_t at = j < lim ? j : 0u;
+      bv[u] = d.blockVis[at]; bc[u] = d.blockCand[at];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kPrefixBatch; ++u) {
+      const uint32_t j = j0 + u * kTile + threadIdx.x;
+      if (j < pre) { sums.x += bv[u]; sums.y += bc[u]; }
+      else if (j < lim) { sums.z += bv[u]; sums.w += bc[u]; }
+    }
+  };
+  if (doCull && lim && !(SC_DIAG_EOT & 4)) {
+    prefixBatch(0u);                                   // (the first batch outside the loop: a loop head waits for every load in flight)
+    for (uint32_t j0 = kPrefixBatch * kTile; j0 < lim; j0 += kPrefixBatch * kTile) prefixBatch(j0);
+  }
 
   // SC_TICK_PRODUCE_NEXT: this tick is over for the span, so the NEXT frame's producer runs here instead of as a
   // launch of its own (nothing else in this kernel reads positions); the "moved" ballots wait in LDS and are OR-ed into
   // the cleared dirty words below.
-  const bool produce = (p.flags & SC_TICK_PRODUCE_NEXT) != 0;
+  const bool produce = !(SC_DIAG_EOT & 1) && (p.flags & SC_TICK_PRODUCE_NEXT) != 0;
   const bool produceEarly = produce && (wEnd - wBegin) <= kMaxSpanWords;
   if (produceEarly) {
     if (p.producerKind == 1u) {
-      // root nudge: link word and x of four tiles are requested together, then written
+      // root nudge: the root-mask word and x of six tiles are requested together (clamped indices: no branch to wait at),
+      // then written.  The mask is 1 bit per entity against the 32 of a link word.
       constexpr uint32_t kBatch = 6;                      // (a compaction workgroup of two 768-entity spans: all of it in one round trip)
       for (uint32_t base = begin; base < end; base += kBatch * kTile) {
-        uint32_t lk[kBatch]; float x[kBatch];
+        uint32_t rm[kBatch]; float x[kBatch];
 #pragma unroll
         for (uint32_t u = 0; u < kBatch; ++u) {
           const uint32_t i = base + u * kTile + threadIdx.x;
-          const bool in = i < end;
-          lk[u] = in ? d.link[i] : ((kUnreachable << kDepthShift) | 1u);
-          x[u] = in ? d.px[i] : 0.0f;
+          const uint32_t at = i < end ? i : end - 1u;
+          rm[u] = d.rootMask[at >> 5];
+          x[u] = d.px[at];
         }
 #pragma unroll
         for (uint32_t u = 0; u < kBatch; ++u) {
           const uint32_t tileBase = base + u * kTile, i = tileBase + threadIdx.x;
-          const bool root = i < end && (lk[u] & kParentMask) == kNoParent && linkDepth(lk[u]) != kUnreachable;
+          const bool root = i < end && ((rm[u] >> (i & 31u)) & 1u);
           if (root) d.px[i] = x[u] + p.producerParam;
           const unsigned long long m = ballot64(root);
           if (lane == 0 && tileBase < end) { moved[((tileBase >> 5) - wBegin) + 2u * wave] = (uint32_t)m; moved[((tileBase >> 5) - wBegin) + 2u * wave + 1u] = (uint32_t)(m >> 32); }
@@ -991,12 +1037,10 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
   }
 
   if (doCull) {
-    uint32_t visBase = blockSum(pv, scratch);
-    uint32_t culBase = blockSum(pc, scratch) - visBase;
-    if (bid == nblocks - 1 && threadIdx.x == 0) {
-      uint32_t tv = visBase, tc = culBase + visBase;
-      const uint32_t spans = (p.n + p.span - 1u) / p.span;
-      for (uint32_t j = bid * group; j < spans; ++j) { tv += d.blockVis[j]; tc += d.blockCand[j]; }
+    const uint4 tot = blockSum4(sums, scratch);
+    uint32_t visBase = tot.x, culBase = tot.y - tot.x;
+    if (lastBlock && threadIdx.x == 0) {
+      const uint32_t tv = tot.x + tot.z, tc = tot.y + tot.w;
       d.counters[0] = tv;            // CullingStats::visible
       d.counters[1] = tc - tv;       // CullingStats::culled
       d.counters[6] = tc;            // renderablesTotal
@@ -1013,6 +1057,8 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
     const unsigned long long below = (1ull << lane) - 1ull;
     if (fast) {
       // exclusive scan of the words' popcounts over the workgroup (one word per thread)
+      const bool mine = threadIdx.x < vWords;
+      const unsigned long long myVis = mine ? rawVis : 0ull, myCul = (mine && doCulled) ? (rawCand & ~rawVis) : 0ull;
       uint32_t cv = (uint32_t)__popcll(myVis), cc = (uint32_t)__popcll(myCul);
       uint32_t iv = cv, ic = cc;
 #pragma unroll
@@ -1020,7 +1066,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
         const uint32_t uv = __shfl_up(iv, o, 64), uc = __shfl_up(ic, o, 64);
         if (lane >= o) { iv += uv; ic += uc; }
       }
-      __syncthreads();                                   // (blockSum's readers are done with `scratch`)
+      __syncthreads();                                   // (blockSum4's readers are done with `scratch`)
       if (lane == 63u) scratch[wave] = iv | (ic << 16);    // a wave holds at most 64 x 64 = 4096 of either: 16 bits each
       __syncthreads();
       uint32_t bv = visBase, bc = culBase;
@@ -1034,7 +1080,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
         if (doCulled) { sCul[threadIdx.x] = myCul; sOffC[threadIdx.x] = bc + ic - cc; }
       }
       __syncthreads();
-      for (uint32_t base = begin; base < end; base += kTile) {
+      for (uint32_t base = begin; base < end && !(SC_DIAG_EOT & 2); base += kTile) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t wi = (i >> 6) - vBegin;           // this thread's wave-tile
         if (wi < vWords) {
@@ -1084,7 +1130,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
   }
 
   // Transform::dirty = false for every visited entity; entities in a cycle keep theirs (sc_ecs.cpp:201)
-  if (clearDirty) d.dirty[dirtyWord] = dirtyKeep | (produceEarly ? moved[dirtyWord - wBegin] : 0u);
+  if (clearDirty) d.dirty[dirtyWord] = (rawDirty & rawUnreach) | (produceEarly ? moved[dirtyWord - wBegin] : 0u);
   if (p.flags & SC_TICK_XFORM) {
     for (uint32_t w = wBegin + kTile + threadIdx.x; w < wEnd; w += kTile) d.dirty[w] &= d.unreach[w];   // spans wider than 8192 entities
   }
@@ -1100,7 +1146,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
 
 __global__ __launch_bounds__(kTile) void k_compact(const DeviceState d, const TickParams p, uint32_t group)
 {
-  __shared__ uint32_t scratch[kTile / 64];
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
   __shared__ uint32_t moved[kMaxSpanWords];
   __shared__ uint32_t words[kCompactLdsWords];
   compactBody<false>(d, p, blockIdx.x, gridDim.x, group, scratch, moved, words);
@@ -1954,7 +2000,7 @@ __global__ __launch_bounds__(kTile) SC_PAIR_OCC void k_compact_pairs(const Devic
   __shared__ __attribute__((aligned(16))) uint16_t pairTab[kPairTabSize];
   __shared__ uint2 pairBuf[kTile / 64][kWavePairBuf];
   __shared__ unsigned long long cellMembers[kTile / 64][kCellWords];
-  __shared__ uint32_t scratch[kTile / 64];
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
   __shared__ uint32_t moved[kMaxSpanWords];
   // (a workgroup plays one role: the compaction role borrows the pair role's tile area -- 8 KiB >= kCompactLdsWords dwords)
   static_assert(sizeof(tile) >= kCompactLdsWords * sizeof(uint32_t), "compaction scratch does not fit the pair tiles");
@@ -2196,7 +2242,7 @@ __global__ __launch_bounds__(kTile) void k_border_pack(const DeviceState d, cons
 // split flow: the compaction role and the eight pack workgroups both depend only on the fused kernel -- one launch
 __global__ __launch_bounds__(kTile) void k_compact_pack(const DeviceState d, const TickParams p, uint32_t compactBlocks, uint32_t group)
 {
-  __shared__ uint32_t scratch[kTile / 64];
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
   __shared__ uint32_t moved[kMaxSpanWords];
   __shared__ uint32_t words[kCompactLdsWords];
   // (the eight pack workgroups take the first indices: theirs is the longer chain of round trips, and the exchange waits for them)
@@ -2417,6 +2463,19 @@ __global__ __launch_bounds__(kTile) void k_nudge_roots_x(const DeviceState d, ui
   bits |= (uint32_t)__shfl_xor((int)bits, 2, 64);
   bits |= (uint32_t)__shfl_xor((int)bits, 4, 64);
   if (in && (lane & 7u) == 0u && bits) d.dirty[i0 >> 5] = dw | bits;
+}
+
+// The root mask from the link words: bit i = entity i has no parent and is reachable (the lanes the root nudge moves).
+// One wave per 64 entities; the words past n read as zero.
+__global__ __launch_bounds__(kTile) void k_root_mask(const DeviceState d, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * kTile + threadIdx.x;
+  const uint32_t lk = i < n ? d.link[i] : 0u;
+  const bool root = i < n && (lk & kParentMask) == kNoParent && linkDepth(lk) != kUnreachable;
+  const unsigned long long m = ballot64(root);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (lane == 0u) d.rootMask[i >> 5] = (uint32_t)m;
+  else if (lane == 32u) d.rootMask[i >> 5] = (uint32_t)(m >> 32);
 }
 
 // Read-back / debug only (SC_TICK_DENSE_AABBS): per-entity world AABBs in dense order, from the stored
@@ -2853,7 +2912,7 @@ bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEv
 }
 void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t compactGrid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
-  const uint32_t pairGrid = pairGridFor(p);
+  const uint32_t pairGrid = (SC_DIAG_EOT & 8) ? 0u : pairGridFor(p);
   const uint32_t g = compactGroup(p, compactGrid, true);
   const uint32_t blocks = (compactGrid + g - 1) / g;
   auto kernel = p.emitMode ? k_compact_pairs<true> : k_compact_pairs<false>;      // (draw emission in the compaction role: an instance of its own)
@@ -2887,6 +2946,11 @@ void launchNudgeRootsX(const DeviceState& d, uint32_t n, float dx, hipStream_t s
   if (!n) return;
   const uint32_t quads = (n + 3u) / 4u;
   hipLaunchKernelGGL(k_nudge_roots_x, dim3((quads + kTile - 1) / kTile), dim3(kTile), 0, s, d, n, dx);
+}
+void launchRootMask(const DeviceState& d, uint32_t n, hipStream_t s)
+{
+  if (!n) return;
+  hipLaunchKernelGGL(k_root_mask, dim3((n + kTile - 1) / kTile), dim3(kTile), 0, s, d, n);
 }
 void launchDenseAabbs(const DeviceState& d, uint32_t n, hipStream_t s)
 {
