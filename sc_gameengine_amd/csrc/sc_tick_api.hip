@@ -26,12 +26,19 @@ thread_local std::string gCreateError;
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; };
 
-} // namespace
+// a captured graph of one tick parity and what it was captured for (stale when any of that differs)
+struct CapturedGraph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  TickParams key{};
+  uint64_t epoch = ~0ull;                              // ScTickContext::topoEpoch at capture
+  bool rccl = false;                                   // the library's RCCL group is inside (captured in relaxed mode)
+};
 
-// SC_TICK_HOSTPROBE=1: where scTickRun's host time goes (printed when the context is destroyed; a development aid)
-struct HostProbe { double acc[8] = {0}; uint64_t n = 0; bool on = false; };
-static HostProbe g_probe;
-static inline double probeNow() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// host clock, microseconds (scTickTileStep: host time per half of a step, scTickGetCommInfo)
+double nowUs() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+} // namespace
 
 struct ScTickContext
 {
@@ -66,7 +73,6 @@ struct ScTickContext
 
   uint32_t spansWanted = 1536;
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
-  uint32_t variant = 0;       // SC_TICK_VARIANT: bit0 = chain-walk K1 instead of the wave-cooperative one
   uint32_t lastFlags = 0;
 
   // scratch device buffers for indexed read-back
@@ -88,21 +94,14 @@ struct ScTickContext
 
   // graph
   bool graphMode = false;
-  hipGraph_t graph[kMaxParity] = {};                   // one per broadphase tick parity
-  hipGraphExec_t graphExec[kMaxParity] = {};
-  TickParams graphParams[kMaxParity]{};
-  bool graphWhole[kMaxParity] = {};                    // the captured graph holds the whole tile step (exchange + pair half)
+  CapturedGraph graph[kMaxParity];                     // the tick, one per broadphase tick parity; with its RCCL group: the whole tile step (exchange + pair half)
   bool captureWholeStep = false;                       // set by scTickTileStep around its scTickRun
   bool ownStep = false;                                // scTickTileStep is running: the pair half follows the tick half at once, nothing of the host's in between
-  uint64_t topoEpoch = 0, graphEpoch[kMaxParity] = { ~0ull, ~0ull, ~0ull, ~0ull };
+  uint64_t topoEpoch = 0;
   // pipelined tile + graph replay: the pair half (exchange, merge, queries, pair search, snapshot) is a graph of its own,
   // replayed on the pairs stream; the two graphs of a step are ordered by events recorded between them, outside any capture
-  hipGraph_t pairGraph[kMaxParity] = {};
-  hipGraphExec_t pairGraphExec[kMaxParity] = {};
-  TickParams pairGraphParams[kMaxParity]{};
-  bool pairGraphExchange[kMaxParity] = {};
-  uint64_t pairGraphEpoch[kMaxParity] = { ~0ull, ~0ull, ~0ull, ~0ull };
-  bool lastTickSampled = false;                        // the last scTickRun recorded profiling events (ran eagerly)
+  CapturedGraph pairGraph[kMaxParity];
+  bool lastTickSampled = false;                        // the last scTickRun was sampled for profiling (ran eagerly; its pair half is timed too)
   bool lastTickLearn = false;                          // the last scTickRun was a learn tick of the home slots (ran eagerly)
   // home slots of the bins (binEntityWave): remembered at a learn tick, used until the world's shape changes or they age
   bool homeEnabled = true, homeValid = false, homeCountsLive = false;
@@ -114,7 +113,6 @@ struct ScTickContext
   uint64_t homeEpoch = ~0ull; uint32_t homeAge = 0, homePeriod = 64;
   uint32_t homeXform = 0;                              // SC_TICK_XFORM of the learn tick: entities deeper than the fused kernel's chain are binned by the level
                                                        // kernels on transforming ticks and by the fused kernel otherwise -- slots learned one way are not valid the other
-  bool capturing = false;                              // enqueueStages runs inside a stream capture
   bool packedRides = false;                            // this tick's `packed` event was attached to the compaction + pack dispatch
 
   // broadphase
@@ -416,10 +414,17 @@ EventPair takeEvents(ScTickContext* c)
   return p;
 }
 
+// The profiling sampling rule.  A tick is sampled when profiling is on and its index is a multiple of the period; its pair half
+// goes by the tick's decision (lastTickSampled).  Kernel k is timed on a launch when timing is allowed there -- the tick or its
+// pair half is sampled and runs eagerly: never inside a stream capture -- and k is in the mask.
+bool tickSampled(const ScTickContext* c) { return c->profiling && (c->tickIndex % c->profPeriod) == 0; }
+bool timed(const ScTickContext* c, uint32_t k, bool allowed) { return allowed && c->profiling && ((c->profMask >> k) & 1u); }
+
+// kernel k timed by marker events around the launches in scope (~6 us of gap on the queue per marker)
 struct Scoped
 {
   ScTickContext* c; uint32_t k; EventPair p; bool on;
-  Scoped(ScTickContext* c_, uint32_t k_) : c(c_), k(k_), on(c_->profiling && ((c_->profMask >> k_) & 1u) && (c_->tickIndex % c_->profPeriod) == 0)
+  Scoped(ScTickContext* c_, uint32_t k_, bool allowed) : c(c_), k(k_), on(timed(c_, k_, allowed))
   {
     if (on) { p = takeEvents(c); hipEventRecord(p.a, c->stream); }
   }
@@ -457,7 +462,6 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   p.maxPairs = c->maxPairs;
   p.rankBits = c->rank << 24;
   p.neighbourMask = c->neighbourMask;
-  p.variant = c->variant;
   p.chain = std::min(c->maxDepth, kMaxChain);
   p.ovfCap = ovfRecords(c);
   if (c->pairsStream && (flags & SC_TICK_BROADPHASE)) { p.flags |= kFlagDeferredReset; p.resetParity = (c->parity + 1u) % c->pipeDepth; }
@@ -466,7 +470,7 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   p.trafficMult = c->trafficMult;
   p.bigCap = c->cap + 8u * kBorderBigCap;
   p.cus = c->cus;
-  p.pairRun = pairRunFor(p.binSX * p.binSZ, c->cus, c->variant, false);
+  p.pairRun = pairRunFor(p.binSX * p.binSZ, c->cus, false);
   p.borderRecs = c->borderRecs;
   p.halo = c->halo ? 1u : 0u;
   p.tileX = c->tileX; p.tileZ = c->tileZ; p.tilesX = c->tilesX; p.tilesZ = c->tilesZ;
@@ -487,9 +491,8 @@ void waitParityFree(ScTickContext* c, const TickParams& p)
     // when this tick is issued -- and the queue-to-queue wait then sits in front of this tick's fused kernel on every step: 4-5 us of
     // bubble on the tick stream (tools/trace_timeline.py).  The HOST waits instead (round 4): no tick is issued more than pipeDepth - 1
     // ticks ahead of a finished pair half, the tick stream never sees a barrier, and with the tick before this one already queued the
-    // device does not run dry.  (SC_TICK_VARIANT bit 7: the device-side wait of before, for an A/B.)
-    if (c->variant & 128u) hipStreamWaitEvent(c->stream, c->pairsDone[q], 0);
-    else (void)hipEventSynchronize(c->pairsDone[q]);
+    // device does not run dry.
+    (void)hipEventSynchronize(c->pairsDone[q]);
   }
   (void)hipGetLastError();                        // hipErrorNotReady from the query is not an error
   c->pairsInFlight[q] = false;
@@ -512,27 +515,36 @@ bool raysInPairHalf(const ScTickContext* c, uint32_t flags)
   return c->sensors && c->halo && c->neighbourMask && !c->pairsStream && (flags & SC_TICK_SPLIT_PAIRS) && (flags & SC_TICK_BROADPHASE);
 }
 
+// frame read-back: the block of this frame may still be read by the copy of two frames ago; the tick stream waits for it
+// (asked first: a satisfied wait costs a bubble too)
+void waitFrameBlock(ScTickContext* c)
+{
+  ScTickContext::FrameReadback& rb = c->rb;
+  const uint32_t f = (uint32_t)(rb.frames & 1u);
+  if (!rb.inFlight[f]) return;
+  if (hipEventQuery(rb.copied[f]) != hipSuccess) hipStreamWaitEvent(c->stream, rb.copied[f], 0);
+  (void)hipGetLastError();
+}
+
 // the tick's launches on c->stream, nothing else: safe inside a stream capture (the callers put waitParityFree before
-// and publishPacked behind it)
-void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool allowProfile)
+// and publishPacked behind it).  Launches are timed only on an eager, sampled tick (scTickRun sets lastTickSampled first).
+void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool inCapture)
 {
   const uint32_t flags = p.flags;
   const DeviceState ds = stateFor(c, p.parity);
-  const bool prof = allowProfile && c->profiling;
-  const bool saved = c->profiling;
-  c->profiling = prof;
+  const bool timing = !inCapture && c->lastTickSampled;
   if (c->producerKind && !(flags & SC_TICK_PRODUCE_NEXT)) {
-    Scoped s(c, SC_TICK_K_NUDGE);
+    Scoped s(c, SC_TICK_K_NUDGE, timing);
     if (c->producerKind == 1) launchNudgeRootsX(ds, c->n, c->producerParam, c->stream);
     else launchAdvanceMovers(ds, c->n, c->producerParam, p.trafficSmooth, p.trafficMult, c->stream);
   }
   if (flags & (SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE)) {
     // the dominant kernel is timed by its own begin / end timestamps (the figure the roofline uses)
-    if (c->profiling && (c->profMask & (1u << SC_TICK_K_XFORM_CULL)) && (c->tickIndex % c->profPeriod) == 0) {
+    if (timed(c, SC_TICK_K_XFORM_CULL, timing)) {
       const EventPair ev = takeEvents(c);
       launchXformCull(ds, p, grid, c->stream, ev.a, ev.b);
       c->times[SC_TICK_K_XFORM_CULL].push_back(ev);
-    } else { const double q0 = g_probe.on ? probeNow() : 0.0; launchXformCull(ds, p, grid, c->stream); if (g_probe.on) g_probe.acc[3] += probeNow() - q0; }
+    } else launchXformCull(ds, p, grid, c->stream);
     if (p.homeMode == kHomeLearn) {
       // the slots handed out by the fused kernel are the remembered ones (the level kernels' and the neighbours' records reserve
       // behind them on every tick); the other copies of the bins start their next tick from the same counts
@@ -568,47 +580,41 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool al
   // the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
   const uint32_t drawBudget = c->desc.max_draws_budget;
   const bool stagedEmit = c->rb.bytes && (flags & SC_TICK_DRAWS) && !(flags & SC_TICK_SORT_DRAWS) && drawBudget && drawBudget <= c->rb.maxDraws;
-  const bool foldEmit = needCompact && pairsNow && !(c->variant & (8u | 64u)) && (flags & SC_TICK_CULL) && (flags & SC_TICK_DRAWS) &&
+  const bool foldEmit = needCompact && pairsNow && (flags & SC_TICK_CULL) && (flags & SC_TICK_DRAWS) &&
                         !(flags & SC_TICK_SORT_DRAWS) && (stagedEmit || !c->rb.bytes);
-  bool stagedByEot = false;
-  if (needCompact && pairsNow && !(c->variant & 8u)) {
+  const bool stagedByEot = foldEmit && stagedEmit;
+  if (needCompact && pairsNow) {
     TickParams pe = p;
     hipEvent_t done = nullptr;
     if (foldEmit) {
       pe.emitBudget = drawBudget;
-      if (stagedEmit) {
+      if (stagedByEot) {
         ScTickContext::FrameReadback& rb = c->rb;
         const uint32_t f = (uint32_t)(rb.frames & 1u);
-        if (rb.inFlight[f]) {               // the copy of two frames ago still reads this block? (asked first: a satisfied wait costs a bubble too)
-          if (hipEventQuery(rb.copied[f]) != hipSuccess) hipStreamWaitEvent(c->stream, rb.copied[f], 0);
-          (void)hipGetLastError();
-        }
+        waitFrameBlock(c);
         pe.emitMode = 2u; pe.emitTarget = rb.dBlock[f]; pe.emitMaxVisible = rb.maxVisible;
         pe.emitTickLo = (uint32_t)rb.frames; pe.emitTickHi = (uint32_t)(rb.frames >> 32);
         done = rb.staged[f];
-        stagedByEot = true;
       } else { pe.emitMode = 1u; pe.emitTarget = reinterpret_cast<uint32_t*>(c->dDraws); }
     }
     // both depend only on the fused kernel: one launch, workgroups split by role (timed as K_PAIRS, by the dispatch's own
     // begin / end timestamps like the fused kernel: no marker packets on the queue)
-    if (c->profiling && (c->profMask & (1u << SC_TICK_K_PAIRS)) && (c->tickIndex % c->profPeriod) == 0) {
+    if (timed(c, SC_TICK_K_PAIRS, timing)) {
       const EventPair ev = takeEvents(c);
       launchCompactPairs(ds, pe, grid, c->stream, ev.a, ev.b);
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
   } else {
-    const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS) && !(c->variant & 8u);
+    const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
-      Scoped s(c, SC_TICK_K_COMPACT);
+      Scoped s(c, SC_TICK_K_COMPACT, timing);
       // pipelined tile, eager: the `packed` event rides on the dispatch (publishPacked then only makes the pairs stream wait)
-      const bool ride = c->pairsStream && !c->capturing && !s.on && (c->variant & 4u) == 0u;
-      const double q0 = g_probe.on ? probeNow() : 0.0;
+      const bool ride = c->pairsStream && !inCapture && !s.on;
       launchCompactPack(ds, p, grid, c->stream, ride ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
-      if (g_probe.on) g_probe.acc[4] += probeNow() - q0;
       c->packedRides = ride;
     } else if (needCompact) {
-      Scoped s(c, SC_TICK_K_COMPACT);
+      Scoped s(c, SC_TICK_K_COMPACT, timing);
       launchCompact(ds, p, grid, c->stream);
     }
     if (flags & SC_TICK_BROADPHASE) {
@@ -618,7 +624,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool al
           if (flags & kFlagDeferredReset) launchResetParity(ds, p.resetParity, c->stream);      // (the fused launch does it itself)
         }
       }
-      else { Scoped s(c, SC_TICK_K_PAIRS); launchPairs(ds, p, c->stream); }
+      else { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
     }
   }
   // (not folded -- sorted draws, split flows, a budget beyond the block: with the frame read-back on and a plain draw list whose
@@ -632,10 +638,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool al
   if (c->rb.bytes) {
     ScTickContext::FrameReadback& rb = c->rb;
     const uint32_t f = (uint32_t)(rb.frames & 1u);
-    if (rb.inFlight[f] && !stagedByEot) {  // the copy of two frames ago still reads this block? (asked first: a satisfied wait costs a bubble too)
-      if (hipEventQuery(rb.copied[f]) != hipSuccess) hipStreamWaitEvent(c->stream, rb.copied[f], 0);
-      (void)hipGetLastError();
-    }
+    if (!stagedByEot) waitFrameBlock(c);                  // (the end-of-tick kernel's launch waited already)
     const uint32_t drawMode = (flags & SC_TICK_DRAWS) ? ((flags & SC_TICK_SORT_DRAWS) ? 2u : 1u) : 0u;
     if (stagedByEot) c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + rb.maxVisible;       // the end-of-tick kernel wrote the block
     else if (stagedEmit) {
@@ -649,25 +652,37 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool al
     rb.inFlight[f] = true;
     rb.frames++;
   }
-  c->profiling = saved;
 }
 
-void dropGraph(ScTickContext* c, int q = -1)
+// drop captured graphs: every parity's by default
+void dropGraphs(CapturedGraph* g, uint32_t count = kMaxParity)
 {
-  for (int k = 0; k < (int)kMaxParity; ++k) {
-    if (q >= 0 && k != q) continue;
-    if (c->graphExec[k]) { hipGraphExecDestroy(c->graphExec[k]); c->graphExec[k] = nullptr; }
-    if (c->graph[k]) { hipGraphDestroy(c->graph[k]); c->graph[k] = nullptr; }
+  for (uint32_t k = 0; k < count; ++k) {
+    if (g[k].exec) { hipGraphExecDestroy(g[k].exec); g[k].exec = nullptr; }
+    if (g[k].graph) { hipGraphDestroy(g[k].graph); g[k].graph = nullptr; }
   }
 }
 
-void dropPairGraph(ScTickContext* c, int q = -1)
+// Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for other TickParams, another
+// topology epoch, or with / without the library's RCCL group inside (rccl: the group touches the communicator's own resources
+// during capture, so the capture is relaxed).  body() enqueues the work on s; it returns 0 on an error whose text it has set.
+// what: the graph's name in the error texts.
+template <typename Body>
+int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickParams& key, bool rccl, const char* what, Body body)
 {
-  for (int k = 0; k < (int)kMaxParity; ++k) {
-    if (q >= 0 && k != q) continue;
-    if (c->pairGraphExec[k]) { hipGraphExecDestroy(c->pairGraphExec[k]); c->pairGraphExec[k] = nullptr; }
-    if (c->pairGraph[k]) { hipGraphDestroy(c->pairGraph[k]); c->pairGraph[k] = nullptr; }
+  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl) {
+    dropGraphs(&g, 1);
+    HIP_OK(c, hipStreamBeginCapture(s, rccl ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
+    const int ok = body();
+    const hipError_t ce = hipStreamEndCapture(s, &g.graph);
+    if (!ok) { if (g.graph) { hipGraphDestroy(g.graph); g.graph = nullptr; } return 0; }
+    if (ce != hipSuccess) return fail(c, what, ce);
+    if (!g.graph) return fail(c, (std::string(what) + " returned no graph (the capture was invalidated)").c_str());
+    HIP_OK(c, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl;
   }
+  HIP_OK(c, hipGraphLaunch(g.exec, s));
+  return 1;
 }
 
 void rowsToMat4(const float* r12, float* m16)
@@ -694,13 +709,17 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (e != hipSuccess || count <= 0) { fail(nullptr, "no HIP device available (libsc_tick needs an AMD GPU; there is no CPU fallback)", e); return nullptr; }
   if (desc->device_ordinal < 0 || desc->device_ordinal >= count) { fail(nullptr, "device ordinal out of range"); return nullptr; }
 
+  // SC_TICK_VARIANT: the two A/B switches that remain (include/sc_tick.h); any other bit names a retired experiment
+  const char* vs = std::getenv("SC_TICK_VARIANT");
+  const uint32_t variant = vs ? (uint32_t)std::atoi(vs) : 0u;
+  if (variant & ~(2u | 32u)) { fail(nullptr, "SC_TICK_VARIANT: only bits 1 (2, home slots off) and 5 (32, lazy records off) remain"); return nullptr; }
+
   ScTickContext* c = new ScTickContext();
   c->desc = *desc;
   c->device = desc->device_ordinal;
   if (c->desc.sector_size <= 0.001f) c->desc.sector_size = 64.0f;     // WorldPartition::configure, sc_world_partition.cpp:222-223
   c->cap = ((desc->capacity + kTile - 1) / kTile) * kTile;
   if (const char* s = std::getenv("SC_TICK_SPANS")) { const int v = std::atoi(s); if (v > 0) c->spansWanted = (uint32_t)v; }
-  if (const char* s = std::getenv("SC_TICK_VARIANT")) c->variant = (uint32_t)std::atoi(s);
 
   bool ok = bind(c);
   if (ok) {
@@ -776,9 +795,8 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
       d.pairConst = pc;
     }
   }
-  if (c->variant & 32u) c->lazyEnabled = false;         // SC_TICK_VARIANT bit 5: every remembered slot is written on every tick (A/B)
-  if (c->variant & 2u) c->homeEnabled = false;          // SC_TICK_VARIANT bit 1: every record reserves its slot on every tick (A/B)
-  if (std::getenv("SC_TICK_HOSTPROBE")) g_probe.on = true;
+  if (variant & 32u) c->lazyEnabled = false;            // SC_TICK_VARIANT bit 5: every remembered slot is written on every tick (A/B)
+  if (variant & 2u) c->homeEnabled = false;             // SC_TICK_VARIANT bit 1: every record reserves its slot on every tick (A/B)
   if (const char* fp = std::getenv("SC_TICK_FAST_PAIRS")) c->fastPairs = std::atoi(fp) != 0;      // 0: every bin goes through the general pair search (A/B)
   if (const char* hp = std::getenv("SC_TICK_HOME_PERIOD")) { const int v = std::atoi(hp); if (v > 0) c->homePeriod = (uint32_t)v; }
   if (ok && c->sectors) { e = hipMemset(d.ovfLo, 0xFF, (size_t)c->sectors * sizeof(uint32_t)); if (e != hipSuccess) ok = fail(c, "hipMemset", e); }
@@ -801,17 +819,12 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
 
 void scTickDestroyContext(ScTickContext* c)
 {
-  if (g_probe.on && g_probe.n) {
-    std::fprintf(stderr, "[sc_tick host probe] %llu ticks: waitParityFree %.2f us, enqueueStages %.2f (fused launch %.2f, compaction+pack launch %.2f), publishPacked %.2f\n", (unsigned long long)g_probe.n,
-                 g_probe.acc[0] / g_probe.n, g_probe.acc[1] / g_probe.n, g_probe.acc[3] / g_probe.n, g_probe.acc[4] / g_probe.n, g_probe.acc[2] / g_probe.n);
-    g_probe = HostProbe(); g_probe.on = true;
-  }
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->pairsStream) hipStreamSynchronize(c->pairsStream);
   c->stream = c->ownStream;
-  dropGraph(c); dropPairGraph(c);
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);
   for (auto& v : c->times) for (auto& p : v) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto& p : c->eventPool) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (uint32_t k = 0; k < kMaxParity; ++k) { if (c->packed[k]) hipEventDestroy(c->packed[k]); if (c->pairsDone[k]) hipEventDestroy(c->pairsDone[k]); }
@@ -1329,7 +1342,6 @@ static bool worldCanPair(ScTickContext* c)
 int scTickRun(ScTickContext* c, uint32_t flags)
 {
   if (!c) return 0;
-  const double prA = g_probe.on ? probeNow() : 0.0;
   if (!bind(c)) return 0;
   if (!flushLinks(c)) return 0;
   if ((flags & SC_TICK_BROADPHASE) && c->desc.tile_sectors_x == 0) return fail(c, "broadphase requested but the context has no tile rectangle");
@@ -1374,7 +1386,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     p.homeReset = 1u;
     p.sweepOnly = worldCanPair(c) ? 0u : 1u;
     c->lastTickSweepOnly = p.sweepOnly != 0u;
-    if (p.sweepOnly) p.pairRun = pairRunFor(p.binSX * p.binSZ, c->cus, c->variant, true);
+    if (p.sweepOnly) p.pairRun = pairRunFor(p.binSX * p.binSZ, c->cus, true);
     p.fastPairs = (c->fastPairs && !p.sweepOnly) ? 1u : 0u;
     // lazy records: only while nothing but this tick's own pair search reads the bins, and that search runs before the next
     // tick rewrites the world matrices (it rebuilds unwritten records from them)
@@ -1404,49 +1416,31 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (c->frustumStale && (flags & SC_TICK_CULL)) { launchSetFrustum(c->d, c->frustum, c->stream); c->frustumStale = false; }   // outside any graph
 
   const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
-  const bool sampledTick = c->profiling && (c->tickIndex % c->profPeriod) == 0;     // events need eager launches
-  c->lastTickSampled = sampledTick;
-  const double pr0 = g_probe.on ? probeNow() : 0.0;
-  if (g_probe.on) g_probe.acc[5] += pr0 - prA;
+  c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
   waitParityFree(c, p);
-  const double pr1 = g_probe.on ? probeNow() : 0.0;
-  if (c->graphMode && !sampledTick && !c->lastTickLearn) {
-    const bool stale = !c->graphExec[q] || c->graphEpoch[q] != c->topoEpoch || std::memcmp(&p, &c->graphParams[q], sizeof p) != 0 || c->graphWhole[q] != c->captureWholeStep;
-    if (stale) {
-      dropGraph(c, (int)q);
-      // whole-step capture (scTickTileStep on a tile with neighbours): the RCCL group and the pair half join the graph, so a
-      // step of an in-order tile is ONE hipGraphLaunch.  RCCL operations are captured in relaxed mode (they touch the
-      // communicator's own resources from inside the capture).
-      const bool whole = c->captureWholeStep;
-      HIP_OK(c, hipStreamBeginCapture(c->stream, whole ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
-      c->capturing = true;
-      enqueueStages(c, p, grid, false);
-      c->capturing = false;
-      int okx = 1;
-      if (whole) { okx = exchangeBorders(c, p.parity, c->stream, true); if (okx) enqueuePairHalf(c, p, c->stream); }
-      const hipError_t ce = hipStreamEndCapture(c->stream, &c->graph[q]);
-      if (!okx) { if (c->graph[q]) { hipGraphDestroy(c->graph[q]); c->graph[q] = nullptr; } return 0; }       // (the RCCL error text is already set)
-      if (ce != hipSuccess) return fail(c, "hipStreamEndCapture", ce);
-      if (!c->graph[q]) return fail(c, "hipStreamEndCapture returned no graph (the capture was invalidated)");
-      HIP_OK(c, hipGraphInstantiate(&c->graphExec[q], c->graph[q], nullptr, nullptr, 0));
-      c->graphParams[q] = p; c->graphEpoch[q] = c->topoEpoch; c->graphWhole[q] = whole;
-    }
-    HIP_OK(c, hipGraphLaunch(c->graphExec[q], c->stream));
+  const bool replay = c->graphMode && !c->lastTickSampled && !c->lastTickLearn;
+  if (replay) {
+    // whole-step capture (scTickTileStep on a tile with neighbours): the RCCL group and the pair half join the graph, so a
+    // step of an in-order tile is ONE hipGraphLaunch
+    const bool whole = c->captureWholeStep;
+    if (!replayGraph(c, c->stream, c->graph[q], p, whole, "hipStreamEndCapture", [&] {
+          enqueueStages(c, p, grid, true);
+          if (!whole) return 1;
+          if (!exchangeBorders(c, p.parity, c->stream, true)) return 0;
+          enqueuePairHalf(c, p, c->stream);
+          return 1;
+        })) return 0;
   } else {
-    enqueueStages(c, p, grid, true);
+    enqueueStages(c, p, grid, false);
   }
-  const double pr2 = g_probe.on ? probeNow() : 0.0;
   publishPacked(c, p);
-  double prEnd = 0.0;
-  if (g_probe.on) { const double pr3 = probeNow(); g_probe.acc[0] += pr1 - pr0; g_probe.acc[1] += pr2 - pr1; g_probe.acc[2] += pr3 - pr2; g_probe.n++; prEnd = pr3; }
   if (flags & SC_TICK_BROADPHASE) {
-    const bool pairHalfDone = c->graphMode && !sampledTick && !c->lastTickLearn && c->captureWholeStep;
+    const bool pairHalfDone = replay && c->captureWholeStep;
     if ((flags & SC_TICK_SPLIT_PAIRS) && !pairHalfDone) { c->pairsPending = true; c->pendingParams = p; }
     else { c->lastParity = c->parity; c->parity ^= 1u; }           // (in-order flows alternate between two copies)
   }
   c->tickIndex++;
   const hipError_t e = hipGetLastError();
-  if (g_probe.on) g_probe.acc[6] += probeNow() - prEnd;
   if (e != hipSuccess) return fail(c, "kernel launch", e);
   return 1;
 }
@@ -1461,35 +1455,24 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
   if (c->pairsStream) {
     const TickParams& pp = c->pendingParams;
     if (c->graphMode && !c->lastTickSampled && !c->lastTickLearn) {
-      const bool stale = !c->pairGraphExec[q] || c->pairGraphEpoch[q] != c->topoEpoch || c->pairGraphExchange[q] != withExchange ||
-                         std::memcmp(&pp, &c->pairGraphParams[q], sizeof pp) != 0;
-      if (stale) {
-        dropPairGraph(c, (int)q);
-        HIP_OK(c, hipStreamBeginCapture(ps, withExchange ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
-        const int okx = withExchange ? exchangeBorders(c, q, ps, true) : 1;
-        if (okx) enqueuePairHalf(c, pp, ps);
-        const hipError_t ce = hipStreamEndCapture(ps, &c->pairGraph[q]);
-        if (!okx) { if (c->pairGraph[q]) { hipGraphDestroy(c->pairGraph[q]); c->pairGraph[q] = nullptr; } return 0; }   // (the RCCL error text is already set)
-        if (ce != hipSuccess) return fail(c, "hipStreamEndCapture (pair half)", ce);
-        if (!c->pairGraph[q]) return fail(c, "hipStreamEndCapture (pair half) returned no graph (the capture was invalidated)");
-        HIP_OK(c, hipGraphInstantiate(&c->pairGraphExec[q], c->pairGraph[q], nullptr, nullptr, 0));
-        c->pairGraphParams[q] = pp; c->pairGraphEpoch[q] = c->topoEpoch; c->pairGraphExchange[q] = withExchange;
-      }
-      HIP_OK(c, hipGraphLaunch(c->pairGraphExec[q], ps));
+      if (!replayGraph(c, ps, c->pairGraph[q], pp, withExchange, "hipStreamEndCapture (pair half)", [&] {
+            if (withExchange && !exchangeBorders(c, q, ps, true)) return 0;
+            enqueuePairHalf(c, pp, ps);
+            return 1;
+          })) return 0;
       HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
     } else {
       // a sampled tick times its pair chain too (exchange + merge + queries + pair search, on the pairs stream): SC_TICK_K_PAIRS
-      EventPair ev; const bool timed = c->profiling && c->lastTickSampled && (c->profMask & (1u << SC_TICK_K_PAIRS));
-      if (timed) { ev = takeEvents(c); hipEventRecord(ev.a, ps); }
+      EventPair ev; const bool on = timed(c, SC_TICK_K_PAIRS, c->lastTickSampled);
+      if (on) { ev = takeEvents(c); hipEventRecord(ev.a, ps); }
       if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
-      const bool rides = enqueuePairHalf(c, pp, ps, (c->variant & 4u) ? nullptr : c->pairsDone[q]);
-      if (!rides || (c->variant & 4u)) HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
-      if (timed) { hipEventRecord(ev.b, ps); c->times[SC_TICK_K_PAIRS].push_back(ev); }
+      if (!enqueuePairHalf(c, pp, ps, c->pairsDone[q])) HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
+      if (on) { hipEventRecord(ev.b, ps); c->times[SC_TICK_K_PAIRS].push_back(ev); }
     }
     c->pairsInFlight[q] = true;
   } else {
     if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
-    Scoped s(c, SC_TICK_K_PAIRS);
+    Scoped s(c, SC_TICK_K_PAIRS, c->lastTickSampled);      // (the tick's sampling decision: tickIndex has moved on)
     enqueuePairHalf(c, c->pendingParams, ps);
   }
   c->pairsPending = false;
@@ -1568,7 +1551,7 @@ int scTickSetBorderCapacity(ScTickContext* c, uint32_t recordsPerRingSector)
     for (auto& a : c->alt) a.borderSend[d] = a.borderRecv[d] = nullptr;
     for (uint32_t q = 0; q < kMaxParity; ++q) for (int k = 0; k < 2; ++k) if (c->ownBorder[q][d][k]) { dfree(c, c->ownBorder[q][d][k]); c->ownBorder[q][d][k] = nullptr; }
   }
-  dropGraph(c); dropPairGraph(c); c->topoEpoch++;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
   return 1;
 }
 
@@ -1657,7 +1640,7 @@ int scTickSetStream(ScTickContext* c, void* stream, int external)
 {
   if (!c) return 0;
   if (!bind(c) || !sync(c)) return 0;
-  dropGraph(c);
+  dropGraphs(c->graph);
   c->stream = external ? static_cast<hipStream_t>(stream) : c->ownStream;
   return 1;
 }
@@ -1673,7 +1656,7 @@ int scTickNudgeRootsX(ScTickContext* c, float dx)
 {
   if (!c) return 0;
   if (!bind(c) || !flushLinks(c)) return 0;
-  Scoped s(c, SC_TICK_K_NUDGE);
+  Scoped s(c, SC_TICK_K_NUDGE, tickSampled(c));
   launchNudgeRootsX(c->d, c->n, dx, c->stream);
   return 1;
 }
@@ -1708,7 +1691,7 @@ int scTickAdvanceMovers(ScTickContext* c, float dt)
   if (!c) return 0;
   if (!bind(c) || !flushLinks(c)) return 0;
   if (!c->d.moverKind) return fail(c, "no movers uploaded");
-  Scoped s(c, SC_TICK_K_NUDGE);
+  Scoped s(c, SC_TICK_K_NUDGE, tickSampled(c));
   launchAdvanceMovers(c->d, c->n, dt, 1.0f - std::exp(-2.5f * dt), c->trafficMult, c->stream);
   return 1;
 }
@@ -1719,7 +1702,7 @@ int scTickSetFrameProducer(ScTickContext* c, uint32_t kind, float param)
   if (kind > 2u) return fail(c, "producer kind must be 0 (none), 1 (nudge roots) or 2 (advance movers)");
   if (kind == 2u && !c->d.moverKind) return fail(c, "no movers uploaded");
   if (!bind(c) || !sync(c)) return 0;
-  dropGraph(c);                                   // the captured frame changes
+  dropGraphs(c->graph);                                   // the captured frame changes
   c->producerKind = kind;
   c->producerParam = param;
   return 1;
@@ -2025,7 +2008,7 @@ int scTickSetGraphMode(ScTickContext* c, int enable)
   if (!c) return 0;
   if (!bind(c)) return 0;
   c->graphMode = enable != 0;
-  if (!enable) { sync(c); dropGraph(c); dropPairGraph(c); }
+  if (!enable) { sync(c); dropGraphs(c->graph); dropGraphs(c->pairGraph); }
   return 1;
 }
 
@@ -2059,7 +2042,7 @@ int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDr
     rb.hBlock[k] = static_cast<uint32_t*>(h);
   }
   rb.maxVisible = maxVisible; rb.maxDraws = maxDraws; rb.bytes = bytes;
-  dropGraph(c);
+  dropGraphs(c->graph);
   return 1;
 }
 
@@ -2141,7 +2124,7 @@ int scTickSetTrafficSpeedMultiplier(ScTickContext* c, float multiplier)
 {
   if (!c) return 0;
   if (!bind(c) || !sync(c)) return 0;
-  dropGraph(c);
+  dropGraphs(c->graph);
   c->trafficMult = multiplier;
   return 1;
 }
@@ -2206,7 +2189,7 @@ int scTickSetTrafficSensors(ScTickContext* c, int enable, float frontRayLength, 
     c->halo = wantHalo;
   }
   c->sensors = enable != 0;
-  dropGraph(c); dropPairGraph(c); c->topoEpoch++;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
   return 1;
 }
 
@@ -2436,7 +2419,7 @@ int scTickCommDestroy(ScTickContext* c)
   sync(c);
   const RcclApi* r = needRccl(c);
   // captured steps hold ncclSend / ncclRecv nodes bound to this communicator and to the peers' ranks
-  dropGraph(c); dropPairGraph(c); c->topoEpoch++;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
   if (r) r->CommDestroy(c->comm);
   c->comm = nullptr; c->commSize = 0; c->commRank = 0;
   return 1;
@@ -2446,7 +2429,7 @@ int scTickCommSetPeers(ScTickContext* c, const int32_t peerRank[8])
 {
   if (!c || !peerRank) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !sync(c)) return 0;
-  dropGraph(c); dropPairGraph(c); c->topoEpoch++;       // a captured exchange names the old ranks
+  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;       // a captured exchange names the old ranks
   for (int d = 0; d < 8; ++d) c->peer[d] = peerRank[d];
   c->peersSet = true;
   return 1;
@@ -2477,7 +2460,7 @@ int scTickCommInit(ScTickContext* c, const uint8_t id[SC_TICK_COMM_ID_BYTES], ui
   std::memcpy(&u, id, sizeof u);
   if (!ncclOk(c, r, r->CommInitRank(&c->comm, (int)worldSize, u, (int)rank), "ncclCommInitRank")) { c->comm = nullptr; return 0; }
   c->commSize = worldSize; c->commRank = rank;
-  dropGraph(c); dropPairGraph(c); c->topoEpoch++;       // (a graph captured against an earlier communicator must not be replayed)
+  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;       // (a graph captured against an earlier communicator must not be replayed)
   // the messages of both tick parities live in buffers of the library's own (a caller that runs its own transport binds
   // its buffers with scTickBindBorderBuffers instead and never comes here)
   for (uint32_t q = 0; q < kMaxParity; ++q)
@@ -2507,12 +2490,6 @@ int scTickGetCommInfo(ScTickContext* c, ScTickCommInfo* out)
   }
   if (c->comm) { std::string why; if (const RcclApi* r = rccl(&why)) { int v = 0; if (r->GetVersion(&v) == ncclSuccess) out->rccl_version = (uint32_t)v; } }
   out->host_steps = c->hostSteps;
-  if (g_probe.on && g_probe.n) {
-    std::fprintf(stderr, "[sc_tick host probe] %llu ticks since the reset: waitParityFree %.2f us, enqueueStages %.2f (fused launch %.2f, compaction+pack launch %.2f), publishPacked %.2f, before %.2f, after %.2f\n",
-                 (unsigned long long)g_probe.n, g_probe.acc[0] / g_probe.n, g_probe.acc[1] / g_probe.n, g_probe.acc[3] / g_probe.n, g_probe.acc[4] / g_probe.n, g_probe.acc[2] / g_probe.n,
-                 g_probe.acc[5] / g_probe.n, g_probe.acc[6] / g_probe.n);
-    g_probe = HostProbe(); g_probe.on = true;
-  }
   out->host_tick_half_us = c->hostSteps ? c->hostAcc[0] / (double)c->hostSteps : 0.0;
   out->host_pair_half_us = c->hostSteps ? c->hostAcc[1] / (double)c->hostSteps : 0.0;
   return 1;
@@ -2549,7 +2526,6 @@ int scTickResetHostTimes(ScTickContext* c)
 {
   if (!c) return 0;
   c->hostAcc[0] = c->hostAcc[1] = 0.0; c->hostSteps = 0;
-  if (g_probe.on) { g_probe = HostProbe(); g_probe.on = true; }
   return 1;
 }
 
@@ -2628,26 +2604,25 @@ int scTickTileStep(ScTickContext* c, uint32_t flags)
     return runPendingPairs(c, false);
   }
   if (!c->comm) return fail(c, "no communicator: scTickCommInit first (a tile with neighbours cannot skip the exchange)");
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   if (c->graphMode && !c->pairsStream) {
     // in-order tile, graph replay: the whole step -- producer, fused kernel, compaction + pack, the RCCL group, merge, pair
     // search -- is captured once per tick parity and replayed with one hipGraphLaunch
-    const double g0 = now();
+    const double g0 = nowUs();
     c->captureWholeStep = true;
     const int okr = scTickRun(c, flags | SC_TICK_SPLIT_PAIRS);
     c->captureWholeStep = false;
     if (!okr) return 0;
     const int okp = c->pairsPending ? runPendingPairs(c, true) : 1;     // a sampled (profiled) tick ran eagerly: finish it the eager way
-    c->hostAcc[0] += now() - g0; c->hostSteps++;
+    c->hostAcc[0] += nowUs() - g0; c->hostSteps++;
     return okp;
   }
   // eager, or a pipelined tile: the tick on its stream, then exchange + pair half on theirs (with graph replay on, each
   // half of a pipelined step is one hipGraphLaunch; the events that order them are recorded between the two)
-  const double t0 = now();
+  const double t0 = nowUs();
   if (!scTickRun(c, flags | SC_TICK_SPLIT_PAIRS)) return 0;
-  const double t1 = now();
+  const double t1 = nowUs();
   const int ok = runPendingPairs(c, true);
-  c->hostAcc[0] += t1 - t0; c->hostAcc[1] += now() - t1; c->hostSteps++;
+  c->hostAcc[0] += t1 - t0; c->hostAcc[1] += nowUs() - t1; c->hostSteps++;
   return ok;
 }
 

@@ -201,7 +201,6 @@ struct TickParams {
   uint32_t maxPairs;
   uint32_t rankBits;        // rank << 24, OR-ed into every box id
   uint32_t neighbourMask;   // bit d set: a neighbour tile exists in direction d (its ring side is foreign)
-  uint32_t variant;         // kernel variant selector (A/B tuning; 0 = default)
   uint32_t chain;           // min(deepest hierarchy level, kMaxChain): selects the fused kernel's specialisation
   uint32_t resetParity;     // kFlagDeferredReset: the parity whose counters this tick's end-of-tick kernel clears (the next tick's)
   uint32_t tileX, tileZ, tilesX, tilesZ;   // this tile's place in the grid of equal tiles (tilesX == 0: unknown, no big-box exchange)
@@ -297,7 +296,7 @@ void launchSnapshotHome(const DeviceState& d, uint32_t sectors, uint32_t n, uint
 void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* levelList, uint32_t count, hipStream_t s);
 void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s);
 bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEvent_t done = nullptr);
-uint32_t pairRunFor(uint32_t sectors, uint32_t cus, uint32_t variant, bool sweepOnly);
+uint32_t pairRunFor(uint32_t sectors, uint32_t cus, bool sweepOnly);
 void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t compactGrid, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
 void launchGatherPairs(const DeviceState& d, const TickParams& p, uint32_t parity, uint2* dst, uint32_t* total, hipStream_t s);
 void launchCompactPack(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t done = nullptr);

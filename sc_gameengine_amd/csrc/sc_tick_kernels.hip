@@ -512,7 +512,7 @@ __device__ __forceinline__ void binEntitySingle(const DeviceState& d, const Tick
 // workgroup ever waits for another one.  Everything above `top` is clean, hence its stored matrix
 // is not written by anyone this tick and can be read race-free.
 // ------------------------------------------------------------------------------------------
-// (Variants that were measured and dropped -- a wave-cooperative hierarchy resolve through ds_bpermute, bounds
+// (Alternatives that were measured and dropped -- a wave-cooperative hierarchy resolve through ds_bpermute, bounds
 // loaded before the walk, binning with a single atomic round trip -- are in the history at 72ae167; all of
 // them lost to this form because they cost VGPRs, and this kernel is occupancy-bound.  DESIGN.md section 5.)
 // The body is a device function taking the arguments by reference on purpose: written directly in the
@@ -655,7 +655,7 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
 // trips per tile instead of eight, bit-identical results, all GPU tests green -- and it was no faster: 39.6 against 38.7 us at six
 // and seven waves per SIMD, 48 at five (profiles/r03/ab_lds_kernel.log), 35.6 against 33.0 us once the bins' atomics were gone
 // (ab_kernels_home.log).  The kernel's time was never its chain of round trips; it was the memory-side atomics of the binning
-// (binEntityWave, "home slots").  The variant is in the history at commit 3b44da7.)
+// (binEntityWave, "home slots").  That kernel is in the history at commit 3b44da7.)
 // ------------------------------------------------------------------------------------------
 // Level kernel for entities deeper than kMaxChain (rare): one launch per level, parents final.
 // nodeDirty = dirty || parent recomputed this tick (sc_ecs.cpp:184).
@@ -1512,9 +1512,6 @@ __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams
             T[kTileSlots + at] = make_float4(clo.y, chi.y, clo.w, chi.w);
           }
           fetch();                                                   // (the next sector's records are under way during the tests below)
-#ifdef SC_DIAG_NOSWEEP
-          if (false)                                                 // diagnostic build: what fetching and staging the fast sectors' records alone costs
-#endif
           if (broadcast) {
             // A handful of sweepers (a lone vehicle among props; one visitor): nothing is staged at all.  Every lane keeps its bin slot's
             // record in registers, each sweeper's xz rectangle is read into scalar registers (v_readlane) and tested by all lanes at
@@ -1545,9 +1542,6 @@ __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams
               }
             }
           }
-#ifdef SC_DIAG_NOSWEEP
-          if (false)
-#endif
           if (!broadcast) {
             const uint32_t gi = __builtin_amdgcn_readfirstlane(castTab[S]), G = gi & 0xFFu;
             const uint32_t c = (lane * (gi >> 8)) >> 16;
@@ -1590,9 +1584,6 @@ __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams
               //  bins -- was built and measured: same pairs, no gain; that resolve's global loads stand exposed at the end of the wave's run.
               //  profiles/r04/ab_deferred_resolve_lost.log)
               __builtin_amdgcn_wave_barrier();
-#ifdef SC_DIAG_NORESOLVE
-              cnt = 0;                                            // diagnostic build: what the sweeps alone cost (no pairs reported)
-#endif
               for (uint32_t q0 = 0; q0 < cnt; q0 += 64u) {
                 const uint32_t q = q0 + lane;
                 const uint32_t e = q < cnt ? cand[q] : 0u;
@@ -2852,18 +2843,17 @@ void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* 
   if (!count) return;
   hipLaunchKernelGGL(k_deep_level, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
 }
-// spans of the fused kernel per compaction workgroup (SC_TICK_VARIANT bits 4..6 override, tuning)
+// spans of the fused kernel per compaction workgroup
 // Measured at 1M entities (1536 spans): alone, one span per workgroup is fastest (8.2 us; 9.2 / 10.9 with 2 / 4 -- the
 // tiles of a workgroup are walked one after the other); sharing the launch with the pair search, two spans per
 // workgroup win (10.5 us against 11.3 / 12.2 with 1 / 4): fewer workgroups leave room for the pair role's.
-static uint32_t compactGroup(const TickParams& p, uint32_t grid, bool merged)
+static uint32_t compactGroup(uint32_t grid, bool merged)
 {
-  const uint32_t forced = (p.variant >> 4) & 7u;
-  return forced ? forced : ((merged && grid >= 512u) ? 2u : 1u);
+  return (merged && grid >= 512u) ? 2u : 1u;
 }
 void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s)
 {
-  const uint32_t g = compactGroup(p, grid, false);
+  const uint32_t g = compactGroup(grid, false);
   hipLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
 }
 // Pair-role geometry (round 4, second form): four pair workgroups for every CU -- the fifth resident workgroup of each CU is left to the
@@ -2876,12 +2866,11 @@ void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hip
 // gain from the evener spread itself (config 5: 34.0 us against 33.8, 37.4 with three workgroups per CU, 34.8 with five; config3dyn 23.2
 // / 24.4 / 23.1: profiles/r04/ab_pair_geometry.log); the form stays because it keeps the compaction workgroups resident from the start.
 // A world the host knows cannot pair (TickParams::sweepOnly) is a sweep over counters: runs of 64, about one workgroup per CU (the
-// per-workgroup prologue is what that role costs).  SC_TICK_VARIANT bits 8+: workgroups (tuning).
-uint32_t pairRunFor(uint32_t sectors, uint32_t cus, uint32_t variant, bool sweepOnly)
+// per-workgroup prologue is what that role costs).
+uint32_t pairRunFor(uint32_t sectors, uint32_t cus, bool sweepOnly)
 {
   if (!cus) cus = 256u;
-  uint32_t wgs = (variant >> 8) ? (variant >> 8) : (sweepOnly ? cus : 4u * cus);
-  wgs = std::min(wgs, kOvfWaves / (kTile / 64u));
+  const uint32_t wgs = std::min(sweepOnly ? cus : 4u * cus, kOvfWaves / (kTile / 64u));
   const uint32_t waves = wgs * (kTile / 64u);
   const uint32_t run = (sectors + waves - 1u) / waves;
   return std::max(1u, std::min(run, 64u));
@@ -2893,7 +2882,7 @@ static uint32_t pairGridFor(const TickParams& p)
   const uint32_t runs = (sectors + run - 1u) / run;
   // (a wave takes 64 / run runs per round; the grid gives every wave the same number of rounds, within one)
   const uint32_t perRound = 64u / run;
-  const uint32_t cap = std::min(((p.variant >> 8) ? (p.variant >> 8) : (p.sweepOnly ? 2u * p.cus : 4u * p.cus)) * (kTile / 64u), kOvfWaves);      // (sweep: runs of 64 are capped, leave room for the odd run)
+  const uint32_t cap = std::min((p.sweepOnly ? 2u * p.cus : 4u * p.cus) * (kTile / 64u), kOvfWaves);      // (sweep: runs of 64 are capped, leave room for the odd run)
   uint32_t waves = runs;                                   // a run per wave where the waves suffice (pairRunFor sized the run for that)
   if (runs > std::max(cap, 1u)) {
     const uint32_t rounds = (runs + cap * perRound - 1u) / (cap * perRound);
@@ -2913,7 +2902,7 @@ bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEv
 void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t compactGrid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
   const uint32_t pairGrid = (SC_DIAG_EOT & 8) ? 0u : pairGridFor(p);
-  const uint32_t g = compactGroup(p, compactGrid, true);
+  const uint32_t g = compactGroup(compactGrid, true);
   const uint32_t blocks = (compactGrid + g - 1) / g;
   auto kernel = p.emitMode ? k_compact_pairs<true> : k_compact_pairs<false>;      // (draw emission in the compaction role: an instance of its own)
   if (evA || evB) hipExtLaunchKernelGGL(kernel, dim3(blocks + pairGrid), dim3(kTile), 0, s, evA, evB, 0, d, p, blocks, g);
@@ -2925,7 +2914,7 @@ void launchGatherPairs(const DeviceState& d, const TickParams& p, uint32_t parit
 }
 void launchCompactPack(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t done)
 {
-  const uint32_t g = compactGroup(p, grid, false);
+  const uint32_t g = compactGroup(grid, false);
   const uint32_t blocks = (grid + g - 1) / g;
   // `done`: recorded by the dispatch itself (its completion signal) -- no marker packet behind the kernel on the tick queue
   if (done) hipExtLaunchKernelGGL(k_compact_pack, dim3(blocks + 8u), dim3(kTile), 0, s, nullptr, done, 0, d, p, blocks, g);

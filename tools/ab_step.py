@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """In-process A/B of library BUILDS on one device, by whole-step time (box-to-box variance makes cross-run numbers useless).
 
-    python tools/ab_step.py [--workload config3|config3dyn|config5] libA.so libB.so ...
+    python tools/ab_step.py [--workload config3|config3dyn|config5] libA.so libB.so[#SC_TICK_SPANS=4096,...] ...
 
 Each library is loaded side by side (ctypes, separate handles), gets its own context on the same world, and the builds
 are timed in interleaved rounds: per build the wall time of a burst of steps (device-bound: the host issues two launches
@@ -44,15 +44,8 @@ for path in args.libs:
     for kv in filter(None, envs.split(",")):
         k, _, v = kv.partition("=")
         os.environ[k] = v
-    lib_path, _, variant = path_env.partition("@")        # "lib.so@48": SC_TICK_VARIANT for this context (tuning knobs)
-    variant, _, spans = variant.partition(":")            # "lib.so@0:4096": SC_TICK_SPANS too (workgroups of the fused kernel)
-    os.environ["SC_TICK_VARIANT"] = variant or "0"
-    if spans:
-        os.environ["SC_TICK_SPANS"] = spans
-    else:
-        os.environ.pop("SC_TICK_SPANS", None)
     capi._LIB = None
-    capi.LIB_PATH = os.path.abspath(lib_path)
+    capi.LIB_PATH = os.path.abspath(path_env)
     t = WorldTick.from_world(w, broadphase=True)
     for kv in filter(None, envs.split(",")):
         os.environ.pop(kv.partition("=")[0], None)
