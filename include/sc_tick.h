@@ -121,6 +121,8 @@ void           scTickDestroyContext(ScTickContext* ctx);
 const char*    scTickGetLastError(const ScTickContext* ctx);
 
 /* ---- entity state upload (host -> device SoA).  [first, first+count) are dense indices. ---- */
+/* (scTickSetEntityCount: when the count changes, the per-run words of the bounds classes below are brought up to date for the runs
+ *  of 64 that gained or lost entities -- a small copy on the context's stream, which the call waits for) */
 int scTickSetEntityCount(ScTickContext* ctx, uint32_t count);
 /* setLocal (sc_ecs.h:78-84): position, XYZ Euler radians, scale; marks the range dirty.  sin/cos of
  * the angles are taken here with the host libm, as mat4_rotation_xyz does (sc_math.cpp:102-107), so
@@ -282,6 +284,14 @@ int scTickGatherVisibleCounts(ScTickContext* ctx, uint32_t* counts_out, uint32_t
 int scTickGetBinStats(ScTickContext* ctx, uint32_t stats[4]);
 /* stats[3] of the above alone: learn ticks so far.  Host-side, no read-back, no synchronisation (what a timed loop may ask). */
 int scTickGetLearnTicks(ScTickContext* ctx, uint32_t* learn_ticks);
+/* Bounds classes (diagnostics; no result depends on them).  The library keeps a table of the distinct local boxes it was given
+ * (scTickUploadBounds, compared by bit pattern, up to 4096) and, per run of 64 consecutive dense indices, whether the entities with
+ * Bounds there all have the same box; where they do, the fused kernel fetches that box once per run instead of once per entity.
+ * stats[0] boxes in the table, [1] runs whose bounded entities share a box, [2] runs whose bounded entities do not (different boxes, or
+ * a box the full table could not take; runs without a bounded entity count in neither), [3] bounded entities whose box is not in
+ * the table.  Host-side, no read-back, no synchronisation -- but a walk over every entity's host record (O(n), about a millisecond
+ * at a million entities): for tests and logs, not for the frame loop. */
+int scTickGetBoundsClassStats(ScTickContext* ctx, uint32_t stats[4]);
 /* The layer VOCABULARY of the tiled world: the OR of the group words and the OR of the mask words of every collider that exists on
  * ANY tile, now or later (until the next call; bits 0..15, or 0xFFFFFFFF = all, as scTickUploadLayers).  With it a pipelined tile
  * (scTickSetPipelined / scTickSetPairsStream) leaves the bins unwritten whose own records can meet nothing the world contains --

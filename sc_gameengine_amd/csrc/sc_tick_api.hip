@@ -35,6 +35,15 @@ struct CapturedGraph {
   bool rccl = false;                                   // the library's RCCL group is inside (captured in relaxed mode)
 };
 
+// a local box as uploaded, by bit pattern (-0 is not +0, a NaN is its bits): the key of the bounds palette
+struct BoxKey {
+  uint32_t w[6];
+  bool operator==(const BoxKey& o) const { return std::memcmp(w, o.w, sizeof w) == 0; }
+};
+struct BoxKeyHash {
+  size_t operator()(const BoxKey& k) const { uint64_t h = 0xcbf29ce484222325ull; for (uint32_t x : k.w) { h ^= x; h *= 0x100000001b3ull; } return (size_t)h; }
+};
+
 // host clock, microseconds (scTickTileStep: host time per half of a step, scTickGetCommInfo)
 double nowUs() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -56,6 +65,12 @@ struct ScTickContext
   std::vector<uint32_t> hLayers;     // group | mask << 16 as uploaded (scTickUploadLayers), for the world-vocabulary contract
   bool layerSetStale = true, ownLayersCanPair = true; uint32_t layerSetN = 0;      // worldCanPair(): do any two of this context's layer words admit a pair?
   std::vector<uint8_t> hFlags;       // bit0 has mesh, bit1 has bounds, bits 2..4 rotation about X/Y/Z trivial (sin 0, cos 1)
+  // bounds classes (DeviceState::boundsPalette / tileClass): grow-only palette of the distinct boxes scTickUploadBounds has seen,
+  // the class of every entity's box, and the host copy of the wave-tiles' words (refreshTiles keeps the device copy equal)
+  std::unordered_map<BoxKey, uint32_t, BoxKeyHash> paletteIndex;
+  std::vector<uint32_t> hPalette;    // 8 words per entry, as on the device
+  std::vector<uint16_t> hClass;      // palette index per entity; kClassNone: the palette was full when its box arrived
+  std::vector<uint32_t> hTile;
   std::vector<uint32_t> hChildren;   // direct children per entity (valid while !linksStale)
   // child lists in dense-index space (-1 = none), valid while !linksStale: a despawn patches exactly the links that
   // name a relocated entity instead of re-linking the world
@@ -279,6 +294,62 @@ bool upload3(ScTickContext* c, const float* src3, uint32_t first, uint32_t count
   const bool ok = h2d(c, dx + first, sx.data(), count * 4u) && h2d(c, dy + first, sy.data(), count * 4u) &&
                   h2d(c, dz + first, sz.data(), count * 4u);
   return ok && sync(c);      // staging vectors die here
+}
+
+// ---- bounds classes ------------------------------------------------------------------------------------------------
+// the palette entry of a box, added if it is new and there is room (kClassNone otherwise: always correct, only not faster)
+uint32_t classOfBox(ScTickContext* c, const BoxKey& k)
+{
+  const auto it = c->paletteIndex.find(k);
+  if (it != c->paletteIndex.end()) return it->second;
+  const uint32_t at = (uint32_t)c->paletteIndex.size();
+  if (at >= kPaletteCap) return kClassNone;
+  c->paletteIndex.emplace(k, at);
+  std::copy(k.w, k.w + 6, c->hPalette.begin() + 8u * (size_t)at);
+  return at;
+}
+// entries [from, size) of the palette to the device (entries are never changed once written: a running tick reads older ones only)
+bool uploadPalette(ScTickContext* c, uint32_t from)
+{
+  const uint32_t to = (uint32_t)c->paletteIndex.size();
+  if (to <= from) return true;
+  return h2d(c, const_cast<float*>(c->d.boundsPalette) + 8u * (size_t)from, c->hPalette.data() + 8u * (size_t)from, (size_t)(to - from) * 32u);
+}
+// the two words of wave-tile t from the host mirrors; entities at or past n are not part of it
+void tileWords(const ScTickContext* c, uint32_t t, uint32_t out[2])
+{
+  const uint32_t lo = t * 64u, hi = std::min(c->n, lo + 64u);
+  uint32_t cls = kClassMixed, layers = 0u; bool any = false, sameLayers = true;
+  for (uint32_t i = lo; i < hi; ++i) {
+    if (!(c->hFlags[i] & 2u)) continue;
+    if (!any) { any = true; cls = c->hClass[i]; layers = c->hLayers[i]; continue; }
+    if (c->hClass[i] != cls) cls = kClassMixed;           // (kClassNone == kClassMixed: a box outside the palette mixes its tile)
+    if (c->hLayers[i] != layers) sameLayers = false;
+  }
+  out[0] = (cls & kClassMask) | (any ? 0u : kTileNoBounds) | (sameLayers ? kTileLayersShared : 0u);
+  out[1] = sameLayers ? layers : 0u;
+}
+// recompute the listed wave-tiles and bring the device copy up to date with one contiguous copy (the caller synchronises)
+bool refreshTileList(ScTickContext* c, const std::vector<uint32_t>& tiles)
+{
+  if (tiles.empty()) return true;
+  const uint32_t count = c->cap / 64u;
+  uint32_t lo = count, hi = 0u;
+  for (uint32_t t : tiles) {
+    if (t >= count) continue;
+    tileWords(c, t, &c->hTile[2u * (size_t)t]);
+    lo = std::min(lo, t); hi = std::max(hi, t + 1u);
+  }
+  if (lo >= hi) return true;
+  return h2d(c, const_cast<uint32_t*>(c->d.tileClass) + 2u * (size_t)lo, c->hTile.data() + 2u * (size_t)lo, (size_t)(hi - lo) * 8u);
+}
+// ... the wave-tiles that entities [first, end) lie in
+bool refreshTiles(ScTickContext* c, uint32_t first, uint32_t end)
+{
+  if (end <= first) return true;
+  std::vector<uint32_t> tiles;
+  for (uint32_t t = first >> 6; t <= (end - 1u) >> 6; ++t) tiles.push_back(t);
+  return refreshTileList(c, tiles);
 }
 
 void computeSpan(const ScTickContext* c, uint32_t& span, uint32_t& grid)
@@ -757,6 +828,19 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
           && dalloc(c, d.visibleIdx, N) && dalloc(c, d.culledIdx, N) && dalloc(c, d.counters, kCounterWords)
           && dalloc(c, d.aabbMin, N) && dalloc(c, d.aabbMax, N);
   { float* f = nullptr; ok = ok && dalloc(c, f, 32); d.frustum = f; }
+  {
+    // bounds classes: both tables at their full size from the start, so that their pointers never change under a captured graph,
+    // in ONE allocation, the tile words behind the palette: the fused kernel addresses both from one pointer (a second one held
+    // in SGPRs across the tile cost its cull-only instances a wave per SIMD).  Every wave-tile starts out as "nobody has Bounds"
+    float* pal = nullptr;
+    ok = ok && dalloc(c, pal, (size_t)kPaletteCap * 8u + N / 64 * 2);
+    uint32_t* tc = pal ? reinterpret_cast<uint32_t*>(pal) + (size_t)kPaletteCap * 8u : nullptr;
+    d.boundsPalette = pal; d.tileClass = tc;
+    c->hPalette.assign((size_t)kPaletteCap * 8u, 0u);
+    c->hTile.assign(N / 64 * 2, 0u);
+    for (size_t t = 0; t < N / 64; ++t) c->hTile[2 * t] = kClassMixed | kTileNoBounds | kTileLayersShared;
+    ok = ok && h2d(c, tc, c->hTile.data(), c->hTile.size() * sizeof(uint32_t)) && sync(c);
+  }
   c->sectors = desc->tile_sectors_x ? (desc->tile_sectors_x + 2u) * (desc->tile_sectors_z + 2u) : 0u;
   c->maxPairs = desc->max_pairs ? desc->max_pairs : desc->capacity * 4u;
   c->maxPairs = ((c->maxPairs + kPairShards - 1u) / kPairShards) * kPairShards;   // equal shard segments
@@ -812,6 +896,8 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (!ok) { gCreateError = c->err; scTickDestroyContext(c); return nullptr; }
   c->hParent.assign(desc->capacity, SC_TICK_NO_PARENT);
   c->hFlags.assign(desc->capacity, 0);
+  c->hClass.assign(desc->capacity, (uint16_t)kClassNone);
+  c->hLayers.assign(desc->capacity, 0u);               // (as the device stream starts out)
   c->hChildren.assign(desc->capacity, 0);
   c->hFirstChild.assign(desc->capacity, -1); c->hNextSib.assign(desc->capacity, -1); c->hPrevSib.assign(desc->capacity, -1);
   return c;
@@ -845,9 +931,13 @@ int scTickSetEntityCount(ScTickContext* c, uint32_t count)
 {
   if (!c) return 0;
   if (count > c->desc.capacity) return fail(c, "count exceeds capacity");
+  const uint32_t before = c->n;
   c->n = count;
   c->linksStale = true;
-  return 1;
+  if (before == count) return 1;
+  // the wave-tiles that gained or lost entities (bounds classes: lanes at or past n are not part of a tile)
+  if (!bind(c) || !refreshTiles(c, std::min(before, count), std::max(before, count))) return 0;
+  return sync(c) ? 1 : 0;
 }
 
 int scTickUploadLocals(ScTickContext* c, uint32_t first, uint32_t count, const float* pos3, const float* rot3,
@@ -907,7 +997,20 @@ int scTickUploadBounds(ScTickContext* c, uint32_t first, uint32_t count, const f
     const uint8_t nf = (uint8_t)((f & ~2u) | ((!has || has[i]) ? 2u : 0u));
     if (nf != f) { f = nf; c->linksStale = true; }          // link words only change when membership does
   }
-  return 1;
+  // bounds classes, behind the streams they are derived from: the class of every uploaded box (a run of equal boxes is looked
+  // up once), then the wave-tiles of the range
+  {
+    const uint32_t paletteWas = (uint32_t)c->paletteIndex.size();
+    BoxKey prev{}; uint32_t prevClass = kClassNone; bool havePrev = false;
+    for (uint32_t i = 0; i < count; ++i) {
+      BoxKey k;
+      std::memcpy(k.w, min3 + 3 * (size_t)i, 12); std::memcpy(k.w + 3, max3 + 3 * (size_t)i, 12);
+      if (!havePrev || !(k == prev)) { prevClass = classOfBox(c, k); prev = k; havePrev = true; }
+      c->hClass[first + i] = (uint16_t)prevClass;
+    }
+    if (!uploadPalette(c, paletteWas) || !refreshTiles(c, first, first + count)) return 0;
+  }
+  return sync(c) ? 1 : 0;
 }
 
 int scTickUploadRenderMeshes(ScTickContext* c, uint32_t first, uint32_t count, const uint8_t* has, const uint32_t* mesh, const uint32_t* material)
@@ -946,6 +1049,7 @@ int scTickUploadLayers(ScTickContext* c, uint32_t first, uint32_t count, const u
   std::copy(packed.begin(), packed.end(), c->hLayers.begin() + first);      // (host mirror: what a later, narrower vocabulary is checked against)
   c->layerSetStale = true;
   c->homeValid = false;                 // the bins' remembered layer summaries are behind
+  if (!refreshTiles(c, first, first + count)) return 0;      // (bounds classes: the tiles' shared layer words)
   return sync(c) ? 1 : 0;
 }
 
@@ -1087,6 +1191,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
     if (!sync(c)) return 0;                          // the scratch buffer is reused for the parent patches below
     for (uint32_t k = 0; k < moves; ++k)             // (the layer words' host mirror moves along: sources lie beyond every target)
       if (src[k] < c->hLayers.size()) { if (c->hLayers.size() <= dst[k]) c->hLayers.resize((size_t)dst[k] + 1u, 0u); c->hLayers[dst[k]] = c->hLayers[src[k]]; }
+    for (uint32_t k = 0; k < moves; ++k) c->hClass[dst[k]] = c->hClass[src[k]];      // (and the class of its box)
     c->layerSetStale = true;
   }
 
@@ -1145,6 +1250,13 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   }
   c->n = n1;
   c->topoEpoch++;
+  {
+    // bounds classes: the wave-tiles that took a relocated entity, and those of the shrunk tail
+    std::vector<uint32_t> tiles;
+    for (uint32_t k = 0; k < moves; ++k) if (tiles.empty() || tiles.back() != dst[k] >> 6) tiles.push_back(dst[k] >> 6);      // (dst ascends)
+    for (uint32_t t = n1 >> 6; t <= (n0 - 1u) >> 6; ++t) tiles.push_back(t);
+    if (!refreshTileList(c, tiles)) return 0;
+  }
   if (movedFrom && movedTo) { std::copy(src.begin(), src.end(), movedFrom); std::copy(dst.begin(), dst.end(), movedTo); }
   if (movedCount) *movedCount = moves;
   if (relink) return flushLinks(c);
@@ -2356,6 +2468,19 @@ int scTickGetLearnTicks(ScTickContext* c, uint32_t* learn_ticks)
 {
   if (!c || !learn_ticks) return c ? fail(c, "null argument") : 0;
   *learn_ticks = c->learnTicks;            // (host-side: no read-back, no synchronisation)
+  return 1;
+}
+
+int scTickGetBoundsClassStats(ScTickContext* c, uint32_t stats[4])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  stats[0] = (uint32_t)c->paletteIndex.size(); stats[1] = stats[2] = stats[3] = 0u;
+  for (uint32_t t = 0; t < (c->n + 63u) / 64u; ++t) {
+    const uint32_t w = c->hTile[2u * (size_t)t];
+    if (w & kTileNoBounds) continue;
+    if ((w & kClassMask) < kPaletteCap) stats[1]++; else stats[2]++;
+  }
+  for (uint32_t i = 0; i < c->n; ++i) if ((c->hFlags[i] & 2u) && c->hClass[i] == kClassNone) stats[3]++;
   return 1;
 }
 

@@ -32,6 +32,10 @@ constexpr uint32_t kUnreachable = 7;
 constexpr uint32_t kRotTrivialX = 1u << 29, kRotTrivialY = 1u << 30, kRotTrivialZ = 1u << 31;
 __host__ __device__ inline uint32_t linkDepth(uint32_t lk) { return (lk >> kDepthShift) & kDepthMask; }
 
+constexpr uint32_t kPaletteCap = 4096;    // distinct local boxes a context tells apart; entities beyond that are of class "none"
+constexpr uint32_t kClassMask = 0xFFFFu, kClassMixed = 0xFFFFu, kClassNone = 0xFFFFu;
+constexpr uint32_t kTileNoBounds = 1u << 30;         // host bookkeeping: no entity of the tile has Bounds (the kernel never looks)
+constexpr uint32_t kTileLayersShared = 1u << 31;
 constexpr uint32_t kTile = 256;           // entities per workgroup pass (4 waves of 64)
 constexpr uint32_t kMaxSpanWords = 128;   // spans up to 4096 entities keep the fused producer's ballots in LDS
 
@@ -83,6 +87,14 @@ struct DeviceState {
   // RenderMesh + collision layers
   uint32_t *meshId, *materialId;
   uint32_t* layers;         // group | mask << 16
+  // Bounds classes: a table of the distinct local boxes (found by bit pattern) and, per wave-tile of 64 consecutive entities,
+  // what its entities share -- derived from the streams above by the host for the fused kernel alone, which then fetches a
+  // shared box / layer word once per tile through the scalar path instead of once per lane.  The streams stay authoritative.
+  const float* boundsPalette;  // [kPaletteCap][8]: bmin.xyz, bmax.xyz as uploaded, two words of padding
+  const uint32_t* tileClass;   // [cap / 64][2], == boundsPalette + kPaletteCap * 8 words (one allocation: the kernel addresses both from boundsPalette).
+                               // word 0 = palette index shared by the tile's entities with Bounds (kClassMixed: none shared) | kTileLayersShared when
+                               // the layer words of its entities WITH BOUNDS are all equal (only colliders use the word: never take it for a lane
+                               // without Bounds); word 1 = that layer word
   // outputs
   float4 *w0, *w1, *w2;     // world matrix rows 0..2 (affine 3x4; row 3 is 0,0,0,1)
   uint64_t* vis;            // visibility bits, word i/64

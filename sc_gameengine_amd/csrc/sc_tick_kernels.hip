@@ -134,6 +134,19 @@ __device__ __forceinline__ BoundsCE loadBounds(const DeviceState& d, uint32_t j)
   b.ex = (x1 - x0) * 0.5f; b.ey = (y1 - y0) * 0.5f; b.ez = (z1 - z0) * 0.5f;
   return b;
 }
+// Bounds classes (DeviceState::tileClass / boundsPalette): what the 64 entities of a wave-tile share is not fetched per lane.
+// The tile's two words and the palette entry are read through wave-uniform addresses in the constant address space -- scalar
+// loads, no vector memory request -- and the box is formed by loadBounds' arithmetic on the same values: the same bits.
+typedef const __attribute__((address_space(4))) float* ConstF;
+typedef const __attribute__((address_space(4))) uint32_t* ConstU;
+__device__ __forceinline__ BoundsCE paletteBounds(ConstF e)
+{
+  const float x0 = e[0], y0 = e[1], z0 = e[2], x1 = e[3], y1 = e[4], z1 = e[5];
+  BoundsCE b;
+  b.cx = (x0 + x1) * 0.5f; b.cy = (y0 + y1) * 0.5f; b.cz = (z0 + z1) * 0.5f;
+  b.ex = (x1 - x0) * 0.5f; b.ey = (y1 - y0) * 0.5f; b.ez = (z1 - z0) * 0.5f;
+  return b;
+}
 
 // computeWorldBoundsSphere + sphereInFrustum (sc_world_partition.cpp:1105-1144).  All six planes
 // are evaluated; OR-ing "d < -radius" equals the reference's early-out (NaN compares false in both).
@@ -163,7 +176,6 @@ __device__ __forceinline__ bool sphereVisible(const Aff& M, const BoundsCE& b, c
 
 // Same test with the planes read through a uniform pointer into the constant address space: scalar loads at
 // the point of use.  The fused kernel uses it so that the 24 coefficients are not held in SGPRs across the tile.
-typedef const __attribute__((address_space(4))) float* ConstF;
 __device__ __forceinline__ bool sphereVisibleAt(const Aff& M, const BoundsCE& b, ConstF fr)
 {
   const float c0 = M.r0[0] * b.cx + M.r0[1] * b.cy + M.r0[2] * b.cz + M.r0[3];
@@ -332,8 +344,9 @@ __device__ __forceinline__ void spillLane(const DeviceState& d, const TickParams
 // Same records in the same bins -- the pair search sees a few null records more, which pass no filter and overlap nothing.
 template <uint32_t kHome>
 __device__ __forceinline__ void binEntityWave(const DeviceState& d, const TickParams& p, uint32_t i, bool collider,
-                                              const Aff& M, const BoundsCE& b, bool storeM, bool lazyOn)
+                                              const Aff& M, const BoundsCE& b, bool storeM, bool lazyOn, uint32_t tile0, uint32_t tile1)
 {
+  // (tile0 / tile1: the wave-tile's class words, wave-uniform -- a layer word the tile's colliders share is not loaded per lane)
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
   BinPlan plan; plan.collide = false; plan.big = false; plan.x0 = plan.z0 = 0.0f; plan.nx = plan.nz = 0;
   float4 rmin = make_float4(0, 0, 0, 0), rmax = make_float4(0, 0, 0, 0);
@@ -343,7 +356,7 @@ __device__ __forceinline__ void binEntityWave(const DeviceState& d, const TickPa
   if (collider) {
     worldAabb(M, b, mn, mx);
     plan = planBins(p, mn, mx);
-    rmin = make_float4(mn[0], mn[1], mn[2], __uint_as_float(ldU(d, kLAYERS, i)));
+    rmin = make_float4(mn[0], mn[1], mn[2], __uint_as_float((tile0 & kTileLayersShared) ? tile1 : ldU(d, kLAYERS, i)));
     rmax = make_float4(mx[0], mx[1], mx[2], __uint_as_float(i | p.rankBits));
   }
   const bool want = plan.collide && !plan.big;
@@ -609,8 +622,15 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
     if (kCull || kAabb) {
       const bool cand = active && (lk & kHasMesh);
       const bool hb = active && (lk & kHasBounds);
+      // the wave-tile's class words, read here and not at the head of the tile: held across the walk they cost the instances
+      // without culling or without binning a wave per SIMD
+      const uint32_t t = __builtin_amdgcn_readfirstlane((base >> 6) + wave);
+      ConstU tw = (ConstU)d.boundsPalette + (kPaletteCap * 8u + 2u * t);      // (== d.tileClass: one allocation, one pointer held in SGPRs)
+      const uint32_t tile0 = tw[0], tile1 = kAabb ? tw[1] : 0u;
+      const uint32_t cls = tile0 & kClassMask;
       BoundsCE b = {0, 0, 0, 0, 0, 0};
-      if (hb) b = loadBounds(d, i);
+      if (cls < kPaletteCap) b = paletteBounds((ConstF)d.boundsPalette + 8u * cls);      // (wave-uniform branch; a lane without Bounds never uses b)
+      else if (hb) b = loadBounds(d, i);
 
       if (kCull) {
         bool visible = cand;
@@ -633,7 +653,7 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
       if (kAabb) {
         // deeper entities are binned by the level kernels once their matrix is final
         const bool collider = hb && !(doXform && depth > kChain && depth != kUnreachable);
-        binEntityWave<kHome>(d, p, i, collider, M, b, recompute, lazyOn);
+        binEntityWave<kHome>(d, p, i, collider, M, b, recompute, lazyOn, tile0, tile1);
       }
     }
   }

@@ -450,6 +450,13 @@ class WorldTick:
         self._ok(self.lib.scTickGetLearnTicks(self.ctx, _u(st)), "scTickGetLearnTicks")
         return int(st[0])
 
+    def bounds_class_stats(self):
+        """bounds classes (host-side counters): distinct boxes in the palette, wave-tiles whose bounded entities share one, wave-tiles whose do not,
+        bounded entities whose box the full palette could not take"""
+        st = np.zeros(4, np.uint32)
+        self._ok(self.lib.scTickGetBoundsClassStats(self.ctx, _u(st)), "scTickGetBoundsClassStats")
+        return {"palette_entries": int(st[0]), "tiles_shared": int(st[1]), "tiles_mixed": int(st[2]), "entities_no_class": int(st[3])}
+
     def reset_host_times(self):
         self._ok(self.lib.scTickResetHostTimes(self.ctx), "scTickResetHostTimes")
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """In-process A/B of library BUILDS on one device, by whole-step time (box-to-box variance makes cross-run numbers useless).
 
-    python tools/ab_step.py [--workload config3|config3dyn|config5] libA.so libB.so[#SC_TICK_SPANS=4096,...] ...
+    python tools/ab_step.py [--workload config3|config3dyn|config3mixed|config5] libA.so libB.so[#SC_TICK_SPANS=4096,...] ...
 
 Each library is loaded side by side (ctypes, separate handles), gets its own context on the same world, and the builds
 are timed in interleaved rounds: per build the wall time of a burst of steps (device-bound: the host issues two launches
@@ -34,6 +34,12 @@ else:
     if args.workload == "config3dyn":
         dyn = (np.arange(w.n) % 16) == 4
         w.group[dyn], w.mask[dyn] = sw.GROUP_DYNAMIC, sw.MASK_ALL
+    elif args.workload == "config3mixed":
+        # two local boxes alternating inside every wave-tile of 64: no tile shares a box, the fused kernel's per-lane fallback is what gets timed
+        odd = (np.arange(w.n) & 1) == 1
+        w.bmin[odd], w.bmax[odd] = np.float32(-0.25), np.float32(0.25)
+    elif args.workload != "config3":
+        ap.error(f"unknown workload {args.workload}")
     kind, param = 1, 0.01
 vp = camera_view_proj(w.camera)
 flags = capi.FULL | (0 if args.separate_producer else capi.PRODUCE_NEXT)
