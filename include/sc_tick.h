@@ -141,6 +141,25 @@ int scTickUploadRenderMeshes(ScTickContext* ctx, uint32_t first, uint32_t count,
 /* collision filter group / mask (sc_physics.cpp:372-379); low 16 bits are kept, 0xFFFFFFFF = all */
 int scTickUploadLayers(ScTickContext* ctx, uint32_t first, uint32_t count,
                        const uint32_t* group, const uint32_t* mask);
+/* Collider (sc_physics.h:12-28; createShape, sc_physics.cpp:136-166): what an entity's broadphase proxy is formed from.
+ * BOUNDS, the default of every entity, is the box of its Bounds (an entity without Bounds then has no proxy); NONE is an
+ * entity without a Collider component: it enters no bin and no big list, forms no pair and answers no ray; BOX / SPHERE /
+ * CAPSULE are the reference's three shapes, centred on the entity's ORIGIN, and need no Bounds.  With M the entity's world
+ * matrix, c = M[:,3], n_k the squared norm of column k of M (own spec; fp32, unfused, left to right):
+ *   BOX      h_r = (|M[r,0]| hx + |M[r,1]| hy) + |M[r,2]| hz
+ *   SPHERE   h_r = radius * sqrt(max(n_0, n_1, n_2))
+ *   CAPSULE  h_r = |M[r,1]| * max(0, half_height) + radius * sqrt(max(n_0, n_2))
+ * and the box is [c - h, c + h].  Culling is not affected: the cull sphere always comes from Bounds.
+ * type NULL = BOX for every entity; half_extents3 / radius / half_height NULL = the reference's defaults 0.5 / 0.5 / 0.5.
+ * Fails for an unknown type, a negative or non-finite half extent or radius, a non-finite half_height (a negative one is
+ * stored as 0).  All five values are kept per entity whatever its type, travel with it through scTickRemoveEntities, and
+ * come back through scTickReadColliders; scTickAppendEntities and a growing scTickSetEntityCount start new entities as
+ * BOUNDS.  A context that never calls scTickUploadColliders runs exactly the kernels it ran without this call. */
+enum { SC_TICK_COLLIDER_BOUNDS = 0, SC_TICK_COLLIDER_NONE = 1, SC_TICK_COLLIDER_BOX = 2, SC_TICK_COLLIDER_SPHERE = 3, SC_TICK_COLLIDER_CAPSULE = 4 };
+int scTickUploadColliders(ScTickContext* ctx, uint32_t first, uint32_t count, const uint8_t* type,
+                          const float* half_extents3, const float* radius, const float* half_height);
+int scTickReadColliders(ScTickContext* ctx, uint32_t first, uint32_t count, uint8_t* type,
+                        float* half_extents3, float* radius, float* half_height);
 /* Transform::parent for every entity as a dense index (SC_TICK_NO_PARENT = root).  A parent that is
  * out of range or the entity itself is detached and the entity marked dirty (sc_ecs.cpp:151-160).
  * Computes hierarchy depth; entities in or below a parent cycle are flagged unreachable. */

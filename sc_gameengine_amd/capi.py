@@ -14,6 +14,8 @@ XFORM, CULL, BROADPHASE, CULLED_LIST, DRAWS, DENSE_AABBS, SPLIT_PAIRS, SORT_DRAW
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 NO_PARENT = -1
+# collider types (SC_TICK_COLLIDER_*): what an entity's broadphase proxy is formed from
+COLLIDER_BOUNDS, COLLIDER_NONE, COLLIDER_BOX, COLLIDER_SPHERE, COLLIDER_CAPSULE = 0, 1, 2, 3, 4
 COMM_ID_BYTES = 128
 HAVE_PAIR_SEARCH = True       # flipped when the broadphase pair kernels are in the library
 
@@ -102,6 +104,8 @@ SYMBOLS = {
     "scTickUploadLocals": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P, F32P, F32P, U8P]),
     "scTickUploadPositions": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P]),
     "scTickUploadBounds": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P, F32P, U8P]),
+    "scTickUploadColliders": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U8P, F32P, F32P, F32P]),
+    "scTickReadColliders": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U8P, F32P, F32P, F32P]),
     "scTickUploadRenderMeshes": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U8P, U32P, U32P]),
     "scTickUploadLayers": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P, U32P]),
     "scTickSetTopology": (C.c_int, [_CTX, I32P, C.c_uint32]),

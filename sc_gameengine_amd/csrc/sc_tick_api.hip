@@ -71,6 +71,10 @@ struct ScTickContext
   std::vector<uint32_t> hPalette;    // 8 words per entry, as on the device
   std::vector<uint16_t> hClass;      // palette index per entity; kClassNone: the palette was full when its box arrived
   std::vector<uint32_t> hTile;
+  // colliders (scTickUploadColliders): the five values per entity as uploaded -- what scTickReadColliders returns; the device keeps
+  // the derived record (DeviceState::colShape / colType).  Empty until the first upload: every entity is SC_TICK_COLLIDER_BOUNDS.
+  std::vector<uint8_t> hColType;
+  std::vector<float> hColValues;     // [capacity][5]: half extents xyz, radius, half height
   std::vector<uint32_t> hChildren;   // direct children per entity (valid while !linksStale)
   // child lists in dense-index space (-1 = none), valid while !linksStale: a despawn patches exactly the links that
   // name a relocated entity instead of re-linking the world
@@ -315,16 +319,27 @@ bool uploadPalette(ScTickContext* c, uint32_t from)
   if (to <= from) return true;
   return h2d(c, const_cast<float*>(c->d.boundsPalette) + 8u * (size_t)from, c->hPalette.data() + 8u * (size_t)from, (size_t)(to - from) * 32u);
 }
-// the two words of wave-tile t from the host mirrors; entities at or past n are not part of it
+// does entity i have a broadphase proxy?  Its Bounds, until a collider says otherwise.
+bool hasProxyHost(const ScTickContext* c, uint32_t i)
+{
+  const uint32_t type = c->hColType.empty() ? (uint32_t)SC_TICK_COLLIDER_BOUNDS : c->hColType[i];
+  return type == SC_TICK_COLLIDER_BOUNDS ? (c->hFlags[i] & 2u) != 0u : type != SC_TICK_COLLIDER_NONE;
+}
+// the two words of wave-tile t from the host mirrors; entities at or past n are not part of it.  The shared box is over the
+// entities with Bounds (culling and BOUNDS colliders read it), the shared layer word over the entities with a proxy.
 void tileWords(const ScTickContext* c, uint32_t t, uint32_t out[2])
 {
   const uint32_t lo = t * 64u, hi = std::min(c->n, lo + 64u);
-  uint32_t cls = kClassMixed, layers = 0u; bool any = false, sameLayers = true;
+  uint32_t cls = kClassMixed, layers = 0u; bool any = false, anyProxy = false, sameLayers = true;
   for (uint32_t i = lo; i < hi; ++i) {
-    if (!(c->hFlags[i] & 2u)) continue;
-    if (!any) { any = true; cls = c->hClass[i]; layers = c->hLayers[i]; continue; }
-    if (c->hClass[i] != cls) cls = kClassMixed;           // (kClassNone == kClassMixed: a box outside the palette mixes its tile)
-    if (c->hLayers[i] != layers) sameLayers = false;
+    if (c->hFlags[i] & 2u) {
+      if (!any) { any = true; cls = c->hClass[i]; }
+      else if (c->hClass[i] != cls) cls = kClassMixed;    // (kClassNone == kClassMixed: a box outside the palette mixes its tile)
+    }
+    if (hasProxyHost(c, i)) {
+      if (!anyProxy) { anyProxy = true; layers = c->hLayers[i]; }
+      else if (c->hLayers[i] != layers) sameLayers = false;
+    }
   }
   out[0] = (cls & kClassMask) | (any ? 0u : kTileNoBounds) | (sameLayers ? kTileLayersShared : 0u);
   out[1] = sameLayers ? layers : 0u;
@@ -350,6 +365,19 @@ bool refreshTiles(ScTickContext* c, uint32_t first, uint32_t end)
   std::vector<uint32_t> tiles;
   for (uint32_t t = first >> 6; t <= (end - 1u) >> 6; ++t) tiles.push_back(t);
   return refreshTileList(c, tiles);
+}
+
+// entities [first, first + count) back to SC_TICK_COLLIDER_BOUNDS with the default values (new indices: an appended entity must not
+// inherit the collider of whoever held its index before)
+bool resetColliders(ScTickContext* c, uint32_t first, uint32_t count)
+{
+  if (!c->d.colType || !count) return true;
+  std::fill(c->hColType.begin() + first, c->hColType.begin() + first + count, (uint8_t)SC_TICK_COLLIDER_BOUNDS);
+  std::fill(c->hColValues.begin() + 5u * (size_t)first, c->hColValues.begin() + 5u * ((size_t)first + count), 0.5f);
+  const hipError_t e = hipMemsetAsync(c->d.colType + first, (int)kColliderBounds, count, c->stream);
+  if (e != hipSuccess) return fail(c, "hipMemsetAsync", e);
+  c->boxesTouched = true;
+  return true;
 }
 
 void computeSpan(const ScTickContext* c, uint32_t& span, uint32_t& grid)
@@ -545,6 +573,7 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   p.borderRecs = c->borderRecs;
   p.halo = c->halo ? 1u : 0u;
   p.tileX = c->tileX; p.tileZ = c->tileZ; p.tilesX = c->tilesX; p.tilesZ = c->tilesZ;
+  p.colliders = c->d.colType ? 1u : 0u;         // (part of a captured graph's key: the instance choice follows it)
 }
 
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
@@ -935,8 +964,10 @@ int scTickSetEntityCount(ScTickContext* c, uint32_t count)
   c->n = count;
   c->linksStale = true;
   if (before == count) return 1;
+  if (!bind(c)) return 0;
+  if (count > before && !resetColliders(c, before, count - before)) return 0;      // new indices start without a collider of their own
   // the wave-tiles that gained or lost entities (bounds classes: lanes at or past n are not part of a tile)
-  if (!bind(c) || !refreshTiles(c, std::min(before, count), std::max(before, count))) return 0;
+  if (!refreshTiles(c, std::min(before, count), std::max(before, count))) return 0;
   return sync(c) ? 1 : 0;
 }
 
@@ -1011,6 +1042,75 @@ int scTickUploadBounds(ScTickContext* c, uint32_t first, uint32_t count, const f
     if (!uploadPalette(c, paletteWas) || !refreshTiles(c, first, first + count)) return 0;
   }
   return sync(c) ? 1 : 0;
+}
+
+int scTickUploadColliders(ScTickContext* c, uint32_t first, uint32_t count, const uint8_t* type, const float* he3, const float* radius, const float* halfHeight)
+{
+  if (!c) return 0;
+  if (!bind(c) || !rangeOk(c, first, count)) return 0;
+  // validate before anything is stored: a failed call leaves the context as it was
+  for (uint32_t i = 0; i < count; ++i) {
+    if (type && type[i] > SC_TICK_COLLIDER_CAPSULE) return fail(c, "unknown collider type (SC_TICK_COLLIDER_*)");
+    if (he3) for (int k = 0; k < 3; ++k) { const float v = he3[3 * (size_t)i + k]; if (!std::isfinite(v) || v < 0.0f) return fail(c, "collider half extents must be finite and not negative"); }
+    if (radius && (!std::isfinite(radius[i]) || radius[i] < 0.0f)) return fail(c, "collider radius must be finite and not negative");
+    if (halfHeight && !std::isfinite(halfHeight[i])) return fail(c, "collider half height must be finite");
+    // (the declared layer vocabulary covers every collider there is, scTickSetWorldLayers: an entity cannot become one outside it)
+    if (c->worldLayersKnown && (!type || type[i] >= SC_TICK_COLLIDER_BOX) && first + i < c->hLayers.size() && (c->hLayers[first + i] & ~c->worldLayers))
+      return fail(c, "collider on an entity whose layers lie outside the declared world vocabulary (scTickSetWorldLayers)");
+  }
+  DeviceState& d = c->d;
+  if (!d.colType) {
+    // first call: the storage (every entity SC_TICK_COLLIDER_BOUNDS = 0, as the zeroed allocation has it), and from now on the
+    // collider instances of the fused and level kernels -- captured graphs are stale (TickParams::colliders is part of their key)
+    if (!sync(c)) return 0;
+    const size_t N = c->cap;
+    if (!dalloc(c, d.colShape, N) || !dalloc(c, d.colType, N)) { d.colShape = nullptr; d.colType = nullptr; return 0; }
+    c->hColType.assign(c->desc.capacity, (uint8_t)SC_TICK_COLLIDER_BOUNDS);
+    c->hColValues.assign((size_t)c->desc.capacity * 5u, 0.5f);
+  }
+  if (!count) return 1;
+  std::vector<float4> shape(count);
+  std::vector<uint8_t> types(count);
+  bool membership = false;
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t g = first + i;
+    const uint8_t t = type ? type[i] : (uint8_t)SC_TICK_COLLIDER_BOX;
+    float* v = &c->hColValues[5u * (size_t)g];
+    const bool had = hasProxyHost(c, g);
+    c->hColType[g] = t;
+    if (he3) { v[0] = he3[3 * (size_t)i]; v[1] = he3[3 * (size_t)i + 1]; v[2] = he3[3 * (size_t)i + 2]; } else v[0] = v[1] = v[2] = 0.5f;
+    v[3] = radius ? radius[i] : 0.5f;
+    v[4] = halfHeight ? (halfHeight[i] < 0.0f ? 0.0f : halfHeight[i]) : 0.5f;      // max(0, ...), sc_physics.cpp:154
+    membership = membership || had != hasProxyHost(c, g);
+    types[i] = t;
+    // the record as the box rule consumes it (colliderAabb): extents of the flat part, radius of the round part
+    shape[i] = t == SC_TICK_COLLIDER_BOX ? make_float4(v[0], v[1], v[2], 0.0f)
+             : t == SC_TICK_COLLIDER_SPHERE ? make_float4(0.0f, 0.0f, 0.0f, v[3])
+             : t == SC_TICK_COLLIDER_CAPSULE ? make_float4(0.0f, v[4], 0.0f, v[3]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  // what a bounds upload invalidates: unmoved entities' records are no longer this tick's (cleanStay), and where an entity gained or
+  // lost its proxy, the remembered slots and the captured graphs (as a Bounds membership change does through the link words)
+  c->boxesTouched = true;
+  if (membership) { c->homeValid = false; c->topoEpoch++; }
+  if (!h2d(c, d.colShape + first, shape.data(), (size_t)count * sizeof(float4)) || !h2d(c, d.colType + first, types.data(), count)) return 0;
+  if (!refreshTiles(c, first, first + count)) return 0;      // (the tiles' shared layer words are over the entities with a proxy)
+  return sync(c) ? 1 : 0;
+}
+
+int scTickReadColliders(ScTickContext* c, uint32_t first, uint32_t count, uint8_t* type, float* he3, float* radius, float* halfHeight)
+{
+  if (!c) return 0;
+  if (!rangeOk(c, first, count)) return 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t g = first + i;
+    const bool have = !c->hColType.empty();
+    const float* v = have ? &c->hColValues[5u * (size_t)g] : nullptr;
+    if (type) type[i] = have ? c->hColType[g] : (uint8_t)SC_TICK_COLLIDER_BOUNDS;
+    if (he3) for (int k = 0; k < 3; ++k) he3[3 * (size_t)i + k] = have ? v[k] : 0.5f;
+    if (radius) radius[i] = have ? v[3] : 0.5f;
+    if (halfHeight) halfHeight[i] = have ? v[4] : 0.5f;
+  }
+  return 1;
 }
 
 int scTickUploadRenderMeshes(ScTickContext* c, uint32_t first, uint32_t count, const uint8_t* has, const uint32_t* mesh, const uint32_t* material)
@@ -1092,6 +1192,7 @@ int scTickAppendEntities(ScTickContext* c, uint32_t count, const float* pos3, co
     c->hFirstChild[i] = -1; c->hNextSib[i] = -1; c->hPrevSib[i] = -1;
   }
 
+  if (!resetColliders(c, first, count)) { c->n = first; c->linksStale = true; return 0; }
   std::vector<float> cube;
   if (!bmin3) { cube.assign((size_t)count * 6, 0.5f); for (size_t i = 0; i < (size_t)count * 3; ++i) cube[i] = -0.5f; }   // kUnitCubeBounds
   std::vector<uint32_t> all;
@@ -1192,6 +1293,11 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
     for (uint32_t k = 0; k < moves; ++k)             // (the layer words' host mirror moves along: sources lie beyond every target)
       if (src[k] < c->hLayers.size()) { if (c->hLayers.size() <= dst[k]) c->hLayers.resize((size_t)dst[k] + 1u, 0u); c->hLayers[dst[k]] = c->hLayers[src[k]]; }
     for (uint32_t k = 0; k < moves; ++k) c->hClass[dst[k]] = c->hClass[src[k]];      // (and the class of its box)
+    if (!c->hColType.empty())                                                        // (and its collider)
+      for (uint32_t k = 0; k < moves; ++k) {
+        c->hColType[dst[k]] = c->hColType[src[k]];
+        std::copy(c->hColValues.begin() + 5u * (size_t)src[k], c->hColValues.begin() + 5u * (size_t)src[k] + 5u, c->hColValues.begin() + 5u * (size_t)dst[k]);
+      }
     c->layerSetStale = true;
   }
 
@@ -2454,7 +2560,7 @@ int scTickSetWorldLayers(ScTickContext* c, uint32_t groupOr, uint32_t maskOr, in
   if (known) {                                        // the contract holds for what is already here, too
     const size_t upto = std::min<size_t>(c->hLayers.size(), c->n);
     for (size_t i = 0; i < upto; ++i)
-      if ((c->hFlags[i] & 2u) && (c->hLayers[i] & ~v)) return fail(c, "the vocabulary does not cover the layers already uploaded to this tile");
+      if (hasProxyHost(c, (uint32_t)i) && (c->hLayers[i] & ~v)) return fail(c, "the vocabulary does not cover the layers already uploaded to this tile");
   }
   if ((known != 0) != c->worldLayersKnown || v != c->worldLayers) {
     if (!sync(c)) return 0;

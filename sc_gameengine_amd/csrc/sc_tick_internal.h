@@ -32,6 +32,8 @@ constexpr uint32_t kUnreachable = 7;
 constexpr uint32_t kRotTrivialX = 1u << 29, kRotTrivialY = 1u << 30, kRotTrivialZ = 1u << 31;
 __host__ __device__ inline uint32_t linkDepth(uint32_t lk) { return (lk >> kDepthShift) & kDepthMask; }
 
+// collider types (== SC_TICK_COLLIDER_*)
+constexpr uint32_t kColliderBounds = 0, kColliderNone = 1, kColliderBox = 2, kColliderSphere = 3, kColliderCapsule = 4;
 constexpr uint32_t kPaletteCap = 4096;    // distinct local boxes a context tells apart; entities beyond that are of class "none"
 constexpr uint32_t kClassMask = 0xFFFFu, kClassMixed = 0xFFFFu, kClassNone = 0xFFFFu;
 constexpr uint32_t kTileNoBounds = 1u << 30;         // host bookkeeping: no entity of the tile has Bounds (the kernel never looks)
@@ -93,8 +95,8 @@ struct DeviceState {
   const float* boundsPalette;  // [kPaletteCap][8]: bmin.xyz, bmax.xyz as uploaded, two words of padding
   const uint32_t* tileClass;   // [cap / 64][2], == boundsPalette + kPaletteCap * 8 words (one allocation: the kernel addresses both from boundsPalette).
                                // word 0 = palette index shared by the tile's entities with Bounds (kClassMixed: none shared) | kTileLayersShared when
-                               // the layer words of its entities WITH BOUNDS are all equal (only colliders use the word: never take it for a lane
-                               // without Bounds); word 1 = that layer word
+                               // the layer words of its entities WITH A PROXY -- with Bounds, while no collider was ever uploaded -- are all equal
+                               // (only colliders use the word: never take it for a lane without a proxy); word 1 = that layer word
   // outputs
   float4 *w0, *w1, *w2;     // world matrix rows 0..2 (affine 3x4; row 3 is 0,0,0,1)
   uint64_t* vis;            // visibility bits, word i/64
@@ -161,6 +163,13 @@ struct DeviceState {
   // multi-GPU border exchange: one message per neighbour direction (caller-owned device buffers)
   uint32_t* borderSend[8];
   uint32_t* borderRecv[8];
+  // Colliders (scTickUploadColliders; allocated on its first call, nullptr before: every entity is then kColliderBounds and the
+  // kernels' collider instances are never launched).  One 16-byte record per entity, outside the stream slab, in the form the box
+  // rule consumes it: (ex, ey, ez, radius) -- a box's half extents, (0, 0, 0) for a sphere, (0, max(0,
+  // halfHeight), 0) for a capsule -- and the type in a byte of its own.
+  float4* colShape;
+  uint8_t* colType;
+  // (last on purpose: the offsets of everything above in the kernels' argument block stay what they were)
 };
 
 // Border message layout (uint32 words): [0] records in the spill-over area, [1] overflow flag, [2..2+L) per-cell counts,
@@ -244,6 +253,7 @@ struct TickParams {
   uint32_t vocabKnown;      // scTickSetWorldLayers declared the world's layer vocabulary (`vocab`): the border merge counts arrivals outside it
   uint32_t sweepOnly;       // host hint (worldCanPair): no two layer words of this world admit a pair -- the pair role only sweeps the counters; sizes its grid, nothing else
   uint32_t fastPairs;       // the pair role takes bins that hold nothing but their ordered reserved records through the fast path (homeCast)
+  uint32_t colliders;       // scTickUploadColliders was called (DeviceState::colType exists): the fused and level kernels run their collider instances
 };
 // neighbour directions: d = (dz+1)*3 + (dx+1), skipping the centre -> 0..7; opposite(d) = 7 - d
 __host__ __device__ inline void borderDir(uint32_t d, int& dx, int& dz) { const uint32_t k = d < 4 ? d : d + 1; dx = (int)(k % 3) - 1; dz = (int)(k / 3) - 1; }

@@ -211,6 +211,39 @@ __device__ __forceinline__ void worldAabb(const Aff& M, const BoundsCE& b, float
   mx[0] = c0 + h0; mx[1] = c1 + h1; mx[2] = c2 + h2;
 }
 
+// world AABB of a typed collider (kColliderBox / Sphere / Capsule), centred on the entity's origin:
+// c_r = M[r,3], h_r = ((|M[r,0]|*ex + |M[r,1]|*ey) + |M[r,2]|*ez) + pad with s = (ex, ey, ez, radius) as DeviceState::colShape holds
+// it; pad = 0 for a box, radius * sqrt(largest squared column norm) for a sphere (the three columns) and a capsule (columns 0
+// and 2: its round part lies in the local xz plane) -- the squared norms and their selection as sphereVisible forms them.
+__device__ __forceinline__ void colliderAabb(const Aff& M, const float4& s, uint32_t type, float mn[3], float mx[3])
+{
+  float pad = 0.0f;
+  if (type != kColliderBox) {
+    const float nx = M.r0[0] * M.r0[0] + M.r1[0] * M.r1[0] + M.r2[0] * M.r2[0];
+    const float ny = M.r0[1] * M.r0[1] + M.r1[1] * M.r1[1] + M.r2[1] * M.r2[1];
+    const float nz = M.r0[2] * M.r0[2] + M.r1[2] * M.r1[2] + M.r2[2] * M.r2[2];
+    const float nyz = (type == kColliderSphere && nz < ny) ? ny : nz;      // sphere: max(n1, n2); capsule: n2
+    pad = s.w * sqrtf((nx < nyz) ? nyz : nx);
+  }
+  const float h0 = fabsf(M.r0[0]) * s.x + fabsf(M.r0[1]) * s.y + fabsf(M.r0[2]) * s.z + pad;
+  const float h1 = fabsf(M.r1[0]) * s.x + fabsf(M.r1[1]) * s.y + fabsf(M.r1[2]) * s.z + pad;
+  const float h2 = fabsf(M.r2[0]) * s.x + fabsf(M.r2[1]) * s.y + fabsf(M.r2[2]) * s.z + pad;
+  mn[0] = M.r0[3] - h0; mn[1] = M.r1[3] - h1; mn[2] = M.r2[3] - h2;
+  mx[0] = M.r0[3] + h0; mx[1] = M.r1[3] + h1; mx[2] = M.r2[3] + h2;
+}
+// "has a proxy" (DESIGN.md section 6): a typed collider always, a kColliderBounds entity when it has Bounds, kColliderNone never
+__device__ __forceinline__ bool hasProxy(uint32_t type, bool hasBounds) { return type == kColliderBounds ? hasBounds : type != kColliderNone; }
+// the box of entity i's proxy from its stored matrix, for the callers off the hot path (level kernels, lazy records, dense AABBs);
+// false = no proxy (mn / mx untouched).  d.colType == nullptr: no collider was ever uploaded, every entity is kColliderBounds.
+__device__ __forceinline__ bool proxyAabb(const DeviceState& d, uint32_t i, uint32_t lk, const Aff& M, float mn[3], float mx[3])
+{
+  const uint32_t type = d.colType ? d.colType[i] : kColliderBounds;
+  if (!hasProxy(type, (lk & kHasBounds) != 0u)) return false;
+  if (type == kColliderBounds) { const BoundsCE b = loadBounds(d, i); worldAabb(M, b, mn, mx); }
+  else colliderAabb(M, d.colShape[i], type, mn, mx);
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------
 // Broadphase binning.  A box is entered into every sector its xz range
 // [floor(min*inv), floor(max*inv)] touches (worldToSector arithmetic, sc_world_partition.cpp:268-275)
@@ -342,9 +375,11 @@ __device__ __forceinline__ void spillLane(const DeviceState& d, const TickParams
 // on every tick and no parity copy of the bins ever shows a stale record; a copy without a reservation (the box entered a
 // new sector, a bin was full at the learn tick, level kernels, border records) reserves behind the remembered slots as before.
 // Same records in the same bins -- the pair search sees a few null records more, which pass no filter and overlap nothing.
-template <uint32_t kHome>
+// kColl (collider instances, after the first scTickUploadColliders): ctype is the lane's collider type; a typed collider's box comes
+// from its colShape record (colliderAabb), a kColliderBounds lane keeps the Bounds box `b` it already holds for culling.
+template <uint32_t kHome, bool kColl>
 __device__ __forceinline__ void binEntityWave(const DeviceState& d, const TickParams& p, uint32_t i, bool collider,
-                                              const Aff& M, const BoundsCE& b, bool storeM, bool lazyOn, uint32_t tile0, uint32_t tile1)
+                                              const Aff& M, const BoundsCE& b, bool storeM, bool lazyOn, uint32_t tile0, uint32_t tile1, uint32_t ctype)
 {
   // (tile0 / tile1: the wave-tile's class words, wave-uniform -- a layer word the tile's colliders share is not loaded per lane)
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
@@ -354,7 +389,8 @@ __device__ __forceinline__ void binEntityWave(const DeviceState& d, const TickPa
   uint32_t hA = kNoHome, hB = 0xFFFFFFFFu;
   if (mode == kHomeUse && i < p.n) { hA = d.homeA[i]; hB = d.homeB[i]; }
   if (collider) {
-    worldAabb(M, b, mn, mx);
+    if (kColl && ctype != kColliderBounds) colliderAabb(M, d.colShape[i], ctype, mn, mx);
+    else worldAabb(M, b, mn, mx);
     plan = planBins(p, mn, mx);
     rmin = make_float4(mn[0], mn[1], mn[2], __uint_as_float((tile0 & kTileLayersShared) ? tile1 : ldU(d, kLAYERS, i)));
     rmax = make_float4(mx[0], mx[1], mx[2], __uint_as_float(i | p.rankBits));
@@ -496,10 +532,8 @@ __device__ __forceinline__ void binEntityWave(const DeviceState& d, const TickPa
 }
 
 // Same for a single lane (level kernels: entities of one level are scattered, no runs to aggregate).
-__device__ __forceinline__ void binEntitySingle(const DeviceState& d, const TickParams& p, uint32_t i, const Aff& M, const BoundsCE& b)
+__device__ __forceinline__ void binBoxSingle(const DeviceState& d, const TickParams& p, uint32_t i, const float mn[3], const float mx[3])
 {
-  float mn[3], mx[3];
-  worldAabb(M, b, mn, mx);
   const BinPlan plan = planBins(p, mn, mx);
   const float4 rmin = make_float4(mn[0], mn[1], mn[2], __uint_as_float(ldU(d, kLAYERS, i)));
   float4 rmax = make_float4(mx[0], mx[1], mx[2], __uint_as_float(i | p.rankBits));
@@ -512,6 +546,13 @@ __device__ __forceinline__ void binEntitySingle(const DeviceState& d, const Tick
     float4 rm = rmax; if (k == 0) rm.w = __uint_as_float(i | p.rankBits | kPrimary);
     binInsertLane(d, p, (sz + dz) * p.binSX + (sx + dx), rmin, rm);
   }
+}
+
+__device__ __forceinline__ void binEntitySingle(const DeviceState& d, const TickParams& p, uint32_t i, const Aff& M, const BoundsCE& b)
+{
+  float mn[3], mx[3];
+  worldAabb(M, b, mn, mx);
+  binBoxSingle(d, p, i, mn, mx);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -534,13 +575,17 @@ __device__ __forceinline__ void binEntitySingle(const DeviceState& d, const Tick
 // host after scTickSetTopology.  Specialising on it removes dead levels from worlds that are flat or shallow.
 // (Requesting all levels' locals before multiplying -- one round trip instead of one per level -- was measured:
 // it needs 12 more VGPRs per level, 104-116 in all, and lost 5-25 %)
-template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
+template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl>
 __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickParams& p);
 
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
-__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome>(d, p); }
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome, false>(d, p); }
+// The collider instances (kAabb only: without binning nothing reads a collider), launched once scTickUploadColliders was called:
+// kernels of their own name, so that a context that never made the call runs exactly the instances above.
+template <bool kCull, uint32_t kChain, uint32_t kHome>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders(const DeviceState d, const TickParams p) { xformCullBody<kCull, true, kChain, kHome, true>(d, p); }
 
-template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
+template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl>
 __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickParams& p)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -622,6 +667,9 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
     if (kCull || kAabb) {
       const bool cand = active && (lk & kHasMesh);
       const bool hb = active && (lk & kHasBounds);
+      // (collider instances: the lane's type, requested with the bounds; a lane past the end has no proxy)
+      uint32_t ctype = kColliderNone;
+      if (kColl && active) ctype = d.colType[i];
       // the wave-tile's class words, read here and not at the head of the tile: held across the walk they cost the instances
       // without culling or without binning a wave per SIMD
       const uint32_t t = __builtin_amdgcn_readfirstlane((base >> 6) + wave);
@@ -652,8 +700,8 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
       }
       if (kAabb) {
         // deeper entities are binned by the level kernels once their matrix is final
-        const bool collider = hb && !(doXform && depth > kChain && depth != kUnreachable);
-        binEntityWave<kHome>(d, p, i, collider, M, b, recompute, lazyOn, tile0, tile1);
+        const bool collider = (kColl ? hasProxy(ctype, hb) : hb) && !(doXform && depth > kChain && depth != kUnreachable);
+        binEntityWave<kHome, kColl>(d, p, i, collider, M, b, recompute, lazyOn, tile0, tile1, ctype);
       }
     }
   }
@@ -680,8 +728,9 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
 // Level kernel for entities deeper than kMaxChain (rare): one launch per level, parents final.
 // nodeDirty = dirty || parent recomputed this tick (sc_ecs.cpp:184).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kTile) void k_deep_level(const DeviceState d, const TickParams p,
-                                                      const uint32_t* __restrict__ list, uint32_t count)
+// (kColl: the collider instance, as for the fused kernel -- proxies by the collider rule, an instance of its own name)
+template <bool kColl>
+__device__ __forceinline__ void deepLevelBody(const DeviceState& d, const TickParams& p, const uint32_t* __restrict__ list, uint32_t count)
 {
   const uint32_t t = blockIdx.x * kTile + threadIdx.x;
   if (t >= count) return;
@@ -713,9 +762,12 @@ __global__ __launch_bounds__(kTile) void k_deep_level(const DeviceState d, const
     }
   }
   if (p.flags & SC_TICK_BROADPHASE) {
-    if (hb) binEntitySingle(d, p, i, M, b);
+    if (kColl) { float mn[3], mx[3]; if (proxyAabb(d, i, lk, M, mn, mx)) binBoxSingle(d, p, i, mn, mx); }
+    else if (hb) binEntitySingle(d, p, i, M, b);
   }
 }
+__global__ __launch_bounds__(kTile) void k_deep_level(const DeviceState d, const TickParams p, const uint32_t* __restrict__ list, uint32_t count) { deepLevelBody<false>(d, p, list, count); }
+__global__ __launch_bounds__(kTile) void k_deep_level_colliders(const DeviceState d, const TickParams p, const uint32_t* __restrict__ list, uint32_t count) { deepLevelBody<true>(d, p, list, count); }
 
 // ------------------------------------------------------------------------------------------
 // K2: ordered (stable) compaction of the visibility bits into CullingState::visible (and ::culled),
@@ -1302,11 +1354,13 @@ __device__ __forceinline__ bool pairHit(const TickParams& p, const float4& amin,
 // A bin that had to be rebuilt once is likely to be needed again (a vehicle that drove into a street of props stays a while):
 // its owners are told to write it from the next tick on (kSlotAlways in their homeB byte for this copy; kHomeHot in the bin's
 // homeCount), until the next learn tick sorts the bins afresh.
+// (kColl: the pair kernels' collider instances -- the owner's proxy and its box by the collider rule, proxyAabb)
+template <bool kColl>
 __device__ __forceinline__ void rebuildHomeRecord(const DeviceState& d, const TickParams& p, uint32_t sector, float4& rmin, float4& rmax)
 {
   const uint32_t i = __float_as_uint(rmax.w) & 0x00FFFFFFu;
   float4 lo, hi; nullRecord(lo, hi, i | p.rankBits);
-  if (i < p.n && (ldU(d, kLINK, i) & kHasBounds)) {
+  if (i < p.n && (kColl ? hasProxy(d.colType[i], (ldU(d, kLINK, i) & kHasBounds) != 0u) : (ldU(d, kLINK, i) & kHasBounds) != 0u)) {
     const uint32_t hA = d.homeA[i];
     {
       const uint32_t offH = sector - hA;                  // which of the owner's copies this slot is
@@ -1314,9 +1368,9 @@ __device__ __forceinline__ void rebuildHomeRecord(const DeviceState& d, const Ti
       atomicOr(&d.homeB[i], kSlotAlways << (8u * k));
     }
     const Aff M = loadRows(d, i);
-    const BoundsCE b = loadBounds(d, i);
     float mn[3], mx[3];
-    worldAabb(M, b, mn, mx);
+    if (kColl) proxyAabb(d, i, ldU(d, kLINK, i), M, mn, mx);
+    else { const BoundsCE b = loadBounds(d, i); worldAabb(M, b, mn, mx); }
     const BinPlan plan = planBins(p, mn, mx);
     if (plan.collide && !plan.big) {
       const uint32_t s0 = (uint32_t)plan.z0 * p.binSX + (uint32_t)plan.x0;
@@ -1339,7 +1393,7 @@ __device__ uint32_t g_waveRows[8192 * 8];      // per wave: duration, fast secto
 #endif
 // (kVocab: the vocabulary form of the lazy records, TickParams::lazy 2 -- an instance of its own, only ever the pairs-stream
 //  kernel's: with its branches merely present the in-order end-of-tick kernel ran 0.6 us (config 3) to 2.4 us (config 5) longer)
-template <bool kVocab>
+template <bool kVocab, bool kColl = false>
 __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams& p, uint32_t bid, uint32_t nblocks,
                                           float4 (*tile)[2 * kTileSlots], uint16_t* pairTab, uint2 (*pairBuf)[kWavePairBuf],
                                           unsigned long long (*cellMembers)[kCellWords])
@@ -1647,7 +1701,7 @@ __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams
           float4* r = d.bins + 2u * ((size_t)sK * kBinCap + lane);
           float4 lo, hi;
           if (vocabMode) nullRecord(lo, hi);               // (the owners' records meet nothing: records from elsewhere are searched among themselves)
-          else { lo = r[0]; hi = r[1]; rebuildHomeRecord(d, p, sK, lo, hi); }
+          else { lo = r[0]; hi = r[1]; rebuildHomeRecord<kColl>(d, p, sK, lo, hi); }
           r[0] = lo; r[1] = hi;
         }
       }
@@ -1841,7 +1895,7 @@ __device__ __forceinline__ void pairsBody(const DeviceState& d, const TickParams
         float4* r = d.bins + 2u * ((size_t)s * kBinCap + lane);
         float4 lo, hi;
         if (vocabMode) nullRecord(lo, hi);
-        else { lo = r[0]; hi = r[1]; rebuildHomeRecord(d, p, s, lo, hi); }
+        else { lo = r[0]; hi = r[1]; rebuildHomeRecord<kColl>(d, p, s, lo, hi); }
         r[0] = lo; r[1] = hi;
       }
       __threadfence();
@@ -1983,6 +2037,17 @@ __global__ __launch_bounds__(kTile) SC_PAIR_OCC void k_pairs(const DeviceState d
   pairsBody<kVocab>(d, p, blockIdx.x, gridDim.x, tile, pairTab, pairBuf, cellMembers);
 }
 
+// (the collider instance: lazy records are rebuilt by the collider rule -- a kernel of its own name, launched once a collider was uploaded)
+template <bool kVocab>
+__global__ __launch_bounds__(kTile) SC_PAIR_OCC void k_pairs_colliders(const DeviceState d, const TickParams p)
+{
+  __shared__ float4 tile[kTile / 64][2 * kTileSlots];
+  __shared__ __attribute__((aligned(16))) uint16_t pairTab[kPairTabSize];
+  __shared__ uint2 pairBuf[kTile / 64][kWavePairBuf];
+  __shared__ unsigned long long cellMembers[kTile / 64][kCellWords];
+  pairsBody<kVocab, true>(d, p, blockIdx.x, gridDim.x, tile, pairTab, pairBuf, cellMembers);
+}
+
 // read-back helper: concatenates the shards' segments into one list and writes the total found
 __global__ __launch_bounds__(kTile) void k_gather_pairs(const DeviceState d, const TickParams p, uint32_t parity, uint2* __restrict__ dst, uint32_t* __restrict__ total)
 {
@@ -2024,6 +2089,21 @@ __global__ __launch_bounds__(kTile) SC_PAIR_OCC void k_compact_pairs(const Devic
   // is what their look-back needs.  (Both orders behind a run-time switch doubled the kernel's code and cost every world 2-4 us.)
   const uint32_t pairBlocks = gridDim.x - compactBlocks;
   if (blockIdx.x < pairBlocks) pairsBody<false>(d, p, blockIdx.x, pairBlocks, tile, pairTab, pairBuf, cellMembers);
+  else compactBody<kEmit>(d, p, blockIdx.x - pairBlocks, compactBlocks, group, scratch, moved, reinterpret_cast<uint32_t*>(&tile[0][0]));
+}
+
+// (the collider instance, as k_pairs_colliders)
+template <bool kEmit>
+__global__ __launch_bounds__(kTile) SC_PAIR_OCC void k_compact_pairs_colliders(const DeviceState d, const TickParams p, uint32_t compactBlocks, uint32_t group)
+{
+  __shared__ float4 tile[kTile / 64][2 * kTileSlots];
+  __shared__ __attribute__((aligned(16))) uint16_t pairTab[kPairTabSize];
+  __shared__ uint2 pairBuf[kTile / 64][kWavePairBuf];
+  __shared__ unsigned long long cellMembers[kTile / 64][kCellWords];
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
+  __shared__ uint32_t moved[kMaxSpanWords];
+  const uint32_t pairBlocks = gridDim.x - compactBlocks;
+  if (blockIdx.x < pairBlocks) pairsBody<false, true>(d, p, blockIdx.x, pairBlocks, tile, pairTab, pairBuf, cellMembers);
   else compactBody<kEmit>(d, p, blockIdx.x - pairBlocks, compactBlocks, group, scratch, moved, reinterpret_cast<uint32_t*>(&tile[0][0]));
 }
 
@@ -2497,7 +2577,7 @@ __global__ __launch_bounds__(kTile) void k_dense_aabbs(const DeviceState d, uint
   if (i >= n) return;
   const uint32_t lk = ldU(d, kLINK, i);
   float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-  if (lk & kHasBounds) { const Aff M = loadRows(d, i); const BoundsCE b = loadBounds(d, i); worldAabb(M, b, mn, mx); }
+  proxyAabb(d, i, lk, loadRows(d, i), mn, mx);      // (no proxy: the "no box" value stays)
   d.aabbMin[i] = make_float4(mn[0], mn[1], mn[2], 0.0f);
   d.aabbMax[i] = make_float4(mx[0], mx[1], mx[2], 0.0f);
 }
@@ -2606,7 +2686,7 @@ __global__ __launch_bounds__(kTile) void k_gather_rows(const DeviceState d, cons
 // Swap-remove relocations (ComponentPool::remove, sc_ecs.h:240-262, applied to every per-entity array at
 // once): entity src[k] moves to slot dst[k].  The host guarantees every src lies at or beyond the new
 // entity count and every dst below it, so no slot is both read and written.  One thread per (move, array).
-constexpr uint32_t kMoveSlots = 40;     // 22 streams, 3 matrix rows, the dirty bit, 7 mover arrays, 5 traffic-agent arrays, 2 sensor arrays
+constexpr uint32_t kMoveSlots = 42;     // 22 streams, 3 matrix rows, the dirty bit, 7 mover arrays, 5 traffic-agent arrays, 2 sensor arrays, 2 collider arrays
 __global__ __launch_bounds__(kTile) void k_move_entities(const DeviceState d, const uint32_t* __restrict__ src,
                                                          const uint32_t* __restrict__ dst, uint32_t moves)
 {
@@ -2637,7 +2717,8 @@ __global__ __launch_bounds__(kTile) void k_move_entities(const DeviceState d, co
   } else if (d.aRayLen && slot >= kStreamCount + 16u && slot < kStreamCount + 18u) {      // per-agent TrafficSensors values travel with their entity
     float* a = slot == kStreamCount + 16u ? d.aRayLen : d.aSafe;
     a[to] = a[from];
-  }
+  } else if (d.colType && slot == kStreamCount + 18u) d.colShape[to] = d.colShape[from];      // a collider travels with its entity
+  else if (d.colType && slot == kStreamCount + 19u) d.colType[to] = d.colType[from];
 }
 
 // Children of a relocated entity: pairs (entity, new parent index); depth and flags are untouched.
@@ -2828,9 +2909,22 @@ static void launchHome(const DeviceState& d, const TickParams& p, uint32_t grid,
   if (evA) hipExtLaunchKernelGGL((k_xform_cull<kCull, kAabb, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
   else hipLaunchKernelGGL((k_xform_cull<kCull, kAabb, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, d, p);
 }
+template <bool kCull, uint32_t kChain, uint32_t kHome>
+static void launchHomeColliders(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
+{
+  if (evA) hipExtLaunchKernelGGL((k_xform_cull_colliders<kCull, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
+  else hipLaunchKernelGGL((k_xform_cull_colliders<kCull, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, d, p);
+}
 template <bool kCull, bool kAabb, uint32_t kChain>
 static void launchOne(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
+  // collider instances: only where boxes are binned, and only once a collider was uploaded (TickParams::colliders)
+  if (kAabb && p.colliders) {
+    if (p.homeMode == kHomeOff) launchHomeColliders<kCull, kChain, kHomeOff>(d, p, grid, s, evA, evB);
+    else if (p.homeMode == kHomeUse) launchHomeColliders<kCull, kChain, kHomeUse>(d, p, grid, s, evA, evB);
+    else launchHomeColliders<kCull, kChain, kHomeLearn>(d, p, grid, s, evA, evB);
+    return;
+  }
   // the bins' home slots: an instance per mode, and only where boxes are binned at all
   if (!kAabb || p.homeMode == kHomeOff) launchHome<kCull, kAabb, kChain, kHomeOff>(d, p, grid, s, evA, evB);
   else if (p.homeMode == kHomeUse) launchHome<kCull, kAabb, kChain, kHomeUse>(d, p, grid, s, evA, evB);
@@ -2861,7 +2955,8 @@ void launchXformCull(const DeviceState& d, const TickParams& p, uint32_t grid, h
 void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* list, uint32_t count, hipStream_t s)
 {
   if (!count) return;
-  hipLaunchKernelGGL(k_deep_level, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
+  if (p.colliders) hipLaunchKernelGGL(k_deep_level_colliders, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
+  else hipLaunchKernelGGL(k_deep_level, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
 }
 // spans of the fused kernel per compaction workgroup
 // Measured at 1M entities (1536 spans): alone, one span per workgroup is fastest (8.2 us; 9.2 / 10.9 with 2 / 4 -- the
@@ -2914,7 +3009,7 @@ static uint32_t pairGridFor(const TickParams& p)
 bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEvent_t done)
 {
   if (!(p.binSX * p.binSZ)) return false;
-  auto kernel = p.lazy == 2u ? k_pairs<true> : k_pairs<false>;
+  auto kernel = p.colliders ? (p.lazy == 2u ? k_pairs_colliders<true> : k_pairs_colliders<false>) : (p.lazy == 2u ? k_pairs<true> : k_pairs<false>);
   if (done) hipExtLaunchKernelGGL(kernel, dim3(pairGridFor(p)), dim3(kTile), 0, s, nullptr, done, 0, d, p);
   else hipLaunchKernelGGL(kernel, dim3(pairGridFor(p)), dim3(kTile), 0, s, d, p);
   return true;
@@ -2924,7 +3019,8 @@ void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t comp
   const uint32_t pairGrid = (SC_DIAG_EOT & 8) ? 0u : pairGridFor(p);
   const uint32_t g = compactGroup(compactGrid, true);
   const uint32_t blocks = (compactGrid + g - 1) / g;
-  auto kernel = p.emitMode ? k_compact_pairs<true> : k_compact_pairs<false>;      // (draw emission in the compaction role: an instance of its own)
+  auto kernel = p.colliders ? (p.emitMode ? k_compact_pairs_colliders<true> : k_compact_pairs_colliders<false>)
+                            : (p.emitMode ? k_compact_pairs<true> : k_compact_pairs<false>);      // (draw emission in the compaction role: an instance of its own)
   if (evA || evB) hipExtLaunchKernelGGL(kernel, dim3(blocks + pairGrid), dim3(kTile), 0, s, evA, evB, 0, d, p, blocks, g);
   else hipLaunchKernelGGL(kernel, dim3(blocks + pairGrid), dim3(kTile), 0, s, d, p, blocks, g);
 }

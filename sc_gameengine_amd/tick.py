@@ -146,6 +146,26 @@ class WorldTick:
         self._ok(self.lib.scTickUploadBounds(self.ctx, first, len(a), _f(a), _f(b),
                                              None if h is None else h.ctypes.data_as(capi.U8P)), "scTickUploadBounds")
 
+    def upload_colliders(self, first, type, half_extents=None, radius=None, half_height=None):
+        """Collider per entity from `first` on (capi.COLLIDER_*; type None = BOX for len(half_extents) entities): the broadphase
+        proxy is formed from it instead of the Bounds box.  None for a value array = the reference's default 0.5."""
+        t = None if type is None else np.ascontiguousarray(type, np.uint8).reshape(-1)
+        he = None if half_extents is None else _c32(half_extents).reshape(-1, 3)
+        r = None if radius is None else _c32(radius).reshape(-1)
+        hh = None if half_height is None else _c32(half_height).reshape(-1)
+        given = [len(a) for a in (t, he, r, hh) if a is not None]
+        assert given and min(given) == max(given), "upload_colliders: arrays of one length, at least one of them"
+        self._ok(self.lib.scTickUploadColliders(self.ctx, first, given[0], None if t is None else t.ctypes.data_as(capi.U8P),
+                                                None if he is None else _f(he), None if r is None else _f(r),
+                                                None if hh is None else _f(hh)), "scTickUploadColliders")
+
+    def colliders(self):
+        """(type, half_extents[n,3], radius, half_height) of every entity as stored (BOUNDS and 0.5s where none was uploaded)"""
+        t, he = np.zeros(self.n, np.uint8), np.zeros((self.n, 3), np.float32)
+        r, hh = np.zeros(self.n, np.float32), np.zeros(self.n, np.float32)
+        self._ok(self.lib.scTickReadColliders(self.ctx, 0, self.n, t.ctypes.data_as(capi.U8P), _f(he), _f(r), _f(hh)), "scTickReadColliders")
+        return t, he, r, hh
+
     def upload_render_meshes(self, first, has, mesh, material):
         h = np.ascontiguousarray(has, np.uint8)
         m, t = np.ascontiguousarray(mesh, np.uint32), np.ascontiguousarray(material, np.uint32)

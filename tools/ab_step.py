@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """In-process A/B of library BUILDS on one device, by whole-step time (box-to-box variance makes cross-run numbers useless).
 
-    python tools/ab_step.py [--workload config3|config3dyn|config3mixed|config5] libA.so libB.so[#SC_TICK_SPANS=4096,...] ...
+    python tools/ab_step.py [--workload config3|config3dyn|config3dyncoll|config3mixed|config5] libA.so libB.so[#SC_TICK_SPANS=4096,...] ...
 
 Each library is loaded side by side (ctypes, separate handles), gets its own context on the same world, and the builds
 are timed in interleaved rounds: per build the wall time of a burst of steps (device-bound: the host issues two launches
-per step) plus the kernels' own durations from dispatch timestamps on a separate profiled burst."""
+per step) plus the kernels' own durations from dispatch timestamps on a separate profiled burst.
+
+--workload config3dyncoll: every build runs config3dyn twice in the same interleaved rounds -- as it is, and ("lib.so+colliders") with
+every entity given a BOX collider of its bounds' half extents (scTickUploadColliders).  SynthWorld's bounds are centred, so the
+boxes and pairs are the same: the difference is what the collider instances and their 17 bytes per entity cost."""
 import argparse
 import json
 import os
@@ -31,7 +35,7 @@ if args.workload == "config5":
     kind, param = 2, 1.0 / 60.0
 else:
     w = sw.config("config3")
-    if args.workload == "config3dyn":
+    if args.workload in ("config3dyn", "config3dyncoll"):
         dyn = (np.arange(w.n) % 16) == 4
         w.group[dyn], w.mask[dyn] = sw.GROUP_DYNAMIC, sw.MASK_ALL
     elif args.workload == "config3mixed":
@@ -45,7 +49,8 @@ vp = camera_view_proj(w.camera)
 flags = capi.FULL | (0 if args.separate_producer else capi.PRODUCE_NEXT)
 
 ctxs = {}
-for path in args.libs:
+variants = [(p, False) for p in args.libs] + ([(p, True) for p in args.libs] if args.workload == "config3dyncoll" else [])
+for path, colliders in variants:
     path_env, _, envs = path.partition("#")               # "lib.so#SC_TICK_FAST_PAIRS=0,SC_TICK_HOME_PERIOD=8": environment for this context's creation
     for kv in filter(None, envs.split(",")):
         k, _, v = kv.partition("=")
@@ -55,6 +60,9 @@ for path in args.libs:
     t = WorldTick.from_world(w, broadphase=True)
     for kv in filter(None, envs.split(",")):
         os.environ.pop(kv.partition("=")[0], None)
+    if colliders:
+        t.upload_colliders(0, np.full(w.n, capi.COLLIDER_BOX, np.uint8), half_extents=(w.bmax - w.bmin) * np.float32(0.5))
+        path += "+colliders"
     t.set_view_proj(vp)
     t.set_frame_producer(kind, param)
     (t.advance_movers if kind == 2 else t.nudge_roots_x)(param)
@@ -63,7 +71,7 @@ for path in args.libs:
     t.sync()
     ctxs[path] = t
 
-res = {p: {"step_us": [], "k1_us": [], "eot_us": []} for p in args.libs}
+res = {p: {"step_us": [], "k1_us": [], "eot_us": []} for p in ctxs}
 for rnd in range(args.rounds):
     for path, t in ctxs.items():
         for _ in range(20):
@@ -82,7 +90,7 @@ for rnd in range(args.rounds):
         t.set_profiling(0)
 vis = {p: int(t.counts().visible) for p, t in ctxs.items()}
 prs = {p: int(t.counts().pairs) for p, t in ctxs.items()}
-for path in args.libs:
+for path in ctxs:
     r = res[path]
     print(json.dumps({"lib": os.path.basename(path.partition("#")[0].partition("@")[0]) + path[len(path.partition("#")[0].partition("@")[0]):], "workload": args.workload,
                       "step_us_median": round(float(np.median(r["step_us"])), 2), "step_us_min": round(float(np.min(r["step_us"])), 2),
