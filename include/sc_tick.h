@@ -58,6 +58,7 @@ enum {
   SC_TICK_PRODUCE_NEXT = 1u << 9,  /* with XFORM: the frame producer (scTickSetFrameProducer) is applied at the END of this run, inside
                                       the end-of-tick kernel, as the producer of the NEXT frame -- instead of at the start of the next
                                       scTickRun.  Results of this run are unaffected; positions read back are already the next frame's. */
+  SC_TICK_SWEEPS      = 1u << 10,  /* with BROADPHASE: answer the capsule sweeps set by scTickSetSweepQueries against this tick's boxes */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -586,6 +587,48 @@ int scTickSetRayQueries(ScTickContext* ctx, uint32_t count, const float* origin3
                         const float* max_dist, const uint32_t* mask);
 /* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_RAYS) (after scTickRunPairs on a tiled world) */
 int scTickReadRayHits(ScTickContext* ctx, ScTickRayHit* hits, uint32_t capacity, uint32_t* count);
+
+/* ---- capsule sweeps over the broadphase bins ----
+ * A batch of upright-capsule sweeps answered where the rays are: after the bins are filled (on a tiled world: after the border
+ * merge) and before the pair search consumes them.  Shaped like PhysicsWorld::sweepCapsule (src/engine/physics/sc_physics.h:179,
+ * sc_physics.cpp:779-810), which sweeps btCapsuleShape(radius, 2 * halfHeight) through Bullet's exact shapes.  Bullet is not in
+ * the tree, so -- as for the rays -- this is this build's OWN SPEC: the candidates are the broadphase's world AABBs, the sweeper is
+ * the capsule's own AABB, and a box swept against a box is a ray against the box grown by the sweeper's half extents: the slab
+ * arithmetic is intersectRayAABB again (editor_core.cpp:438-470).
+ * All arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt.  For (start, end, radius, half_height, mask, skip_id):
+ *   sweeper     hh = (half_height > 0) ? half_height : 0;   e = (radius, hh + radius, radius)
+ *   segment     d = end - start;  lenSq = (d.x*d.x + d.y*d.y) + d.z*d.z;
+ *               lenSq > 1e-6:  far = sqrt(lenSq), inv = 1 / far, ndir = d * inv
+ *               otherwise an OVERLAP test at start: ndir = (0,0,0), far = 0 (every axis of the slab test is then containment, closed)
+ *   candidates  every record the ray queries see, under their filter -- (group & mask) != 0 and the proxy's own mask not empty --
+ *               applied before the box is touched; a box whose id == skip_id never answers (0xFFFFFFFF: none)
+ *   test        lo' = lo - e, hi' = hi + e per component, then the rays' slab test of (start, ndir, far) against (lo', hi');
+ *               the smallest t wins, equal t goes to the lower id
+ * On a tiled world the rays' rule holds: a context answers for the boxes registered in its own sectors (the neighbours' boxes that
+ * reach into them included); the part of a sweep beyond the tile is the neighbour's.  A pipelined tile sees what its rays see. */
+typedef struct ScTickSweepHit   /* SweepHit, sc_physics.h:116; laid out like ScTickRayHit */
+{
+  uint32_t hit;                /* 0 / 1 */
+  uint32_t id;                 /* rank << 24 | dense index of the box that was hit (0xFFFFFFFF: none) */
+  float    distance;           /* the hit FRACTION of the sweep, t / far (SweepHit::distance = m_closestHitFraction, sc_physics.cpp:801); 0 when far == 0 */
+  float    position[3];        /* start + ndir * t: the capsule's CENTRE at the hit -- not Bullet's contact point */
+  float    normal[3];          /* axis normal of the grown box's face the centre entered through; (0,1,0) when the sweep starts in overlap (t = 0) */
+  uint32_t layer;              /* the box's collision group */
+  float    travel;             /* t in metres */
+  uint32_t pad;
+} ScTickSweepHit;              /* a miss is SweepHit{}: id 0xFFFFFFFF, normal (0,1,0), zeros */
+#ifdef __cplusplus
+static_assert(sizeof(ScTickSweepHit) == 48, "ScTickSweepHit is 48 bytes, like ScTickRayHit");
+#else
+_Static_assert(sizeof(ScTickSweepHit) == 48, "ScTickSweepHit is 48 bytes, like ScTickRayHit");
+#endif
+/* start3 / end3: [count][3]; radius, half_height, mask: [count]; skip_id: [count] or NULL (none).  The set stays until it is replaced
+ * (count 0 clears it).  Fails -- and leaves the previous set in place -- when a start, end, radius or half_height is not finite, a
+ * radius is negative, or a segment's squared length overflows fp32. */
+int scTickSetSweepQueries(ScTickContext* ctx, uint32_t count, const float* start3, const float* end3, const float* radius,
+                          const float* half_height, const uint32_t* mask, const uint32_t* skip_id);
+/* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_SWEEPS) (after scTickRunPairs on a tiled world) */
+int scTickReadSweepHits(ScTickContext* ctx, ScTickSweepHit* hits, uint32_t capacity, uint32_t* count);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

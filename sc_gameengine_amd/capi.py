@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SC_TICK_LIB") or os.path.join(HERE, "libsc_tick.so") 
 
 # scTickRun flags (include/sc_tick.h)
 XFORM, CULL, BROADPHASE, CULLED_LIST, DRAWS, DENSE_AABBS, SPLIT_PAIRS, SORT_DRAWS, RAYS, PRODUCE_NEXT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+SWEEPS = 1 << 10
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 NO_PARENT = -1
@@ -49,6 +50,11 @@ class DrawItem(C.Structure):
 class RayHit(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("id", C.c_uint32), ("distance", C.c_float), ("position", C.c_float * 3),
                 ("normal", C.c_float * 3), ("layer", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class SweepHit(C.Structure):
+    _fields_ = [("hit", C.c_uint32), ("id", C.c_uint32), ("distance", C.c_float), ("position", C.c_float * 3),
+                ("normal", C.c_float * 3), ("layer", C.c_uint32), ("travel", C.c_float), ("pad", C.c_uint32)]
 
 
 class Frame(C.Structure):
@@ -176,6 +182,8 @@ SYMBOLS = {
     "scTickReadDraws": (C.c_int, [_CTX, C.POINTER(DrawItem), C.c_uint32, U32P]),
     "scTickSetRayQueries": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, F32P, U32P]),
     "scTickReadRayHits": (C.c_int, [_CTX, C.POINTER(RayHit), C.c_uint32, U32P]),
+    "scTickSetSweepQueries": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, F32P, F32P, U32P, U32P]),
+    "scTickReadSweepHits": (C.c_int, [_CTX, C.POINTER(SweepHit), C.c_uint32, U32P]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

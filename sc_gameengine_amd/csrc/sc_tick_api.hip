@@ -100,6 +100,8 @@ struct ScTickContext
   void* lastDraws = nullptr;           // where the last SC_TICK_DRAWS wrote its items (dDraws, or the frame read-back block)
   RayQueryState rays{};                // scTickSetRayQueries: device copies of the batch + the hit buffer
   uint32_t rayCap = 0;
+  SweepQueryState sweeps{};            // scTickSetSweepQueries: the same for the capsule sweeps
+  uint32_t sweepCap = 0;
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
 
@@ -675,6 +677,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   const bool needCompact = (flags & (SC_TICK_XFORM | SC_TICK_CULL)) != 0;
   const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, c->stream);      // the bins are full, not yet consumed
+  if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, c->stream);
   // Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
   // entity's place in the list, i.e. its draw item (emitVisible).  With the frame read-back on (and a budget that fits the block)
   // the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
@@ -1526,6 +1529,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   const DeviceState ds = stateFor(c, pp.parity);
   launchBorderMerge(ds, pp, ps);
   if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, ps);   // sees the neighbours' border boxes too
+  if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, ps);   // ... as do the capsule sweeps
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   return launchPairs(ds, pp, ps, done);
 }
@@ -1578,6 +1582,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (c->pairsStream && (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS)) return fail(c, "a pairs stream is set: run the broadphase with SC_TICK_SPLIT_PAIRS + scTickRunPairs");
   if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");
   if ((flags & SC_TICK_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
+  if ((flags & SC_TICK_SWEEPS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_SWEEPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_SORT_DRAWS) && !c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
   TickParams p; uint32_t grid;
   fillParams(c, flags, p, grid);
@@ -1614,7 +1619,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
     const bool hostBetweenHalves = (flags & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & SC_TICK_RAYS) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
     c->lastTickLazy = p.lazy != 0u;
@@ -2121,6 +2126,21 @@ int scTickReadDraws(ScTickContext* c, ScTickDrawItem* items, uint32_t cap, uint3
   return 1;
 }
 
+// (one read-back path for both hit types: they share the 48-byte layout)
+static int readQueryHits(ScTickContext* c, uint32_t flag, const char* notRequested, const char* pending, const void* src, uint32_t have,
+                         void* hits, uint32_t cap, uint32_t* count)
+{
+  if (!c || !count) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & flag)) return fail(c, notRequested);
+  if (c->pairsPending) return fail(c, pending);
+  if (!joinPairs(c)) return 0;
+  *count = have;
+  const uint32_t take = std::min(have, cap);
+  if (take && hits) { if (!d2h(c, hits, src, (size_t)take * sizeof(RayHit48)) || !sync(c)) return 0; }
+  return 1;
+}
+
 int scTickSetRayQueries(ScTickContext* c, uint32_t count, const float* origin3, const float* dir3, const float* maxDist, const uint32_t* mask)
 {
   if (!c) return 0;
@@ -2150,16 +2170,51 @@ int scTickSetRayQueries(ScTickContext* c, uint32_t count, const float* origin3, 
 
 int scTickReadRayHits(ScTickContext* c, ScTickRayHit* hits, uint32_t cap, uint32_t* count)
 {
-  if (!c || !count) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_RAYS)) return fail(c, "the last scTickRun did not request SC_TICK_RAYS");
-  if (c->pairsPending) return fail(c, "ray hits are ready after scTickRunPairs");
-  if (!joinPairs(c)) return 0;
   static_assert(sizeof(ScTickRayHit) == sizeof(RayHit48), "ray hit layouts differ");
-  *count = c->rays.count;
-  const uint32_t take = std::min(c->rays.count, cap);
-  if (take && hits) { if (!d2h(c, hits, c->rays.hits, (size_t)take * sizeof(ScTickRayHit)) || !sync(c)) return 0; }
-  return 1;
+  return readQueryHits(c, SC_TICK_RAYS, "the last scTickRun did not request SC_TICK_RAYS", "ray hits are ready after scTickRunPairs",
+                       c ? c->rays.hits : nullptr, c ? c->rays.count : 0u, hits, cap, count);
+}
+
+int scTickSetSweepQueries(ScTickContext* c, uint32_t count, const float* start3, const float* end3, const float* radius, const float* halfHeight,
+                          const uint32_t* mask, const uint32_t* skipId)
+{
+  if (!c) return 0;
+  if (count && (!start3 || !end3 || !radius || !halfHeight || !mask)) return fail(c, "null argument");
+  // the kernel never sees a value it has no answer for: checked before anything changes, so a refused call leaves the previous set in place
+  std::vector<float4> a(count), b(count); std::vector<uint2> f(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    a[i] = make_float4(start3[3 * i], start3[3 * i + 1], start3[3 * i + 2], radius[i]);
+    b[i] = make_float4(end3[3 * i], end3[3 * i + 1], end3[3 * i + 2], halfHeight[i]);
+    f[i] = make_uint2(mask[i], skipId ? skipId[i] : 0xFFFFFFFFu);
+    const float v[8] = { a[i].x, a[i].y, a[i].z, a[i].w, b[i].x, b[i].y, b[i].z, b[i].w };
+    for (float x : v) if (!std::isfinite(x)) return fail(c, "sweep queries: start, end, radius and half_height must be finite");
+    if (radius[i] < 0.0f) return fail(c, "sweep queries: radius must be >= 0");
+    const float dx = b[i].x - a[i].x, dy = b[i].y - a[i].y, dz = b[i].z - a[i].z;
+    if (!std::isfinite((dx * dx + dy * dy) + dz * dz)) return fail(c, "sweep queries: the segment's squared length overflows fp32");
+  }
+  if (!bind(c) || !sync(c)) return 0;
+  if (count > c->sweepCap) {
+    dfree(c, const_cast<float4*>(c->sweeps.start)); dfree(c, const_cast<float4*>(c->sweeps.end)); dfree(c, const_cast<uint2*>(c->sweeps.filter)); dfree(c, c->sweeps.hits);
+    c->sweeps = SweepQueryState{}; c->sweepCap = 0;
+    const uint32_t want = std::max(count, 1024u);
+    float4 *st = nullptr, *en = nullptr; uint2* fl = nullptr; SweepHit48* h = nullptr;
+    if (!dalloc(c, st, want, false) || !dalloc(c, en, want, false) || !dalloc(c, fl, want, false) || !dalloc(c, h, want)) return 0;
+    c->sweeps.start = st; c->sweeps.end = en; c->sweeps.filter = fl; c->sweeps.hits = h; c->sweepCap = want;
+  }
+  c->sweeps.count = count;
+  c->topoEpoch++;                      // a captured frame holds the old batch size
+  if (!count) return 1;
+  if (!h2d(c, const_cast<float4*>(c->sweeps.start), a.data(), (size_t)count * 16u) ||
+      !h2d(c, const_cast<float4*>(c->sweeps.end), b.data(), (size_t)count * 16u) ||
+      !h2d(c, const_cast<uint2*>(c->sweeps.filter), f.data(), (size_t)count * 8u)) return 0;
+  return sync(c) ? 1 : 0;
+}
+
+int scTickReadSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, uint32_t* count)
+{
+  static_assert(sizeof(ScTickSweepHit) == sizeof(SweepHit48) && offsetof(ScTickSweepHit, travel) == offsetof(SweepHit48, travel), "sweep hit layouts differ");
+  return readQueryHits(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS", "sweep hits are ready after scTickRunPairs",
+                       c ? c->sweeps.hits : nullptr, c ? c->sweeps.count : 0u, hits, cap, count);
 }
 
 int scTickQueryOccupied(ScTickContext* c, uint32_t count, const float* pos3, const float* radius, const uint32_t* mask, uint8_t* blocked)

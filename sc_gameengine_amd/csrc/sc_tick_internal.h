@@ -305,6 +305,17 @@ struct RayQueryState {
   uint32_t count;
 };
 void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, hipStream_t s);
+// ---- capsule sweeps over the bins: a kernel argument of their own (DeviceState and TickParams keep their layout) ----
+struct SweepHit48 { uint32_t hit, id; float distance; float position[3]; float normal[3]; uint32_t layer; float travel; uint32_t pad; };   // == ScTickSweepHit, laid out like RayHit48
+static_assert(sizeof(SweepHit48) == sizeof(RayHit48), "sweep hits are read back like ray hits");
+struct SweepQueryState {
+  const float4* start;      // xyz + radius
+  const float4* end;        // xyz + half height
+  const uint2* filter;      // (mask, skip id)
+  SweepHit48* hits;
+  uint32_t count;
+};
+void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s);
 void launchAgentFrontRays(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchAgentRaySnapshot(const DeviceState& d, const TickParams& p, hipStream_t s);         // tick half: list the agents, note their rays
 void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p, hipStream_t s); // pair half, behind the merge: cast them

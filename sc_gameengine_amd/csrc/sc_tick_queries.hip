@@ -46,18 +46,15 @@ __device__ __forceinline__ Slab rayBox(const float o[3], const float dir[3], flo
 // The result is wave-uniform.  skipId: a box that never answers (0xFFFFFFFF = none) -- an agent's own box for its front ray.
 struct WaveRay { bool valid, hit; float t; uint32_t id, axis, layer; float dir[3]; };
 
-__device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickParams& p, const float o[3], const float dm[3], float maxDist,
-                                               uint32_t rayMask, uint32_t skipId)
+// The segment o + dir * [0, maxDist] against this tick's records, by a whole wave; fills hit / t / id / axis / layer of `w`.
+// kSweep (capsule sweeps, k_sweep_queries): every candidate box is grown by `grow` per axis before the slab test, and the sector
+// walk reaches `reach` (the sweeper's xz half extent) further on every side.  The ray instance (kSweep false) takes neither and
+// is the routine the ray kernels always had.
+template <bool kSweep>
+__device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d, const TickParams& p, const float o[3], const float dir[3], float maxDist,
+                                                uint32_t rayMask, uint32_t skipId, const float grow[3], float reach)
 {
   const uint32_t lane = threadIdx.x & 63u;
-  WaveRay w; w.valid = false; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u; w.dir[0] = w.dir[1] = w.dir[2] = 0.0f;
-  const float lenSq = dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2];
-  // (a NaN or non-positive length is no segment either)
-  if (!(lenSq > 1e-6f) || !(maxDist >= 0.0f)) return w;
-  w.valid = true;
-  const float invLen = 1.0f / sqrtf(lenSq);
-  const float dir[3] = { dm[0] * invLen, dm[1] * invLen, dm[2] * invLen };
-  w.dir[0] = dir[0]; w.dir[1] = dir[1]; w.dir[2] = dir[2];
   const float ex = o[0] + dir[0] * maxDist, ez = o[2] + dir[2] * maxDist;
 
   // this lane's best so far
@@ -68,14 +65,26 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
     if (!((lay & 0xFFFFu) & rayMask) || !(lay >> 16)) return;
     const uint32_t id = __float_as_uint(hi.w) & ~kPrimary;
     if (id == skipId) return;
-    const Slab s = rayBox(o, dir, maxDist, lo, hi);
+    // (the filter came first on purpose: a null record -- layers 0, inverted box -- grown by the sweeper could become a real box)
+    const Slab s = kSweep ? rayBox(o, dir, maxDist, make_float4(lo.x - grow[0], lo.y - grow[1], lo.z - grow[2], 0.0f),
+                                   make_float4(hi.x + grow[0], hi.y + grow[1], hi.z + grow[2], 0.0f))
+                          : rayBox(o, dir, maxDist, lo, hi);
     if (!s.hit) return;
     if (s.t < bt || (s.t == bt && id < bid)) { bt = s.t; bid = id; baxis = s.axis; blayer = lay & 0xFFFFu; }
   };
 
   // sectors under the segment's xz extent, clamped to the bin grid (boxes outside it are in the big list)
-  const float fx0 = floorf((o[0] < ex ? o[0] : ex) * p.invSector) - p.binOx, fx1 = floorf((o[0] < ex ? ex : o[0]) * p.invSector) - p.binOx;
-  const float fz0 = floorf((o[2] < ez ? o[2] : ez) * p.invSector) - p.binOz, fz1 = floorf((o[2] < ez ? ez : o[2]) * p.invSector) - p.binOz;
+  // Sweeps: the extent grown by `reach` on every side.  That suffices: a box whose grown form the segment meets has a point within
+  // `reach` (per axis, in x and z) of a point of the segment; that point of the box lies in a sector of the grown extent, and a box is
+  // registered in every sector it overlaps -- or is in the big list.  The long-segment skip test below grows by the same amount.
+  float fx0, fx1, fz0, fz1;
+  if (kSweep) {
+    fx0 = floorf(((o[0] < ex ? o[0] : ex) - reach) * p.invSector) - p.binOx; fx1 = floorf(((o[0] < ex ? ex : o[0]) + reach) * p.invSector) - p.binOx;
+    fz0 = floorf(((o[2] < ez ? o[2] : ez) - reach) * p.invSector) - p.binOz; fz1 = floorf(((o[2] < ez ? ez : o[2]) + reach) * p.invSector) - p.binOz;
+  } else {
+    fx0 = floorf((o[0] < ex ? o[0] : ex) * p.invSector) - p.binOx; fx1 = floorf((o[0] < ex ? ex : o[0]) * p.invSector) - p.binOx;
+    fz0 = floorf((o[2] < ez ? o[2] : ez) * p.invSector) - p.binOz; fz1 = floorf((o[2] < ez ? ez : o[2]) * p.invSector) - p.binOz;
+  }
   const float gridX = (float)p.binSX - 1.0f, gridZ = (float)p.binSZ - 1.0f;
   bool anyOverflow = false;
   if (p.binSX && fx1 >= 0.0f && fz1 >= 0.0f && fx0 <= gridX && fz0 <= gridZ) {
@@ -85,9 +94,10 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
     for (uint32_t gz = gz0; gz <= gz1; ++gz)
       for (uint32_t gx = gx0; gx <= gx1; ++gx) {
         if (gx1 - gx0 > 1u || gz1 - gz0 > 1u) {
-          // long ray: skip sectors the segment cannot touch (the sector's square, grown by a metre, as a flat box)
-          const float4 lo = make_float4(((float)gx + p.binOx) * size - 1.0f, -INFINITY, ((float)gz + p.binOz) * size - 1.0f, 0.0f);
-          const float4 hi = make_float4(((float)gx + p.binOx + 1.0f) * size + 1.0f, INFINITY, ((float)gz + p.binOz + 1.0f) * size + 1.0f, 0.0f);
+          // long ray: skip sectors the segment cannot touch (the sector's square, grown by a metre -- a sweep: and by its reach -- as a flat box)
+          const float margin = kSweep ? 1.0f + reach : 1.0f;
+          const float4 lo = make_float4(((float)gx + p.binOx) * size - margin, -INFINITY, ((float)gz + p.binOz) * size - margin, 0.0f);
+          const float4 hi = make_float4(((float)gx + p.binOx + 1.0f) * size + margin, INFINITY, ((float)gz + p.binOz + 1.0f) * size + margin, 0.0f);
           if (!rayBox(o, dir, maxDist, lo, hi).hit) continue;
         }
         const uint32_t s = gz * p.binSX + gx;
@@ -121,10 +131,25 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
   }
   const bool found = bid != 0xFFFFFFFFu && key == best;
   const unsigned long long winners = ballot64(found);
-  if (!winners) return w;
+  if (!winners) return;
   const int win = __ffsll((long long)winners) - 1;
   w.hit = true;
   w.t = __shfl(bt, win, 64); w.id = __shfl(bid, win, 64); w.axis = __shfl(baxis, win, 64); w.layer = __shfl(blayer, win, 64);
+}
+
+__device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickParams& p, const float o[3], const float dm[3], float maxDist,
+                                               uint32_t rayMask, uint32_t skipId)
+{
+  WaveRay w; w.valid = false; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u; w.dir[0] = w.dir[1] = w.dir[2] = 0.0f;
+  const float lenSq = dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2];
+  // (a NaN or non-positive length is no segment either)
+  if (!(lenSq > 1e-6f) || !(maxDist >= 0.0f)) return w;
+  w.valid = true;
+  const float invLen = 1.0f / sqrtf(lenSq);
+  const float dir[3] = { dm[0] * invLen, dm[1] * invLen, dm[2] * invLen };
+  w.dir[0] = dir[0]; w.dir[1] = dir[1]; w.dir[2] = dir[2];
+  const float none[3] = { 0.0f, 0.0f, 0.0f };
+  castSegmentWave<false>(w, d, p, o, dir, maxDist, rayMask, skipId, none, 0.0f);
   return w;
 }
 
@@ -148,6 +173,48 @@ __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, cons
     if (w.axis < 3u) {                                  // the face the ray entered through; a ray starting inside keeps (0,1,0)
       out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
       out.normal[w.axis] = w.dir[w.axis] > 0.0f ? -1.0f : 1.0f;
+    }
+  }
+  if (lane == 0) q.hits[r] = out;
+}
+
+// ---- capsule sweeps (own spec, include/sc_tick.h "capsule sweeps"; shaped like PhysicsWorld::sweepCapsule, sc_physics.cpp:779-810) --
+// The sweeper is the upright capsule's own AABB, e = (radius, max(0, halfHeight) + radius, radius); a box swept against a box is the
+// segment against the box grown by e, so the test is rayBox again.  A segment of |d|^2 <= 1e-6 is an overlap test at `start`: direction
+// (0, 0, 0) and length 0 send every axis of the slab test through its containment branch.  One wave per sweep.
+__global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, const TickParams p, const SweepQueryState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
+  if (r >= q.count) return;
+  const float4 a = q.start[r], b = q.end[r];
+  const uint2 f = q.filter[r];
+  const float o[3] = { a.x, a.y, a.z };
+  const float radius = a.w, hh = (b.w > 0.0f) ? b.w : 0.0f;
+  const float grow[3] = { radius, hh + radius, radius };
+  const float dv[3] = { b.x - a.x, b.y - a.y, b.z - a.z };
+  const float lenSq = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];
+  float far = 0.0f, dir[3] = { 0.0f, 0.0f, 0.0f };
+  if (lenSq > 1e-6f) {
+    far = sqrtf(lenSq);
+    const float inv = 1.0f / far;
+    dir[0] = dv[0] * inv; dir[1] = dv[1] * inv; dir[2] = dv[2] * inv;
+  }
+  WaveRay w; w.valid = true; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u;
+  castSegmentWave<true>(w, d, p, o, dir, far, f.x, f.y, grow, radius);
+  SweepHit48 out;
+  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
+  out.position[0] = out.position[1] = out.position[2] = 0.0f;
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;           // SweepHit{} (sc_physics.h:116)
+  out.layer = 0u; out.travel = 0.0f; out.pad = 0u;
+  if (w.hit) {
+    out.hit = 1u; out.id = w.id; out.layer = w.layer; out.travel = w.t;
+    out.distance = far > 0.0f ? w.t / far : 0.0f;                              // the hit FRACTION (m_closestHitFraction, :801)
+    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;   // the capsule's centre
+    if (w.axis < 3u) {                                  // the face entered; a sweep that starts in overlap keeps (0,1,0)
+      const float dn = w.axis == 0u ? dir[0] : (w.axis == 1u ? dir[1] : dir[2]);
+      const float sgn = dn > 0.0f ? -1.0f : 1.0f;
+      out.normal[0] = w.axis == 0u ? sgn : 0.0f; out.normal[1] = w.axis == 1u ? sgn : 0.0f; out.normal[2] = w.axis == 2u ? sgn : 0.0f;
     }
   }
   if (lane == 0) q.hits[r] = out;
@@ -338,6 +405,13 @@ void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryS
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
   hipLaunchKernelGGL(k_ray_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+}
+
+void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s)
+{
+  if (!q.count) return;
+  const uint32_t perBlock = kTile / 64u;
+  hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 } // namespace sctick

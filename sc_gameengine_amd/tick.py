@@ -22,6 +22,11 @@ def _c32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+# what WorldTick.sweep_hits() returns (== ScTickSweepHit)
+SWEEP_HIT_DTYPE = np.dtype([("hit", np.uint32), ("id", np.uint32), ("distance", np.float32), ("position", np.float32, 3),
+                            ("normal", np.float32, 3), ("layer", np.uint32), ("travel", np.float32), ("pad", np.uint32)])
+
+
 # ---- host-side camera math (CameraSystem stays on the host, sc_ecs.cpp:213-272) ----------------
 def host_mat4_trs(pos, rot, scale):
     p, r, s, o = _c32(pos), _c32(rot), _c32(scale), np.zeros(16, np.float32)
@@ -243,6 +248,27 @@ class WorldTick:
         dt = np.dtype([("hit", np.uint32), ("id", np.uint32), ("distance", np.float32), ("position", np.float32, 3),
                        ("normal", np.float32, 3), ("layer", np.uint32), ("pad", np.uint32, 2)])
         return np.frombuffer(buf, dtype=dt, count=n.value).copy()
+
+    # ---- capsule sweeps over this tick's boxes ----
+    def set_sweep_queries(self, start, end, radius, half_height, mask, skip_id=None):
+        """Upright-capsule sweeps from start to end (scTickSetSweepQueries); skip_id: per sweep, a box id that never answers (None: none)."""
+        a, b = _c32(start).reshape(-1, 3), _c32(end).reshape(-1, 3)
+        r, hh = _c32(radius).reshape(-1), _c32(half_height).reshape(-1)
+        mk = np.ascontiguousarray(mask, np.uint32).reshape(-1)
+        sk = None if skip_id is None else np.ascontiguousarray(skip_id, np.uint32).reshape(-1)
+        assert len(b) == len(a) and len(r) == len(a) and len(hh) == len(a) and len(mk) == len(a) and (sk is None or len(sk) == len(a))
+        self._ok(self.lib.scTickSetSweepQueries(self.ctx, len(a), _f(a), _f(b), _f(r), _f(hh), _u(mk), None if sk is None else _u(sk)),
+                 "scTickSetSweepQueries")
+
+    def sweep_hits(self):
+        """Structured array (hit, id, distance = hit fraction, position[3] = the capsule's centre, normal[3], layer, travel = metres, pad)
+        of the last run's sweep batch."""
+        n = C.c_uint32()
+        self._ok(self.lib.scTickReadSweepHits(self.ctx, None, 0, C.byref(n)), "scTickReadSweepHits")
+        buf = (capi.SweepHit * max(n.value, 1))()
+        if n.value:
+            self._ok(self.lib.scTickReadSweepHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadSweepHits")
+        return np.frombuffer(buf, dtype=SWEEP_HIT_DTYPE, count=n.value).copy()
 
     def occupied(self, pos, radius, mask):
         """isOccupiedWorld for a batch of points (sc_traffic_spawner.cpp:93-116); returns a uint8 array."""

@@ -15,7 +15,7 @@ for line in out.splitlines():
     if m and cur: rows[cur][m.group(1).strip()] = int(m.group(2))
 for name, r in rows.items():
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r"\(.*", "", dem)
+    dem = re.sub(r"\(.*", "", dem.replace("(anonymous namespace)::", ""))
     if flt and not any(f in dem for f in flt): continue
-    print(f"{dem:60s} vgpr {r.get('VGPRs', -1):3d} agpr {r.get('AGPRs', 0):3d} sgpr {r.get('SGPRs', -1):3d} spill v{r.get('VGPRs Spill', 0)} s{r.get('SGPRs Spill', 0)} "
-          f"occ {r.get('Occupancy [waves/SIMD]', -1)} lds {r.get('LDS Size [bytes/block]', 0)}")
+    print(f"{dem:60s} vgpr {r.get('VGPRs', -1):3d} agpr {r.get('AGPRs', 0):3d} sgpr {r.get('TotalSGPRs', r.get('SGPRs', -1)):3d} spill v{r.get('VGPRs Spill', 0)} s{r.get('SGPRs Spill', 0)} "
+          f"scratch {r.get('ScratchSize [bytes/lane]', 0)} occ {r.get('Occupancy [waves/SIMD]', -1)} lds {r.get('LDS Size [bytes/block]', 0)}")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the ray batch inside the tick: config-5 world, 1M entities, one front ray per vehicle
-as the traffic AI casts it (sc_traffic_ai.cpp:303-319), tick time with and without SC_TICK_RAYS."""
+as the traffic AI casts it (sc_traffic_ai.cpp:303-319), tick time with and without SC_TICK_RAYS; then, on the same world in the
+same process, 4096 capsule sweeps (radius 0.4 m, half height 0.5 m, 20 m along the same headings) with SC_TICK_SWEEPS."""
 import os, sys, time, json
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,4 +29,17 @@ for name, rays in (("tick_us", 0), ("tick_with_rays_us", len(veh)), ("tick_with_
     out[name] = round((time.perf_counter() - t0) / n * 1e6, 2)
     if rays:
         h = t.ray_hits(); out[name.replace("_us", "_hits")] = int(h["hit"].sum())
+# the sweeps leg: a pedestrian-sized capsule from where the first 4096 front rays start, 20 m ahead
+k = 4096
+t.set_ray_queries(o[:0], fwd[:0], np.zeros(0, np.float32), np.zeros(0, np.uint32))
+t.set_sweep_queries(o[:k], o[:k] + fwd[:k] * np.float32(20.0), np.full(k, 0.4, np.float32), np.full(k, 0.5, np.float32), np.full(k, 1, np.uint32))
+fl = capi.FULL | capi.PRODUCE_NEXT | capi.SWEEPS
+for _ in range(20): t.run(fl)
+t.sync()
+n = 200
+t0 = time.perf_counter()
+for _ in range(n): t.run(fl)
+t.sync()
+out["tick_with_4096_sweeps_us"] = round((time.perf_counter() - t0) / n * 1e6, 2)
+out["tick_with_4096_sweeps_hits"] = int(t.sweep_hits()["hit"].sum())
 print(json.dumps(out))
