@@ -302,6 +302,15 @@ int scTickGatherVisibleCounts(ScTickContext* ctx, uint32_t* counts_out, uint32_t
  * (nor, on a tile, of the declared world vocabulary) admit a pair, so the pair role was launched as a sweep over the bins' counters
  * (a quarter of the workgroups; a launch shape, never a shortcut of the search), [3] learn ticks so far.  Reads the slots back (a few MB): not for the frame loop. */
 int scTickGetBinStats(ScTickContext* ctx, uint32_t stats[4]);
+/* Where the tick ends (diagnostics; no result depends on it).  The fused kernel works in spans of consecutive dense indices, one
+ * workgroup each.  In a world where no parent link crosses a span boundary ("span-closed") the workgroup also ends the tick for its
+ * span -- clears Transform::dirty and, with SC_TICK_PRODUCE_NEXT and producer kind 1, nudges the roots -- instead of the end-of-tick
+ * kernel; a tick with SC_TICK_XFORM but neither SC_TICK_CULL nor a pair half then has no second launch at all.  Worlds with hierarchy
+ * levels beyond the fused kernel's chain, producer kind 2, traffic sensors, and contexts created under SC_TICK_TAIL=0 keep the
+ * end-of-tick kernel's form.  stats[0] 1 = the last scTickRun's fused kernel owned the dirty words, [1] 1 = the world is span-closed for
+ * the current span.  Host-side, no read-back (flushes a pending re-link; the span-closed state is rescanned, O(n), only after the
+ * entity count moved to another span). */
+int scTickGetTailStats(ScTickContext* ctx, uint32_t stats[2]);
 /* stats[3] of the above alone: learn ticks so far.  Host-side, no read-back, no synchronisation (what a timed loop may ask). */
 int scTickGetLearnTicks(ScTickContext* ctx, uint32_t* learn_ticks);
 /* Bounds classes (diagnostics; no result depends on them).  The library keeps a table of the distinct local boxes it was given
@@ -503,6 +512,9 @@ int scTickHostMat4PerspectiveRhZo(float fov_y_radians, float aspect, float z_nea
 /* viewProj = perspective(fovY*pi/180, aspect, near, far, flipY) * inverse(cameraWorld), sc_ecs.cpp:261-270 */
 int scTickHostCameraViewProj(const float camera_world[16], float fov_y_degrees, float aspect,
                              float z_near, float z_far, float out_view_proj[16]);
+/* 1 when no parent link crosses a boundary between runs of `span` consecutive dense indices (parent[i] / span == i / span for every
+ * entity with a parent; negative or out-of-range entries are no links), else 0 -- the rule scTickGetTailStats reports on. */
+int scTickHostSpanClosed(const int32_t* parent, uint32_t count, uint32_t span);
 
 /* ---- sector data (.scsector) and residency: the callers either side of the tick ----
  * Host-side reader of the editor/streamer sector format, tools/shared/world_format.cpp:185-338 (ReadSectorFile;

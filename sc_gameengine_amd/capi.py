@@ -140,6 +140,7 @@ SYMBOLS = {
     "scTickGatherVisibleCounts": (C.c_int, [_CTX, U32P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "scTickGetBinStats": (C.c_int, [_CTX, U32P]),
     "scTickGetLearnTicks": (C.c_int, [_CTX, U32P]),
+    "scTickGetTailStats": (C.c_int, [_CTX, U32P]),
     "scTickGetBoundsClassStats": (C.c_int, [_CTX, U32P]),
     "scTickSetWorldLayers": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int]),
     "scTickResetHostTimes": (C.c_int, [_CTX]),
@@ -201,6 +202,7 @@ SYMBOLS = {
     "scTickHostMat4Inverse": (C.c_int, [F32P, F32P]),
     "scTickHostMat4PerspectiveRhZo": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, F32P]),
     "scTickHostCameraViewProj": (C.c_int, [F32P, C.c_float, C.c_float, C.c_float, C.c_float, F32P]),
+    "scTickHostSpanClosed": (C.c_int, [I32P, C.c_uint32, C.c_uint32]),
 }
 
 _LIB = None

@@ -91,6 +91,13 @@ struct ScTickContext
   int freeze = 0;
 
   uint32_t spansWanted = 1536;
+  // Span-closed: no parent link crosses a span boundary (for every entity with a parent, parent / span == index / span; all ancestors
+  // by induction).  Then the fused kernel's workgroups end the tick for their own spans (kFlagTailOwnsDirty).  Kept for the span it was
+  // derived for (closureSpan; 0 = never derived): by rebuildLinks, by fillParams when another entity count gives another span, and by the
+  // in-place remove path for the entities it relocates or re-parents.  A tick on which nothing changed scans nothing.
+  bool tailEnabled = true;             // SC_TICK_TAIL=0 at creation: the end-of-tick kernel keeps the dirty clear and the producer (A/B switch)
+  bool spanClosed = false; uint32_t closureSpan = 0;
+  bool lastTickTail = false;           // the last tick's fused kernel owned the dirty words (scTickGetTailStats)
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
   uint32_t lastFlags = 0;
 
@@ -392,6 +399,15 @@ void computeSpan(const ScTickContext* c, uint32_t& span, uint32_t& grid)
   grid = (n + span - 1) / span;
 }
 
+// the span-closed state from the parent mirror, for the span the current entity count gives (O(n): only where links or the span changed)
+void deriveSpanClosed(ScTickContext* c)
+{
+  uint32_t span, grid;
+  computeSpan(c, span, grid);
+  c->closureSpan = span;
+  c->spanClosed = scTickHostSpanClosed(c->hParent.data(), c->n, span) != 0;
+}
+
 // Transform::parent validation (sc_ecs.cpp:151-160) + depth / cycle classification.
 // Returns the dense indices that were detached (they are marked dirty by the caller).
 void rebuildLinks(ScTickContext* c, std::vector<uint32_t>& link, std::vector<uint32_t>& unreachBits,
@@ -467,6 +483,7 @@ void rebuildLinks(ScTickContext* c, std::vector<uint32_t>& link, std::vector<uin
     link[i] = p | ((c->hFlags[i] & 1u) ? kHasMesh : 0u) | ((c->hFlags[i] & 2u) ? kHasBounds : 0u) | (dfield << kDepthShift) |
               ((c->hFlags[i] & 4u) ? kRotTrivialX : 0u) | ((c->hFlags[i] & 8u) ? kRotTrivialY : 0u) | ((c->hFlags[i] & 16u) ? kRotTrivialZ : 0u);
   }
+  deriveSpanClosed(c);
 }
 
 int flushLinks(ScTickContext* c)
@@ -550,6 +567,13 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   computeSpan(c, p.span, grid);
   p.flags = flags & 0xFFFFu;        // SC_TICK_DENSE_AABBS == kFlagDenseAabbs
   if (c->levelOffsets.size() > 1 && (flags & SC_TICK_XFORM)) p.flags |= kFlagHasDeep;
+  // The fused kernel's workgroups end the tick for their own spans (spanTail) when the world is span-closed, no level kernel reads `dirty`
+  // behind the fused kernel, and the tick's producer is none or the root nudge.  The movers' producer stays in the end-of-tick kernel
+  // (the agents' front rays are cast between the two kernels against this frame's positions), and so does the nudge while traffic
+  // sensors are on, for the same reason.  Part of a captured graph's key, like every flag.
+  if (p.span != c->closureSpan) deriveSpanClosed(c);       // (appends / removes moved the entity count to another span; hParent is current: flushLinks ran)
+  const bool producerOk = !(flags & SC_TICK_PRODUCE_NEXT) || (c->producerKind == 1u && !c->sensors);
+  if (c->tailEnabled && (flags & SC_TICK_XFORM) && !(p.flags & kFlagHasDeep) && c->spanClosed && producerOk) p.flags |= kFlagTailOwnsDirty;
   p.freeze = c->freeze ? 1u : 0u;
   p.frustumValid = c->frustumValid ? 1u : 0u;
   // the bin grid is the tile plus a ring of one sector: boxes that poke over the tile edge stay
@@ -674,7 +698,8 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
     else launchAgentFrontRays(ds, p, c->stream);
   }
   if ((flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_DENSE_AABBS)) launchDenseAabbs(ds, c->n, c->stream);   // read-back aid, off the hot path
-  const bool needCompact = (flags & (SC_TICK_XFORM | SC_TICK_CULL)) != 0;
+  // (kFlagTailOwnsDirty: the transform half left nothing for the end-of-tick kernel -- without culling there is no compaction role to launch)
+  const bool needCompact = (flags & SC_TICK_CULL) != 0 || ((flags & SC_TICK_XFORM) && !(flags & kFlagTailOwnsDirty));
   const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, c->stream);      // the bins are full, not yet consumed
   if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, c->stream);
@@ -823,6 +848,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (c->desc.sector_size <= 0.001f) c->desc.sector_size = 64.0f;     // WorldPartition::configure, sc_world_partition.cpp:222-223
   c->cap = ((desc->capacity + kTile - 1) / kTile) * kTile;
   if (const char* s = std::getenv("SC_TICK_SPANS")) { const int v = std::atoi(s); if (v > 0) c->spansWanted = (uint32_t)v; }
+  if (const char* s = std::getenv("SC_TICK_TAIL")) c->tailEnabled = std::atoi(s) != 0;      // A/B switch: 0 keeps the dirty clear and the root nudge in the end-of-tick kernel
 
   bool ok = bind(c);
   if (ok) {
@@ -1338,6 +1364,14 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
     }
     // 3. apply (writes that meet on one field carry the same value)
     for (const Set& w : sets) (*w.arr)[w.at] = w.value;
+    // span-closed state: only the relocated entities and the children re-parented to them have new links (a removed link can only
+    // have been a crossing one in a world that was not closed: that stays "not closed" until the next re-link)
+    if (c->spanClosed) {
+      const uint32_t sp = c->closureSpan;
+      auto crosses = [&](uint32_t i) { return par[i] >= 0 && (uint32_t)par[i] / sp != i / sp; };
+      for (uint32_t k = 0; k < moves && c->spanClosed; ++k) if (crosses(dst[k])) c->spanClosed = false;
+      for (size_t k = 0; k < patch.size() && c->spanClosed; k += 2) if (crosses(patch[k])) c->spanClosed = false;
+    }
     if (!patch.empty()) {
       const uint32_t pairs = (uint32_t)(patch.size() / 2);
       if (!needScratch(c, patch.size())) return 0;
@@ -1572,6 +1606,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   // messages (header-only) and take part in the exchange, the merge and the pair search of the boxes its neighbours send.
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
+    c->lastTickTail = false;
     HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
     return 1;
   }
@@ -1587,6 +1622,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   TickParams p; uint32_t grid;
   fillParams(c, flags, p, grid);
   c->lastFlags = flags;
+  c->lastTickTail = (p.flags & kFlagTailOwnsDirty) != 0;
   c->lastTickLearn = false;
   if ((flags & SC_TICK_XFORM) && !(flags & SC_TICK_BROADPHASE)) c->boxesTouched = true;      // matrices change, the bins do not follow
   if ((flags & SC_TICK_BROADPHASE) && c->homeEnabled) {
@@ -2642,6 +2678,18 @@ int scTickGetBoundsClassStats(ScTickContext* c, uint32_t stats[4])
     if ((w & kClassMask) < kPaletteCap) stats[1]++; else stats[2]++;
   }
   for (uint32_t i = 0; i < c->n; ++i) if ((c->hFlags[i] & 2u) && c->hClass[i] == kClassNone) stats[3]++;
+  return 1;
+}
+
+int scTickGetTailStats(ScTickContext* c, uint32_t stats[2])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  if (!bind(c) || !flushLinks(c)) return 0;
+  uint32_t span, grid;
+  computeSpan(c, span, grid);
+  if (span != c->closureSpan) deriveSpanClosed(c);
+  stats[0] = c->lastTickTail ? 1u : 0u;
+  stats[1] = c->spanClosed ? 1u : 0u;
   return 1;
 }
 

@@ -160,4 +160,17 @@ int scTickHostCameraViewProj(const float camWorld[16], float fovYDeg, float aspe
   return 1;
 }
 
+// The span-closed rule (scTickGetTailStats): no parent link crosses a boundary between runs of `span` consecutive dense indices.
+// Entries that name no entity of the world (negative: no parent; >= count) are not links.
+int scTickHostSpanClosed(const int32_t* parent, uint32_t count, uint32_t span)
+{
+  if ((!parent && count) || !span) return 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const int32_t q = parent[i];
+    if (q < 0 || (uint32_t)q >= count) continue;
+    if ((uint32_t)q / span != i / span) return 0;
+  }
+  return 1;
+}
+
 } // extern "C"

@@ -281,6 +281,8 @@ constexpr uint32_t kFlagHasDeep = 1u << 16;   // write recomp bits for the level
 constexpr uint32_t kFlagDeferredReset = 1u << 17;   // pipelined tiles: a pair kernel never clears the other parity's counters / big bits; a small kernel
                                                     // behind it on the pairs stream snapshots the results and clears its OWN parity
 constexpr uint32_t kFlagDenseAabbs = 1u << 5; // == SC_TICK_DENSE_AABBS
+constexpr uint32_t kFlagTailOwnsDirty = 1u << 18;   // span-closed world: every workgroup of the fused kernel ends the tick for its own span (dirty clear, and the
+                                                    // root nudge with SC_TICK_PRODUCE_NEXT: spanTail); the end-of-tick kernel then touches neither
 
 // ---- renderer draw order (sc_tick_drawsort.hip) ----
 constexpr uint32_t kSortThreads = 1024, kSortGroup = 8192;     // keys one workgroup orders per pass

@@ -575,8 +575,64 @@ __device__ __forceinline__ void binEntitySingle(const DeviceState& d, const Tick
 // host after scTickSetTopology.  Specialising on it removes dead levels from worlds that are flat or shallow.
 // (Requesting all levels' locals before multiplying -- one round trip instead of one per level -- was measured:
 // it needs 12 more VGPRs per level, 104-116 in all, and lost 5-25 %)
-template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl>
+template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl, bool kTail = false>
 __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickParams& p);
+
+// kFlagTailOwnsDirty: the end of the tick for ONE span, by the workgroup that just walked it -- the dirty clear (sc_ecs.cpp:201; entities in
+// a cycle keep their bit) and, with SC_TICK_PRODUCE_NEXT, the next frame's root nudge -- instead of in the end-of-tick kernel, where both cost
+// a pass of their own over px and the dirty words.  The host sets the flag only for a span-closed world (no parent link crosses a span
+// boundary): then nobody outside this workgroup reads the span's px or dirty words during the kernel, and behind one barrier nobody inside does.
+// Nothing in the kernel writes either before its tail, so everything is requested in front of the barrier (clamped indices, uniform
+// conditions, as compactBody does) and stored behind it.  The final dirty word is what the end-of-tick kernel writes: (dirty & unreach) | moved,
+// and `moved` is the root-mask word itself (its bits past n are zero: k_root_mask).
+// `tid`: the thread's index in the workgroup, rebuilt by the caller from a scalar wave index and the lane count -- threadIdx.x itself, kept in a
+// VGPR across the tile loop for this tail alone, cost most instances a register and some a wave per SIMD (profiles/r09).
+__device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams& p, uint32_t begin, uint32_t end, uint32_t tid)
+{
+  if (begin >= end) return;                            // (uniform: the one workgroup of an empty world)
+  const bool produce = (p.flags & SC_TICK_PRODUCE_NEXT) != 0;      // (the root nudge: the host leaves the movers' producer where it was)
+  const uint32_t wBegin = begin >> 5, wEnd = (end + 31u) >> 5;      // a span is a multiple of kTile: no dirty word straddles two spans
+  const uint32_t w = wBegin + tid;
+  const uint32_t wAt = w < wEnd ? w : wEnd - 1u;
+  const uint32_t dw = d.dirty[wAt], uw = d.unreach[wAt];
+  uint32_t rw = 0u;
+  if (produce) rw = d.rootMask[wAt];
+  constexpr uint32_t kBatch = 3;                       // (the usual span of three tiles: all of it in one round trip)
+  uint32_t rm[kBatch]; float x[kBatch];
+  if (produce) {
+#pragma unroll
+    for (uint32_t u = 0; u < kBatch; ++u) {
+      const uint32_t i = begin + u * kTile + tid;
+      const uint32_t at = i < end ? i : end - 1u;
+      rm[u] = d.rootMask[at >> 5];
+      x[u] = d.px[at];
+    }
+  }
+  __syncthreads();                                     // every wave of the workgroup is through its tiles (the trip count is uniform)
+  if (produce) {
+#pragma unroll
+    for (uint32_t u = 0; u < kBatch; ++u) {
+      const uint32_t i = begin + u * kTile + tid;
+      if (i < end && ((rm[u] >> (i & 31u)) & 1u)) d.px[i] = x[u] + p.producerParam;
+    }
+    for (uint32_t base = begin + kBatch * kTile; base < end; base += kBatch * kTile) {      // wider spans
+#pragma unroll
+      for (uint32_t u = 0; u < kBatch; ++u) {
+        const uint32_t i = base + u * kTile + tid;
+        const uint32_t at = i < end ? i : end - 1u;
+        rm[u] = d.rootMask[at >> 5];
+        x[u] = d.px[at];
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kBatch; ++u) {
+        const uint32_t i = base + u * kTile + tid;
+        if (i < end && ((rm[u] >> (i & 31u)) & 1u)) d.px[i] = x[u] + p.producerParam;
+      }
+    }
+  }
+  if (w < wEnd) d.dirty[w] = (dw & uw) | rw;
+  for (uint32_t v = w + kTile; v < wEnd; v += kTile) d.dirty[v] = (d.dirty[v] & d.unreach[v]) | (produce ? d.rootMask[v] : 0u);   // spans wider than 8192 entities
+}
 
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
 __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome, false>(d, p); }
@@ -584,8 +640,14 @@ __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceS
 // kernels of their own name, so that a context that never made the call runs exactly the instances above.
 template <bool kCull, uint32_t kChain, uint32_t kHome>
 __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders(const DeviceState d, const TickParams p) { xformCullBody<kCull, true, kChain, kHome, true>(d, p); }
+// The tail instances (kFlagTailOwnsDirty, spanTail), again under names of their own: behind a run-time flag in the instances above the tail
+// cost most of them a VGPR (profiles/r09), and a context that is never eligible launches exactly what it launched before.
+template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_tail(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome, false, true>(d, p); }
+template <bool kCull, uint32_t kChain, uint32_t kHome>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders_tail(const DeviceState d, const TickParams p) { xformCullBody<kCull, true, kChain, kHome, true, true>(d, p); }
 
-template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl>
+template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome, bool kColl, bool kTail>
 __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickParams& p)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -595,6 +657,8 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
   const bool doXform = (p.flags & SC_TICK_XFORM) != 0;
   const bool wantCand = (p.flags & SC_TICK_CULLED_LIST) != 0;
   const bool hasDeep = (p.flags & kFlagHasDeep) != 0;
+  uint32_t tailWave = 0;
+  if (kTail && !kCull) tailWave = __builtin_amdgcn_readfirstlane(wave);      // (scalar: see spanTail; with culling, wave and lane live to the end anyway)
 
   uint32_t visCount = 0, candCount = 0;      // wave-uniform running sums
   // lazy records (binWrittenEveryTick): off while big boxes are about -- they are tested against every bin; the tick's pair
@@ -716,6 +780,7 @@ __device__ __forceinline__ void xformCullBody(const DeviceState& d, const TickPa
       d.blockCand[blockIdx.x] = sCand[0] + sCand[1] + sCand[2] + sCand[3];
     }
   }
+  if (kTail) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 }
 
 // (Round 3 built a second form of this kernel in which a workgroup's tile shares the walk through LDS -- link words, dirty
@@ -1030,11 +1095,14 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
   // these requests (dirty words, visibility words, each trip of the predecessors' counts) one dependent round trip each.
   const uint32_t wBegin = begin >> 5, wEnd = (end + 31u) >> 5;
   const uint32_t dirtyWord = wBegin + threadIdx.x;
-  const bool clearDirty = (p.flags & SC_TICK_XFORM) && dirtyWord < wEnd;
+  // kFlagTailOwnsDirty: the fused kernel's workgroups cleared their spans' dirty words and ran the frame producer themselves (spanTail):
+  // no dirty / unreach loads, no producer, no `moved` ballots and no dirty store here
+  const bool tailOwns = (p.flags & kFlagTailOwnsDirty) != 0;
+  const bool clearDirty = (p.flags & SC_TICK_XFORM) && !tailOwns && dirtyWord < wEnd;
   const bool some = begin < end;                       // (uniform; false only for the one workgroup of an empty world)
   const uint32_t dirtyAt = dirtyWord < wEnd ? dirtyWord : wEnd - 1u;
   uint32_t rawDirty = 0u, rawUnreach = 0u;
-  if (some) { rawDirty = d.dirty[dirtyAt]; rawUnreach = d.unreach[dirtyAt]; }
+  if (some && !tailOwns) { rawDirty = d.dirty[dirtyAt]; rawUnreach = d.unreach[dirtyAt]; }
 
   const uint32_t vBegin = begin >> 6, vEnd = (end + 63u) >> 6, vWords = vEnd - vBegin;
   const bool fast = doCull && vWords <= kCompactWordsMax;
@@ -1074,7 +1142,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
   // SC_TICK_PRODUCE_NEXT: this tick is over for the span, so the NEXT frame's producer runs here instead of as a
   // launch of its own (nothing else in this kernel reads positions); the "moved" ballots wait in LDS and are OR-ed into
   // the cleared dirty words below.
-  const bool produce = !(SC_DIAG_EOT & 1) && (p.flags & SC_TICK_PRODUCE_NEXT) != 0;
+  const bool produce = !(SC_DIAG_EOT & 1) && (p.flags & SC_TICK_PRODUCE_NEXT) != 0 && !tailOwns;
   const bool produceEarly = produce && (wEnd - wBegin) <= kMaxSpanWords;
   if (produceEarly) {
     if (p.producerKind == 1u) {
@@ -1203,7 +1271,7 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
 
   // Transform::dirty = false for every visited entity; entities in a cycle keep theirs (sc_ecs.cpp:201)
   if (clearDirty) d.dirty[dirtyWord] = (rawDirty & rawUnreach) | (produceEarly ? moved[dirtyWord - wBegin] : 0u);
-  if (p.flags & SC_TICK_XFORM) {
+  if ((p.flags & SC_TICK_XFORM) && !tailOwns) {
     for (uint32_t w = wBegin + kTile + threadIdx.x; w < wEnd; w += kTile) d.dirty[w] &= d.unreach[w];   // spans wider than 8192 entities
   }
   // spans too wide for the LDS ballots: the producer runs behind the dirty clear, one more pass over the span
@@ -2906,14 +2974,16 @@ void launchStageFrame(const DeviceState& d, uint32_t* block, uint32_t maxVisible
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
 static void launchHome(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
-  if (evA) hipExtLaunchKernelGGL((k_xform_cull<kCull, kAabb, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
-  else hipLaunchKernelGGL((k_xform_cull<kCull, kAabb, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, d, p);
+  auto kernel = (p.flags & kFlagTailOwnsDirty) ? k_xform_cull_tail<kCull, kAabb, kChain, kHome> : k_xform_cull<kCull, kAabb, kChain, kHome>;
+  if (evA) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
+  else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, d, p);
 }
 template <bool kCull, uint32_t kChain, uint32_t kHome>
 static void launchHomeColliders(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
-  if (evA) hipExtLaunchKernelGGL((k_xform_cull_colliders<kCull, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
-  else hipLaunchKernelGGL((k_xform_cull_colliders<kCull, kChain, kHome>), dim3(grid), dim3(kTile), 0, s, d, p);
+  auto kernel = (p.flags & kFlagTailOwnsDirty) ? k_xform_cull_colliders_tail<kCull, kChain, kHome> : k_xform_cull_colliders<kCull, kChain, kHome>;
+  if (evA) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
+  else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, d, p);
 }
 template <bool kCull, bool kAabb, uint32_t kChain>
 static void launchOne(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)

@@ -490,6 +490,13 @@ class WorldTick:
         return {"remembered_slots": int(st[0]), "written_every_tick": int(st[1]), "lazy_last_tick": bool(st[2] & 1),
                 "unchanged_records_stay": bool(st[2] & 2), "pair_role_sweep_only": bool(st[2] & 4), "learn_ticks": int(st[3])}
 
+    def tail_stats(self):
+        """where the last tick ended: whether its fused kernel owned the dirty words (dirty clear and root nudge per span), and whether the
+        world is span-closed -- no parent link crosses a span boundary (host-side: no read-back)"""
+        st = np.zeros(2, np.uint32)
+        self._ok(self.lib.scTickGetTailStats(self.ctx, _u(st)), "scTickGetTailStats")
+        return {"tail_owned_dirty": bool(st[0]), "span_closed": bool(st[1])}
+
     def learn_ticks(self):
         """learn ticks so far (host-side counter: no read-back)"""
         st = np.zeros(1, np.uint32)
