@@ -22,32 +22,7 @@ def sorted_pairs(p):
     return p[np.argsort(k)]
 
 
-class Colliders:
-    """Host model of the per-entity collider state: what was uploaded, hence what the witness and colliders() must show."""
-
-    def __init__(self, n):
-        self.type = np.zeros(n, np.uint8)
-        self.he = np.full((n, 3), 0.5, F)
-        self.radius = np.full(n, 0.5, F)
-        self.hh = np.full(n, 0.5, F)
-
-    @classmethod
-    def random(cls, n, rng, p=(0.2, 0.15, 0.25, 0.2, 0.2)):
-        c = cls(n)
-        c.type[:] = rng.choice(5, n, p=p).astype(np.uint8)
-        c.he[:] = rng.uniform(0.05, 2.5, (n, 3)).astype(F)
-        c.radius[:] = rng.uniform(0.05, 2.0, n).astype(F)
-        c.hh[:] = rng.uniform(-0.5, 2.5, n).astype(F)          # some negative: stored as 0
-        return c
-
-    def upload(self, t, first=0, count=None):
-        sl = slice(first, len(self.type) if count is None else first + count)
-        t.upload_colliders(first, self.type[sl], self.he[sl], self.radius[sl], self.hh[sl])
-        self.hh[sl] = np.maximum(self.hh[sl], F(0.0))
-
-    def witness(self, ow, n):
-        bmn, bmx = ow.world_aabbs()
-        return cr.boxes(ow.world_matrices()[:n], self.type[:n], self.he[:n], self.radius[:n], self.hh[:n], bmn[:n], bmx[:n])
+Colliders = cr.Colliders          # the host model of the per-entity collider state (shared with tests/test_gpu_tail_matrix.py)
 
 
 def check_tick(oracle, t, ow, w, col, brute=True, cell=64.0):

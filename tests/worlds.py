@@ -54,6 +54,84 @@ def chain_world(length, branches=3, seed=1):
     return w
 
 
+TILE = 256                                                # entities per tile of the fused kernel (kTile)
+
+
+def compute_span(n, spans):
+    """The library's computeSpan restated: entities per span of the fused kernel for n entities under SC_TICK_SPANS=spans."""
+    tiles = -(-max(n, 1) // TILE)
+    g = min(max(spans, 1), tiles)
+    return -(-tiles // g) * TILE
+
+
+def span_closed_world(n, span, depth, seed, far_links=True):
+    """A forest in which no parent link crosses a multiple of `span` (a multiple of 256), levels 0..depth present in every span that is
+    long enough, the last span ragged.  Levels run root, child, ..., level `depth`, root, root, ... along the dense order and restart at
+    every span; a non-root's parent is the index before, or -- far_links, about half of them -- any entity of the level above in the same
+    span: before or behind the child, in its own 256-tile or in another.  The last entity of every 256-tile is a root and the first one a
+    root without children, so one more link from a tile's first entity to the entity before it deepens nothing past level 1.
+    Children get a small local offset (a family's boxes overlap); Bounds and meshes are missing here and there as in random_world."""
+    assert span % TILE == 0 and 0 <= depth <= 3 and n % 32 != 0
+    w = random_world(n, seed=seed, p_child=0.0, spread=max(40.0, 1.8 * n ** 0.5))          # (sparser in the plane as n grows: the oracle's grid search stays quick)
+    rng = np.random.default_rng([seed, 0x5CA1])
+    i = np.arange(n)
+    j = i % span                                           # index inside the span
+    forced = np.isin(i % TILE, (0, 1, TILE - 1)) | (j % (depth + 2) == depth + 1)
+    level = np.zeros(n, np.int32)
+    for k in range(1, n):
+        if j[k] and not forced[k] and level[k - 1] < depth:
+            level[k] = level[k - 1] + 1
+    w.parent[:] = np.where(level > 0, i - 1, -1)
+    if far_links:
+        far = (level > 0) & (rng.random(n) < 0.5)
+        for b in range(0, n, span):
+            e = min(b + span, n)
+            for lv in range(1, depth + 1):
+                kids = b + np.flatnonzero(far[b:e] & (level[b:e] == lv))
+                cand = b + np.flatnonzero((level[b:e] == lv - 1) & (i[b:e] % TILE != 0))
+                if len(kids) and len(cand):
+                    w.parent[kids] = rng.choice(cand, len(kids))
+    w.pos[level > 0] = np.float32([0.3, 0.1, -0.2])
+    return w
+
+
+def depths(parent):
+    """Level of every entity of a forest (0 = root); -1 for members of a parent cycle and whatever hangs below one."""
+    parent = np.asarray(parent)
+    n = len(parent)
+    d = np.where(parent < 0, 0, -1).astype(np.int32)
+    for _ in range(n):
+        todo = (d < 0) & (parent >= 0)
+        known = todo & (d[np.where(todo, parent, 0)] >= 0)
+        if not known.any():
+            break
+        d[known] = d[parent[known]] + 1
+    return d
+
+
+def add_cycle(w, at):
+    """at <-> at + 1 become a parent cycle and at + 2 hangs below it; what hung below the three before becomes a root."""
+    trio = np.arange(at, at + 3)
+    w.parent[np.isin(w.parent, trio)] = -1
+    w.parent[at], w.parent[at + 1], w.parent[at + 2] = at + 1, at, at + 1
+    return trio
+
+
+# (tiles per span, n, SC_TICK_SPANS, depth, seed) of tests/test_gpu_tail_matrix.py, shared with its CPU twin tests/test_tail_worlds_cpu.py.
+# n is two full spans and a ragged third that ends inside a tile and inside a dirty word.  computeSpan evens the spans out, so the third
+# cannot be shorter than (tiles - 3) * 256 + 1 entities: about 0.4 spans up to four tiles per span, and the shortest possible beyond.
+TAIL_LADDER = [(1, 614, 3, 2, 11), (3, 1843, 3, 2, 12), (4, 2458, 3, 2, 13), (17, 12389, 3, 2, 14), (33, 24677, 3, 2, 15), (65, 49253, 3, 2, 16)]
+TAIL_MATRIX_N, TAIL_MATRIX_SPANS, TAIL_MATRIX_TILES = 1900, 3, 3          # 768 + 768 + 364
+TAIL_MATRIX_DEPTHS = (0, 1, 2, 3)
+
+
+def tail_cases():
+    """every (n, span, depth, seed) the tail matrix runs"""
+    out = [(n, tiles * TILE, depth, seed) for tiles, n, spans, depth, seed in TAIL_LADDER]
+    out += [(TAIL_MATRIX_N, TAIL_MATRIX_TILES * TILE, depth, 20 + depth) for depth in TAIL_MATRIX_DEPTHS]
+    return out
+
+
 def oracle_world(oracle, w, camera=True):
     """Load a SynthWorld into the oracle's ECS; optionally append the camera entity (index n)."""
     ow = oracle.OracleWorld.from_arrays(w.pos, w.rot, w.scale, w.parent, w.bmin, w.bmax,
