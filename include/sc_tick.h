@@ -59,6 +59,7 @@ enum {
                                       the end-of-tick kernel, as the producer of the NEXT frame -- instead of at the start of the next
                                       scTickRun.  Results of this run are unaffected; positions read back are already the next frame's. */
   SC_TICK_SWEEPS      = 1u << 10,  /* with BROADPHASE: answer the capsule sweeps set by scTickSetSweepQueries against this tick's boxes */
+  SC_TICK_ANCHORED_RAYS = 1u << 11, /* with BROADPHASE: answer the entity-anchored rays set by scTickSetAnchoredRays against this tick's boxes */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -641,6 +642,50 @@ int scTickSetSweepQueries(ScTickContext* ctx, uint32_t count, const float* start
                           const float* half_height, const uint32_t* mask, const uint32_t* skip_id);
 /* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_SWEEPS) (after scTickRunPairs on a tiled world) */
 int scTickReadSweepHits(ScTickContext* ctx, ScTickSweepHit* hits, uint32_t capacity, uint32_t* count);
+
+/* ---- entity-anchored rays over the broadphase bins ----
+ * Rays that follow an entity on the device.  scTickSetRayQueries takes world-space rays and replacing them costs a learn tick and a
+ * fresh graph capture; the callers the ray section cites do not have world-space rays: the vehicle camera's occlusion ray starts behind
+ * the vehicle along a direction fixed in its frame (sc_vehicle.cpp:570-611), the raycast vehicle's wheel probes are chassis-local by
+ * definition (VehicleWheelConfig::connectionPoint / direction, sc_physics.h:63-72; their answers are what getVehicleTelemetry reports,
+ * sc_physics.cpp:1034-1055), the traffic debug sensor ray rides on a moving agent (sc_traffic_ai.cpp:622-652) -- and in resident mode
+ * the entity's pose of this frame exists only on the device.  An anchored ray is given once, in its anchor's LOCAL frame; every tick the
+ * kernel that casts it resolves it against that tick's world matrix of the anchor and answers it against that tick's boxes.  The frame
+ * loop makes no host round trip, runs no learn tick and re-captures no graph.
+ * This build's OWN SPEC, like the rays and the sweeps.  All arithmetic is fp32, unfused, left to right.  For ray k with anchor a, local
+ * origin l, local direction v, and R_r = (w_r.x, w_r.y, w_r.z, w_r.w) row r (0..2) of a's world matrix as this run's transform stage
+ * leaves it (without SC_TICK_XFORM: as it stands on the device):
+ *   o_r = ((R_r.x*l.x + R_r.y*l.y) + R_r.z*l.z) + R_r.w
+ *   d_r =  (R_r.x*v.x + R_r.y*v.y) + R_r.z*v.z
+ * The ray (o, d, max_dist, mask) is then answered exactly as a ray of scTickSetRayQueries: same normalisation (|d|^2 <= 1e-6 is a miss),
+ * same filter, same slab arithmetic, same tie rule, same ScTickRayHit with the pad words 0.
+ *   max_dist    world metres along the NORMALISED direction; the anchor's scale does not scale it
+ *   skip_self   != 0 (NULL: every ray): the box with id (rank << 24 | a), the anchor's own, never answers
+ *   anchor      SC_TICK_ANCHOR_NONE: no anchor, l and v are world space and go through untouched -- the answer equals the plain ray
+ *               query's bit for bit
+ *   a miss      (RaycastHit{}: id 0xFFFFFFFF, normal (0,1,0), zeros) when the anchor is >= the entity count at run time (a dead anchor
+ *               always is), when a resolved origin is not finite, or when the resolved direction's squared length
+ *               (d.x*d.x + d.y*d.y) + d.z*d.z is not finite
+ * On a tiled world the rays' rule holds: the cast runs behind the border merge and a context answers for the boxes registered in its own
+ * sectors (the neighbours' boxes that reach into them included).  In a split flow the tick half resolves the rays into a snapshot of
+ * its tick parity and the pair half casts from it -- a pipelined tile's matrices may be the next tick's by then; the arithmetic is the
+ * same, so are the bits.  A pipelined tile sees what its rays see.
+ * Residency: scTickRemoveEntities renames the anchors of relocated entities (moved_from -> moved_to) and turns the anchors of removed
+ * entities into SC_TICK_ANCHOR_DEAD, which always misses; O(rays) per call, no learn tick of its own.  scTickAppendEntities and
+ * scTickSetEntityCount leave the anchors alone: an anchor beyond a shrunken count simply misses. */
+#define SC_TICK_ANCHOR_NONE 0xFFFFFFFFu   /* anchor[k]: the ray is world space */
+#define SC_TICK_ANCHOR_DEAD 0xFFFFFFFEu   /* what scTickReadAnchoredRays reports for a ray whose anchor was removed */
+/* anchor, max_dist, mask: [count]; local_origin3 / local_dir3: [count][3]; skip_self: [count] or NULL (all 1).  The set stays until it is
+ * replaced (count 0 clears it).  A call with THE SAME COUNT as the current set only rewrites the device arrays, behind whatever is queued:
+ * no learn tick, and a captured graph stays valid; another count behaves like scTickSetRayQueries.  Fails -- and leaves the previous set
+ * in place -- when a local origin, local direction or max_dist is not finite, a max_dist is negative, a required array is NULL, or
+ * scTickRunPairs is pending. */
+int scTickSetAnchoredRays(ScTickContext* ctx, uint32_t count, const uint32_t* anchor, const float* local_origin3,
+                          const float* local_dir3, const float* max_dist, const uint32_t* mask, const uint8_t* skip_self);
+/* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_ANCHORED_RAYS) (after scTickRunPairs on a tiled world) */
+int scTickReadAnchoredRayHits(ScTickContext* ctx, ScTickRayHit* hits, uint32_t capacity, uint32_t* count);
+/* the anchors of rays first .. first + count - 1 as they stand now (after removals); host-side, no read-back */
+int scTickReadAnchoredRays(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("SC_TICK_LIB") or os.path.join(HERE, "libsc_tick.so") 
 # scTickRun flags (include/sc_tick.h)
 XFORM, CULL, BROADPHASE, CULLED_LIST, DRAWS, DENSE_AABBS, SPLIT_PAIRS, SORT_DRAWS, RAYS, PRODUCE_NEXT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 SWEEPS = 1 << 10
+ANCHORED_RAYS = 1 << 11
+ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 NO_PARENT = -1
@@ -185,6 +187,9 @@ SYMBOLS = {
     "scTickReadRayHits": (C.c_int, [_CTX, C.POINTER(RayHit), C.c_uint32, U32P]),
     "scTickSetSweepQueries": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, F32P, F32P, U32P, U32P]),
     "scTickReadSweepHits": (C.c_int, [_CTX, C.POINTER(SweepHit), C.c_uint32, U32P]),
+    "scTickSetAnchoredRays": (C.c_int, [_CTX, C.c_uint32, U32P, F32P, F32P, F32P, U32P, U8P]),
+    "scTickReadAnchoredRayHits": (C.c_int, [_CTX, C.POINTER(RayHit), C.c_uint32, U32P]),
+    "scTickReadAnchoredRays": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

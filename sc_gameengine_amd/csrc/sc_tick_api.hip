@@ -109,6 +109,12 @@ struct ScTickContext
   uint32_t rayCap = 0;
   SweepQueryState sweeps{};            // scTickSetSweepQueries: the same for the capsule sweeps
   uint32_t sweepCap = 0;
+  // scTickSetAnchoredRays: the same for the entity-anchored rays, plus one snapshot of the resolved rays per tick parity (split flows:
+  // parity q's lies q * anchoredCap entries into each snapshot array) and the host mirror of (anchor, skip_self) that
+  // scTickRemoveEntities keeps current
+  AnchoredRayState anchored{};
+  uint32_t anchoredCap = 0;
+  std::vector<uint2> hAnchor;
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
 
@@ -602,6 +608,14 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   p.colliders = c->d.colType ? 1u : 0u;         // (part of a captured graph's key: the instance choice follows it)
 }
 
+// the anchored rays as a tick of parity q sees them: its own copy of the snapshot
+AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
+{
+  AnchoredRayState a = c->anchored;
+  if (a.snapOrigin) { const size_t off = (size_t)q * c->anchoredCap; a.snapOrigin += off; a.snapDir += off; a.snapSkip += off; }
+  return a;
+}
+
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
 // the tick before it clears those counters.  That half finished long ago unless the exchange is very slow; wait for it.
 // (Cross-stream: never captured.)
@@ -703,6 +717,13 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, c->stream);      // the bins are full, not yet consumed
   if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, c->stream);
+  // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
+  // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
+  // already be the next tick's
+  if (flags & SC_TICK_ANCHORED_RAYS) {
+    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), c->stream);
+    else if (flags & SC_TICK_BROADPHASE) launchAnchoredRaySnapshot(ds, p, anchoredFor(c, p.parity), c->stream);
+  }
   // Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
   // entity's place in the list, i.e. its draw item (emitVisible).  With the frame read-back on (and a budget that fits the block)
   // the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
@@ -1393,6 +1414,19 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   }
   c->n = n1;
   c->topoEpoch++;
+  // anchored rays follow their entity: a relocated anchor is renamed, a removed one becomes dead (it misses from now on); the words
+  // go to the device behind whatever is queued, and the set keeps its size -- no epoch bump of its own
+  if (c->anchored.count) {
+    bool changed = false;
+    for (uint32_t k = 0; k < c->anchored.count; ++k) {
+      uint32_t& a = c->hAnchor[k].x;
+      if (a >= n0) continue;                            // no anchor, dead, or beyond the count: nothing to follow
+      if (removed.count(a)) { a = kAnchorDead; changed = true; continue; }
+      const auto m = newIndexOf.find(a);
+      if (m != newIndexOf.end()) { a = m->second; changed = true; }
+    }
+    if (changed && !h2d(c, const_cast<uint2*>(c->anchored.anchor), c->hAnchor.data(), (size_t)c->anchored.count * sizeof(uint2))) return 0;
+  }
   {
     // bounds classes: the wave-tiles that took a relocated entity, and those of the shrunk tail
     std::vector<uint32_t> tiles;
@@ -1564,6 +1598,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   launchBorderMerge(ds, pp, ps);
   if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, ps);   // sees the neighbours' border boxes too
   if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, ps);   // ... as do the capsule sweeps
+  if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), ps);   // ... and the anchored rays, as the tick half resolved them
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   return launchPairs(ds, pp, ps, done);
 }
@@ -1618,6 +1653,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");
   if ((flags & SC_TICK_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_SWEEPS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_SWEEPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
+  if ((flags & SC_TICK_ANCHORED_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_ANCHORED_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_SORT_DRAWS) && !c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
   TickParams p; uint32_t grid;
   fillParams(c, flags, p, grid);
@@ -1655,7 +1691,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
     const bool hostBetweenHalves = (flags & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
     c->lastTickLazy = p.lazy != 0u;
@@ -2251,6 +2287,66 @@ int scTickReadSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, ui
   static_assert(sizeof(ScTickSweepHit) == sizeof(SweepHit48) && offsetof(ScTickSweepHit, travel) == offsetof(SweepHit48, travel), "sweep hit layouts differ");
   return readQueryHits(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS", "sweep hits are ready after scTickRunPairs",
                        c ? c->sweeps.hits : nullptr, c ? c->sweeps.count : 0u, hits, cap, count);
+}
+
+int scTickSetAnchoredRays(ScTickContext* c, uint32_t count, const uint32_t* anchor, const float* localOrigin3, const float* localDir3,
+                          const float* maxDist, const uint32_t* mask, const uint8_t* skipSelf)
+{
+  static_assert(kAnchorNone == SC_TICK_ANCHOR_NONE && kAnchorDead == SC_TICK_ANCHOR_DEAD, "anchor sentinels differ");
+  if (!c) return 0;
+  if (count && (!anchor || !localOrigin3 || !localDir3 || !maxDist || !mask)) return fail(c, "null argument");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending (its rays are resolved already)");
+  // checked before anything changes, so a refused call leaves the previous set in place
+  std::vector<float4> o(count), dd(count); std::vector<uint2> an(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    o[i] = make_float4(localOrigin3[3 * i], localOrigin3[3 * i + 1], localOrigin3[3 * i + 2], maxDist[i]);
+    float w; std::memcpy(&w, &mask[i], 4);
+    dd[i] = make_float4(localDir3[3 * i], localDir3[3 * i + 1], localDir3[3 * i + 2], w);
+    an[i] = make_uint2(anchor[i], skipSelf ? (skipSelf[i] ? 1u : 0u) : 1u);
+    const float v[7] = { o[i].x, o[i].y, o[i].z, o[i].w, dd[i].x, dd[i].y, dd[i].z };
+    for (float x : v) if (!std::isfinite(x)) return fail(c, "anchored rays: local_origin, local_dir and max_dist must be finite");
+    if (maxDist[i] < 0.0f) return fail(c, "anchored rays: max_dist must be >= 0");
+  }
+  if (!bind(c)) return 0;
+  // The same count as the current set: only the device arrays are rewritten, behind whatever is queued on the tick stream (the pair
+  // half of a split flow reads the snapshot, never these arrays) -- no epoch bump, so no learn tick, and a captured graph stays valid.
+  if (count != c->anchored.count) {
+    if (!sync(c)) return 0;
+    if (count > c->anchoredCap) {
+      AnchoredRayState& a = c->anchored;
+      dfree(c, const_cast<float4*>(a.origin)); dfree(c, const_cast<float4*>(a.dir)); dfree(c, const_cast<uint2*>(a.anchor)); dfree(c, a.hits);
+      dfree(c, a.snapOrigin); dfree(c, a.snapDir); dfree(c, a.snapSkip);
+      a = AnchoredRayState{}; c->anchoredCap = 0;
+      const uint32_t want = std::max(count, 1024u);
+      float4 *lo = nullptr, *lv = nullptr, *so = nullptr, *sd = nullptr; uint2* w = nullptr; uint32_t* ss = nullptr; RayHit48* h = nullptr;
+      if (!dalloc(c, lo, want, false) || !dalloc(c, lv, want, false) || !dalloc(c, w, want, false) || !dalloc(c, h, want) ||
+          !dalloc(c, so, (size_t)want * kMaxParity) || !dalloc(c, sd, (size_t)want * kMaxParity) || !dalloc(c, ss, (size_t)want * kMaxParity)) return 0;
+      a.origin = lo; a.dir = lv; a.anchor = w; a.hits = h; a.snapOrigin = so; a.snapDir = sd; a.snapSkip = ss; c->anchoredCap = want;
+    }
+    c->anchored.count = count;
+    c->topoEpoch++;                    // a captured frame holds the old batch size
+  }
+  c->hAnchor = an;
+  if (!count) return 1;
+  if (!h2d(c, const_cast<float4*>(c->anchored.origin), o.data(), (size_t)count * 16u) ||
+      !h2d(c, const_cast<float4*>(c->anchored.dir), dd.data(), (size_t)count * 16u) ||
+      !h2d(c, const_cast<uint2*>(c->anchored.anchor), an.data(), (size_t)count * 8u)) return 0;
+  return sync(c) ? 1 : 0;
+}
+
+int scTickReadAnchoredRayHits(ScTickContext* c, ScTickRayHit* hits, uint32_t cap, uint32_t* count)
+{
+  return readQueryHits(c, SC_TICK_ANCHORED_RAYS, "the last scTickRun did not request SC_TICK_ANCHORED_RAYS", "anchored ray hits are ready after scTickRunPairs",
+                       c ? c->anchored.hits : nullptr, c ? c->anchored.count : 0u, hits, cap, count);
+}
+
+int scTickReadAnchoredRays(ScTickContext* c, uint32_t first, uint32_t count, uint32_t* anchor)
+{
+  if (!c) return 0;
+  if (count && !anchor) return fail(c, "null argument");
+  if ((uint64_t)first + count > c->anchored.count) return fail(c, "range exceeds the anchored ray count");
+  for (uint32_t k = 0; k < count; ++k) anchor[k] = c->hAnchor[first + k].x;      // (host mirror: no read-back)
+  return 1;
 }
 
 int scTickQueryOccupied(ScTickContext* c, uint32_t count, const float* pos3, const float* radius, const uint32_t* mask, uint8_t* blocked)

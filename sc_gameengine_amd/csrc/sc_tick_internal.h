@@ -318,6 +318,23 @@ struct SweepQueryState {
   uint32_t count;
 };
 void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s);
+// ---- entity-anchored rays (include/sc_tick.h "entity-anchored rays"): given in an entity's local frame, resolved against this tick's
+// world matrix of that entity by the kernel that casts them.  A kernel argument of their own, like the sweeps'. ----
+constexpr uint32_t kAnchorNone = 0xFFFFFFFFu;    // == SC_TICK_ANCHOR_NONE: origin and direction are world space
+constexpr uint32_t kAnchorDead = 0xFFFFFFFEu;    // == SC_TICK_ANCHOR_DEAD: the anchor was removed (beyond every entity count: a miss)
+struct AnchoredRayState {
+  const float4* origin;     // local xyz + maxDist (world metres)
+  const float4* dir;        // local xyz + mask (bit pattern)
+  const uint2* anchor;      // (dense index of the anchor | kAnchorNone | kAnchorDead, skip_self)
+  RayHit48* hits;
+  // split flows: the tick half resolves into a snapshot -- world-space (origin, maxDist), (direction, mask), skip id -- of the tick's
+  // parity, the pair half casts from it (the next tick's fused kernel may have rewritten the matrices by then)
+  float4* snapOrigin; float4* snapDir; uint32_t* snapSkip;
+  uint32_t count;
+};
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);              // resolve + cast
+void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);      // tick half: resolve
+void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s); // pair half: cast
 void launchAgentFrontRays(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchAgentRaySnapshot(const DeviceState& d, const TickParams& p, hipStream_t s);         // tick half: list the agents, note their rays
 void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p, hipStream_t s); // pair half, behind the merge: cast them

@@ -11,6 +11,7 @@
 // One wave per ray.  The wave walks the sectors under the ray's xz extent, skipping those the segment misses;
 // lanes take one bin record each; then the big list.  Every lane keeps its own best hit; one 64-bit min over
 // (distance bits, id) picks the winner, whose lane writes the result.
+// The capsule sweeps, the entity-anchored rays and the traffic AI's obstacle rays below share that wave routine.
 #include "sc_tick_internal.h"
 
 namespace sctick {
@@ -153,20 +154,14 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
   return w;
 }
 
-__global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, const TickParams p, const RayQueryState q)
+// what a ray leaves for the host: RaycastHit{} (sc_physics.h:106-114) unless the wave found a box
+__device__ __forceinline__ RayHit48 rayHitOf(const WaveRay& w, const float o[3])
 {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
-  if (r >= q.count) return;
-  const float4 od = q.origin[r], dm = q.dir[r];
-  const float o[3] = { od.x, od.y, od.z };
-  const float dv[3] = { dm.x, dm.y, dm.z };
   RayHit48 out;
   out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
   out.position[0] = out.position[1] = out.position[2] = 0.0f;
-  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;           // RaycastHit{} (sc_physics.h:106-114)
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;
   out.layer = 0u; out.pad = 0u; out.pad2 = 0u;
-  const WaveRay w = castRayWave(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu);
   if (w.hit) {
     out.hit = 1u; out.id = w.id; out.distance = w.t; out.layer = w.layer;
     out.position[0] = o[0] + w.dir[0] * w.t; out.position[1] = o[1] + w.dir[1] * w.t; out.position[2] = o[2] + w.dir[2] * w.t;
@@ -175,7 +170,83 @@ __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, cons
       out.normal[w.axis] = w.dir[w.axis] > 0.0f ? -1.0f : 1.0f;
     }
   }
+  return out;
+}
+
+__global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, const TickParams p, const RayQueryState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
+  if (r >= q.count) return;
+  const float4 od = q.origin[r], dm = q.dir[r];
+  const float o[3] = { od.x, od.y, od.z };
+  const float dv[3] = { dm.x, dm.y, dm.z };
+  const WaveRay w = castRayWave(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu);
+  const RayHit48 out = rayHitOf(w, o);
   if (lane == 0) q.hits[r] = out;
+}
+
+// ---- entity-anchored rays (own spec, include/sc_tick.h "entity-anchored rays") -----------------------------------------------
+// A ray given in an entity's local frame -- a wheel probe (VehicleWheelConfig::connectionPoint / direction, sc_physics.h:63-72), the
+// vehicle camera's occlusion ray (sc_vehicle.cpp:570-611), the traffic debug sensor ray (sc_traffic_ai.cpp:622-652) -- is taken through
+// this tick's world matrix of its anchor, fp32, unfused, left to right:
+//   o_r = ((R_r.x*l.x + R_r.y*l.y) + R_r.z*l.z) + R_r.w        d_r = (R_r.x*v.x + R_r.y*v.y) + R_r.z*v.z
+// and then answered as a ray of k_ray_queries is; max_dist is world metres.  An anchor beyond the entity count (a dead anchor is), a
+// resolved origin that is not finite or a resolved direction whose squared length is not finite: a miss, noted as direction (0, 0, 0),
+// which castRayWave rejects.  kAnchorNone: the ray is world space already and goes through untouched -- bit for bit a plain ray.
+struct ResolvedRay { float o[3], dv[3]; float maxDist; uint32_t mask, skipId; };
+
+__device__ __forceinline__ ResolvedRay resolveAnchoredRay(const DeviceState& d, const TickParams& p, const float4& lo, const float4& lv, const uint2 an)
+{
+  ResolvedRay r;
+  r.o[0] = lo.x; r.o[1] = lo.y; r.o[2] = lo.z; r.dv[0] = lv.x; r.dv[1] = lv.y; r.dv[2] = lv.z;
+  r.maxDist = lo.w; r.mask = __float_as_uint(lv.w); r.skipId = 0xFFFFFFFFu;
+  if (an.x == kAnchorNone) return r;
+  r.o[0] = r.o[1] = r.o[2] = 0.0f; r.dv[0] = r.dv[1] = r.dv[2] = 0.0f;
+  if (an.x >= p.n) return r;
+  const float4 row[3] = { d.w0[an.x], d.w1[an.x], d.w2[an.x] };
+  float o[3], dv[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    o[k] = ((row[k].x * lo.x + row[k].y * lo.y) + row[k].z * lo.z) + row[k].w;
+    dv[k] = (row[k].x * lv.x + row[k].y * lv.y) + row[k].z * lv.z;
+  }
+  const float lenSq = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];          // (as castRayWave forms it)
+  if (!(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(lenSq))) return r;
+  r.o[0] = o[0]; r.o[1] = o[1]; r.o[2] = o[2]; r.dv[0] = dv[0]; r.dv[1] = dv[1]; r.dv[2] = dv[2];
+  if (an.y) r.skipId = p.rankBits | an.x;                                     // the anchor's own box never answers
+  return r;
+}
+
+// One wave per ray, like k_ray_queries.  The ray index is made scalar, so the ray, its anchor word and the twelve words of the anchor's
+// matrix rows come through the scalar path: one fetch per wave, not one per lane.  kFromSnapshot (the pair half of a split flow): the
+// ray was resolved by k_anchored_ray_snapshot in the tick half and is cast as it stands there.
+template <bool kFromSnapshot>
+__global__ __launch_bounds__(kTile) void k_anchored_rays(const DeviceState d, const TickParams p, const AnchoredRayState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
+  if (r >= q.count) return;
+  ResolvedRay ray;
+  if (kFromSnapshot) {
+    const float4 a = q.snapOrigin[r], b = q.snapDir[r];
+    ray.o[0] = a.x; ray.o[1] = a.y; ray.o[2] = a.z; ray.dv[0] = b.x; ray.dv[1] = b.y; ray.dv[2] = b.z;
+    ray.maxDist = a.w; ray.mask = __float_as_uint(b.w); ray.skipId = q.snapSkip[r];
+  } else ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
+  const WaveRay w = castRayWave(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId);
+  const RayHit48 out = rayHitOf(w, ray.o);
+  if (lane == 0) q.hits[r] = out;
+}
+
+// The resolve-only form (the tick half of a split flow): a thread per ray, the same arithmetic, the result noted in the parity's snapshot.
+__global__ __launch_bounds__(kTile) void k_anchored_ray_snapshot(const DeviceState d, const TickParams p, const AnchoredRayState q)
+{
+  const uint32_t r = blockIdx.x * kTile + threadIdx.x;
+  if (r >= q.count) return;
+  const ResolvedRay ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
+  q.snapOrigin[r] = make_float4(ray.o[0], ray.o[1], ray.o[2], ray.maxDist);
+  q.snapDir[r] = make_float4(ray.dv[0], ray.dv[1], ray.dv[2], __uint_as_float(ray.mask));
+  q.snapSkip[r] = ray.skipId;
 }
 
 // ---- capsule sweeps (own spec, include/sc_tick.h "capsule sweeps"; shaped like PhysicsWorld::sweepCapsule, sc_physics.cpp:779-810) --
@@ -412,6 +483,26 @@ void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQu
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
   hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+}
+
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
+{
+  if (!q.count) return;
+  const uint32_t perBlock = kTile / 64u;
+  hipLaunchKernelGGL(k_anchored_rays<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+}
+
+void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
+{
+  if (!q.count) return;
+  hipLaunchKernelGGL(k_anchored_ray_snapshot, dim3((q.count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, q);
+}
+
+void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
+{
+  if (!q.count) return;
+  const uint32_t perBlock = kTile / 64u;
+  hipLaunchKernelGGL(k_anchored_rays<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 } // namespace sctick

@@ -27,6 +27,11 @@ SWEEP_HIT_DTYPE = np.dtype([("hit", np.uint32), ("id", np.uint32), ("distance", 
                             ("normal", np.float32, 3), ("layer", np.uint32), ("travel", np.float32), ("pad", np.uint32)])
 
 
+# what WorldTick.ray_hits() and anchored_ray_hits() return (== ScTickRayHit)
+RAY_HIT_DTYPE = np.dtype([("hit", np.uint32), ("id", np.uint32), ("distance", np.float32), ("position", np.float32, 3),
+                          ("normal", np.float32, 3), ("layer", np.uint32), ("pad", np.uint32, 2)])
+
+
 # ---- host-side camera math (CameraSystem stays on the host, sc_ecs.cpp:213-272) ----------------
 def host_mat4_trs(pos, rot, scale):
     p, r, s, o = _c32(pos), _c32(rot), _c32(scale), np.zeros(16, np.float32)
@@ -245,9 +250,38 @@ class WorldTick:
         buf = (capi.RayHit * max(n.value, 1))()
         if n.value:
             self._ok(self.lib.scTickReadRayHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadRayHits")
-        dt = np.dtype([("hit", np.uint32), ("id", np.uint32), ("distance", np.float32), ("position", np.float32, 3),
-                       ("normal", np.float32, 3), ("layer", np.uint32), ("pad", np.uint32, 2)])
-        return np.frombuffer(buf, dtype=dt, count=n.value).copy()
+        return np.frombuffer(buf, dtype=RAY_HIT_DTYPE, count=n.value).copy()
+
+    # ---- entity-anchored rays: given in an entity's local frame, resolved on the device every tick ----
+    def set_anchored_rays(self, anchor, local_origin, local_dir, max_dist, mask, skip_self=None):
+        """Rays in the local frame of the entities `anchor` (dense indices; capi.ANCHOR_NONE: a world-space ray), answered by every run
+        with capi.ANCHORED_RAYS against that tick's matrices and boxes (scTickSetAnchoredRays).  skip_self: per ray, whether the anchor's
+        own box never answers (None: all).  A call with as many rays as the current set costs no learn tick and no graph capture."""
+        an = np.ascontiguousarray(anchor, np.uint32).reshape(-1)
+        o, dd = _c32(local_origin).reshape(-1, 3), _c32(local_dir).reshape(-1, 3)
+        md, mk = _c32(max_dist).reshape(-1), np.ascontiguousarray(mask, np.uint32).reshape(-1)
+        sk = None if skip_self is None else np.ascontiguousarray(skip_self, np.uint8).reshape(-1)
+        assert len(o) == len(an) and len(dd) == len(an) and len(md) == len(an) and len(mk) == len(an) and (sk is None or len(sk) == len(an))
+        self._ok(self.lib.scTickSetAnchoredRays(self.ctx, len(an), _u(an), _f(o), _f(dd), _f(md), _u(mk),
+                                                None if sk is None else sk.ctypes.data_as(capi.U8P)), "scTickSetAnchoredRays")
+        self._anchored_rays = len(an)
+
+    def anchored_ray_hits(self):
+        """Structured array like ray_hits() of the last run's anchored rays."""
+        n = C.c_uint32()
+        self._ok(self.lib.scTickReadAnchoredRayHits(self.ctx, None, 0, C.byref(n)), "scTickReadAnchoredRayHits")
+        buf = (capi.RayHit * max(n.value, 1))()
+        if n.value:
+            self._ok(self.lib.scTickReadAnchoredRayHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadAnchoredRayHits")
+        return np.frombuffer(buf, dtype=RAY_HIT_DTYPE, count=n.value).copy()
+
+    def anchored_ray_anchors(self):
+        """The anchors as they stand now: renamed by remove_entities where their entity moved, capi.ANCHOR_DEAD where it was removed."""
+        k = getattr(self, "_anchored_rays", 0)
+        out = np.zeros(max(k, 1), np.uint32)
+        if k:
+            self._ok(self.lib.scTickReadAnchoredRays(self.ctx, 0, k, _u(out)), "scTickReadAnchoredRays")
+        return out[:k].copy()
 
     # ---- capsule sweeps over this tick's boxes ----
     def set_sweep_queries(self, start, end, radius, half_height, mask, skip_id=None):

@@ -1,0 +1,495 @@
+"""Entity-anchored rays (scTickSetAnchoredRays / SC_TICK_ANCHORED_RAYS) through the C ABI against the witness (tests/anchored_ref.py:
+the spec in numpy fp32 over the oracle's world matrices, around the oracle's brute-force ray test over its world AABBs).  Own spec, like
+the rays: the candidates are the world AABBs.  GPU matrices and AABBs equal the oracle's as IEEE values, so hit, id and layer must be
+equal and distance, position and normal equal as bit patterns, misses included."""
+import numpy as np
+import pytest
+
+from sc_gameengine_amd import capi, synth_world as sw
+from sc_gameengine_amd.tick import WorldTick
+from tests import anchored_ref as ar, worlds
+
+pytestmark = pytest.mark.gpu
+FLAGS = capi.XFORM | capi.BROADPHASE | capi.DENSE_AABBS
+ANCH = FLAGS | capi.ANCHORED_RAYS
+F = np.float32
+ALL = 0xFFFFFFFF
+NONE, DEAD = capi.ANCHOR_NONE, capi.ANCHOR_DEAD
+
+
+def compare(got, want):
+    assert len(got) == len(want)
+    for f in ("hit", "id", "layer"):
+        assert np.array_equal(got[f], want[f]), f"{f}: {np.flatnonzero(got[f] != want[f])[:8]}"
+    for f in ("distance", "position", "normal"):
+        assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), f        # bit patterns, misses included
+    assert (got["pad"] == 0).all()
+
+
+def same_world(t, ow):
+    """The GPU's matrices and boxes equal the oracle's; returns (matrices, mn, mx) of the oracle."""
+    m = ow.world_matrices()
+    mn, mx = ow.world_aabbs()
+    assert np.array_equal(t.world_matrices(), m), "world matrices differ from the oracle"
+    gmn, gmx = t.world_aabbs()
+    assert np.array_equal(gmn, mn) and np.array_equal(gmx, mx), "world AABBs differ from the oracle"
+    return m, mn, mx
+
+
+def witness(oracle, w, ow, q, skip_self=None, matrices=None):
+    mn, mx = ow.world_aabbs()
+    return ar.cast(oracle, mn, mx, w.group, w.mask, ow.world_matrices() if matrices is None else matrices, *q, skip_self=skip_self)
+
+
+def local_rays(rng, k, reach=4.0):
+    """(local_origin, local_dir, max_dist, mask): origins inside and outside a box of half extent 0.1 .. 2, directions not normalised"""
+    l = rng.uniform(-reach, reach, (k, 3)).astype(F)
+    l[: k // 4] = rng.uniform(-0.1, 0.1, (k // 4, 3))                             # inside every box random_world makes
+    v = rng.normal(size=(k, 3)).astype(F)
+    v[:, 1] *= 0.15
+    v *= rng.uniform(0.01, 50.0, (k, 1)).astype(F)
+    md = np.where(rng.random(k) < 0.2, rng.uniform(200, 900, k), rng.uniform(2, 60, k)).astype(F)
+    mask = rng.choice(np.array([1, 2, 3, ALL], np.uint32), k)
+    return l, v, md, mask
+
+
+# ---- 1. random world, the rays never re-set -------------------------------------------------------------------------
+SEED_WORLD, SEED_RAYS = 61, 101       # (chosen on the CPU: the witness reports more than 300 hits and more than 100 misses on every tick;
+NUDGE = 0.8                           #  tests/test_anchored_rays_cpu.py asserts it without a GPU)
+
+
+def random_case():
+    """(world, rays (anchor, l, v, max_dist, mask), skip_self): 2 000 rays on random anchors of a 4 000-entity forest with rotated and
+    scaled parents; 300 roots are left unrotated so that axis-parallel local directions stay axis-parallel in the world."""
+    w = worlds.random_world(4000, seed=SEED_WORLD, spread=220.0, max_depth=3)
+    roots = np.flatnonzero(w.parent < 0)
+    big, flat = roots[:30], roots[100:400]
+    w.rot[big] = 0.0; w.scale[big] = 1.0; w.has_bounds[big] = 1
+    w.bmin[big], w.bmax[big] = F([-80, -1, -80]), F([80, 1, 80])                 # 160 m plates: they are only in the big list
+    w.rot[flat] = 0.0
+    rng = np.random.default_rng(SEED_RAYS)
+    k = 2000
+    anchor = rng.integers(0, w.n, k).astype(np.uint32)
+    anchor[500:1000] = rng.choice(flat, 500)
+    l, v, md, mask = local_rays(rng, k)
+    v[500:650, 0] = 0.0                                                          # the |dir| < 1e-6 branch of one or two axes
+    v[650:800, 2] = 0.0
+    v[800:900, [0, 2]] = 0.0
+    v[900:950, [0, 1]] = 0.0
+    skip = (rng.random(k) < 0.5).astype(np.uint8)
+    return w, (anchor, l, v, md, mask), skip
+
+
+def test_random_world_rays_follow_their_anchors_without_being_set_again(oracle):
+    w, q, skip = random_case()
+    ow = worlds.oracle_world(oracle, w, camera=False)
+    t = WorldTick.from_world(w, broadphase=True)
+    t.set_anchored_rays(*q, skip_self=skip)
+    before = None
+    for tick in range(3):
+        if tick:
+            ow.nudge_roots_x(NUDGE); t.nudge_roots_x(NUDGE)
+        ow.transform_system()
+        t.run(ANCH)
+        _, mn, mx = same_world(t, ow)
+        want = witness(oracle, w, ow, q, skip)
+        compare(t.anchored_ray_hits(), want)
+        assert want["hit"].sum() > 300 and (want["hit"] == 0).sum() > 100
+        _, total = t.pairs()                                                    # the pair search still sees full bins afterwards
+        assert total == len(oracle.broadphase_bruteforce(mn, mx, w.group, w.mask))
+        if before is not None:                                                  # the rays moved with their anchors
+            both = (before["hit"] == 1) & (want["hit"] == 1)
+            assert (before["position"][both] != want["position"][both]).any(axis=1).sum() > 200
+        before = want
+    assert t.counts().big_boxes >= 30 and t.learn_ticks() == 1
+    t.close(); ow.close()
+
+
+# ---- 2. self-skip ---------------------------------------------------------------------------------------------------
+def test_skip_self_never_returns_the_anchor(oracle):
+    w = worlds.random_world(1500, seed=102, spread=60.0, max_depth=2, p_no_bounds=0.0)
+    w.group[:] = 1; w.mask[:] = ALL
+    ow = worlds.oracle_world(oracle, w, camera=False); ow.transform_system()
+    m, mn, mx = ow.world_matrices(), *ow.world_aabbs()
+    centre = ((w.bmin + w.bmax) * F(0.5)).astype(F)
+    o, _, ok = ar.resolve(m, np.arange(w.n, dtype=np.uint32), centre, np.ones((w.n, 3), F))
+    assert ok.all()
+    # anchors whose box centre lies in no box but their own: without the skip the answer can only be the anchor itself
+    inside = ((o[:, None, :] >= mn[None]) & (o[:, None, :] <= mx[None])).all(axis=2)
+    assert inside.diagonal().all()
+    alone = np.flatnonzero(inside.sum(axis=1) == 1)
+    assert len(alone) > 200
+    rng = np.random.default_rng(103)
+    k = 400
+    anchor = rng.choice(alone, k).astype(np.uint32)
+    v = rng.normal(size=(k, 3)).astype(F)
+    q = (anchor, centre[anchor], v, np.full(k, 40.0, F), np.full(k, ALL, np.uint32))
+    t = WorldTick.from_world(w, broadphase=True)
+    for skip in (np.zeros(k, np.uint8), None, np.ones(k, np.uint8)):             # None: every ray skips its anchor
+        t.set_anchored_rays(*q, skip_self=skip)
+        t.run(ANCH)
+        same_world(t, ow)
+        got = t.anchored_ray_hits()
+        compare(got, witness(oracle, w, ow, q, skip))
+        if skip is not None and not skip.any():
+            assert (got["hit"] == 1).all() and np.array_equal(got["id"], anchor)
+            assert (got["distance"] == 0).all() and (got["normal"] == F([0, 1, 0])).all()
+            assert np.array_equal(got["position"].view(np.uint32), o[anchor].view(np.uint32))
+        else:
+            hit = got["hit"] == 1
+            assert (got["id"][hit] != anchor[hit]).all()
+            assert hit.sum() > 50 and (~hit).sum() > 50                         # the second choice, or a miss
+    t.close(); ow.close()
+
+
+# ---- 3. edge cases --------------------------------------------------------------------------------------------------
+def test_edge_cases_in_one_small_world(oracle):
+    from tests import sweep_ref
+    from tests.test_gpu_rays import compare as compare_rays
+    from tests.test_gpu_sweeps import compare as compare_sweeps
+    n = 64
+    w = worlds.random_world(n, seed=104, spread=25.0, p_child=0.0, p_no_bounds=0.0)
+    w.group[:] = 1; w.mask[:] = ALL
+    tiny, nan_rot, inf_pos = 5, 6, 7
+    w.scale[tiny] = F(1e-4)                                                     # collapses a unit direction: |d|^2 = 1e-8
+    w.has_bounds[[nan_rot, inf_pos]] = 0                                        # (their matrices become non-finite below: no box)
+    ow = worlds.oracle_world(oracle, w, camera=False); ow.transform_system()
+    rng = np.random.default_rng(105)
+    k = 48
+    wo = rng.uniform(-25, 25, (k, 3)).astype(F)
+    wd = rng.normal(size=(k, 3)).astype(F)
+    md, mask = np.full(k, 60.0, F), np.full(k, ALL, np.uint32)
+    free = (np.full(k, NONE, np.uint32), wo, wd, md, mask)
+    t = WorldTick.from_world(w, broadphase=True)
+
+    # no anchor: the plain ray query of the same tick, bit for bit
+    t.set_ray_queries(wo, wd, md, mask)
+    t.set_anchored_rays(*free)
+    t.run(ANCH | capi.RAYS)
+    m, mn, mx = same_world(t, ow)
+    plain, got = t.ray_hits(), t.anchored_ray_hits()
+    assert plain.tobytes() == got.tobytes()
+    compare(got, witness(oracle, w, ow, free))
+    compare_rays(plain, oracle.raycast_boxes(mn, mx, w.group, w.mask, wo, wd, md, mask))
+    assert 5 < got["hit"].sum() < k
+
+    # anchors beyond the entity count miss; so does a direction the anchor's scale collapses, although the ray starts inside a box
+    anchor = np.array([n, n + 5, DEAD, 1 << 24, tiny, tiny, 3], np.uint32)
+    l = np.zeros((7, 3), F)
+    v = F([[1, 0, 0]] * 5 + [[9000.0, 0, 0], [1, 0, 0]])                        # (0.9 m after the scale: that one is a ray again)
+    q = (anchor, l, v, np.full(7, 50.0, F), np.full(7, ALL, np.uint32))
+    skip = np.zeros(7, np.uint8)
+    t.set_anchored_rays(*q, skip_self=skip)
+    t.run(ANCH)
+    got = t.anchored_ray_hits()
+    compare(got, witness(oracle, w, ow, q, skip))
+    assert list(got["hit"]) == [0, 0, 0, 0, 0, 1, 1] and list(got["id"][5:]) == [tiny, 3]
+    d = ar.resolve(m, anchor[4:5], l[4:5], v[4:5])[1][0]
+    assert (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= F(1e-6)
+
+    # non-finite uploaded world matrices, in a run without XFORM: a NaN in the rotation part, an infinite translation
+    bad = m.copy()
+    bad[nan_rot, 0] = np.nan
+    bad[inf_pos, 12] = np.inf
+    t.upload_world_matrices(nan_rot, bad[nan_rot:inf_pos + 1])
+    anchor = np.array([nan_rot, inf_pos, inf_pos, 3], np.uint32)
+    l = F([[0, 0, 0], [0, 0, 0], [1, 2, 3], [0, 0, 0]])
+    v = F([[1, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 0]])
+    q = (anchor, l, v, np.full(4, 1e6, F), np.full(4, ALL, np.uint32))
+    t.set_anchored_rays(*q, skip_self=np.zeros(4, np.uint8))
+    t.run((ANCH | capi.RAYS) & ~capi.XFORM)
+    assert np.array_equal(t.world_matrices().view(np.uint32), bad.view(np.uint32))
+    gmn, gmx = t.world_aabbs()
+    assert np.array_equal(gmn, mn) and np.array_equal(gmx, mx)
+    got = t.anchored_ray_hits()
+    compare(got, witness(oracle, w, ow, q, np.zeros(4, np.uint8), matrices=bad))
+    assert list(got["hit"]) == [0, 0, 0, 1]
+    assert plain.tobytes() == t.ray_hits().tobytes()                            # the boxes did not change
+    t.upload_world_matrices(nan_rot, m[nan_rot:inf_pos + 1])
+
+    # rays, sweeps and anchored rays in one tick
+    anchor = rng.integers(0, n, k).astype(np.uint32)
+    q = (anchor, *local_rays(rng, k))
+    q[4][:] = ALL
+    a = rng.uniform(-25, 25, (k, 3)).astype(F)
+    sweeps = [a, (a + rng.normal(size=(k, 3)) * 20).astype(F), rng.uniform(0, 2, k).astype(F), rng.uniform(0, 1, k).astype(F), mask]
+    t.set_anchored_rays(*q)
+    t.set_sweep_queries(*sweeps)
+    for flags in (capi.RAYS | capi.SWEEPS | capi.ANCHORED_RAYS, capi.ANCHORED_RAYS, capi.SWEEPS | capi.ANCHORED_RAYS):
+        t.run(FLAGS | flags)
+        same_world(t, ow)
+        compare(t.anchored_ray_hits(), witness(oracle, w, ow, q))
+        if flags & capi.RAYS:
+            assert plain.tobytes() == t.ray_hits().tobytes()
+        if flags & capi.SWEEPS:
+            want = sweep_ref.sweep_boxes(oracle, mn, mx, w.group, w.mask, *sweeps)
+            compare_sweeps(t.sweep_hits(), want)
+            assert want["hit"].sum() > 3
+    assert witness(oracle, w, ow, q)["hit"].sum() > 10
+    t.close(); ow.close()
+
+
+# ---- 4. graph replay and the epoch ----------------------------------------------------------------------------------
+def test_graph_replay_follows_the_movers_and_a_same_count_set_costs_no_learn_tick(oracle):
+    w = worlds.random_world(1500, seed=106, spread=70.0, max_depth=2)
+    rng = np.random.default_rng(107)
+    k = 500
+    roots = np.flatnonzero(w.parent < 0)
+    sets = [(rng.choice(roots, k).astype(np.uint32), *local_rays(rng, k)) for _ in range(2)]
+    ow = worlds.oracle_world(oracle, w, camera=False)
+    t = WorldTick.from_world(w, broadphase=True)
+    t.set_anchored_rays(*sets[0])
+    t.set_graph_mode(True)
+    t.set_frame_producer(1, 0.5)
+    q, seen = sets[0], []
+    for tick in range(6):
+        if tick == 3:
+            learn = t.learn_ticks()
+            t.set_anchored_rays(*sets[1])                                       # the same count: device arrays only
+            q = sets[1]
+        ow.transform_system()
+        t.run(ANCH | capi.PRODUCE_NEXT)
+        same_world(t, ow)
+        want = witness(oracle, w, ow, q)
+        compare(t.anchored_ray_hits(), want)
+        assert want["hit"].sum() > 50 and (want["hit"] == 0).sum() > 50
+        if tick == 3:
+            old = witness(oracle, w, ow, sets[0])
+            assert (old["id"] != want["id"]).sum() > 50                          # the answers changed with the set
+        seen.append(want)
+        ow.nudge_roots_x(0.5)                                                    # what the producer did at the end of the run
+    assert t.learn_ticks() == learn == 1
+    both = (seen[0]["hit"] == 1) & (seen[2]["hit"] == 1)
+    assert (seen[0]["position"][both, 0] != seen[2]["position"][both, 0]).sum() > 20      # the hits follow the moving roots
+    t.set_anchored_rays(*[x[:100] for x in q])                                  # another count: like scTickSetRayQueries
+    ow.transform_system()
+    t.run(ANCH | capi.PRODUCE_NEXT)
+    same_world(t, ow)
+    compare(t.anchored_ray_hits(), witness(oracle, w, ow, [x[:100] for x in q]))
+    assert t.learn_ticks() == learn + 1
+    t.close(); ow.close()
+
+
+# ---- 5. after lazy ticks --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("graph", [False, True])
+def test_an_anchored_ray_tick_after_lazy_ticks_sees_every_record(oracle, graph):
+    """An all-static world leaves its bins unwritten between learn ticks (lazy records); a tick with ANCHORED_RAYS reads the bins, so it
+    writes them -- the roots moved 2.4 m since the learn tick, stale records would show."""
+    w = sw.generate(4, 4, 15)
+    rng = np.random.default_rng(108)
+    k = 600
+    q = (rng.integers(0, w.n, k).astype(np.uint32), rng.uniform(-1, 1, (k, 3)).astype(F), rng.normal(size=(k, 3)).astype(F),
+         rng.uniform(1, 30, k).astype(F), np.full(k, ALL, np.uint32))
+    ow = worlds.oracle_world(oracle, w, camera=False)
+    t = WorldTick.from_world(w, broadphase=True)
+    t.set_anchored_rays(*q)
+    if graph:
+        t.set_graph_mode(True)
+
+    def tick(flags):
+        ow.nudge_roots_x(0.8); t.nudge_roots_x(0.8)
+        ow.transform_system()
+        t.run(flags)
+        _, mn, mx = same_world(t, ow)
+        assert t.pairs()[1] == 0 == len(oracle.broadphase_grid(mn, mx, w.group, w.mask, 64.0))
+    for _ in range(4):                                   # the learn tick and three ticks on remembered slots
+        tick(FLAGS)
+    assert t.bin_stats()["lazy_last_tick"] and t.bin_stats()["learn_ticks"] == 1
+    tick(ANCH)
+    assert not t.bin_stats()["lazy_last_tick"]
+    want = witness(oracle, w, ow, q)
+    compare(t.anchored_ray_hits(), want)
+    assert want["hit"].sum() > 50 and (want["hit"] == 0).sum() > 50
+    for _ in range(2):
+        tick(FLAGS)
+    assert t.bin_stats()["lazy_last_tick"] and t.bin_stats()["learn_ticks"] == 1
+    t.close(); ow.close()
+
+
+# ---- 6. two tiles ---------------------------------------------------------------------------------------------------
+def test_tiles_see_neighbour_boxes_and_a_pipelined_tile_answers_like_an_in_order_one(oracle):
+    """2 x 1 tiles on one GPU, the caller-owned split flow.  Four root props of tile 0 stand 4 m before the shared edge, 200 m above
+    every other prop, and look across it; four of tile 1 lie on the edge and reach 0.2 m into tile 0: tile 0 knows them from the border
+    merge alone.  Every ray's first box in the whole world is one its context has registered in its own sectors, so the witness over the
+    whole world is the witness over those.  Tile 1 casts short rays from props deep inside it."""
+    import torch
+    from sc_gameengine_amd import tiles
+    from tests.test_gpu_tiles import split_world
+    from tests.test_gpu_tiles_edge import network
+    grid, S = (2, 1), (6, 6)
+    w = sw.generate(S[0] * grid[0], S[1], 15, tiles=grid)
+    w.group[:], w.mask[:] = sw.GROUP_DYNAMIC, sw.MASK_ALL
+    n = w.n // 2
+    edge = 64.0 * S[0]
+    props = (w.parent < 0) & (np.arange(w.n) % 16 != 0)
+    lone = props & ~np.isin(np.arange(w.n), w.parent[w.parent >= 0])             # root props without children
+    zs = F([40.0, 110.0, 200.0, 300.0])
+    near = np.flatnonzero(lone & (np.arange(w.n) >= n))[:4]                      # tile 1's, moved onto the edge
+    w.pos[near] = np.stack([np.full(4, edge + 0.3, F), np.full(4, 200.0, F), zs], axis=1)
+    lookers = np.flatnonzero(lone & (np.arange(w.n) < n))[:4]                    # tile 0's, looking at them
+    w.pos[lookers] = np.stack([np.full(4, edge - 4.0, F), np.full(4, 200.0, F), zs + F([0, 0, 0, 0.9])], axis=1)
+    for e in (near, lookers):
+        w.scale[e] = 1.0; w.rot[e] = 0.0
+        w.bmin[e], w.bmax[e] = F([-0.5] * 3), F([0.5] * 3)
+    w.scale[lookers[1]] = F([2.0, 1.0, 1.0])                                     # (the anchor's scale does not scale max_dist)
+    deep = np.flatnonzero(props & (np.arange(w.n) >= n) & (w.pos[:, 0] > edge + 70.0))[:40]
+    rng = np.random.default_rng(109)
+    # tile 0: along +x at the box ahead (the fourth passes 0.9 m beside its box's centre: a miss), one that stops 0.5 m short, and
+    # one with the skip off that starts inside its own box
+    a0 = np.concatenate([lookers, lookers[:2]]).astype(np.uint32)
+    q0 = (a0, np.zeros((6, 3), F), np.tile(F([1, 0, 0]), (6, 1)), F([10, 10, 10, 10, 2.8, 10]), np.full(6, ALL, np.uint32))
+    skip0 = np.array([1, 1, 1, 1, 1, 0], np.uint8)
+    a1 = deep.astype(np.uint32)
+    q1 = (a1, rng.uniform(-1, 1, (40, 3)).astype(F), rng.normal(size=(40, 3)).astype(F), np.full(40, 5.0, F), np.full(40, ALL, np.uint32))
+    parts, n = split_world(w, grid, S)
+    ow = worlds.oracle_world(oracle, w, camera=False)
+    flags = capi.XFORM | capi.BROADPHASE | capi.SPLIT_PAIRS | capi.DENSE_AABBS | capi.ANCHORED_RAYS
+
+    def two_ticks(pipelined):
+        ticks = [WorldTick.from_world(p, broadphase=True, max_pairs=1 << 16) for p in parts]
+        streams = [torch.cuda.Stream() for _ in ticks]
+        if pipelined:
+            for t, s in zip(ticks, streams):
+                t.set_pairs_stream(s.cuda_stream)
+        bufs = [tiles.BorderBuffers(t, r, grid, "cuda", pipelined=pipelined) for r, t in enumerate(ticks)]
+        ticks[0].set_anchored_rays(q0[0], *q0[1:], skip_self=skip0)
+        ticks[1].set_anchored_rays(q1[0] - n, *q1[1:])
+        for step in range(2):
+            if step:
+                for t in ticks:
+                    t.nudge_roots_x(0.1)
+            for t in ticks:
+                t.run(flags)
+            if step == 0 and not pipelined:
+                with pytest.raises(capi.ScTickError, match="after scTickRunPairs"):
+                    ticks[0].anchored_ray_hits()                                 # not before scTickRunPairs
+            network(bufs, grid, parity=step)
+            for t in ticks:
+                t.run_pairs()
+        out = [t.anchored_ray_hits() for t in ticks]                             # the first read: both ticks were queued
+        mats = np.concatenate([t.world_matrices() for t in ticks])
+        boxes = [np.concatenate(x) for x in zip(*[t.world_aabbs() for t in ticks])]
+        assert all(t.counts().border_lost == 0 for t in ticks)
+        for t in ticks:
+            t.close()
+        return out, mats, boxes
+
+    in_order, mats, boxes = two_ticks(False)
+    ow.transform_system(); ow.nudge_roots_x(0.1); ow.transform_system()
+    m = ow.world_matrices()
+    mn, mx = ow.world_aabbs()
+    assert np.array_equal(mats, m) and np.array_equal(boxes[0], mn) and np.array_equal(boxes[1], mx)
+    want = [ar.cast(oracle, mn, mx, w.group, w.mask, m, *q0, skip_self=skip0), ar.cast(oracle, mn, mx, w.group, w.mask, m, *q1)]
+    assert list(want[0]["hit"]) == [1, 1, 1, 0, 0, 1]
+    assert np.array_equal(want[0]["id"][:3], near[:3].astype(np.uint32)) and want[0]["id"][5] == lookers[1]
+    assert want[0]["distance"][1] == want[0]["distance"][0]                      # 3.8 m both: the scale did not stretch the ray
+    assert 3 < want[1]["hit"].sum() < 40
+    for r, (got, exp) in enumerate(zip(in_order, want)):
+        found = got["hit"] == 1
+        assert np.array_equal(got["hit"], exp["hit"]) and np.array_equal(got["layer"], exp["layer"])
+        assert np.array_equal(tiles.global_pair_ids(got["id"][found].reshape(-1, 1), n).ravel(), exp["id"][found].astype(np.uint64))
+        assert (got["id"][~found] == ALL).all() and (got["pad"] == 0).all()
+        for f in ("distance", "position", "normal"):
+            assert np.array_equal(got[f].view(np.uint32), exp[f].view(np.uint32)), (r, f)
+    assert ((in_order[0]["id"][:3] >> 24) == 1).all()                           # boxes of rank 1, answered by rank 0
+    ow.close()
+    piped, mats2, boxes2 = two_ticks(True)
+    assert np.array_equal(mats2, m) and np.array_equal(boxes2[0], mn) and np.array_equal(boxes2[1], mx)
+    for a, b in zip(piped, in_order):
+        assert a.tobytes() == b.tobytes()
+
+
+# ---- 7. residency ---------------------------------------------------------------------------------------------------
+def test_anchors_follow_relocated_entities_and_die_with_removed_ones(oracle):
+    w = worlds.random_world(900, seed=110, spread=50.0, p_child=0.0)
+    rng = np.random.default_rng(111)
+    k = 300
+    gone = rng.choice(np.arange(100, 700), 60, replace=False).astype(np.uint32)
+    tail = np.arange(w.n - 60, w.n, dtype=np.uint32)                            # the entities the swap-removes relocate
+    anchor = rng.integers(0, w.n, k).astype(np.uint32)
+    anchor[:40] = rng.choice(gone, 40)
+    anchor[40:90] = rng.choice(tail, 50)
+    anchor[90] = NONE
+    q = [anchor, *local_rays(rng, k)]
+    ow = worlds.oracle_world(oracle, w, camera=False)
+    t = WorldTick.from_world(w, broadphase=True)
+    bare = WorldTick.from_world(w, broadphase=True)                             # the same sequence without anchored rays
+    t.set_anchored_rays(*q)
+    assert np.array_equal(t.anchored_ray_anchors(), anchor)
+    for _ in range(2):
+        ow.transform_system()
+        t.run(ANCH); bare.run(FLAGS)
+        same_world(t, ow)
+        compare(t.anchored_ray_hits(), witness(oracle, w, ow, q))
+    before = ow.dense_entities()
+    for e in before[gone]:
+        assert ow.destroy(int(e))
+    after = ow.dense_entities()
+    src, dst = t.remove_entities(gone)
+    bare.remove_entities(gone)
+    assert len(src) > 20
+    # where every entity went, from the oracle's pool alone
+    slot = {int(e): i for i, e in enumerate(after)}
+    expect = np.array([a if a == NONE else slot.get(int(before[a]), DEAD) for a in anchor], np.uint32)
+    now = t.anchored_ray_anchors()
+    assert np.array_equal(now, expect)
+    assert (now[:40] == DEAD).all() and (now[40:90] != anchor[40:90]).sum() > 20 and now[90] == NONE
+    n1 = len(after)
+    group, mask = w.group[:n1].copy(), w.mask[:n1].copy()
+    group[dst], mask[dst] = w.group[src], w.mask[src]
+    q1 = [expect, *q[1:]]
+    for _ in range(2):
+        ow.transform_system()
+        t.run(ANCH); bare.run(FLAGS)
+        same_world(t, ow)
+        mn, mx = ow.world_aabbs()
+        want = ar.cast(oracle, mn, mx, group, mask, ow.world_matrices(), *q1)
+        got = t.anchored_ray_hits()
+        compare(got, want)
+        assert (got["hit"][:40] == 0).all() and want["hit"][40:90].sum() > 3    # dead rays miss, relocated anchors still answer
+    assert t.learn_ticks() == bare.learn_ticks()
+    t.close(); bare.close(); ow.close()
+
+
+# ---- 8. errors ------------------------------------------------------------------------------------------------------
+def test_anchored_ray_api_errors(oracle):
+    w = worlds.random_world(300, seed=112, spread=40.0)
+    ow = worlds.oracle_world(oracle, w, camera=False); ow.transform_system()
+    t = WorldTick.from_world(w, broadphase=True)
+    assert t.lib.scTickRun(t.ctx, capi.XFORM | capi.ANCHORED_RAYS) == 0
+    assert b"SC_TICK_ANCHORED_RAYS needs SC_TICK_BROADPHASE" in t.lib.scTickGetLastError(t.ctx)
+    t.run(FLAGS)
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_ANCHORED_RAYS"):
+        t.anchored_ray_hits()
+    t.run(ANCH)                                                                  # an empty set is fine
+    assert len(t.anchored_ray_hits()) == 0 and len(t.anchored_ray_anchors()) == 0
+    rng = np.random.default_rng(113)
+    k = 64
+    q = [rng.integers(0, w.n, k).astype(np.uint32), *local_rays(rng, k)]
+    t.set_anchored_rays(*q)
+    t.run(ANCH)
+    same_world(t, ow)
+    want = witness(oracle, w, ow, q)
+    assert 5 < want["hit"].sum() < k
+    compare(t.anchored_ray_hits(), want)
+    # refused sets: non-finite origins, directions and lengths, a negative length, null arrays; the previous set stays
+    for arg, idx, bad, msg in ((1, (5, 0), np.nan, "finite"), (1, (7, 2), np.inf, "finite"), (2, (0, 1), -np.inf, "finite"),
+                               (2, (3, 0), np.nan, "finite"), (3, (9,), np.inf, "finite"), (3, (2,), np.nan, "finite"),
+                               (3, (1,), -0.5, "max_dist must be >= 0")):
+        broken = [x.copy() for x in q]
+        broken[arg][idx] = bad
+        with pytest.raises(capi.ScTickError, match=msg):
+            t.set_anchored_rays(*broken)
+    a, l, v, md, mk = (x.ctypes.data_as(p) for x, p in zip(q, (capi.U32P, capi.F32P, capi.F32P, capi.F32P, capi.U32P)))
+    for args in ((None, l, v, md, mk), (a, None, v, md, mk), (a, l, None, md, mk), (a, l, v, None, mk), (a, l, v, md, None)):
+        assert t.lib.scTickSetAnchoredRays(t.ctx, k, *args, None) == 0
+        assert b"null argument" in t.lib.scTickGetLastError(t.ctx)
+    out = np.zeros(4, np.uint32)
+    assert t.lib.scTickReadAnchoredRays(t.ctx, k - 2, 4, out.ctypes.data_as(capi.U32P)) == 0
+    assert np.array_equal(t.anchored_ray_anchors(), q[0])
+    t.run(ANCH)
+    compare(t.anchored_ray_hits(), want)
+    t.set_anchored_rays(*[x[:0] for x in q])                                     # count 0 clears the set
+    t.run(ANCH)
+    assert len(t.anchored_ray_hits()) == 0
+    t.close(); ow.close()

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Cost of the ray batch inside the tick: config-5 world, 1M entities, one front ray per vehicle
 as the traffic AI casts it (sc_traffic_ai.cpp:303-319), tick time with and without SC_TICK_RAYS; then, on the same world in the
-same process, 4096 capsule sweeps (radius 0.4 m, half height 0.5 m, 20 m along the same headings) with SC_TICK_SWEEPS."""
+same process, 4096 capsule sweeps (radius 0.4 m, half height 0.5 m, 20 m along the same headings) with SC_TICK_SWEEPS; then 4096
+entity-anchored rays of 20 m riding on the vehicles (the same probe given in each vehicle's local frame) with SC_TICK_ANCHORED_RAYS:
+tick_us and tick_with_4096_rays_us of this same process are the yardsticks, anchored_minus_plain_us the difference."""
 import os, sys, time, json
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,4 +44,19 @@ for _ in range(n): t.run(fl)
 t.sync()
 out["tick_with_4096_sweeps_us"] = round((time.perf_counter() - t0) / n * 1e6, 2)
 out["tick_with_4096_sweeps_hits"] = int(t.sweep_hits()["hit"].sum())
+# the anchored leg: the front ray of the first 4096 vehicles in their own frames -- 1.7 m ahead, 0.6 m up in world metres, along local +z
+t.set_sweep_queries(o[:0], o[:0], np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.uint32))
+local = (np.float32([0.0, 0.6, 1.7]) / w.scale[veh[:k]]).astype(np.float32)
+t.set_anchored_rays(veh[:k].astype(np.uint32), local, np.tile(np.float32([0, 0, 1]), (k, 1)), np.full(k, 20.0, np.float32), np.full(k, 1, np.uint32))
+fl = capi.FULL | capi.PRODUCE_NEXT | capi.ANCHORED_RAYS
+for _ in range(20): t.run(fl)
+t.sync()
+learn = t.learn_ticks()
+t0 = time.perf_counter()
+for _ in range(n): t.run(fl)
+t.sync()
+out["tick_with_4096_anchored_rays_us"] = round((time.perf_counter() - t0) / n * 1e6, 2)
+out["tick_with_4096_anchored_rays_hits"] = int(t.anchored_ray_hits()["hit"].sum())
+out["anchored_learn_ticks_while_timed"] = t.learn_ticks() - learn
+out["anchored_minus_plain_us"] = round(out["tick_with_4096_anchored_rays_us"] - out["tick_with_4096_rays_us"], 2)
 print(json.dumps(out))
