@@ -60,6 +60,7 @@ enum {
                                       scTickRun.  Results of this run are unaffected; positions read back are already the next frame's. */
   SC_TICK_SWEEPS      = 1u << 10,  /* with BROADPHASE: answer the capsule sweeps set by scTickSetSweepQueries against this tick's boxes */
   SC_TICK_ANCHORED_RAYS = 1u << 11, /* with BROADPHASE: answer the entity-anchored rays set by scTickSetAnchoredRays against this tick's boxes */
+  SC_TICK_PAIR_EVENTS = 1u << 12,  /* with BROADPHASE: report which pairs begun and which ended since the last run with this flag (scTickSetPairEvents) */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -686,6 +687,47 @@ int scTickSetAnchoredRays(ScTickContext* ctx, uint32_t count, const uint32_t* an
 int scTickReadAnchoredRayHits(ScTickContext* ctx, ScTickRayHit* hits, uint32_t capacity, uint32_t* count);
 /* the anchors of rays first .. first + count - 1 as they stand now (after removals); host-side, no read-back */
 int scTickReadAnchoredRays(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
+
+/* ---- pair events: the tick-to-tick difference of the pair set ----
+ * What a broadphase hands its narrow phase besides "the pairs of this tick": Bullet's btDbvtBroadphase (behind sc_physics.cpp:218-225) keeps
+ * an overlapping-pair cache and reports pairs as they are ADDED and REMOVED (btOverlappingPairCache::addOverlappingPair /
+ * removeOverlappingPair).  scTickReadPairs returns the whole set on every tick; a host that keeps contact caches or trigger enter / exit
+ * would diff two such lists on the CPU.  With pair events the device remembers the set and reports the difference.  This build's OWN SPEC:
+ *   scTickSetPairEvents(max_tracked_pairs, max_events) enables them (and sizes every buffer; (0, 0) switches them off and frees the buffers).
+ *   The context then remembers the pair set of the last run that carried SC_TICK_PAIR_EVENTS.  A run with the flag reports
+ *     begun   the pairs of this tick's set that are not in the remembered set
+ *     ended   the pairs of the remembered set that are not in this tick's set
+ *   and then remembers its own set.  Pairs look as in scTickReadPairs: ids a < b, id = rank << 24 | dense index.  The order inside a list
+ *   is unspecified.  Runs without the flag leave the remembered set alone: the next flagged run diffs against the last flagged one.
+ *   RESYNC     begun = every pair of this tick, ended = nothing, resync = 1: on the first flagged run after enabling, after anything that
+ *              renames or invalidates dense indices (scTickRemoveEntities, a shrinking scTickSetEntityCount), and after an overflow tick.
+ *              Appending entities forces no resync, nor do topology, layer or collider uploads: their effect arrives as ordinary events.
+ *   OVERFLOW   this tick's set does not fit max_tracked_pairs, or the pair list itself was truncated (ScTickCounts::pairs_truncated):
+ *              overflow = 1, both lists empty with counts 0 (tracked and resync 0 too), the remembered set is dropped; the next flagged
+ *              run that fits is a resync tick.
+ *   TRUNCATED  more than max_events pairs begin, or end: begun / ended carry the true totals, each list holds max_events valid members,
+ *              events_truncated = 1.  The remembered set is complete all the same -- the next tick's events are right -- and the host
+ *              recovers this tick with scTickReadPairs.
+ *   Nothing is lost silently: every loss sets one of the three flags.
+ * The events are formed on the device behind the pair search, on its stream (after scTickRunPairs in a split flow): no host round trip,
+ * and the launches replay from a captured graph.  Device memory: two tables of slots x 8 bytes, slots = the power of two >=
+ * 2 x max_tracked_pairs, plus slots / 4 bytes of marks, plus 2 x max_events x 8 bytes.  A context that never enables them allocates and
+ * launches exactly what it did without this call.
+ * scTickRun / scTickTileStep fail for SC_TICK_PAIR_EVENTS without SC_TICK_BROADPHASE, without a prior scTickSetPairEvents, or on a
+ * pipelined context (scTickSetPipelined / scTickSetPairsStream: its tick parities overlap in time).  scTickReadPairEvents fails when the
+ * last run did not carry the flag and while scTickRunPairs is pending. */
+typedef struct ScTickPairEventInfo
+{
+  uint32_t begun, ended;       /* pairs that begun / ended this tick (true totals: may exceed max_events, and the caller's capacities) */
+  uint32_t tracked;            /* size of the remembered set after this tick */
+  uint32_t resync;             /* 1 = nothing was remembered: begun is this tick's whole set */
+  uint32_t overflow;           /* 1 = the set did not fit: nothing is listed, nothing is remembered */
+  uint32_t events_truncated;   /* 1 = begun or ended exceeds max_events */
+} ScTickPairEventInfo;
+int scTickSetPairEvents(ScTickContext* ctx, uint32_t max_tracked_pairs, uint32_t max_events);
+/* begun2 / ended2: [cap][2] (a, b), either may be NULL with capacity 0; min(count, max_events, capacity) pairs are written to each.
+ * Synchronises; copies the 24 bytes of `info` and the listed pairs, nothing else. */
+int scTickReadPairEvents(ScTickContext* ctx, uint32_t* begun2, uint32_t begun_cap, uint32_t* ended2, uint32_t ended_cap, ScTickPairEventInfo* info);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SC_TICK_LIB") or os.path.join(HERE, "libsc_tick.so") 
 XFORM, CULL, BROADPHASE, CULLED_LIST, DRAWS, DENSE_AABBS, SPLIT_PAIRS, SORT_DRAWS, RAYS, PRODUCE_NEXT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 SWEEPS = 1 << 10
 ANCHORED_RAYS = 1 << 11
+PAIR_EVENTS = 1 << 12         # SC_TICK_PAIR_EVENTS: which pairs begun / ended since the last run with this flag (scTickSetPairEvents)
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
@@ -57,6 +58,10 @@ class RayHit(C.Structure):
 class SweepHit(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("id", C.c_uint32), ("distance", C.c_float), ("position", C.c_float * 3),
                 ("normal", C.c_float * 3), ("layer", C.c_uint32), ("travel", C.c_float), ("pad", C.c_uint32)]
+
+
+class PairEventInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("begun", "ended", "tracked", "resync", "overflow", "events_truncated")]
 
 
 class Frame(C.Structure):
@@ -190,6 +195,8 @@ SYMBOLS = {
     "scTickSetAnchoredRays": (C.c_int, [_CTX, C.c_uint32, U32P, F32P, F32P, F32P, U32P, U8P]),
     "scTickReadAnchoredRayHits": (C.c_int, [_CTX, C.POINTER(RayHit), C.c_uint32, U32P]),
     "scTickReadAnchoredRays": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
+    "scTickSetPairEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "scTickReadPairEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairEventInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

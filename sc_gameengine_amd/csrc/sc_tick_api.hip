@@ -115,6 +115,11 @@ struct ScTickContext
   AnchoredRayState anchored{};
   uint32_t anchoredCap = 0;
   std::vector<uint2> hAnchor;
+  // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
+  // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
+  PairEventState pairEvents{};
+  void* pairEventSlab = nullptr; size_t pairEventSlabBytes = 0;
+  bool pairEventsResyncAgain = false;      // ids were renamed between the halves of a split tick: forget again what its pair half remembers
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
 
@@ -616,6 +621,19 @@ AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
   return a;
 }
 
+// pair events: forget the remembered set (dense indices were renamed, or are no longer valid) -- the next flagged tick is a resync tick.
+// Queued on the tick stream, behind the ticks already issued.
+bool resyncPairEvents(ScTickContext* c)
+{
+  if (!c->pairEventSlab) return true;
+  const hipError_t e = hipMemsetAsync(c->pairEventSlab, 0, c->pairEventSlabBytes, c->stream);
+  if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair events)", e);
+  // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
+  // the rename -- runPendingPairs forgets it again behind that half
+  if (c->pairsPending && (c->pendingParams.flags & SC_TICK_PAIR_EVENTS)) c->pairEventsResyncAgain = true;
+  return true;
+}
+
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
 // the tick before it clears those counters.  That half finished long ago unless the exchange is very slow; wait for it.
 // (Cross-stream: never captured.)
@@ -754,6 +772,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
+    if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // the pair set is complete: what begun, what ended
   } else {
     const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
@@ -773,7 +792,10 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
           if (flags & kFlagDeferredReset) launchResetParity(ds, p.resetParity, c->stream);      // (the fused launch does it itself)
         }
       }
-      else { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
+      else {
+        { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
+        if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);
+      }
     }
   }
   // (not folded -- sorted draws, split flows, a budget beyond the block: with the frame read-back on and a plain draw list whose
@@ -1016,6 +1038,7 @@ int scTickSetEntityCount(ScTickContext* c, uint32_t count)
   if (before == count) return 1;
   if (!bind(c)) return 0;
   if (count > before && !resetColliders(c, before, count - before)) return 0;      // new indices start without a collider of their own
+  if (count < before && !resyncPairEvents(c)) return 0;                            // remembered pairs may name indices that are gone
   // the wave-tiles that gained or lost entities (bounds classes: lanes at or past n are not part of a tile)
   if (!refreshTiles(c, std::min(before, count), std::max(before, count))) return 0;
   return sync(c) ? 1 : 0;
@@ -1414,6 +1437,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   }
   c->n = n1;
   c->topoEpoch++;
+  if (!resyncPairEvents(c)) return 0;                 // dense indices were renamed: the remembered pair set names entities that moved or are gone
   // anchored rays follow their entity: a relocated anchor is renamed, a removed one becomes dead (it misses from now on); the words
   // go to the device behind whatever is queued, and the set keeps its size -- no epoch bump of its own
   if (c->anchored.count) {
@@ -1600,7 +1624,10 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, ps);   // ... as do the capsule sweeps
   if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), ps);   // ... and the anchored rays, as the tick half resolved them
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
-  return launchPairs(ds, pp, ps, done);
+  // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
+  const bool rode = launchPairs(ds, pp, ps, done);
+  if (pp.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, pp, c->pairEvents, ps);      // behind the pair search, on its stream
+  return rode;
 }
 
 // Can any two colliders this context may ever hold in its bins meet (Bullet's filter, sc_physics.cpp:700-712 via SURVEY 8a)?  From the
@@ -1639,6 +1666,11 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   // An empty context without a broadphase has nothing to launch: the per-tick counts read as zero.  With the broadphase
   // the stages still run (every kernel copes with n == 0): an emptied tile of a multi-GPU world must rewrite its border
   // messages (header-only) and take part in the exchange, the merge and the pair search of the boxes its neighbours send.
+  if (flags & SC_TICK_PAIR_EVENTS) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's pair set)");
+    if (!c->pairEvents.ctl) return fail(c, "SC_TICK_PAIR_EVENTS needs scTickSetPairEvents first");
+    if (c->pairsStream) return fail(c, "SC_TICK_PAIR_EVENTS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its tick parities overlap in time");
+  }
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
     c->lastTickTail = false;
@@ -1770,6 +1802,11 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
     Scoped s(c, SC_TICK_K_PAIRS, c->lastTickSampled);      // (the tick's sampling decision: tickIndex has moved on)
     enqueuePairHalf(c, c->pendingParams, ps);
   }
+  if (c->pairEventsResyncAgain) {                     // (in-order flows only: the pair half ran on the tick stream)
+    c->pairEventsResyncAgain = false;
+    c->pairsPending = false;
+    if (!resyncPairEvents(c)) return 0;
+  }
   c->pairsPending = false;
   c->lastParity = c->parity;
   c->parity = c->pairsStream ? (c->parity + 1u) % c->pipeDepth : (c->parity ^ 1u);
@@ -1792,6 +1829,7 @@ int scTickSetTile(ScTickContext* c, uint32_t rank, uint32_t neighbourMask)
   if (rank > 127u) return fail(c, "rank must be < 128 (7 id bits)");
   // records in remembered slots carry the rank in their ids, and which slots are written on every tick depends on the ring's ownership
   if (c->rank != rank || c->neighbourMask != (neighbourMask & 0xFFu)) { c->homeValid = false; c->topoEpoch++; }
+  if (c->rank != rank && (!bind(c) || !resyncPairEvents(c))) return 0;      // pair ids carry the rank: remembered pairs would name the old one
   c->rank = rank;
   c->neighbourMask = neighbourMask & 0xFFu;
   return 1;
@@ -2287,6 +2325,54 @@ int scTickReadSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, ui
   static_assert(sizeof(ScTickSweepHit) == sizeof(SweepHit48) && offsetof(ScTickSweepHit, travel) == offsetof(SweepHit48, travel), "sweep hit layouts differ");
   return readQueryHits(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS", "sweep hits are ready after scTickRunPairs",
                        c ? c->sweeps.hits : nullptr, c ? c->sweeps.count : 0u, hits, cap, count);
+}
+
+int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
+{
+  if (!c) return 0;
+  if ((maxTracked == 0u) != (maxEvents == 0u)) return fail(c, "pair events: max_tracked_pairs and max_events are both positive, or both 0 (off)");
+  if (maxTracked && !c->sectors) return fail(c, "the context has no broadphase");
+  if (maxTracked > (1u << 27) || maxEvents > (1u << 27)) return fail(c, "pair events: at most 2^27 tracked pairs and 2^27 events");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  PairEventState& e = c->pairEvents;
+  dfree(c, c->pairEventSlab); dfree(c, e.info); dfree(c, e.begun); dfree(c, e.ended);
+  e = PairEventState{}; c->pairEventSlab = nullptr; c->pairEventSlabBytes = 0;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); the pair search itself is not concerned
+  if (!maxTracked) return 1;
+  uint32_t slots = 64u;
+  while (slots < 2u * maxTracked) slots <<= 1;
+  // one allocation: table 0, table 1, marks 0, marks 1, control words
+  const size_t tableBytes = (size_t)slots * sizeof(unsigned long long), markBytes = (size_t)(slots / 32u) * sizeof(uint32_t);
+  const size_t bytes = 2u * tableBytes + 2u * markBytes + kPeCtlWords * sizeof(uint32_t);
+  char* slab = nullptr;
+  if (!dalloc(c, slab, bytes)) return 0;
+  c->pairEventSlab = slab; c->pairEventSlabBytes = bytes;
+  if (!dalloc(c, e.info, kPeInfoWords) || !dalloc(c, e.begun, maxEvents, false) || !dalloc(c, e.ended, maxEvents, false)) return 0;
+  e.table[0] = reinterpret_cast<unsigned long long*>(slab); e.table[1] = reinterpret_cast<unsigned long long*>(slab + tableBytes);
+  e.marks[0] = reinterpret_cast<uint32_t*>(slab + 2u * tableBytes); e.marks[1] = reinterpret_cast<uint32_t*>(slab + 2u * tableBytes + markBytes);
+  e.ctl = reinterpret_cast<uint32_t*>(slab + 2u * tableBytes + 2u * markBytes);
+  e.slots = slots; e.maxTracked = maxTracked; e.maxEvents = maxEvents;
+  return 1;
+}
+
+int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickPairEventInfo* info)
+{
+  static_assert(sizeof(ScTickPairEventInfo) == 6u * sizeof(uint32_t) && kPeInfoWords >= 6u, "the device writes the report word by word");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_PAIR_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_EVENTS");
+  if (c->pairsPending) return fail(c, "pair events are ready after scTickRunPairs");
+  const PairEventState& e = c->pairEvents;
+  if (!e.ctl) return fail(c, "pair events were switched off since the last scTickRun");
+  if (!joinPairs(c)) return 0;
+  if (!d2h(c, info, e.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t nb = std::min(std::min(info->begun, e.maxEvents), begun2 ? begunCap : 0u);
+  const uint32_t ne = std::min(std::min(info->ended, e.maxEvents), ended2 ? endedCap : 0u);
+  if (nb && !d2h(c, begun2, e.begun, (size_t)nb * sizeof(uint2))) return 0;
+  if (ne && !d2h(c, ended2, e.ended, (size_t)ne * sizeof(uint2))) return 0;
+  if ((nb || ne) && !sync(c)) return 0;
+  return 1;
 }
 
 int scTickSetAnchoredRays(ScTickContext* c, uint32_t count, const uint32_t* anchor, const float* localOrigin3, const float* localDir3,

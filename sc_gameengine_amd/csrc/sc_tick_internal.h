@@ -335,6 +335,24 @@ struct AnchoredRayState {
 void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);              // resolve + cast
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);      // tick half: resolve
 void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s); // pair half: cast
+// ---- pair begin / end events (sc_tick_pair_events.hip; include/sc_tick.h "pair events"): the difference between this tick's pair set and
+// the set of the last tick that ran with SC_TICK_PAIR_EVENTS, formed on the device behind the pair search.  A kernel argument of its own.
+// Two open-addressing tables of 64-bit keys a << 32 | b (0 = empty: a < b rules it out) are used in turn: the one holding the remembered
+// set ("previous") is probed, marked and -- by the sweep -- emptied, the other ("current") is filled and becomes the remembered set.
+struct PairEventState {
+  unsigned long long* table[2];   // [slots] each
+  uint32_t* marks[2];             // [slots / 32] each: bit = "this slot's pair is in this tick's set too"
+  uint32_t* ctl;                  // kPe* words below; tables, marks and ctl are ONE allocation: zero bytes all over = nothing remembered
+  uint32_t* info;                 // what the last flagged tick reports (== ScTickPairEventInfo)
+  uint2* begun; uint2* ended;     // [maxEvents] each
+  uint32_t slots;                 // power of two >= 2 * maxTracked (and >= 64)
+  uint32_t maxTracked, maxEvents;
+};
+// ctl words: which table is filled this tick; 1 = the other one holds a remembered set (0: the next flagged tick is a resync tick);
+// the tick's running counts; != 0: this tick's set does not fit (or a probe ran out of slots)
+constexpr uint32_t kPeCur = 0, kPeValid = 1, kPeBegun = 2, kPeEnded = 3, kPeTracked = 4, kPeOverflow = 5, kPeCtlWords = 16;
+constexpr uint32_t kPeInfoWords = 8;
+void launchPairEvents(const DeviceState& d, const TickParams& p, const PairEventState& e, hipStream_t s);
 void launchAgentFrontRays(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchAgentRaySnapshot(const DeviceState& d, const TickParams& p, hipStream_t s);         // tick half: list the agents, note their rays
 void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p, hipStream_t s); // pair half, behind the merge: cast them

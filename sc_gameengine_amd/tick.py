@@ -656,6 +656,23 @@ class WorldTick:
         out = out[out[:, 1] != 0xFFFFFFFF]              # a full shard segment keeps fewer than were found
         return out.copy(), cnt.value
 
+    # ---- pair events: which pairs begun / ended since the last run with capi.PAIR_EVENTS ----
+    def set_pair_events(self, max_tracked, max_events):
+        """Remember the pair set on the device and report its tick-to-tick difference on every run with capi.PAIR_EVENTS
+        (scTickSetPairEvents): room for max_tracked pairs in the set and max_events pairs in each list; (0, 0) switches it off."""
+        self._ok(self.lib.scTickSetPairEvents(self.ctx, int(max_tracked), int(max_events)), "scTickSetPairEvents")
+        self._max_events = int(max_events)
+
+    def pair_events(self):
+        """(begun[k, 2], ended[m, 2], info) of the last run with capi.PAIR_EVENTS: uint32 ids a < b in unspecified order; info is a dict
+        (begun, ended, tracked, resync, overflow, events_truncated) whose begun / ended are the true totals -- the lists hold at most max_events."""
+        cap = getattr(self, "_max_events", 0)
+        b, e = np.zeros((max(cap, 1), 2), np.uint32), np.zeros((max(cap, 1), 2), np.uint32)
+        info = capi.PairEventInfo()
+        self._ok(self.lib.scTickReadPairEvents(self.ctx, _u(b), cap, _u(e), cap, C.byref(info)), "scTickReadPairEvents")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairEventInfo._fields_}
+        return b[:min(out["begun"], cap)].copy(), e[:min(out["ended"], cap)].copy(), out
+
     def draws(self):
         cnt = C.c_uint32()
         self._ok(self.lib.scTickReadDraws(self.ctx, None, 0, C.byref(cnt)), "scTickReadDraws")

@@ -3,7 +3,9 @@
 as the traffic AI casts it (sc_traffic_ai.cpp:303-319), tick time with and without SC_TICK_RAYS; then, on the same world in the
 same process, 4096 capsule sweeps (radius 0.4 m, half height 0.5 m, 20 m along the same headings) with SC_TICK_SWEEPS; then 4096
 entity-anchored rays of 20 m riding on the vehicles (the same probe given in each vehicle's local frame) with SC_TICK_ANCHORED_RAYS:
-tick_us and tick_with_4096_rays_us of this same process are the yardsticks, anchored_minus_plain_us the difference."""
+tick_us and tick_with_4096_rays_us of this same process are the yardsticks, anchored_minus_plain_us the difference; then the pair-events
+leg: the same tick without queries, SC_TICK_PAIR_EVENTS off and on (room for 2^17 tracked pairs and 2^14 events), and what one frame
+reads back through scTickReadPairEvents against scTickReadPairs -- bytes, and the host time of the one call."""
 import os, sys, time, json
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -59,4 +61,20 @@ out["tick_with_4096_anchored_rays_us"] = round((time.perf_counter() - t0) / n * 
 out["tick_with_4096_anchored_rays_hits"] = int(t.anchored_ray_hits()["hit"].sum())
 out["anchored_learn_ticks_while_timed"] = t.learn_ticks() - learn
 out["anchored_minus_plain_us"] = round(out["tick_with_4096_anchored_rays_us"] - out["tick_with_4096_rays_us"], 2)
+# the pair-events leg: no queries, the flag off and on in the same process; then one frame's read-back either way
+fl = capi.FULL | capi.PRODUCE_NEXT
+t.set_pair_events(1 << 17, 1 << 14)
+for name, f in (("tick_pair_events_off_us", fl), ("tick_pair_events_on_us", fl | capi.PAIR_EVENTS)):
+    for _ in range(20): t.run(f)
+    t.sync()
+    t0 = time.perf_counter()
+    for _ in range(n): t.run(f)
+    t.sync()
+    out[name] = round((time.perf_counter() - t0) / n * 1e6, 2)
+out["pair_events_minus_off_us"] = round(out["tick_pair_events_on_us"] - out["tick_pair_events_off_us"], 2)
+t0 = time.perf_counter(); b, e, info = t.pair_events(); out["read_pair_events_call_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+t0 = time.perf_counter(); got, total = t.pairs(); out["read_pairs_call_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+out["pair_events_info"] = info
+out["read_pair_events_bytes"] = 24 + 8 * (len(b) + len(e))
+out["read_pairs_bytes"] = 8 * len(got)
 print(json.dumps(out))
