@@ -61,6 +61,7 @@ enum {
   SC_TICK_SWEEPS      = 1u << 10,  /* with BROADPHASE: answer the capsule sweeps set by scTickSetSweepQueries against this tick's boxes */
   SC_TICK_ANCHORED_RAYS = 1u << 11, /* with BROADPHASE: answer the entity-anchored rays set by scTickSetAnchoredRays against this tick's boxes */
   SC_TICK_PAIR_EVENTS = 1u << 12,  /* with BROADPHASE: report which pairs begun and which ended since the last run with this flag (scTickSetPairEvents) */
+  SC_TICK_BIND_RUNS   = 1u << 13,  /* with DRAWS | SORT_DRAWS: also the bind runs of the sorted list and the material touch set (scTickSetBindRuns) */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -501,6 +502,71 @@ typedef struct ScTickFrame
 } ScTickFrame;
 int scTickSetFrameReadback(ScTickContext* ctx, uint32_t max_visible, uint32_t max_draws);
 int scTickAcquireFrame(ScTickContext* ctx, uint32_t frames_back, ScTickFrame* out);
+
+/* ---- bind runs of the sorted draw list, and the material touch set ----
+ * What a renderer does with the sorted list, found on the device behind the sort.  The specification is the reference's own loop and
+ * its own touchMaterial, not one of this build's.
+ *
+ * RUNS.  VkRenderer::recordCommandBuffer walks the sorted list, binds the pipeline when it changes, the material's descriptor set when
+ * it changes, the mesh buffers when they change, and issues one vkCmdDrawIndexed per item (src/engine/src/sc_vk.cpp:1866-1911).  A run
+ * is a maximal stretch of equal key (pipeline, material, mesh) in the first draws_sorted items of the list scTickReadDraws returns.  The
+ * runs come in list order: `first` ascends, the counts sum to draws_sorted.  A host that instances issues one instanced or indirect draw
+ * per run instead of `count` draws.  `binds` is the state machine of that loop (:1866-1907): run 0 has all three bits; for every later
+ * run, against the run before it,
+ *     bit 0  bind pipeline   `pipeline` differs (boundPipeline != targetPipeline, which also resets boundMesh and boundMaterial)
+ *     bit 1  bind material   bit 0 is set, or `material` differs
+ *     bit 2  bind mesh       bit 0 is set, or `mesh` differs
+ * so two adjacent runs with different materials and the same mesh do NOT bind the mesh again -- the sort order produces that case.
+ * PipelineId has two values, each mapped to its own VkPipeline (sc_assets.h:22-26): comparing ids is comparing pipelines.
+ * A mesh whose indexCount is 0 is skipped by the reference before its mesh bind (:1898-1899).  The library does not know index counts:
+ * a consumer that skips such runs reproduces the reference's binds (the only adjacent run with the same mesh is empty as well).
+ * Equal keys keep the order of the stable sort (scTickSetDrawSortTable); the reference's std::sort leaves it unspecified.
+ *
+ * TOUCHES.  RenderPrepStreamingSystem calls assets->touchMaterial(rm->materialId) for every draw it emits (sc_world_partition.cpp:
+ * 1322-1326), which keeps the texture streamer's LRU alive (sc_assets.cpp:441-455).  Bit h of the bitmap is set if and only if some
+ * EMITTED draw -- the first draws_emitted entries of the visible list: behind the budget, before the renderer's filter -- has
+ * materialId == h and h < material_count.  Like touchMaterial (sc_assets.cpp:441-445) it does not care whether the draw's mesh handle is
+ * valid and ignores handles past the table; a handle below material_count whose table entry is 0xFF is touched all the same.  Draws
+ * dropped by the budget touch nothing.  touchMesh is an empty function in the reference (sc_assets.h:151): there is no mesh bitmap.
+ * The bitmap is rebuilt from zero on every flagged run; material_count is the one of the last scTickSetDrawSortTable.
+ *
+ * scTickSetBindRuns(max_runs) sizes the run table (0 = off, frees it); it needs scTickSetDrawSortTable first and drops captured graphs.
+ * A later scTickSetDrawSortTable with another material_count resizes the bitmap.  scTickRun with SC_TICK_BIND_RUNS fails without
+ * scTickSetBindRuns and without SC_TICK_DRAWS | SC_TICK_SORT_DRAWS in the same run.  The launches sit behind the sort on the tick's
+ * stream and replay from a captured graph; a run without the flag launches what it launched before this call existed. */
+typedef struct ScTickBindRun            /* 24 bytes */
+{
+  uint32_t first, count;                /* items [first, first+count) of the sorted list scTickReadDraws returns */
+  uint32_t pipeline, material, mesh;    /* the run's key */
+  uint32_t binds;                       /* bit 0: bind pipeline, bit 1: bind material, bit 2: bind mesh -- before this run's first draw */
+} ScTickBindRun;
+typedef struct ScTickBindInfo
+{
+  uint32_t runs;               /* runs found (may exceed max_runs; the table then holds the first max_runs) */
+  uint32_t runs_truncated;     /* 1 if runs > max_runs */
+  uint32_t draws;              /* == ScTickCounts::draws_sorted: sum of count over ALL runs */
+  uint32_t pipeline_binds, material_binds, mesh_binds;   /* over ALL runs, truncated or not */
+  uint32_t materials_touched;  /* set bits of the touch bitmap */
+  uint32_t touch_words;        /* (material_count + 31) / 32 at the time of the run */
+} ScTickBindInfo;
+int scTickSetBindRuns(ScTickContext* ctx, uint32_t max_runs);
+/* results of the last scTickRun(... | SC_TICK_BIND_RUNS); each synchronises.  runs may be NULL with capacity 0: min(info->runs,
+ * max_runs, capacity) rows are written.  words: bit h % 32 of word h / 32; *word_count = touch_words, min(that, word_capacity) are written. */
+int scTickReadBindRuns(ScTickContext* ctx, ScTickBindRun* runs, uint32_t capacity, ScTickBindInfo* info);
+int scTickReadMaterialTouches(ScTickContext* ctx, uint32_t* words, uint32_t word_capacity, uint32_t* word_count);
+/* Overlapped read-back, next to scTickSetFrameReadback: with both switched on (in either order; switching either on or off
+ * reallocates) every run with SC_TICK_BIND_RUNS stages report, table and bitmap into a double-buffered block of their own, copied on
+ * the frame's copy stream behind the frame's block: scTickAcquireFrame and scTickAcquireFrameBinds of one frame wait on the same event.
+ * A run without the flag stages nothing: its runs_in_buffer is 0 and its info all zeros.  Fails without both features. */
+typedef struct ScTickFrameBinds
+{
+  uint64_t tick;                        /* == ScTickFrame::tick of the same frames_back */
+  ScTickBindInfo info;
+  uint32_t runs_in_buffer;              /* min(info.runs, max_runs); 0 when the run had no SC_TICK_BIND_RUNS */
+  const ScTickBindRun* runs;            /* pinned host memory, valid as long as the frame's own pointers */
+  const uint32_t* touch_words;          /* info.touch_words words */
+} ScTickFrameBinds;
+int scTickAcquireFrameBinds(ScTickContext* ctx, uint32_t frames_back, ScTickFrameBinds* out);
 
 /* ---- host-side helpers (no GPU work) ----
  * CameraSystem stays on the host (O(#cameras), sc_ecs.cpp:213-272).  These restate the four sc_math

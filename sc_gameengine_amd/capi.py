@@ -14,6 +14,7 @@ XFORM, CULL, BROADPHASE, CULLED_LIST, DRAWS, DENSE_AABBS, SPLIT_PAIRS, SORT_DRAW
 SWEEPS = 1 << 10
 ANCHORED_RAYS = 1 << 11
 PAIR_EVENTS = 1 << 12         # SC_TICK_PAIR_EVENTS: which pairs begun / ended since the last run with this flag (scTickSetPairEvents)
+BIND_RUNS = 1 << 13           # SC_TICK_BIND_RUNS: with DRAWS | SORT_DRAWS, the bind runs of the sorted list and the material touch set (scTickSetBindRuns)
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
@@ -69,6 +70,20 @@ class Frame(C.Structure):
                 ("draws_emitted", C.c_uint32), ("draws_dropped", C.c_uint32), ("draws_sorted", C.c_uint32),
                 ("visible_in_buffer", C.c_uint32), ("draws_in_buffer", C.c_uint32),
                 ("visible_indices", U32P), ("draws", C.POINTER(DrawItem))]
+
+
+class BindRun(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("first", "count", "pipeline", "material", "mesh", "binds")]
+
+
+class BindInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("runs", "runs_truncated", "draws", "pipeline_binds", "material_binds", "mesh_binds",
+                                          "materials_touched", "touch_words")]
+
+
+class FrameBinds(C.Structure):
+    _fields_ = [("tick", C.c_uint64), ("info", BindInfo), ("runs_in_buffer", C.c_uint32),
+                ("runs", C.POINTER(BindRun)), ("touch_words", U32P)]
 
 
 class LaneGraph(C.Structure):
@@ -159,6 +174,10 @@ SYMBOLS = {
     "scTickSetFrameProducer": (C.c_int, [_CTX, C.c_uint32, C.c_float]),
     "scTickSetFrameReadback": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "scTickAcquireFrame": (C.c_int, [_CTX, C.c_uint32, C.POINTER(Frame)]),
+    "scTickSetBindRuns": (C.c_int, [_CTX, C.c_uint32]),
+    "scTickReadBindRuns": (C.c_int, [_CTX, C.POINTER(BindRun), C.c_uint32, C.POINTER(BindInfo)]),
+    "scTickReadMaterialTouches": (C.c_int, [_CTX, U32P, C.c_uint32, U32P]),
+    "scTickAcquireFrameBinds": (C.c_int, [_CTX, C.c_uint32, C.POINTER(FrameBinds)]),
     "scTickSetLaneGraph": (C.c_int, [_CTX, C.POINTER(LaneGraph)]),
     "scTickSetLaneActive": (C.c_int, [_CTX, U32P, C.c_uint32, C.c_int]),
     "scTickUploadTrafficAgents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U8P, U32P, F32P, F32P, U8P, F32P]),

@@ -122,6 +122,10 @@ struct ScTickContext
   bool pairEventsResyncAgain = false;      // ids were renamed between the halves of a split tick: forget again what its pair half remembers
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
+  // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched); what the
+  // last flagged run was sized for, and whether it was the run of an empty context (nothing launched: the report reads as zeros)
+  BindRunState bind{};
+  uint32_t bindLastTouchWords = 0; bool bindLastEmpty = false;
 
   // profiling
   bool profiling = false;
@@ -189,6 +193,9 @@ struct ScTickContext
     uint32_t* dBlock[2] = {}; uint32_t* hBlock[2] = {};
     hipStream_t copyStream = nullptr; hipEvent_t staged[2] = {}, copied[2] = {};
     bool inFlight[2] = { false, false }; uint64_t frames = 0;
+    // bind runs next to the frame (scTickAcquireFrameBinds): [kBiWords report][max_runs rows][touch words], copied behind the frame's block
+    uint32_t* dBinds[2] = {}; uint32_t* hBinds[2] = {}; size_t bindBytes = 0;
+    bool bindsStaged[2] = { false, false };      // that frame's run carried SC_TICK_BIND_RUNS
   } rb;
   ncclComm_t comm = nullptr;
   uint32_t commSize = 0, commRank = 0;
@@ -673,6 +680,46 @@ bool raysInPairHalf(const ScTickContext* c, uint32_t flags)
   return c->sensors && c->halo && c->neighbourMask && !c->pairsStream && (flags & SC_TICK_SPLIT_PAIRS) && (flags & SC_TICK_BROADPHASE);
 }
 
+// Bind runs next to the frame read-back: the two staging blocks and their pinned copies exist while both features are on.  Called
+// by whichever of scTickSetBindRuns, scTickSetDrawSortTable and scTickSetFrameReadback changed a size (the tick stream is idle by then).
+bool reallocBindBlocks(ScTickContext* c)
+{
+  ScTickContext::FrameReadback& rb = c->rb;
+  if (rb.copyStream && hipStreamSynchronize(rb.copyStream) != hipSuccess) return fail(c, "hipStreamSynchronize (copy stream)");
+  for (int k = 0; k < 2; ++k) {
+    dfree(c, rb.dBinds[k]); rb.dBinds[k] = nullptr; rb.bindsStaged[k] = false;
+    if (rb.hBinds[k]) { hipHostFree(rb.hBinds[k]); rb.hBinds[k] = nullptr; }
+  }
+  rb.bindBytes = 0;
+  if (!rb.bytes || !c->bind.info) return true;
+  const size_t words = (size_t)kBiWords + (size_t)c->bind.maxRuns * 6u + c->bind.touchWords;
+  for (int k = 0; k < 2; ++k) {
+    if (!dalloc(c, rb.dBinds[k], words)) return false;
+    void* h = nullptr;
+    if (hipHostMalloc(&h, words * 4u, hipHostMallocDefault) != hipSuccess) return fail(c, "hipHostMalloc (bind runs)");
+    std::memset(h, 0, words * 4u);
+    rb.hBinds[k] = static_cast<uint32_t*>(h);
+  }
+  rb.bindBytes = words * 4u;
+  return true;
+}
+
+// the run table (one row more than reported: sc_tick_bindruns.hip), the report and -- sized by the sort table's material_count -- the bitmap.
+// The callers see to it that no captured graph keeps the old buffers.
+bool reallocBindRuns(ScTickContext* c, uint32_t maxRuns)
+{
+  BindRunState& b = c->bind;
+  dfree(c, b.runs); dfree(c, b.info);
+  b = BindRunState{};
+  if (maxRuns) {
+    const uint32_t touchWords = (c->sort.materialCount + 31u) / 32u;
+    if (!dalloc(c, b.runs, (size_t)maxRuns + 1u) || !dalloc(c, b.info, (size_t)kBiWords + touchWords)) return false;
+    b.touch = b.info + kBiWords;
+    b.maxRuns = maxRuns; b.touchWords = touchWords; b.materialCount = c->sort.materialCount;
+  }
+  return reallocBindBlocks(c);
+}
+
 // frame read-back: the block of this frame may still be read by the copy of two frames ago; the tick stream waits for it
 // (asked first: a satisfied wait costs a bubble too)
 void waitFrameBlock(ScTickContext* c)
@@ -803,22 +850,32 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   c->lastDraws = c->dDraws;
   if ((flags & SC_TICK_DRAWS) && !stagedEmit && !foldEmit) {
     const uint32_t budget = drawBudget;
-    if (flags & SC_TICK_SORT_DRAWS) launchSortedDraws(ds, c->sort, budget, (budget && budget < c->n) ? budget : c->n, c->dDraws, c->stream);
-    else launchEmitDraws(ds, budget, c->dDraws, c->stream);
+    const uint32_t bound = (budget && budget < c->n) ? budget : c->n;
+    if (flags & SC_TICK_SORT_DRAWS) {
+      launchSortedDraws(ds, c->sort, budget, bound, c->dDraws, c->stream);
+      if (flags & SC_TICK_BIND_RUNS) launchBindRuns(ds, c->sort, c->bind, bound, c->stream);      // the sorted keys are still in place
+    } else launchEmitDraws(ds, budget, c->dDraws, c->stream);
   }
   if (c->rb.bytes) {
     ScTickContext::FrameReadback& rb = c->rb;
     const uint32_t f = (uint32_t)(rb.frames & 1u);
     if (!stagedByEot) waitFrameBlock(c);                  // (the end-of-tick kernel's launch waited already)
     const uint32_t drawMode = (flags & SC_TICK_DRAWS) ? ((flags & SC_TICK_SORT_DRAWS) ? 2u : 1u) : 0u;
+    rb.bindsStaged[f] = false;
     if (stagedByEot) c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + rb.maxVisible;       // the end-of-tick kernel wrote the block
     else if (stagedEmit) {
       launchEmitDrawsStaged(ds, drawBudget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);
       c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + rb.maxVisible;       // what scTickReadDraws returns for this tick
-    } else launchStageFrame(ds, rb.dBlock[f], rb.maxVisible, rb.maxDraws, c->dDraws, drawMode, rb.frames, c->stream, rb.staged[f]);
+    } else {
+      // (a flagged run is a sorted one, so it comes through here: its bind block is staged ahead of the frame's, whose `staged` covers both)
+      rb.bindsStaged[f] = rb.bindBytes && (flags & SC_TICK_BIND_RUNS);
+      if (rb.bindsStaged[f]) launchStageBinds(c->bind, rb.dBinds[f], c->stream);
+      launchStageFrame(ds, rb.dBlock[f], rb.maxVisible, rb.maxDraws, c->dDraws, drawMode, rb.frames, c->stream, rb.staged[f]);
+    }
     // (`staged` rides on the staging dispatch: its completion signal, no marker packet on the tick queue)
     hipStreamWaitEvent(rb.copyStream, rb.staged[f], 0);
     hipMemcpyAsync(rb.hBlock[f], rb.dBlock[f], rb.bytes, hipMemcpyDeviceToHost, rb.copyStream);
+    if (rb.bindsStaged[f]) hipMemcpyAsync(rb.hBinds[f], rb.dBinds[f], rb.bindBytes, hipMemcpyDeviceToHost, rb.copyStream);      // before `copied`
     hipEventRecord(rb.copied[f], rb.copyStream);
     rb.inFlight[f] = true;
     rb.frames++;
@@ -1017,7 +1074,7 @@ void scTickDestroyContext(ScTickContext* c)
   for (uint32_t k = 0; k < kMaxParity; ++k) { if (c->packed[k]) hipEventDestroy(c->packed[k]); if (c->pairsDone[k]) hipEventDestroy(c->pairsDone[k]); }
   if (c->rb.copyStream) {
     hipStreamSynchronize(c->rb.copyStream);
-    for (int k = 0; k < 2; ++k) { if (c->rb.hBlock[k]) hipHostFree(c->rb.hBlock[k]); if (c->rb.staged[k]) hipEventDestroy(c->rb.staged[k]); if (c->rb.copied[k]) hipEventDestroy(c->rb.copied[k]); }
+    for (int k = 0; k < 2; ++k) { if (c->rb.hBinds[k]) hipHostFree(c->rb.hBinds[k]); if (c->rb.hBlock[k]) hipHostFree(c->rb.hBlock[k]); if (c->rb.staged[k]) hipEventDestroy(c->rb.staged[k]); if (c->rb.copied[k]) hipEventDestroy(c->rb.copied[k]); }
     hipStreamDestroy(c->rb.copyStream);
   }
   if (c->pairsStream) hipStreamSynchronize(c->pairsStream);
@@ -1535,6 +1592,7 @@ int scTickSetDrawSortTable(ScTickContext* c, const uint8_t* pipelineOfMaterial, 
   for (uint32_t b = 0; b < bytesOf(materialCount); ++b) st.shift[st.passes++] = 24u + 8u * b;
   st.shift[st.passes++] = 48u;
   c->topoEpoch++;                      // captured graphs hold the old pass list
+  if (c->bind.info && c->bind.materialCount != materialCount && !reallocBindRuns(c, c->bind.maxRuns)) return 0;      // the touch bitmap follows the table
   return 1;
 }
 
@@ -1670,6 +1728,14 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's pair set)");
     if (!c->pairEvents.ctl) return fail(c, "SC_TICK_PAIR_EVENTS needs scTickSetPairEvents first");
     if (c->pairsStream) return fail(c, "SC_TICK_PAIR_EVENTS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its tick parities overlap in time");
+  }
+  if (flags & SC_TICK_BIND_RUNS) {
+    if ((flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS)) != (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS))
+      return fail(c, "SC_TICK_BIND_RUNS needs SC_TICK_DRAWS | SC_TICK_SORT_DRAWS in the same run (the runs are those of the sorted list; scTickSetDrawSortTable)");
+    if (!c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
+    if (!c->bind.info) return fail(c, "SC_TICK_BIND_RUNS needs scTickSetBindRuns first");
+    c->bindLastTouchWords = c->bind.touchWords;
+    c->bindLastEmpty = c->n == 0 && !(flags & SC_TICK_BROADPHASE);
   }
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
@@ -2514,7 +2580,7 @@ int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDr
   if (rb.copyStream) HIP_OK(c, hipStreamSynchronize(rb.copyStream));
   for (int k = 0; k < 2; ++k) { dfree(c, rb.dBlock[k]); rb.dBlock[k] = nullptr; if (rb.hBlock[k]) { hipHostFree(rb.hBlock[k]); rb.hBlock[k] = nullptr; } rb.inFlight[k] = false; }
   rb.bytes = 0; rb.frames = 0; rb.maxVisible = rb.maxDraws = 0;
-  if (!maxVisible && !maxDraws) return 1;
+  if (!maxVisible && !maxDraws) return reallocBindBlocks(c) ? 1 : 0;      // (the bind runs lose their staging blocks)
   if (maxVisible > c->cap || maxDraws > c->cap) return fail(c, "read-back sizes exceed the context's capacity");
   maxVisible = (maxVisible + 3u) & ~3u;                        // keeps the draw items 16-byte aligned inside the block
   const size_t bytes = (size_t)kFrameHeaderWords * 4u + (size_t)maxVisible * 4u + (size_t)maxDraws * sizeof(ScTickDrawItem);
@@ -2534,7 +2600,7 @@ int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDr
   }
   rb.maxVisible = maxVisible; rb.maxDraws = maxDraws; rb.bytes = bytes;
   dropGraphs(c->graph);
-  return 1;
+  return reallocBindBlocks(c) ? 1 : 0;      // (... or get them)
 }
 
 int scTickAcquireFrame(ScTickContext* c, uint32_t framesBack, ScTickFrame* out)
@@ -2555,6 +2621,77 @@ int scTickAcquireFrame(ScTickContext* c, uint32_t framesBack, ScTickFrame* out)
   out->visible_in_buffer = h[8]; out->draws_in_buffer = h[9];
   out->visible_indices = h + kFrameHeaderWords;
   out->draws = reinterpret_cast<const ScTickDrawItem*>(h + kFrameHeaderWords + rb.maxVisible);
+  return 1;
+}
+
+// ---- bind runs of the sorted draw list + material touch set (sc_tick_bindruns.hip; the spec is restated in include/sc_tick.h) --------
+// runs: maximal stretches of equal (pipeline, material, mesh) among the first draws_sorted items, with the binds VkRenderer's loop issues
+// ahead of each (sc_vk.cpp:1866-1907); touches: the handles RenderPrepStreamingSystem hands touchMaterial (sc_world_partition.cpp:1322-1326,
+// sc_assets.cpp:441-445) -- every emitted draw's, inside the table, whatever its mesh.
+int scTickSetBindRuns(ScTickContext* c, uint32_t maxRuns)
+{
+  static_assert(sizeof(ScTickBindRun) == sizeof(BindRun24) && sizeof(ScTickBindRun) == 24, "bind run layouts differ");
+  static_assert(sizeof(ScTickBindInfo) == kBiWords * sizeof(uint32_t) && offsetof(ScTickBindInfo, materials_touched) == kBiMaterialsTouched * 4u &&
+                offsetof(ScTickBindInfo, mesh_binds) == kBiMeshBinds * 4u, "the device writes the report word by word");
+  if (!c) return 0;
+  if (maxRuns && !c->sort.pipeline) return fail(c, "scTickSetBindRuns needs scTickSetDrawSortTable first (the touch bitmap is sized by its material_count)");
+  if (maxRuns > c->cap) return fail(c, "max_runs exceeds the context's capacity (a list has at most one run per draw)");
+  if (!bind(c) || !sync(c)) return 0;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none)
+  return reallocBindRuns(c, maxRuns) ? 1 : 0;
+}
+
+static bool bindRunsReadable(ScTickContext* c)
+{
+  if (!(c->lastFlags & SC_TICK_BIND_RUNS)) return fail(c, "the last scTickRun did not request SC_TICK_BIND_RUNS");
+  if (!c->bind.info) return fail(c, "bind runs were switched off since the last scTickRun");
+  if (c->bind.touchWords != c->bindLastTouchWords) return fail(c, "the draw sort table was resized since the last scTickRun");
+  return true;
+}
+
+int scTickReadBindRuns(ScTickContext* c, ScTickBindRun* runs, uint32_t cap, ScTickBindInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c) || !bindRunsReadable(c)) return 0;
+  if (c->bindLastEmpty) { std::memset(info, 0, sizeof *info); info->touch_words = c->bindLastTouchWords; return 1; }
+  if (!d2h(c, info, c->bind.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t take = std::min(std::min(info->runs, c->bind.maxRuns), runs ? cap : 0u);
+  if (take && (!d2h(c, runs, c->bind.runs, (size_t)take * sizeof(ScTickBindRun)) || !sync(c))) return 0;
+  return 1;
+}
+
+int scTickReadMaterialTouches(ScTickContext* c, uint32_t* words, uint32_t wordCap, uint32_t* wordCount)
+{
+  if (!c || !wordCount) return c ? fail(c, "null argument") : 0;
+  if (!bind(c) || !bindRunsReadable(c)) return 0;
+  *wordCount = c->bindLastTouchWords;
+  const uint32_t take = std::min(c->bindLastTouchWords, words ? wordCap : 0u);
+  if (!take) return 1;
+  if (c->bindLastEmpty) { std::memset(words, 0, (size_t)take * 4u); return 1; }
+  if (!d2h(c, words, c->bind.touch, (size_t)take * 4u) || !sync(c)) return 0;
+  return 1;
+}
+
+int scTickAcquireFrameBinds(ScTickContext* c, uint32_t framesBack, ScTickFrameBinds* out)
+{
+  if (!c || !out) return c ? fail(c, "null argument") : 0;
+  ScTickContext::FrameReadback& rb = c->rb;
+  if (!rb.bytes) return fail(c, "scTickAcquireFrameBinds needs scTickSetFrameReadback first");
+  if (!rb.bindBytes) return fail(c, "scTickAcquireFrameBinds needs scTickSetBindRuns first");
+  if (framesBack > 1u) return fail(c, "frames_back must be 0 (the latest frame) or 1 (the one before): two frames are kept");
+  if (rb.frames <= framesBack) return fail(c, "that frame has not been produced yet");
+  if (!bind(c)) return 0;
+  const uint64_t tick = rb.frames - 1u - framesBack;
+  const uint32_t f = (uint32_t)(tick & 1u);
+  HIP_OK(c, hipEventSynchronize(rb.copied[f]));               // the event scTickAcquireFrame waits on: the bind block is copied ahead of it
+  std::memset(out, 0, sizeof *out);
+  out->tick = tick;                                           // (what the frame's own header carries: its index at staging time)
+  const uint32_t* h = rb.hBinds[f];
+  out->runs = reinterpret_cast<const ScTickBindRun*>(h + kBiWords);
+  out->touch_words = h + kBiWords + (size_t)c->bind.maxRuns * 6u;
+  if (!rb.bindsStaged[f]) return 1;                           // a run without SC_TICK_BIND_RUNS: zeros, nothing in the buffer
+  std::memcpy(&out->info, h, sizeof out->info);
+  out->runs_in_buffer = std::min(out->info.runs, c->bind.maxRuns);
   return 1;
 }
 

@@ -353,6 +353,20 @@ struct PairEventState {
 constexpr uint32_t kPeCur = 0, kPeValid = 1, kPeBegun = 2, kPeEnded = 3, kPeTracked = 4, kPeOverflow = 5, kPeCtlWords = 16;
 constexpr uint32_t kPeInfoWords = 8;
 void launchPairEvents(const DeviceState& d, const TickParams& p, const PairEventState& e, hipStream_t s);
+// ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----
+struct BindRun24 { uint32_t first, count, pipeline, material, mesh, binds; };      // == ScTickBindRun
+// the report's words (== ScTickBindInfo)
+constexpr uint32_t kBiRuns = 0, kBiTruncated = 1, kBiDraws = 2, kBiPipelineBinds = 3, kBiMaterialBinds = 4, kBiMeshBinds = 5, kBiMaterialsTouched = 6,
+                   kBiTouchWords = 7, kBiWords = 8;
+struct BindRunState {
+  BindRun24* runs;          // [maxRuns + 1]: the row behind the last reported one is kept for that one's count
+  uint32_t* info;           // [kBiWords], and behind it in the same allocation ...
+  uint32_t* touch;          // ... [touchWords]: bit h % 32 of word h / 32 = material handle h was touched
+  uint32_t maxRuns, touchWords, materialCount;
+};
+void launchBindRuns(const DeviceState& d, const DrawSortState& st, const BindRunState& b, uint32_t bound, hipStream_t s);
+// frame read-back: [kBiWords report][maxRuns rows of 6 words][touchWords] into `block`
+void launchStageBinds(const BindRunState& b, uint32_t* block, hipStream_t s);
 void launchAgentFrontRays(const DeviceState& d, const TickParams& p, hipStream_t s);
 void launchAgentRaySnapshot(const DeviceState& d, const TickParams& p, hipStream_t s);         // tick half: list the agents, note their rays
 void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p, hipStream_t s); // pair half, behind the merge: cast them

@@ -317,6 +317,7 @@ class WorldTick:
         what the renderer's filter + sort of the draw list reads (sc_vk.cpp:1842-1864)."""
         p = np.ascontiguousarray(pipeline_of_material, np.uint8)
         self._ok(self.lib.scTickSetDrawSortTable(self.ctx, p.ctypes.data_as(capi.U8P), len(p), int(mesh_count)), "scTickSetDrawSortTable")
+        self._material_count = len(p)
 
     # ---- sector residency (WorldPartition::pumpCompletedLoads / pumpUnloadQueue) ----
     def append_entities(self, pos, rot, scale, bmin=None, bmax=None, mesh=None, material=None, group=None, mask=None, parent=None):
@@ -591,6 +592,47 @@ class WorldTick:
         vis = np.ctypeslib.as_array(fr.visible_indices, shape=(nv,)) if nv else np.zeros(0, np.uint32)
         draws = (np.ctypeslib.as_array(C.cast(fr.draws, capi.U8P), shape=(nd * 80,)).reshape(nd, 80) if nd else np.zeros((0, 80), np.uint8))
         return fr, (vis.copy() if copy else vis), (draws.copy() if copy else draws)
+
+    # ---- bind runs of the sorted draw list + material touch set (capi.BIND_RUNS with DRAWS | SORT_DRAWS) ----
+    BIND_RUN_DTYPE = np.dtype([(n, np.uint32) for n, _ in capi.BindRun._fields_])
+
+    def set_bind_runs(self, max_runs):
+        """Room for max_runs rows in the run table (scTickSetBindRuns; after set_draw_sort_table; 0 switches it off)."""
+        self._ok(self.lib.scTickSetBindRuns(self.ctx, int(max_runs)), "scTickSetBindRuns")
+        self._max_runs = int(max_runs)
+
+    def bind_runs(self):
+        """(runs, info) of the last run with capi.BIND_RUNS: a structured array (first, count, pipeline, material, mesh, binds) of the
+        first min(info["runs"], max_runs) runs in list order, and the report as a dict whose totals cover all runs."""
+        cap = getattr(self, "_max_runs", 0)
+        runs = np.zeros(max(cap, 1), self.BIND_RUN_DTYPE)
+        info = capi.BindInfo()
+        self._ok(self.lib.scTickReadBindRuns(self.ctx, runs.ctypes.data_as(C.POINTER(capi.BindRun)), cap, C.byref(info)), "scTickReadBindRuns")
+        out = {k: int(getattr(info, k)) for k, _ in capi.BindInfo._fields_}
+        return runs[:min(out["runs"], cap)].copy(), out
+
+    def material_touches(self):
+        """bool[material_count]: handle h was the materialId of some emitted draw of the last run with capi.BIND_RUNS."""
+        cnt = C.c_uint32()
+        self._ok(self.lib.scTickReadMaterialTouches(self.ctx, None, 0, C.byref(cnt)), "scTickReadMaterialTouches")
+        words = np.zeros(max(cnt.value, 1), np.uint32)
+        if cnt.value:
+            self._ok(self.lib.scTickReadMaterialTouches(self.ctx, _u(words), cnt.value, C.byref(cnt)), "scTickReadMaterialTouches")
+        bits = np.unpackbits(words[:cnt.value].view(np.uint8), bitorder="little").astype(bool)
+        return bits[:getattr(self, "_material_count", len(bits))].copy()
+
+    def acquire_frame_binds(self, frames_back=0):
+        """The bind runs staged with frame `frames_back` (set_frame_readback + set_bind_runs): (tick, runs, info dict, touches bool array);
+        a frame whose run had no capi.BIND_RUNS has no runs and an all-zero report."""
+        fb = capi.FrameBinds()
+        self._ok(self.lib.scTickAcquireFrameBinds(self.ctx, int(frames_back), C.byref(fb)), "scTickAcquireFrameBinds")
+        nr, nw = fb.runs_in_buffer, fb.info.touch_words
+        runs = (np.ctypeslib.as_array(C.cast(fb.runs, capi.U32P), shape=(nr * 6,)).copy().view(self.BIND_RUN_DTYPE) if nr
+                else np.zeros(0, self.BIND_RUN_DTYPE))
+        words = np.ctypeslib.as_array(fb.touch_words, shape=(nw,)).copy() if nw else np.zeros(0, np.uint32)
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little").astype(bool)
+        info = {k: int(getattr(fb.info, k)) for k, _ in capi.BindInfo._fields_}
+        return int(fb.tick), runs, info, bits[:getattr(self, "_material_count", len(bits))].copy()
 
     # ---- results ----
     def counts(self):
