@@ -754,6 +754,67 @@ int scTickReadAnchoredRayHits(ScTickContext* ctx, ScTickRayHit* hits, uint32_t c
 /* the anchors of rays first .. first + count - 1 as they stand now (after removals); host-side, no read-back */
 int scTickReadAnchoredRays(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
 
+/* ---- exact shapes for rays: oriented box, sphere, capsule ----
+ * The ray queries and the entity-anchored rays answer from the broadphase's WORLD AABBs; a box yawed by 45 degrees is then as wide as its
+ * diagonal and a sphere answers at the face of its bounding cube.  scTickSetRayShapes(SC_TICK_RAY_SHAPES_EXACT) makes the runs with
+ * SC_TICK_RAYS and SC_TICK_ANCHORED_RAYS answer a candidate whose proxy comes from a typed collider (scTickUploadColliders: BOX, SPHERE,
+ * CAPSULE) by the shape itself, taken through the entity's world matrix of this tick.  The AABB test stays as the pre-filter; the sector
+ * walk, the filter, the skip rule, the tie rule and ScTickRayHit are what they were.  Capsule sweeps, the traffic AI's front rays,
+ * scTickQueryOccupied and the pair search do not change: they see AABBs in either mode.
+ * This build's OWN SPEC, like the rays.  All arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt;
+ * dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * A candidate record passes the filter and the skip test, then the slab test against its AABB (dir: the normalised direction, L: max_dist).
+ *   An AABB miss: the candidate does not answer, in both modes.
+ *   An AABB hit in EXACT mode is REFINED when colliders were uploaded, the id's rank is this context's, e = id & 0xFFFFFF is below the
+ *   entity count and the collider type of e is BOX, SPHERE or CAPSULE.  Otherwise the AABB answer stands, bit for bit as in AABB mode:
+ *   BOUNDS proxies, a neighbour tile's border records, a context without colliders, and the degenerate box matrices named below.
+ * With R_r = row r (0..2) of e's world matrix as this run's transform stage leaves it:
+ *   c_k = (R_0[k], R_1[k], R_2[k]) column k (0..2);  T = (R_0.w, R_1.w, R_2.w);  n_k = dot(c_k, c_k);  q = o - T;
+ *   (ex, ey, ez, radius) = the collider's record: a box's half extents, (0, 0, 0, radius) for a sphere, (0, max(0, half_height), 0, radius)
+ *   for a capsule.
+ * "Inside" always means hit, t = +0, normal (0,1,0): the rule for a ray that starts inside a box.  Every reported t is (t > 0) ? t : +0,
+ * never -0.  Every acceptance below is a positive comparison (t <= L, disc >= 0, ...): a NaN is a miss.
+ *   BOX       some n_k not > 0 or not finite: the AABB answer stands.  Otherwise lo_k = dot(c_k, q) / n_k, ld_k = dot(c_k, dir) / n_k and
+ *             s = the slab test of (lo, ld, L) against (-(ex,ey,ez), +(ex,ey,ez)) -- the same routine, parallel-axis rule included.
+ *             A miss: the candidate does not answer.  t = s.t.  Face axis a < 3: sgn = ld_a > 0 ? -1 : 1, inv = 1 / sqrt(n_a),
+ *             normal_r = sgn * (c_a[r] * inv) + 0   (the addition of +0 makes a zero component +0 whatever the sign: an axis-aligned
+ *             box reports the AABB answer's bits).  No face (the origin is inside): inside.
+ *   roundHit(qc, R)   b = dot(qc, dir);  c = dot(qc, qc) - R*R;  c <= 0: inside.  Require b < 0, else miss.  disc = b*b - c; require
+ *             disc >= 0, else miss.  t = (-b) - sqrt(disc), clamped as above; require t <= L, else miss.  normal_r = (qc_r + dir_r*t) / R.
+ *   SPHERE    R = radius * sqrt(max(n_0, n_1, n_2)), the maximum selected as the collider's AABB selects it: m = (n_2 < n_1) ? n_1 : n_2,
+ *             then (n_0 < m) ? m : n_0.  The answer is roundHit(q, R).
+ *   CAPSULE   hh = ey;  R = radius * sqrt((n_0 < n_2) ? n_2 : n_0);  A = c_1 * hh per component;  aa = dot(A, A).
+ *             Not aa > 0: the answer is roundHit(q, R).  Otherwise
+ *               ad = dot(A, dir); aq = dot(A, q); dq = dot(dir, q); qq = dot(q, q);
+ *               ka = aa - ad*ad;  kb = aa*dq - aq*ad;  kc = (aa*qq - aq*aq) - (R*R)*aa;
+ *             inside the body: kc <= 0 and -aa <= aq and aq <= aa.
+ *             side: needs kc > 0, ka > 0, kb < 0 (the ray approaches the axis: with kb >= 0 both roots lie behind the origin) and
+ *               disc = kb*kb - ka*kc >= 0;  tb = ((-kb) - sqrt(disc)) / ka, clamped;  yb = aq + tb*ad;  valid when -aa <= yb, yb <= aa
+ *               and tb <= L;  normal_r = ((q_r + dir_r*tb) - A_r*(yb/aa)) / R.
+ *             caps: roundHit(q + A, R) and roundHit(q - A, R).
+ *             Any inside among body and caps: inside.  Otherwise the smallest t among the valid of side, cap q + A, cap q - A, in that
+ *             order, a later one replacing an earlier one only when strictly smaller.  None valid: the candidate does not answer.
+ * Among candidates the smallest t wins -- refined or standing alike -- and equal t goes to the lower id; position = o + dir*t, layer and
+ * id as in AABB mode, the pad words 0.
+ * For a matrix whose columns are mutually orthogonal (every root, every chain under uniformly scaled parents) this is the shape itself:
+ * the box with half extents e_k * |c_k|, the sphere and the capsule's round part scaled by the largest column they span.  For a sheared
+ * matrix it is the shape in the frame these formulas define.
+ * The mode is a property of the context and stays until it is changed (default AABB).  Setting it drops captured graphs and asks for no
+ * learn tick: the bins are not concerned.  It fails on an unknown mode and while scTickRunPairs is pending.  A run with SC_TICK_RAYS or
+ * SC_TICK_ANCHORED_RAYS in EXACT mode fails on a pipelined context (scTickSetPipelined / scTickSetPairsStream): by the time its rays are
+ * cast the matrices may be the next tick's.  In-order tiles (scTickTileStep) and the caller-owned split flow work, with ONE RESTRICTION on
+ * the latter: the pair half refines against the matrix rows, the collider records and the dense indices as they stand when scTickRunPairs
+ * runs (the bins hold tick t's boxes; nothing holds tick t's shapes, and the snapshot of the anchored rays holds the resolved ray, not the
+ * candidates).  So between scTickRun(.. | SC_TICK_SPLIT_PAIRS) with SC_TICK_RAYS or SC_TICK_ANCHORED_RAYS in EXACT mode and its
+ * scTickRunPairs, the calls that rewrite one of them fail with a last-error text and change nothing: scTickUploadWorldMatrices,
+ * scTickUploadColliders, scTickRemoveEntities, scTickSetEntityCount and scTickRun with SC_TICK_XFORM.  Everything else a host does in the
+ * gap -- locals, positions, layers, bounds, appends, read-backs -- is the next tick's and is welcome; in AABB mode, and for a pending tick
+ * without ray flags, the gap is as free as before.  A context that never calls scTickSetRayShapes launches exactly the kernels it launched
+ * before. */
+enum { SC_TICK_RAY_SHAPES_AABB = 0, SC_TICK_RAY_SHAPES_EXACT = 1 };
+int scTickSetRayShapes(ScTickContext* ctx, uint32_t mode);   /* default SC_TICK_RAY_SHAPES_AABB */
+int scTickGetRayShapes(ScTickContext* ctx, uint32_t* mode);
+
 /* ---- pair events: the tick-to-tick difference of the pair set ----
  * What a broadphase hands its narrow phase besides "the pairs of this tick": Bullet's btDbvtBroadphase (behind sc_physics.cpp:218-225) keeps
  * an overlapping-pair cache and reports pairs as they are ADDED and REMOVED (btOverlappingPairCache::addOverlappingPair /

@@ -16,6 +16,7 @@ ANCHORED_RAYS = 1 << 11
 PAIR_EVENTS = 1 << 12         # SC_TICK_PAIR_EVENTS: which pairs begun / ended since the last run with this flag (scTickSetPairEvents)
 BIND_RUNS = 1 << 13           # SC_TICK_BIND_RUNS: with DRAWS | SORT_DRAWS, the bind runs of the sorted list and the material touch set (scTickSetBindRuns)
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
+RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 NO_PARENT = -1
@@ -214,6 +215,8 @@ SYMBOLS = {
     "scTickSetAnchoredRays": (C.c_int, [_CTX, C.c_uint32, U32P, F32P, F32P, F32P, U32P, U8P]),
     "scTickReadAnchoredRayHits": (C.c_int, [_CTX, C.POINTER(RayHit), C.c_uint32, U32P]),
     "scTickReadAnchoredRays": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
+    "scTickSetRayShapes": (C.c_int, [_CTX, C.c_uint32]),
+    "scTickGetRayShapes": (C.c_int, [_CTX, U32P]),
     "scTickSetPairEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "scTickReadPairEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairEventInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),

@@ -114,6 +114,9 @@ struct ScTickContext
   // scTickRemoveEntities keeps current
   AnchoredRayState anchored{};
   uint32_t anchoredCap = 0;
+  // scTickSetRayShapes: SC_TICK_RAY_SHAPES_EXACT selects the exact-shape instances of the ray and anchored-ray kernels (launch time:
+  // a captured graph holds the instance it was captured with, so a change drops the graphs)
+  uint32_t rayShapes = SC_TICK_RAY_SHAPES_AABB;
   std::vector<uint2> hAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
@@ -630,6 +633,17 @@ AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
 
 // pair events: forget the remembered set (dense indices were renamed, or are no longer valid) -- the next flagged tick is a resync tick.
 // Queued on the tick stream, behind the ticks already issued.
+// Exact ray shapes in the caller-owned split flow: the pair half refines its candidates against the matrix rows, the collider records and
+// the dense indices AS THEY STAND when it runs (the bins hold tick t's boxes, nothing holds tick t's shapes).  So whatever rewrites one of
+// those is refused between the halves of a tick whose pair half casts rays in EXACT mode -- tick t's answers stay tick t's.
+bool exactRaysPending(const ScTickContext* c)
+{
+  return c->pairsPending && c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS));
+}
+#define REFUSE_WHILE_EXACT_RAYS_PENDING(c, what) \
+  do { if (exactRaysPending(c)) return fail(c, what " is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that casts rays in " \
+                                               "SC_TICK_RAY_SHAPES_EXACT mode: its pair half reads the matrices and colliders as they stand"); } while (0)
+
 bool resyncPairEvents(ScTickContext* c)
 {
   if (!c->pairEventSlab) return true;
@@ -780,13 +794,14 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   // (kFlagTailOwnsDirty: the transform half left nothing for the end-of-tick kernel -- without culling there is no compaction role to launch)
   const bool needCompact = (flags & SC_TICK_CULL) != 0 || ((flags & SC_TICK_XFORM) && !(flags & kFlagTailOwnsDirty));
   const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
-  if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, c->stream);      // the bins are full, not yet consumed
+  const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
+  if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
   if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
   if (flags & SC_TICK_ANCHORED_RAYS) {
-    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), c->stream);
+    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), exactRays, c->stream);
     else if (flags & SC_TICK_BROADPHASE) launchAnchoredRaySnapshot(ds, p, anchoredFor(c, p.parity), c->stream);
   }
   // Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
@@ -1089,6 +1104,7 @@ int scTickSetEntityCount(ScTickContext* c, uint32_t count)
 {
   if (!c) return 0;
   if (count > c->desc.capacity) return fail(c, "count exceeds capacity");
+  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickSetEntityCount");
   const uint32_t before = c->n;
   c->n = count;
   c->linksStale = true;
@@ -1177,6 +1193,7 @@ int scTickUploadBounds(ScTickContext* c, uint32_t first, uint32_t count, const f
 int scTickUploadColliders(ScTickContext* c, uint32_t first, uint32_t count, const uint8_t* type, const float* he3, const float* radius, const float* halfHeight)
 {
   if (!c) return 0;
+  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickUploadColliders");
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
   // validate before anything is stored: a failed call leaves the context as it was
   for (uint32_t i = 0; i < count; ++i) {
@@ -1362,6 +1379,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   if (!c) return 0;
   if (movedCount) *movedCount = 0;
   if (!idx && count) return fail(c, "null argument");
+  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickRemoveEntities");
   if (!bind(c)) return 0;
   if (!count) return 1;
   const uint32_t n0 = c->n;
@@ -1606,6 +1624,7 @@ int scTickSetDrawBudget(ScTickContext* c, uint32_t maxDraws)
 int scTickUploadWorldMatrices(ScTickContext* c, uint32_t first, uint32_t count, const float* m16)
 {
   if (!c || !m16) return c ? fail(c, "null argument") : 0;
+  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickUploadWorldMatrices");
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
   if (!count) return 1;
   c->boxesTouched = true;
@@ -1678,9 +1697,11 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
 {
   const DeviceState ds = stateFor(c, pp.parity);
   launchBorderMerge(ds, pp, ps);
-  if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, ps);   // sees the neighbours' border boxes too
+  // (exact shapes: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
+  const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
+  if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, exactRays, ps);   // sees the neighbours' border boxes too
   if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, ps);   // ... as do the capsule sweeps
-  if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), ps);   // ... and the anchored rays, as the tick half resolved them
+  if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), exactRays, ps);   // ... and the anchored rays, as the tick half resolved them
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);
@@ -1720,6 +1741,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (!c) return 0;
   if (!bind(c)) return 0;
   if (!flushLinks(c)) return 0;
+  if (flags & SC_TICK_XFORM) REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickRun with SC_TICK_XFORM");
   if ((flags & SC_TICK_BROADPHASE) && c->desc.tile_sectors_x == 0) return fail(c, "broadphase requested but the context has no tile rectangle");
   // An empty context without a broadphase has nothing to launch: the per-tick counts read as zero.  With the broadphase
   // the stages still run (every kernel copes with n == 0): an emptied tile of a multi-GPU world must rewrite its border
@@ -1753,6 +1775,8 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if ((flags & SC_TICK_SWEEPS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_SWEEPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_ANCHORED_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_ANCHORED_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_SORT_DRAWS) && !c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
+  if ((flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)) && c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && c->pairsStream)
+    return fail(c, "SC_TICK_RAY_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its rays are cast when the matrices may be the next tick's");
   TickParams p; uint32_t grid;
   fillParams(c, flags, p, grid);
   c->lastFlags = flags;
@@ -2438,6 +2462,25 @@ int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, 
   if (nb && !d2h(c, begun2, e.begun, (size_t)nb * sizeof(uint2))) return 0;
   if (ne && !d2h(c, ended2, e.ended, (size_t)ne * sizeof(uint2))) return 0;
   if ((nb || ne) && !sync(c)) return 0;
+  return 1;
+}
+
+int scTickSetRayShapes(ScTickContext* c, uint32_t mode)
+{
+  if (!c) return 0;
+  if (mode != SC_TICK_RAY_SHAPES_AABB && mode != SC_TICK_RAY_SHAPES_EXACT) return fail(c, "unknown ray shape mode (SC_TICK_RAY_SHAPES_*)");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending (its rays are cast in the mode its tick half ran in)");
+  if (mode == c->rayShapes) return 1;
+  if (!bind(c) || !sync(c)) return 0;
+  c->rayShapes = mode;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
+  return 1;
+}
+
+int scTickGetRayShapes(ScTickContext* c, uint32_t* mode)
+{
+  if (!c || !mode) return c ? fail(c, "null argument") : 0;
+  *mode = c->rayShapes;
   return 1;
 }
 

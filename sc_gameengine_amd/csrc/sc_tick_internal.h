@@ -306,7 +306,9 @@ struct RayQueryState {
   RayHit48* hits;
   uint32_t count;
 };
-void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, hipStream_t s);
+// exact (scTickSetRayShapes, SC_TICK_RAY_SHAPES_EXACT): the instance that refines an AABB hit of an own typed collider by the shape itself --
+// chosen here, on the host; the kernels' arguments are the same either way
+void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, bool exact, hipStream_t s);
 // ---- capsule sweeps over the bins: a kernel argument of their own (DeviceState and TickParams keep their layout) ----
 struct SweepHit48 { uint32_t hit, id; float distance; float position[3]; float normal[3]; uint32_t layer; float travel; uint32_t pad; };   // == ScTickSweepHit, laid out like RayHit48
 static_assert(sizeof(SweepHit48) == sizeof(RayHit48), "sweep hits are read back like ray hits");
@@ -332,9 +334,9 @@ struct AnchoredRayState {
   float4* snapOrigin; float4* snapDir; uint32_t* snapSkip;
   uint32_t count;
 };
-void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);              // resolve + cast
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s);              // resolve + cast
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);      // tick half: resolve
-void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s); // pair half: cast
+void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s); // pair half: cast
 // ---- pair begin / end events (sc_tick_pair_events.hip; include/sc_tick.h "pair events"): the difference between this tick's pair set and
 // the set of the last tick that ran with SC_TICK_PAIR_EVENTS, formed on the device behind the pair search.  A kernel argument of its own.
 // Two open-addressing tables of 64-bit keys a << 32 | b (0 = empty: a < b rules it out) are used in turn: the one holding the remembered

@@ -47,19 +47,120 @@ __device__ __forceinline__ Slab rayBox(const float o[3], const float dir[3], flo
 // The result is wave-uniform.  skipId: a box that never answers (0xFFFFFFFF = none) -- an agent's own box for its front ray.
 struct WaveRay { bool valid, hit; float t; uint32_t id, axis, layer; float dir[3]; };
 
+// ---- exact collider shapes (own spec, include/sc_tick.h "exact shapes for rays") ---------------------------------------------
+// SC_TICK_RAY_SHAPES_EXACT: a candidate that passed the slab test against its AABB and whose proxy comes from a typed collider of this
+// context is answered by the shape itself, taken through the entity's world matrix of this tick.  All of it fp32, unfused, left to right;
+// every acceptance is a positive comparison, so a NaN is a miss.  c_k: column k of the matrix, T: its translation, q = o - T.
+__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+// what a shape reports: never -0 (the wave's 64-bit min orders distances by their bit patterns)
+__device__ __forceinline__ float notNegative(float t) { return t > 0.0f ? t : 0.0f; }
+
+// kShapeStands: the AABB answer stands (a degenerate box matrix); kShapeInside: the ray starts inside -- t = +0, normal (0, 1, 0)
+enum : uint32_t { kShapeStands = 0u, kShapeMiss = 1u, kShapeHit = 2u, kShapeInside = 3u };
+struct ShapeHit { uint32_t kind; float t; float n[3]; };
+
+// a sphere of radius R about the point the ray's origin is qc away from
+__device__ __forceinline__ ShapeHit roundHit(const float qc[3], float R, const float dir[3], float L)
+{
+  ShapeHit h; h.kind = kShapeMiss; h.t = 0.0f; h.n[0] = 0.0f; h.n[1] = 1.0f; h.n[2] = 0.0f;
+  const float b = dot3(qc, dir);
+  const float c = dot3(qc, qc) - R * R;
+  if (c <= 0.0f) { h.kind = kShapeInside; return h; }
+  if (!(b < 0.0f)) return h;
+  const float disc = b * b - c;
+  if (!(disc >= 0.0f)) return h;
+  const float t = notNegative((-b) - sqrtf(disc));
+  if (!(t <= L)) return h;
+  h.kind = kShapeHit; h.t = t;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) h.n[r] = (qc[r] + dir[r] * t) / R;
+  return h;
+}
+
+// entity e's collider (type: box, sphere or capsule) against the ray (o, dir, L) that met its AABB
+__device__ __forceinline__ ShapeHit shapeHit(const DeviceState& d, uint32_t e, uint32_t type, const float o[3], const float dir[3], float L)
+{
+  const float4 s = d.colShape[e];                       // (ex, ey, ez, radius)
+  const float4 r0 = d.w0[e], r1 = d.w1[e], r2 = d.w2[e];
+  const float c0[3] = { r0.x, r1.x, r2.x }, c1[3] = { r0.y, r1.y, r2.y }, c2[3] = { r0.z, r1.z, r2.z };
+  const float q[3] = { o[0] - r0.w, o[1] - r1.w, o[2] - r2.w };
+  const float n0 = dot3(c0, c0), n1 = dot3(c1, c1), n2 = dot3(c2, c2);
+  ShapeHit h; h.kind = kShapeStands; h.t = 0.0f; h.n[0] = 0.0f; h.n[1] = 1.0f; h.n[2] = 0.0f;
+  if (type == kColliderBox) {
+    // the ray in the box's own frame: the slab test again, parallel-axis rule included
+    if (!(n0 > 0.0f && n1 > 0.0f && n2 > 0.0f && isfinite(n0) && isfinite(n1) && isfinite(n2))) return h;
+    const float lo[3] = { dot3(c0, q) / n0, dot3(c1, q) / n1, dot3(c2, q) / n2 };
+    const float ld[3] = { dot3(c0, dir) / n0, dot3(c1, dir) / n1, dot3(c2, dir) / n2 };
+    const Slab sl = rayBox(lo, ld, L, make_float4(-s.x, -s.y, -s.z, 0.0f), make_float4(s.x, s.y, s.z, 0.0f));
+    if (!sl.hit) { h.kind = kShapeMiss; return h; }
+    h.kind = kShapeHit; h.t = sl.t;                     // (tmin starts at +0 and only grows: never -0)
+    if (sl.axis < 3u) {                                 // the face's outward normal: the unit column, against the ray
+      const float lda = sl.axis == 0u ? ld[0] : (sl.axis == 1u ? ld[1] : ld[2]);
+      const float na = sl.axis == 0u ? n0 : (sl.axis == 1u ? n1 : n2);
+      const float sgn = lda > 0.0f ? -1.0f : 1.0f, inv = 1.0f / sqrtf(na);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const float ca = sl.axis == 0u ? c0[r] : (sl.axis == 1u ? c1[r] : c2[r]);
+        h.n[r] = sgn * (ca * inv) + 0.0f;               // (+ 0: a zero component is +0 whatever the sign, as the AABB answer has it)
+      }
+    }
+    return h;
+  }
+  // the round part's radius, the columns selected as colliderAabb selects them for its pad
+  const float nyz = (type == kColliderSphere && n2 < n1) ? n1 : n2;
+  const float R = s.w * sqrtf((n0 < nyz) ? nyz : n0);
+  if (type == kColliderSphere) h = roundHit(q, R, dir, L);
+  else {
+    const float A[3] = { c1[0] * s.y, c1[1] * s.y, c1[2] * s.y };      // half the capsule's axis
+    const float aa = dot3(A, A);
+    if (!(aa > 0.0f)) h = roundHit(q, R, dir, L);
+    else {
+      const float ad = dot3(A, dir), aq = dot3(A, q), dq = dot3(dir, q), qq = dot3(q, q);
+      const float ka = aa - ad * ad, kb = aa * dq - aq * ad, kc = (aa * qq - aq * aq) - (R * R) * aa;
+      const float qp[3] = { q[0] + A[0], q[1] + A[1], q[2] + A[2] }, qm[3] = { q[0] - A[0], q[1] - A[1], q[2] - A[2] };
+      const ShapeHit capP = roundHit(qp, R, dir, L), capM = roundHit(qm, R, dir, L);
+      const bool inBody = kc <= 0.0f && -aa <= aq && aq <= aa;
+      h.kind = kShapeMiss;
+      if (inBody || capP.kind == kShapeInside || capM.kind == kShapeInside) h.kind = kShapeInside;
+      else {
+        if (kc > 0.0f && ka > 0.0f && kb < 0.0f) {      // the side: the infinite cylinder, between the two seams
+          const float disc = kb * kb - ka * kc;
+          if (disc >= 0.0f) {
+            const float tb = notNegative(((-kb) - sqrtf(disc)) / ka);
+            const float yb = aq + tb * ad;
+            if (-aa <= yb && yb <= aa && tb <= L) {
+              const float f = yb / aa;
+              h.kind = kShapeHit; h.t = tb;
+#pragma unroll
+              for (int r = 0; r < 3; ++r) h.n[r] = ((q[r] + dir[r] * tb) - A[r] * f) / R;
+            }
+          }
+        }
+        if (capP.kind == kShapeHit && (h.kind != kShapeHit || capP.t < h.t)) h = capP;
+        if (capM.kind == kShapeHit && (h.kind != kShapeHit || capM.t < h.t)) h = capM;
+      }
+    }
+  }
+  if (h.kind == kShapeInside) { h.kind = kShapeHit; h.t = 0.0f; h.n[0] = 0.0f; h.n[1] = 1.0f; h.n[2] = 0.0f; }
+  return h;
+}
+
 // The segment o + dir * [0, maxDist] against this tick's records, by a whole wave; fills hit / t / id / axis / layer of `w`.
 // kSweep (capsule sweeps, k_sweep_queries): every candidate box is grown by `grow` per axis before the slab test, and the sector
 // walk reaches `reach` (the sweeper's xz half extent) further on every side.  The ray instance (kSweep false) takes neither and
 // is the routine the ray kernels always had.
-template <bool kSweep>
+// kExact (the exact-shape instances of the ray kernels): an AABB hit of an own typed collider is refined by shapeHit, lanes keep the
+// normal instead of the face's axis, and the winner's normal travels with the other shuffles into wn[3] (w.axis is not filled).
+template <bool kSweep, bool kExact = false>
 __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d, const TickParams& p, const float o[3], const float dir[3], float maxDist,
-                                                uint32_t rayMask, uint32_t skipId, const float grow[3], float reach)
+                                                uint32_t rayMask, uint32_t skipId, const float grow[3], float reach, float* wn = nullptr)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const float ex = o[0] + dir[0] * maxDist, ez = o[2] + dir[2] * maxDist;
 
   // this lane's best so far
   float bt = INFINITY; uint32_t bid = 0xFFFFFFFFu, baxis = 3u, blayer = 0u;
+  float bn0 = 0.0f, bn1 = 1.0f, bn2 = 0.0f;
   auto consider = [&](const float4& lo, const float4& hi) {
     const uint32_t lay = __float_as_uint(lo.w);
     // Bullet's needsCollision with the callback's group 0xFFFF: (proxy.group & mask) && (0xFFFF & proxy.mask)
@@ -71,6 +172,27 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
                                    make_float4(hi.x + grow[0], hi.y + grow[1], hi.z + grow[2], 0.0f))
                           : rayBox(o, dir, maxDist, lo, hi);
     if (!s.hit) return;
+    if (kExact) {
+      // the AABB answer, as rayHitOf would report it ...
+      float t = s.t, n[3] = { 0.0f, 1.0f, 0.0f };
+      if (s.axis < 3u) {
+        const float da = s.axis == 0u ? dir[0] : (s.axis == 1u ? dir[1] : dir[2]);
+        const float sgn = da > 0.0f ? -1.0f : 1.0f;
+        n[0] = s.axis == 0u ? sgn : 0.0f; n[1] = s.axis == 1u ? sgn : 0.0f; n[2] = s.axis == 2u ? sgn : 0.0f;
+      }
+      // ... stands for Bounds proxies, a neighbour tile's records and a context without colliders
+      const uint32_t e = id & 0x00FFFFFFu;
+      if (d.colType && (id & 0x7F000000u) == p.rankBits && e < p.n) {
+        const uint32_t type = d.colType[e];
+        if (type == kColliderBox || type == kColliderSphere || type == kColliderCapsule) {
+          const ShapeHit h = shapeHit(d, e, type, o, dir, maxDist);
+          if (h.kind == kShapeMiss) return;
+          if (h.kind == kShapeHit) { t = h.t; n[0] = h.n[0]; n[1] = h.n[1]; n[2] = h.n[2]; }
+        }
+      }
+      if (t < bt || (t == bt && id < bid)) { bt = t; bid = id; blayer = lay & 0xFFFFu; bn0 = n[0]; bn1 = n[1]; bn2 = n[2]; }
+      return;
+    }
     if (s.t < bt || (s.t == bt && id < bid)) { bt = s.t; bid = id; baxis = s.axis; blayer = lay & 0xFFFFu; }
   };
 
@@ -135,11 +257,14 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
   if (!winners) return;
   const int win = __ffsll((long long)winners) - 1;
   w.hit = true;
-  w.t = __shfl(bt, win, 64); w.id = __shfl(bid, win, 64); w.axis = __shfl(baxis, win, 64); w.layer = __shfl(blayer, win, 64);
+  w.t = __shfl(bt, win, 64); w.id = __shfl(bid, win, 64); w.layer = __shfl(blayer, win, 64);
+  if (kExact) { wn[0] = __shfl(bn0, win, 64); wn[1] = __shfl(bn1, win, 64); wn[2] = __shfl(bn2, win, 64); }
+  else w.axis = __shfl(baxis, win, 64);
 }
 
+template <bool kExact = false>
 __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickParams& p, const float o[3], const float dm[3], float maxDist,
-                                               uint32_t rayMask, uint32_t skipId)
+                                               uint32_t rayMask, uint32_t skipId, float* wn = nullptr)
 {
   WaveRay w; w.valid = false; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u; w.dir[0] = w.dir[1] = w.dir[2] = 0.0f;
   const float lenSq = dm[0] * dm[0] + dm[1] * dm[1] + dm[2] * dm[2];
@@ -150,7 +275,7 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
   const float dir[3] = { dm[0] * invLen, dm[1] * invLen, dm[2] * invLen };
   w.dir[0] = dir[0]; w.dir[1] = dir[1]; w.dir[2] = dir[2];
   const float none[3] = { 0.0f, 0.0f, 0.0f };
-  castSegmentWave<false>(w, d, p, o, dir, maxDist, rayMask, skipId, none, 0.0f);
+  castSegmentWave<false, kExact>(w, d, p, o, dir, maxDist, rayMask, skipId, none, 0.0f, wn);
   return w;
 }
 
@@ -173,6 +298,22 @@ __device__ __forceinline__ RayHit48 rayHitOf(const WaveRay& w, const float o[3])
   return out;
 }
 
+// the exact-shape instances: the winner brings its own normal (wn), everything else as above
+__device__ __forceinline__ RayHit48 rayHitExact(const WaveRay& w, const float o[3], const float wn[3])
+{
+  RayHit48 out;
+  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
+  out.position[0] = out.position[1] = out.position[2] = 0.0f;
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;
+  out.layer = 0u; out.pad = 0u; out.pad2 = 0u;
+  if (w.hit) {
+    out.hit = 1u; out.id = w.id; out.distance = w.t; out.layer = w.layer;
+    out.position[0] = o[0] + w.dir[0] * w.t; out.position[1] = o[1] + w.dir[1] * w.t; out.position[2] = o[2] + w.dir[2] * w.t;
+    out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2];
+  }
+  return out;
+}
+
 __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, const TickParams p, const RayQueryState q)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -183,6 +324,21 @@ __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, cons
   const float dv[3] = { dm.x, dm.y, dm.z };
   const WaveRay w = castRayWave(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu);
   const RayHit48 out = rayHitOf(w, o);
+  if (lane == 0) q.hits[r] = out;
+}
+
+// SC_TICK_RAY_SHAPES_EXACT: launched instead of the kernel above, never next to it
+__global__ __launch_bounds__(kTile) void k_ray_queries_exact(const DeviceState d, const TickParams p, const RayQueryState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
+  if (r >= q.count) return;
+  const float4 od = q.origin[r], dm = q.dir[r];
+  const float o[3] = { od.x, od.y, od.z };
+  const float dv[3] = { dm.x, dm.y, dm.z };
+  float wn[3] = { 0.0f, 1.0f, 0.0f };
+  const WaveRay w = castRayWave<true>(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu, wn);
+  const RayHit48 out = rayHitExact(w, o, wn);
   if (lane == 0) q.hits[r] = out;
 }
 
@@ -235,6 +391,25 @@ __global__ __launch_bounds__(kTile) void k_anchored_rays(const DeviceState d, co
   } else ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
   const WaveRay w = castRayWave(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId);
   const RayHit48 out = rayHitOf(w, ray.o);
+  if (lane == 0) q.hits[r] = out;
+}
+
+// SC_TICK_RAY_SHAPES_EXACT (the snapshot of a split flow holds the resolved ray; the candidates are refined against the matrices as they stand)
+template <bool kFromSnapshot>
+__global__ __launch_bounds__(kTile) void k_anchored_rays_exact(const DeviceState d, const TickParams p, const AnchoredRayState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
+  if (r >= q.count) return;
+  ResolvedRay ray;
+  if (kFromSnapshot) {
+    const float4 a = q.snapOrigin[r], b = q.snapDir[r];
+    ray.o[0] = a.x; ray.o[1] = a.y; ray.o[2] = a.z; ray.dv[0] = b.x; ray.dv[1] = b.y; ray.dv[2] = b.z;
+    ray.maxDist = a.w; ray.mask = __float_as_uint(b.w); ray.skipId = q.snapSkip[r];
+  } else ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
+  float wn[3] = { 0.0f, 1.0f, 0.0f };
+  const WaveRay w = castRayWave<true>(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId, wn);
+  const RayHit48 out = rayHitExact(w, ray.o, wn);
   if (lane == 0) q.hits[r] = out;
 }
 
@@ -471,11 +646,12 @@ void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p,
   hipLaunchKernelGGL(k_agent_front_rays_from_snapshot, dim3(std::max(blocks, 1u)), dim3(kTile), 0, s, d, p);
 }
 
-void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, hipStream_t s)
+void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, bool exact, hipStream_t s)
 {
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
-  hipLaunchKernelGGL(k_ray_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  if (exact) hipLaunchKernelGGL(k_ray_queries_exact, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  else hipLaunchKernelGGL(k_ray_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s)
@@ -485,11 +661,12 @@ void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQu
   hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
-void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s)
 {
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
-  hipLaunchKernelGGL(k_anchored_rays<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  if (exact) hipLaunchKernelGGL(k_anchored_rays_exact<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  else hipLaunchKernelGGL(k_anchored_rays<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
@@ -498,11 +675,12 @@ void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const 
   hipLaunchKernelGGL(k_anchored_ray_snapshot, dim3((q.count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, q);
 }
 
-void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
+void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s)
 {
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
-  hipLaunchKernelGGL(k_anchored_rays<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  if (exact) hipLaunchKernelGGL(k_anchored_rays_exact<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  else hipLaunchKernelGGL(k_anchored_rays<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 } // namespace sctick

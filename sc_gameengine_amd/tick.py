@@ -252,6 +252,19 @@ class WorldTick:
             self._ok(self.lib.scTickReadRayHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadRayHits")
         return np.frombuffer(buf, dtype=RAY_HIT_DTYPE, count=n.value).copy()
 
+    # ---- exact collider shapes for the ray queries and the anchored rays (scTickSetRayShapes) ----
+    def set_ray_shapes(self, mode):
+        """capi.RAY_SHAPES_AABB (default) / capi.RAY_SHAPES_EXACT: in EXACT mode the runs with capi.RAYS and capi.ANCHORED_RAYS answer a
+        candidate whose proxy comes from a typed collider (upload_colliders: box, sphere, capsule) by the shape itself, taken through the
+        entity's world matrix of the tick; Bounds proxies and a neighbour tile's records keep their AABB answer.  Drops captured graphs,
+        costs no learn tick (scTickSetRayShapes)."""
+        self._ok(self.lib.scTickSetRayShapes(self.ctx, int(mode)), "scTickSetRayShapes")
+
+    def ray_shapes(self):
+        mode = C.c_uint32()
+        self._ok(self.lib.scTickGetRayShapes(self.ctx, C.byref(mode)), "scTickGetRayShapes")
+        return int(mode.value)
+
     # ---- entity-anchored rays: given in an entity's local frame, resolved on the device every tick ----
     def set_anchored_rays(self, anchor, local_origin, local_dir, max_dist, mask, skip_self=None):
         """Rays in the local frame of the entities `anchor` (dense indices; capi.ANCHOR_NONE: a world-space ray), answered by every run
