@@ -62,6 +62,7 @@ enum {
   SC_TICK_ANCHORED_RAYS = 1u << 11, /* with BROADPHASE: answer the entity-anchored rays set by scTickSetAnchoredRays against this tick's boxes */
   SC_TICK_PAIR_EVENTS = 1u << 12,  /* with BROADPHASE: report which pairs begun and which ended since the last run with this flag (scTickSetPairEvents) */
   SC_TICK_BIND_RUNS   = 1u << 13,  /* with DRAWS | SORT_DRAWS: also the bind runs of the sorted list and the material touch set (scTickSetBindRuns) */
+  SC_TICK_PAIR_SHAPES = 1u << 14,  /* with BROADPHASE: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes) */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -855,6 +856,87 @@ int scTickSetPairEvents(ScTickContext* ctx, uint32_t max_tracked_pairs, uint32_t
 /* begun2 / ended2: [cap][2] (a, b), either may be NULL with capacity 0; min(count, max_events, capacity) pairs are written to each.
  * Synchronises; copies the 24 bytes of `info` and the listed pairs, nothing else. */
 int scTickReadPairEvents(ScTickContext* ctx, uint32_t* begun2, uint32_t begun_cap, uint32_t* ended2, uint32_t ended_cap, ScTickPairEventInfo* info);
+
+/* ---- touching pairs: exact collider-shape overlap over the pair list ----
+ * The pair search reports pairs of WORLD AABBs: a 4.4 m x 2 m vehicle box yawed by 45 degrees is a 4.5 m square to it, and two cars
+ * passing in neighbouring lanes are a pair.  What Bullet's narrow phase answers in the reference (behind sc_physics.cpp:218-225) is whether
+ * the shapes themselves touch.  A run with SC_TICK_PAIR_SHAPES also lists the pairs of this tick's pair list whose collider shapes
+ * (scTickUploadColliders: BOX, SPHERE, CAPSULE) overlap, taken through the members' world matrices of this tick.  The result is boolean:
+ * no contact point, normal or depth.  This build's OWN SPEC, like the exact shapes for rays, whose frame conventions it shares.  All
+ * arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z;
+ * clamp01(x) = (c < 1) ? c : 1 with c = (x > 0) ? x : 0 (a NaN is 0).
+ *   scTickSetPairShapes(max_touching) enables the pass and sizes its list (0 switches it off and frees the buffers).
+ *   The filter only ever REMOVES pairs: a pair (a, b) of the list is dropped only when one of the positive comparisons below proves the
+ *   shapes apart.  A NaN makes such a comparison false, so the pair is kept: a NaN in a matrix column makes its member not refinable, a
+ *   NaN translation reaches every comparison of the pair's routine (in F it makes g_k = 0: no distance, no separation), and collider
+ *   records are finite (scTickUploadColliders refuses others).  Touching is a subset of the pairs.
+ *   A member id is REFINABLE under the conditions under which the exact rays refine a candidate: colliders were uploaded, the id's rank is
+ *   this context's, e = id & 0xFFFFFF is below the entity count, the collider type of e is BOX, SPHERE or CAPSULE, and every n_k below is
+ *   finite and > 0.  A pair with a member that is not refinable is listed on its AABB answer -- it is in the pair list, so it is listed --
+ *   and counted in kept_as_boxes: BOUNDS proxies, a neighbour tile's border records, degenerate matrices, a context without colliders.
+ * Per refinable member, with R_r = row r of e's world matrix as this run's transform stage leaves it:
+ *   c_k = (R_0[k], R_1[k], R_2[k]);  T = (R_0.w, R_1.w, R_2.w);  n_k = dot(c_k, c_k);  (ex, ey, ez, radius) = the collider's record
+ *   (a box's half extents; (0, 0, 0, radius) for a sphere; (0, max(0, half_height), 0, radius) for a capsule).
+ *   SPHERE   the point T (A = 0), R = radius * sqrt(m), m = (n_0 < m') ? m' : n_0 with m' = (n_2 < n_1) ? n_1 : n_2.
+ *   CAPSULE  the segment T - A .. T + A, A = c_1 * ey per component, R = radius * sqrt((n_0 < n_2) ? n_2 : n_0).  Not dot(A, A) > 0:
+ *            A = 0, the sphere of radius R.
+ *   BOX      centre T, q_k = sqrt(n_k), unit axes u_k = c_k / q_k per component, half lengths H_k = e_k * q_k.  The columns are taken as
+ *            orthogonal: for a sheared matrix this is the shape in the frame these formulas define, as for the rays.
+ * Three routines cover the six type pairs (a is the member with the lower id).
+ *   1. ROUND - ROUND (sphere / capsule in any combination): the squared distance of two segments by the clamped closed form.
+ *        p1 = Ta - Aa; d1 = Aa + Aa; p2 = Tb - Ab; d2 = Ab + Ab; r = p1 - p2 (per component);
+ *        a = dot(d1, d1); e = dot(d2, d2); f = dot(d2, r); s = 0; t = 0;
+ *        not a > 0:  when e > 0, t = clamp01(f / e).
+ *        otherwise   c = dot(d1, r);  not e > 0: s = clamp01((-c) / a).  Otherwise b = dot(d1, d2); den = a*e - b*b;
+ *                    when den > 0, s = clamp01((b*f - c*e) / den);  t = (b*s + f) / e;
+ *                    t < 0: t = 0, s = clamp01((-c) / a);  else t > 1: t = 1, s = clamp01((b - c) / a).
+ *        v = (p1 + d1*s) - (p2 + d2*t) per component.  APART when dot(v, v) > (Ra + Rb) * (Ra + Rb).
+ *   2. ROUND - BOX: the segment in the box's frame.  w = Tround - Tbox; per axis k: yc = dot(u_k, w); ya = dot(u_k, A); y0_k = yc - ya;
+ *        dy_k = ya + ya.  F(t) = (g_0*g_0 + g_1*g_1) + g_2*g_2 with g_k = (x > 0) ? x : 0, x = |y0_k + dy_k*t| - H_k: the squared distance
+ *        of the segment's point t from the box, convex and piecewise quadratic in t.  fmin = F(0).  When A is not (0, 0, 0):
+ *        fmin = min(fmin, F(1));  b_0 = 0, b_7 = 1, b_(1+2k) = clamp01((H_k - y0_k) / dy_k), b_(2+2k) = clamp01(((-H_k) - y0_k) / dy_k);
+ *        b_1..b_6 are put in ascending order by the compare-exchanges (1,6) (2,4) (3,5) (2,3) (4,5) (1,4) (3,6) (1,2) (3,4) (5,6) (2,3)
+ *        (4,5), in this order, (i,j) leaving the smaller in b_i.  For i = 0..6: lo = b_i, hi = b_(i+1), tm = (lo + hi) * 0.5; per axis k
+ *        with y = y0_k + dy_k*tm: when |y| - H_k > 0, num_k = (y0_k - ((y > 0) ? H_k : -H_k)) * dy_k and den_k = dy_k*dy_k, else both 0;
+ *        ns = (num_0 + num_1) + num_2, ds likewise; ts = (ds > 0) ? (-ns) / ds : lo; ts = (ts < lo) ? lo : ts; ts = (ts > hi) ? hi : ts;
+ *        fmin = min(fmin, F(ts)), and for i < 6 fmin = min(fmin, F(hi)).  min(m, x) = (x < m) ? x : m.
+ *        APART when fmin > R * R.  (The minimum of F lies at a breakpoint, an end, or the stationary point of one interval: all are
+ *        visited, so no search for the sign change of F' is needed.)
+ *   3. BOX - BOX: the 15-axis separating-axis test in a's frame (Gottschalk; Ericson's TestOBBOBB).  w = Tb - Ta; t_i = dot(w, ua_i);
+ *        R_ij = dot(ua_i, ub_j); Q_ij = |R_ij| + SC_TICK_PAIR_SHAPES_SAT_EPS.
+ *        a's axis i:   APART when |t_i| > Ha_i + ((Hb_0*Q_i0 + Hb_1*Q_i1) + Hb_2*Q_i2).
+ *        b's axis j:   APART when |(t_0*R_0j + t_1*R_1j) + t_2*R_2j| > ((Ha_0*Q_0j + Ha_1*Q_1j) + Ha_2*Q_2j) + Hb_j.
+ *        ua_i x ub_j, with i1 = (i+1) % 3, i2 = (i+2) % 3, j1, j2 likewise:
+ *                      APART when |t_i2*R_i1j - t_i1*R_i2j| > (Ha_i1*Q_i2j + Ha_i2*Q_i1j) + (Hb_j1*Q_ij2 + Hb_j2*Q_ij1).
+ *        The epsilon keeps a cross axis of two (nearly) parallel edges -- a null vector up to rounding -- from separating anything.
+ * Pairs look as in scTickReadPairs: a < b, id = rank << 24 | dense index.  The order inside the list is unspecified.  A pair that the
+ * pair list names twice is tested, counted and listed once per naming.
+ * The pass runs on the device behind the pair search, on its stream (after scTickRunPairs in a split flow; with SC_TICK_PAIR_EVENTS in
+ * the same run, before the events, which still diff the AABB pair set): two launches, no host round trip, replayed from a captured
+ * graph.  It reads the resident collider records and matrix rows and owns no per-entity state.  Device memory: max_touching x 8 bytes.
+ * scTickSetPairShapes drops captured graphs, asks for no learn tick, and fails while scTickRunPairs is pending.  A context that never
+ * calls it allocates and launches exactly what it did before.
+ * scTickRun / scTickTileStep fail, with a last-error text and nothing changed, for SC_TICK_PAIR_SHAPES without SC_TICK_BROADPHASE, without
+ * a prior scTickSetPairShapes, or on a pipelined context (scTickSetPipelined / scTickSetPairsStream: by the time its pair half runs the
+ * matrices may be the next tick's -- the reason EXACT rays refuse it).  In the caller-owned split flow the pair half reads the matrix
+ * rows, the collider records and the dense indices as they stand when scTickRunPairs runs, so between
+ * scTickRun(.. | SC_TICK_SPLIT_PAIRS | SC_TICK_PAIR_SHAPES) and its scTickRunPairs the calls that rewrite one of them fail as they do for
+ * EXACT rays: scTickUploadWorldMatrices, scTickUploadColliders, scTickRemoveEntities, scTickSetEntityCount, scTickRun with SC_TICK_XFORM.
+ * scTickReadPairShapes fails when the last run did not carry the flag and while scTickRunPairs is pending. */
+#define SC_TICK_PAIR_SHAPES_SAT_EPS 1e-6f
+typedef struct ScTickPairShapeInfo
+{
+  uint32_t tested;          /* pairs of this tick's list that were looked at (the clamped total, as pair events count it) */
+  uint32_t touching;        /* true total of pairs listed as touching: may exceed max_touching and the caller's capacity */
+  uint32_t refined;         /* pairs decided by the shapes of both members */
+  uint32_t kept_as_boxes;   /* pairs with a member that cannot be refined: listed on their AABB answer */
+  uint32_t truncated;       /* 1 = touching > max_touching: the list holds max_touching valid members */
+  uint32_t pairs_truncated; /* 1 = the pair list itself was truncated this tick (ScTickCounts::pairs_truncated): the touching list is of what was listed */
+} ScTickPairShapeInfo;
+int scTickSetPairShapes(ScTickContext* ctx, uint32_t max_touching);   /* 0 switches it off and frees the buffers */
+/* pairs2: [capacity][2] (a, b), may be NULL with capacity 0.  Synchronises; copies the 24 bytes of `info` and
+ * min(touching, max_touching, capacity) pairs, nothing else. */
+int scTickReadPairShapes(ScTickContext* ctx, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

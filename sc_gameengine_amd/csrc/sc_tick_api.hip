@@ -123,6 +123,8 @@ struct ScTickContext
   PairEventState pairEvents{};
   void* pairEventSlab = nullptr; size_t pairEventSlabBytes = 0;
   bool pairEventsResyncAgain = false;      // ids were renamed between the halves of a split tick: forget again what its pair half remembers
+  // scTickSetPairShapes: the touching list, its running counts and its report.  All null until the call: nothing is launched.
+  PairShapeState pairShapes{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched); what the
@@ -633,16 +635,22 @@ AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
 
 // pair events: forget the remembered set (dense indices were renamed, or are no longer valid) -- the next flagged tick is a resync tick.
 // Queued on the tick stream, behind the ticks already issued.
-// Exact ray shapes in the caller-owned split flow: the pair half refines its candidates against the matrix rows, the collider records and
-// the dense indices AS THEY STAND when it runs (the bins hold tick t's boxes, nothing holds tick t's shapes).  So whatever rewrites one of
-// those is refused between the halves of a tick whose pair half casts rays in EXACT mode -- tick t's answers stay tick t's.
-bool exactRaysPending(const ScTickContext* c)
+// Collider shapes in the caller-owned split flow: a pair half that refines by shape -- rays in EXACT mode, the touching pairs -- reads the
+// matrix rows, the collider records and the dense indices AS THEY STAND when it runs (the bins hold tick t's boxes, nothing holds tick
+// t's shapes).  So whatever rewrites one of those is refused between the halves of such a tick -- tick t's answers stay tick t's.
+// What the pending pair half does with the shapes (nullptr: nothing, the gap is the host's):
+const char* pendingShapeReader(const ScTickContext* c)
 {
-  return c->pairsPending && c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS));
+  if (!c->pairsPending) return nullptr;
+  if (c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)))
+    return "casts rays in SC_TICK_RAY_SHAPES_EXACT mode";
+  if (c->pendingParams.flags & SC_TICK_PAIR_SHAPES) return "lists the touching pairs (SC_TICK_PAIR_SHAPES)";
+  return nullptr;
 }
-#define REFUSE_WHILE_EXACT_RAYS_PENDING(c, what) \
-  do { if (exactRaysPending(c)) return fail(c, what " is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that casts rays in " \
-                                               "SC_TICK_RAY_SHAPES_EXACT mode: its pair half reads the matrices and colliders as they stand"); } while (0)
+#define REFUSE_WHILE_SHAPES_PENDING(c, what) \
+  do { if (const char* reads = pendingShapeReader(c)) \
+         return fail(c, (std::string(what " is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that ") + reads + \
+                         ": its pair half reads the matrices and colliders as they stand").c_str()); } while (0)
 
 bool resyncPairEvents(ScTickContext* c)
 {
@@ -834,7 +842,8 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
-    if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // the pair set is complete: what begun, what ended
+    if (flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, p, c->pairShapes, c->stream);      // the pair set is complete: which of its pairs touch
+    if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // ... what begun, what ended
   } else {
     const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
@@ -856,6 +865,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       }
       else {
         { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
+        if (flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, p, c->pairShapes, c->stream);
         if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);
       }
     }
@@ -1104,7 +1114,7 @@ int scTickSetEntityCount(ScTickContext* c, uint32_t count)
 {
   if (!c) return 0;
   if (count > c->desc.capacity) return fail(c, "count exceeds capacity");
-  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickSetEntityCount");
+  REFUSE_WHILE_SHAPES_PENDING(c, "scTickSetEntityCount");
   const uint32_t before = c->n;
   c->n = count;
   c->linksStale = true;
@@ -1193,7 +1203,7 @@ int scTickUploadBounds(ScTickContext* c, uint32_t first, uint32_t count, const f
 int scTickUploadColliders(ScTickContext* c, uint32_t first, uint32_t count, const uint8_t* type, const float* he3, const float* radius, const float* halfHeight)
 {
   if (!c) return 0;
-  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickUploadColliders");
+  REFUSE_WHILE_SHAPES_PENDING(c, "scTickUploadColliders");
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
   // validate before anything is stored: a failed call leaves the context as it was
   for (uint32_t i = 0; i < count; ++i) {
@@ -1379,7 +1389,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
   if (!c) return 0;
   if (movedCount) *movedCount = 0;
   if (!idx && count) return fail(c, "null argument");
-  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickRemoveEntities");
+  REFUSE_WHILE_SHAPES_PENDING(c, "scTickRemoveEntities");
   if (!bind(c)) return 0;
   if (!count) return 1;
   const uint32_t n0 = c->n;
@@ -1624,7 +1634,7 @@ int scTickSetDrawBudget(ScTickContext* c, uint32_t maxDraws)
 int scTickUploadWorldMatrices(ScTickContext* c, uint32_t first, uint32_t count, const float* m16)
 {
   if (!c || !m16) return c ? fail(c, "null argument") : 0;
-  REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickUploadWorldMatrices");
+  REFUSE_WHILE_SHAPES_PENDING(c, "scTickUploadWorldMatrices");
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
   if (!count) return 1;
   c->boxesTouched = true;
@@ -1705,7 +1715,9 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);
-  if (pp.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, pp, c->pairEvents, ps);      // behind the pair search, on its stream
+  // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
+  if (pp.flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, pp, c->pairShapes, ps);      // behind the pair search, on its stream
+  if (pp.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, pp, c->pairEvents, ps);
   return rode;
 }
 
@@ -1741,7 +1753,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (!c) return 0;
   if (!bind(c)) return 0;
   if (!flushLinks(c)) return 0;
-  if (flags & SC_TICK_XFORM) REFUSE_WHILE_EXACT_RAYS_PENDING(c, "scTickRun with SC_TICK_XFORM");
+  if (flags & SC_TICK_XFORM) REFUSE_WHILE_SHAPES_PENDING(c, "scTickRun with SC_TICK_XFORM");
   if ((flags & SC_TICK_BROADPHASE) && c->desc.tile_sectors_x == 0) return fail(c, "broadphase requested but the context has no tile rectangle");
   // An empty context without a broadphase has nothing to launch: the per-tick counts read as zero.  With the broadphase
   // the stages still run (every kernel copes with n == 0): an emptied tile of a multi-GPU world must rewrite its border
@@ -1750,6 +1762,11 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's pair set)");
     if (!c->pairEvents.ctl) return fail(c, "SC_TICK_PAIR_EVENTS needs scTickSetPairEvents first");
     if (c->pairsStream) return fail(c, "SC_TICK_PAIR_EVENTS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its tick parities overlap in time");
+  }
+  if (flags & SC_TICK_PAIR_SHAPES) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_SHAPES needs SC_TICK_BROADPHASE in the same run (the touching pairs are those of this tick's pair list)");
+    if (!c->pairShapes.ctl) return fail(c, "SC_TICK_PAIR_SHAPES needs scTickSetPairShapes first");
+    if (c->pairsStream) return fail(c, "SC_TICK_PAIR_SHAPES cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its pair half runs when the matrices may be the next tick's");
   }
   if (flags & SC_TICK_BIND_RUNS) {
     if ((flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS)) != (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS))
@@ -2462,6 +2479,44 @@ int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, 
   if (nb && !d2h(c, begun2, e.begun, (size_t)nb * sizeof(uint2))) return 0;
   if (ne && !d2h(c, ended2, e.ended, (size_t)ne * sizeof(uint2))) return 0;
   if ((nb || ne) && !sync(c)) return 0;
+  return 1;
+}
+
+int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
+{
+  if (!c) return 0;
+  if (maxTouching && !c->sectors) return fail(c, "the context has no broadphase");
+  if (maxTouching > (1u << 27)) return fail(c, "touching pairs: at most 2^27 listed pairs");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  PairShapeState& e = c->pairShapes;
+  dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
+  e = PairShapeState{};
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  if (!maxTouching) return 1;
+  if (!dalloc(c, e.ctl, kPsCtlWords) || !dalloc(c, e.info, kPsInfoWords) || !dalloc(c, e.list, maxTouching, false)) {
+    dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
+    e = PairShapeState{};
+    return 0;
+  }
+  e.maxTouching = maxTouching;
+  return 1;
+}
+
+int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info)
+{
+  static_assert(sizeof(ScTickPairShapeInfo) == 6u * sizeof(uint32_t) && kPsInfoWords >= 6u, "the device writes the report word by word");
+  static_assert(kPairShapesSatEps == SC_TICK_PAIR_SHAPES_SAT_EPS, "the separating-axis epsilon differs from the header's");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
+  if (c->pairsPending) return fail(c, "touching pairs are ready after scTickRunPairs");
+  const PairShapeState& e = c->pairShapes;
+  if (!e.ctl) return fail(c, "touching pairs were switched off since the last scTickRun");
+  if (!joinPairs(c)) return 0;
+  if (!d2h(c, info, e.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t k = std::min(std::min(info->touching, e.maxTouching), pairs2 ? capacity : 0u);
+  if (k && (!d2h(c, pairs2, e.list, (size_t)k * sizeof(uint2)) || !sync(c))) return 0;
   return 1;
 }
 

@@ -355,6 +355,19 @@ struct PairEventState {
 constexpr uint32_t kPeCur = 0, kPeValid = 1, kPeBegun = 2, kPeEnded = 3, kPeTracked = 4, kPeOverflow = 5, kPeCtlWords = 16;
 constexpr uint32_t kPeInfoWords = 8;
 void launchPairEvents(const DeviceState& d, const TickParams& p, const PairEventState& e, hipStream_t s);
+// ---- touching pairs (sc_tick_pair_shapes.hip; include/sc_tick.h "touching pairs"): the pairs of this tick's list whose collider shapes
+// overlap, decided on the device behind the pair search from the resident collider records and this tick's matrix rows.  A kernel
+// argument of its own; the pass owns no per-entity state.
+struct PairShapeState {
+  uint2* list;                    // [maxTouching] (a, b) as the pair list holds them
+  uint32_t* ctl;                  // kPs* words below: the tick's running counts
+  uint32_t* info;                 // what the last flagged tick reports (== ScTickPairShapeInfo)
+  uint32_t maxTouching;
+};
+constexpr uint32_t kPsTouching = 0, kPsRefined = 1, kPsKept = 2, kPsTested = 3, kPsPairsTruncated = 4, kPsCtlWords = 8;
+constexpr uint32_t kPsInfoWords = 8;
+constexpr float kPairShapesSatEps = 1e-6f;      // == SC_TICK_PAIR_SHAPES_SAT_EPS
+void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState& e, hipStream_t s);
 // ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----
 struct BindRun24 { uint32_t first, count, pipeline, material, mesh, binds; };      // == ScTickBindRun
 // the report's words (== ScTickBindInfo)

@@ -1,0 +1,314 @@
+// sc_tick_pair_shapes.hip -- touching pairs: the pairs of this tick's list whose collider shapes overlap (own spec, include/sc_tick.h
+// "touching pairs").
+//
+// What Bullet's narrow phase answers behind src/engine/physics/sc_physics.cpp:218-225, as a boolean: the pair search reports pairs of
+// world AABBs, this pass drops those whose shapes -- oriented box, sphere, capsule, through the members' world matrices of this tick --
+// are provably apart.  Two launches behind the pair search, on its stream, no host round trip; the grids are fixed by capacities and every
+// count is read on the device, so the launches replay unchanged from a captured graph.
+//
+//   k_pair_shapes          a thread per pair of this tick, read in place from the shard segments as k_pair_events_diff reads them: both
+//                          members' collider records and matrix rows, one of three routines (segment-segment distance, segment-box
+//                          distance, 15-axis separating-axis test), one append per wave to the touching list
+//   k_pair_shapes_finish   one thread: the tick's report (ScTickPairShapeInfo), the running counts back to zero
+//
+// The filter only ever removes: a pair is dropped on a positive comparison alone, so a NaN keeps it, and a pair with a member that cannot
+// be refined (a Bounds proxy, a neighbour tile's record, a degenerate matrix) is listed on its AABB answer.  Every loop has a fixed trip
+// count; every index into the entity arrays is below the entity count, every index into the list below its capacity.  Plain HIP atomics
+// and vector stores only.  All arithmetic is fp32, unfused, left to right, as the header states it operation by operation.
+#include "sc_tick_internal.h"
+
+namespace sctick {
+
+namespace {
+
+__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ float clamp01(float x) { const float c = (x > 0.0f) ? x : 0.0f; return (c < 1.0f) ? c : 1.0f; }   // (a NaN is 0)
+
+// One wave appends the pairs of its lanes with `yes` to a list of `cap` entries whose running count is *counter: one atomic per wave,
+// the count is the true total, entries beyond the capacity are not written.  Every lane of the wave must call.
+__device__ __forceinline__ void appendWave(bool yes, uint2 pr, uint32_t* counter, uint2* list, uint32_t cap)
+{
+  const unsigned long long m = ballot64(yes);
+  if (!m) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(counter, (uint32_t)__popcll(m));
+  base = __shfl(base, 0, 64);
+  const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  if (yes && at < cap) list[at] = pr;
+}
+
+// a member of a pair as the routines take it: columns c[k], translation T, n[k] = dot(c[k], c[k]), the record (ex, ey, ez, radius)
+struct Member { float c[3][3]; float T[3]; float n[3]; float4 s; uint32_t type; bool ok; };
+
+// ok = the member can be refined: an own entity below the count with a typed collider and three finite, positive column norms
+__device__ __forceinline__ Member fetchMember(const DeviceState& d, uint32_t id, uint32_t count, uint32_t rankBits)
+{
+  Member m;
+  m.ok = false; m.type = kColliderBounds; m.s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { m.c[k][0] = m.c[k][1] = m.c[k][2] = 0.0f; m.T[k] = 0.0f; m.n[k] = 0.0f; }
+  const uint32_t e = id & 0x00FFFFFFu;
+  if (!d.colType || (id & 0xFF000000u) != rankBits || e >= count) return m;
+  m.type = d.colType[e];
+  if (m.type != kColliderBox && m.type != kColliderSphere && m.type != kColliderCapsule) return m;
+  m.s = d.colShape[e];
+  const float4 r0 = d.w0[e], r1 = d.w1[e], r2 = d.w2[e];
+  m.c[0][0] = r0.x; m.c[0][1] = r1.x; m.c[0][2] = r2.x;
+  m.c[1][0] = r0.y; m.c[1][1] = r1.y; m.c[1][2] = r2.y;
+  m.c[2][0] = r0.z; m.c[2][1] = r1.z; m.c[2][2] = r2.z;
+  m.T[0] = r0.w; m.T[1] = r1.w; m.T[2] = r2.w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) m.n[k] = dot3(m.c[k], m.c[k]);
+  m.ok = m.n[0] > 0.0f && m.n[1] > 0.0f && m.n[2] > 0.0f && isfinite(m.n[0]) && isfinite(m.n[1]) && isfinite(m.n[2]);
+  return m;
+}
+
+// a sphere or a capsule: the segment T - A .. T + A (A = 0: a point) and the radius around it
+struct Round { float A[3]; float R; };
+__device__ __forceinline__ Round roundOf(const Member& m)
+{
+  Round r;
+  if (m.type == kColliderSphere) {
+    const float nyz = (m.n[2] < m.n[1]) ? m.n[1] : m.n[2];
+    r.R = m.s.w * sqrtf((m.n[0] < nyz) ? nyz : m.n[0]);
+    r.A[0] = r.A[1] = r.A[2] = 0.0f;
+  } else {
+    r.R = m.s.w * sqrtf((m.n[0] < m.n[2]) ? m.n[2] : m.n[0]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r.A[i] = m.c[1][i] * m.s.y;
+    if (!(dot3(r.A, r.A) > 0.0f)) r.A[0] = r.A[1] = r.A[2] = 0.0f;      // no axis: the sphere of radius R
+  }
+  return r;
+}
+
+// 1. round - round: the squared distance between two segments by the clamped closed form; apart when it exceeds (Ra + Rb)^2
+__device__ __forceinline__ bool roundRoundApart(const Member& ma, const Member& mb)
+{
+  const Round ra = roundOf(ma), rb = roundOf(mb);
+  float p1[3], d1[3], p2[3], d2[3], r[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    p1[i] = ma.T[i] - ra.A[i]; d1[i] = ra.A[i] + ra.A[i];
+    p2[i] = mb.T[i] - rb.A[i]; d2[i] = rb.A[i] + rb.A[i];
+    r[i] = p1[i] - p2[i];
+  }
+  const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r);
+  float s = 0.0f, t = 0.0f;
+  if (!(a > 0.0f)) { if (e > 0.0f) t = clamp01(f / e); }
+  else {
+    const float c = dot3(d1, r);
+    if (!(e > 0.0f)) s = clamp01((-c) / a);
+    else {
+      const float b = dot3(d1, d2);
+      const float den = a * e - b * b;
+      if (den > 0.0f) s = clamp01((b * f - c * e) / den);
+      t = (b * s + f) / e;
+      if (t < 0.0f) { t = 0.0f; s = clamp01((-c) / a); }
+      else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
+    }
+  }
+  float v[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v[i] = (p1[i] + d1[i] * s) - (p2[i] + d2[i] * t);
+  const float sum = ra.R + rb.R;
+  return dot3(v, v) > sum * sum;
+}
+
+// a box in its own orthonormal frame: unit axes u[k], half lengths H[k]
+struct Frame { float u[3][3]; float H[3]; };
+__device__ __forceinline__ Frame frameOf(const Member& m)
+{
+  Frame f;
+  const float e[3] = { m.s.x, m.s.y, m.s.z };
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float q = sqrtf(m.n[k]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) f.u[k][i] = m.c[k][i] / q;
+    f.H[k] = e[k] * q;
+  }
+  return f;
+}
+
+__device__ __forceinline__ float boxDist2(const float y0[3], const float dy[3], const float H[3], float t)
+{
+  float g[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { const float x = fabsf(y0[k] + dy[k] * t) - H[k]; g[k] = (x > 0.0f) ? x : 0.0f; }
+  return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+}
+
+// 2. round - box: the segment in the box's frame; F(t), the squared distance of its point t from the box, is convex and piecewise
+// quadratic with breakpoints where a coordinate crosses a face plane -- its minimum is F at a breakpoint, at an end, or at the stationary
+// point of one of the seven intervals between them; apart when that minimum exceeds R^2
+__device__ __forceinline__ bool roundBoxApart(const Member& mr, const Member& mx)
+{
+  const Round rd = roundOf(mr);
+  const Frame fr = frameOf(mx);
+  float w[3], y0[3], dy[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = mr.T[i] - mx.T[i];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float yc = dot3(fr.u[k], w), ya = dot3(fr.u[k], rd.A);
+    y0[k] = yc - ya; dy[k] = ya + ya;
+  }
+  float fmin = boxDist2(y0, dy, fr.H, 0.0f);
+  if (rd.A[0] != 0.0f || rd.A[1] != 0.0f || rd.A[2] != 0.0f) {      // (a point: every dy is 0 and every F below would be F(0) again)
+    float x = boxDist2(y0, dy, fr.H, 1.0f);
+    fmin = (x < fmin) ? x : fmin;
+    float b[8];
+    b[0] = 0.0f; b[7] = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      b[1 + 2 * k] = clamp01((fr.H[k] - y0[k]) / dy[k]);
+      b[2 + 2 * k] = clamp01(((-fr.H[k]) - y0[k]) / dy[k]);
+    }
+    // b[1..6] in ascending order: a fixed network of twelve compare-exchanges
+#define SC_CX(i, j) { const float lo = (b[j] < b[i]) ? b[j] : b[i], hi = (b[j] < b[i]) ? b[i] : b[j]; b[i] = lo; b[j] = hi; }
+    SC_CX(1, 6) SC_CX(2, 4) SC_CX(3, 5) SC_CX(2, 3) SC_CX(4, 5) SC_CX(1, 4) SC_CX(3, 6) SC_CX(1, 2) SC_CX(3, 4) SC_CX(5, 6) SC_CX(2, 3) SC_CX(4, 5)
+#undef SC_CX
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const float lo = b[i], hi = b[i + 1];
+      const float tm = (lo + hi) * 0.5f;
+      float num[3], den[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float y = y0[k] + dy[k] * tm;
+        const bool out = fabsf(y) - fr.H[k] > 0.0f;
+        const float face = (y > 0.0f) ? fr.H[k] : -fr.H[k];
+        num[k] = out ? (y0[k] - face) * dy[k] : 0.0f;
+        den[k] = out ? dy[k] * dy[k] : 0.0f;
+      }
+      const float ns = (num[0] + num[1]) + num[2], ds = (den[0] + den[1]) + den[2];
+      float ts = (ds > 0.0f) ? (-ns) / ds : lo;
+      ts = (ts < lo) ? lo : ts;
+      ts = (ts > hi) ? hi : ts;
+      x = boxDist2(y0, dy, fr.H, ts);
+      fmin = (x < fmin) ? x : fmin;
+      if (i < 6) { x = boxDist2(y0, dy, fr.H, hi); fmin = (x < fmin) ? x : fmin; }
+    }
+  }
+  return fmin > rd.R * rd.R;
+}
+
+// 3. box - box: the 15-axis separating-axis test in A's frame; apart when some axis has |t . L| > ra + rb
+__device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
+{
+  const Frame fa = frameOf(ma), fb = frameOf(mb);
+  float Rm[3][3], Ab[3][3], w[3], t[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = mb.T[i] - ma.T[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = dot3(w, fa.u[i]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { Rm[i][j] = dot3(fa.u[i], fb.u[j]); Ab[i][j] = fabsf(Rm[i][j]) + kPairShapesSatEps; }
+  }
+  bool apart = false;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                            // L = A's axis i
+    const float rb = (fb.H[0] * Ab[i][0] + fb.H[1] * Ab[i][1]) + fb.H[2] * Ab[i][2];
+    apart = apart || (fabsf(t[i]) > fa.H[i] + rb);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {                            // L = B's axis j
+    const float ra = (fa.H[0] * Ab[0][j] + fa.H[1] * Ab[1][j]) + fa.H[2] * Ab[2][j];
+    const float tl = (t[0] * Rm[0][j] + t[1] * Rm[1][j]) + t[2] * Rm[2][j];
+    apart = apart || (fabsf(tl) > ra + fb.H[j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                            // L = A's axis i x B's axis j
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      const float ra = fa.H[i1] * Ab[i2][j] + fa.H[i2] * Ab[i1][j];
+      const float rb = fb.H[j1] * Ab[i][j2] + fb.H[j2] * Ab[i][j1];
+      const float tl = t[i2] * Rm[i1][j] - t[i1] * Rm[i2][j];
+      apart = apart || (fabsf(tl) > ra + rb);
+    }
+  }
+  return apart;
+}
+
+__global__ __launch_bounds__(kTile) void k_pair_shapes(const DeviceState d, const PairShapeState e, uint32_t parity, uint32_t maxPairs, uint32_t count,
+                                                       uint32_t rankBits)
+{
+  static_assert(kPairShards == 64, "one lane per shard counter");
+  __shared__ uint32_t prefix[kPairShards + 1];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t shardCap = maxPairs / kPairShards;
+  if (threadIdx.x < 64u) {
+    // pairs per shard segment, clamped to the segment as k_gather_pairs does, and their running sum
+    const uint32_t c = d.pairShardCount[(parity * kPairShards + lane) * kShardStride];
+    uint32_t s = c < shardCap ? c : shardCap;
+#pragma unroll
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+      const uint32_t o = __shfl_up(s, off, 64);
+      if (lane >= off) s += o;
+    }
+    prefix[lane + 1u] = s;
+    if (lane == 0) prefix[0] = 0u;
+  }
+  __syncthreads();
+  const uint32_t total = prefix[kPairShards];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {               // what the report needs besides the running counts
+    e.ctl[kPsTested] = total;
+    e.ctl[kPsPairsTruncated] = d.counters[kCtrPar + 8u * parity + kCtrPairs] != 0u ? 1u : 0u;      // pairs found after every segment was full
+  }
+  const uint32_t stride = gridDim.x * kTile;
+  for (uint32_t base = blockIdx.x * kTile + (threadIdx.x & ~63u); base < total; base += stride) {      // (wave-uniform trip count)
+    const uint32_t i = base + lane;
+    bool touching = false, refined = false, kept = false;
+    uint2 pr = make_uint2(0u, 0u);
+    if (i < total) {
+      uint32_t s = 0;                                         // the segment pair i lies in: the last one that starts at or before i
+#pragma unroll
+      for (uint32_t step = 32u; step; step >>= 1) if (prefix[s + step] <= i) s += step;
+      pr = d.pairs[(size_t)s * shardCap + (i - prefix[s])];
+      const Member ma = fetchMember(d, pr.x, count, rankBits), mb = fetchMember(d, pr.y, count, rankBits);
+      if (!(ma.ok && mb.ok)) { kept = true; touching = true; }
+      else {
+        refined = true;
+        const bool boxA = ma.type == kColliderBox, boxB = mb.type == kColliderBox;
+        bool apart;
+        if (boxA && boxB) apart = boxBoxApart(ma, mb);
+        else if (boxA) apart = roundBoxApart(mb, ma);
+        else if (boxB) apart = roundBoxApart(ma, mb);
+        else apart = roundRoundApart(ma, mb);
+        touching = !apart;
+      }
+    }
+    const unsigned long long mr = ballot64(refined), mk = ballot64(kept);
+    if (lane == 0) {
+      if (mr) atomicAdd(&e.ctl[kPsRefined], (uint32_t)__popcll(mr));
+      if (mk) atomicAdd(&e.ctl[kPsKept], (uint32_t)__popcll(mk));
+    }
+    appendWave(touching, pr, &e.ctl[kPsTouching], e.list, e.maxTouching);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_pair_shapes_finish(const PairShapeState e)
+{
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const uint32_t touching = e.ctl[kPsTouching];
+  e.info[0] = e.ctl[kPsTested]; e.info[1] = touching; e.info[2] = e.ctl[kPsRefined]; e.info[3] = e.ctl[kPsKept];
+  e.info[4] = touching > e.maxTouching ? 1u : 0u; e.info[5] = e.ctl[kPsPairsTruncated];
+  e.ctl[kPsTouching] = 0u; e.ctl[kPsRefined] = 0u; e.ctl[kPsKept] = 0u; e.ctl[kPsTested] = 0u; e.ctl[kPsPairsTruncated] = 0u;
+}
+
+} // namespace
+
+void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState& e, hipStream_t s)
+{
+  if (!e.ctl) return;
+  // the grid by the pair list's capacity alone: a thread per pair it can hold (grid-stride beyond that)
+  const uint32_t blocks = std::min(std::max((p.maxPairs + kTile - 1u) / kTile, 1u), 2048u);
+  hipLaunchKernelGGL(k_pair_shapes, dim3(blocks), dim3(kTile), 0, s, d, e, p.parity, p.maxPairs, p.n, p.rankBits);
+  hipLaunchKernelGGL(k_pair_shapes_finish, dim3(1), dim3(64), 0, s, e);
+}
+
+} // namespace sctick

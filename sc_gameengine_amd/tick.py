@@ -728,6 +728,25 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairEventInfo._fields_}
         return b[:min(out["begun"], cap)].copy(), e[:min(out["ended"], cap)].copy(), out
 
+    # ---- touching pairs: the pairs of the tick's list whose collider shapes overlap ----
+    def set_pair_shapes(self, max_touching):
+        """List, on every run with capi.PAIR_SHAPES, the pairs of the tick's pair list whose collider shapes (upload_colliders: box, sphere,
+        capsule, through the members' world matrices of the tick) overlap: room for max_touching pairs; 0 switches it off
+        (scTickSetPairShapes).  Drops captured graphs, costs no learn tick."""
+        self._ok(self.lib.scTickSetPairShapes(self.ctx, int(max_touching)), "scTickSetPairShapes")
+        self._max_touching = int(max_touching)
+
+    def read_pair_shapes(self):
+        """(touching[n, 2], info) of the last run with capi.PAIR_SHAPES: uint32 ids a < b in unspecified order; info is a dict (tested,
+        touching, refined, kept_as_boxes, truncated, pairs_truncated) whose touching is the true total -- the list holds at most
+        max_touching."""
+        cap = getattr(self, "_max_touching", 0)
+        pairs = np.zeros((max(cap, 1), 2), np.uint32)
+        info = capi.PairShapeInfo()
+        self._ok(self.lib.scTickReadPairShapes(self.ctx, _u(pairs), cap, C.byref(info)), "scTickReadPairShapes")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairShapeInfo._fields_}
+        return pairs[:min(out["touching"], cap)].copy(), out
+
     def draws(self):
         cnt = C.c_uint32()
         self._ok(self.lib.scTickReadDraws(self.ctx, None, 0, C.byref(cnt)), "scTickReadDraws")
