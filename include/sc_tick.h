@@ -94,6 +94,8 @@ typedef struct ScTickCounts    /* CullingStats (sc_world_partition.h:334-339) + 
   uint32_t draws_dropped;
   uint32_t max_depth;          /* deepest hierarchy level after scTickSetTopology */
   uint32_t unreachable;        /* entities in or below a parent cycle (never updated, sc_ecs.cpp:173-210) */
+  /* bin_overflow, big_boxes and border_lost are counted where the bins are filled.  After a QUIET tick (scTickGetBinStats: a broadphase
+     tick of a world that cannot pair and whose bins nothing else reads fills none) they keep the values of the most recent tick that did. */
   uint32_t bin_overflow;       /* bin records that found their sector's bin (64 records) full: they sit in the sector overflow list */
   uint32_t big_boxes;          /* boxes in the big list: larger than 2x2 sectors or outside the tile rectangle */
   uint32_t draws_sorted;       /* with SC_TICK_SORT_DRAWS: draws left after the renderer's mesh / material handle checks */
@@ -116,7 +118,8 @@ typedef struct ScTickDrawItem  /* DrawItem, sc_ecs.h:159-165: 80 bytes, model at
   float    model[16];
 } ScTickDrawItem;
 
-/* kernels whose per-launch durations scTickGetKernelTimes reports */
+/* kernels whose per-launch durations scTickGetKernelTimes reports (SC_TICK_K_PAIRS: the end-of-tick kernel of a tick with
+ * SC_TICK_BROADPHASE -- compaction + pair search in one launch, or the compaction alone on a quiet tick, scTickGetBinStats) */
 enum { SC_TICK_K_XFORM_CULL = 0, SC_TICK_K_COMPACT = 1, SC_TICK_K_PAIRS = 2, SC_TICK_K_NUDGE = 3 /* producer: nudge or movers */, SC_TICK_K_COUNT = 4 };
 
 uint32_t       scTickGetApiVersion(void);
@@ -301,10 +304,19 @@ int scTickGatherVisibleCounts(ScTickContext* ctx, uint32_t* counts_out, uint32_t
  * whose own records cannot pass the group/mask filter against each other -- static props only -- are not even written until a
  * record from elsewhere needs them (the pair search then rebuilds them; SC_TICK_VARIANT bit 5 switches that off; ticks with
  * ray queries or traffic sensors, and pipelined tiles, write every record).
+ * QUIET ticks: a run with SC_TICK_BROADPHASE does the device work of the same call without the flag -- no bin, counter, layer summary
+ * or home word is read or written; the pair set is empty by construction -- while ALL of this holds: no two layer words of the world
+ * admit a pair (bit 2 below); the remembered slots are on, learnt and current (no append, remove, re-link or layer upload since the learn
+ * tick); the flags hold none of SC_TICK_RAYS, _SWEEPS, _ANCHORED_RAYS, _PAIR_EVENTS, _PAIR_SHAPES, _DENSE_AABBS, _SPLIT_PAIRS; traffic
+ * sensors are off, the tile has no neighbours and no pairs stream.  Any other tick bins as ever, and the first one behind a quiet stretch
+ * rewrites every record it would otherwise have left alone (boxes may have moved unseen) and applies the learn rule (the slots age on
+ * through the stretch, but no learn tick falls inside it).  ScTickCounts::bin_overflow, big_boxes and border_lost keep the values of the
+ * most recent tick that binned.  SC_TICK_VARIANT bit 3 (8) switches quiet ticks off.
  * stats[0] remembered slots, [1] of those written on every tick, [2] bit 0: the last tick was allowed to leave the other slots
  * unwritten, bit 1: it left records of entities whose matrix was not rebuilt as they were, bit 2: no two of the uploaded layer words
  * (nor, on a tile, of the declared world vocabulary) admit a pair, so the pair role was launched as a sweep over the bins' counters
- * (a quarter of the workgroups; a launch shape, never a shortcut of the search), [3] learn ticks so far.  Reads the slots back (a few MB): not for the frame loop. */
+ * (a quarter of the workgroups; a launch shape, never a shortcut of the search), bit 3: the last tick was a quiet tick (the other bits then
+ * still tell of the most recent tick that binned), [3] learn ticks so far.  Reads the slots back (a few MB): not for the frame loop. */
 int scTickGetBinStats(ScTickContext* ctx, uint32_t stats[4]);
 /* Where the tick ends (diagnostics; no result depends on it).  The fused kernel works in spans of consecutive dense indices, one
  * workgroup each.  In a world where no parent link crosses a span boundary ("span-closed") the workgroup also ends the tick for its

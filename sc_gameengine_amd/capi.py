@@ -20,6 +20,7 @@ ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a wor
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
+BIN_LAZY, BIN_STAY, BIN_SWEEP_ONLY, BIN_QUIET = 1, 2, 4, 8     # scTickGetBinStats stats[2]: what the last tick did with the bins (BIN_QUIET: nothing at all)
 NO_PARENT = -1
 # collider types (SC_TICK_COLLIDER_*): what an entity's broadphase proxy is formed from
 COLLIDER_BOUNDS, COLLIDER_NONE, COLLIDER_BOX, COLLIDER_SPHERE, COLLIDER_CAPSULE = 0, 1, 2, 3, 4

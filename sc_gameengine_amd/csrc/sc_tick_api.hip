@@ -142,7 +142,8 @@ struct ScTickContext
 
   // graph
   bool graphMode = false;
-  CapturedGraph graph[kMaxParity];                     // the tick, one per broadphase tick parity; with its RCCL group: the whole tile step (exchange + pair half)
+  CapturedGraph graph[kMaxParity + 1];                 // the tick, one per broadphase tick parity; with its RCCL group: the whole tile step (exchange + pair half);
+                                                       // [kMaxParity]: the quiet tick's (it binds to no parity, and alternating with binning ticks must not re-capture either)
   bool captureWholeStep = false;                       // set by scTickTileStep around its scTickRun
   bool ownStep = false;                                // scTickTileStep is running: the pair half follows the tick half at once, nothing of the host's in between
   uint64_t topoEpoch = 0;
@@ -156,6 +157,10 @@ struct ScTickContext
   bool lazyEnabled = true;                             // lazy records (DeviceState::lazyCtl)
   bool fastPairs = true;                               // ordered home slots: bins without visitors take the pair role's fast path (DeviceState::homeCast)
   bool lastTickLazy = false, lastTickStay = false, lastTickSweepOnly = false; uint32_t learnTicks = 0;  // scTickGetBinStats
+  // Quiet ticks (quietTick()): a broadphase tick of a world that cannot pair, whose bins nothing else reads either, runs the device work
+  // of the same call without SC_TICK_BROADPHASE; its pair set is empty by construction and reported so by the host
+  bool quietEnabled = true;                            // SC_TICK_VARIANT bit 3 switches them off (A/B)
+  bool lastTickQuiet = false;                          // scTickGetBinStats bit 3; scTickGetCounts / scTickReadPairs answer from the host
   bool worldLayersKnown = false; uint32_t worldLayers = 0;   // scTickSetWorldLayers: group bits | mask bits << 16 of every collider of the tiled world
   bool boxesTouched = false;                           // bounds or world matrices were uploaded since the last broadphase tick (TickParams::cleanStay)
   uint64_t homeEpoch = ~0ull; uint32_t homeAge = 0, homePeriod = 64;
@@ -853,8 +858,16 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       launchCompactPack(ds, p, grid, c->stream, ride ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
       c->packedRides = ride;
     } else if (needCompact) {
-      Scoped s(c, SC_TICK_K_COMPACT, timing);
-      launchCompact(ds, p, grid, c->stream);
+      // a quiet tick's end-of-tick kernel: timed in the slot of a broadphase tick's end-of-tick kernel, SC_TICK_K_PAIRS, and like it by the
+      // dispatch's own begin / end timestamps (whoever reads that slot sees what the tick's second launch cost, whichever it was)
+      if (c->lastTickQuiet && timed(c, SC_TICK_K_PAIRS, timing)) {
+        const EventPair ev = takeEvents(c);
+        launchCompact(ds, p, grid, c->stream, ev.a, ev.b);
+        c->times[SC_TICK_K_PAIRS].push_back(ev);
+      } else {
+        Scoped s(c, SC_TICK_K_COMPACT, timing && !c->lastTickQuiet);
+        launchCompact(ds, p, grid, c->stream);
+      }
     }
     if (flags & SC_TICK_BROADPHASE) {
       if (flags & SC_TICK_SPLIT_PAIRS) {                                            // the caller exchanges, then scTickRunPairs
@@ -907,14 +920,15 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   }
 }
 
-// drop captured graphs: every parity's by default
-void dropGraphs(CapturedGraph* g, uint32_t count = kMaxParity)
+// drop captured graphs: every one of the array (the tick's: the quiet tick's too)
+void dropGraphs(CapturedGraph* g, uint32_t count)
 {
   for (uint32_t k = 0; k < count; ++k) {
     if (g[k].exec) { hipGraphExecDestroy(g[k].exec); g[k].exec = nullptr; }
     if (g[k].graph) { hipGraphDestroy(g[k].graph); g[k].graph = nullptr; }
   }
 }
+template <uint32_t N> void dropGraphs(CapturedGraph (&g)[N]) { dropGraphs(g, N); }
 
 // Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for other TickParams, another
 // topology epoch, or with / without the library's RCCL group inside (rccl: the group touches the communicator's own resources
@@ -962,10 +976,10 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (e != hipSuccess || count <= 0) { fail(nullptr, "no HIP device available (libsc_tick needs an AMD GPU; there is no CPU fallback)", e); return nullptr; }
   if (desc->device_ordinal < 0 || desc->device_ordinal >= count) { fail(nullptr, "device ordinal out of range"); return nullptr; }
 
-  // SC_TICK_VARIANT: the two A/B switches that remain (include/sc_tick.h); any other bit names a retired experiment
+  // SC_TICK_VARIANT: the three A/B switches that remain (include/sc_tick.h); any other bit names a retired experiment
   const char* vs = std::getenv("SC_TICK_VARIANT");
   const uint32_t variant = vs ? (uint32_t)std::atoi(vs) : 0u;
-  if (variant & ~(2u | 32u)) { fail(nullptr, "SC_TICK_VARIANT: only bits 1 (2, home slots off) and 5 (32, lazy records off) remain"); return nullptr; }
+  if (variant & ~(2u | 8u | 32u)) { fail(nullptr, "SC_TICK_VARIANT: only bits 1 (2, home slots off) and 5 (32, lazy records off) and 3 (8, quiet ticks off) remain"); return nullptr; }
 
   ScTickContext* c = new ScTickContext();
   c->desc = *desc;
@@ -1064,6 +1078,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   }
   if (variant & 32u) c->lazyEnabled = false;            // SC_TICK_VARIANT bit 5: every remembered slot is written on every tick (A/B)
   if (variant & 2u) c->homeEnabled = false;             // SC_TICK_VARIANT bit 1: every record reserves its slot on every tick (A/B)
+  if (variant & 8u) c->quietEnabled = false;            // SC_TICK_VARIANT bit 3: a tick whose bins nobody reads fills and sweeps them all the same (A/B)
   if (const char* fp = std::getenv("SC_TICK_FAST_PAIRS")) c->fastPairs = std::atoi(fp) != 0;      // 0: every bin goes through the general pair search (A/B)
   if (const char* hp = std::getenv("SC_TICK_HOME_PERIOD")) { const int v = std::atoi(hp); if (v > 0) c->homePeriod = (uint32_t)v; }
   if (ok && c->sectors) { e = hipMemset(d.ovfLo, 0xFF, (size_t)c->sectors * sizeof(uint32_t)); if (e != hipSuccess) ok = fail(c, "hipMemset", e); }
@@ -1748,6 +1763,20 @@ static bool worldCanPair(ScTickContext* c)
   return !c->worldLayersKnown || ((c->worldLayers & 0xFFFFu) & (c->worldLayers >> 16)) != 0u;
 }
 
+// A QUIET tick: a broadphase tick none of whose bins, counters, layer summaries or home words anybody reads -- the world cannot pair
+// (worldCanPair), no query, sensor, event, shape pass, dense-box read-back, neighbour or caller-owned pair half looks at the bins, and the
+// remembered slots are current, so nothing is to be learnt either.  Its device work is that of the same call without SC_TICK_BROADPHASE.
+// The slots' age does not end a quiet stretch (nothing ages that anyone reads): the first binning tick behind it applies the usual rule.
+static bool quietTick(ScTickContext* c, uint32_t flags)
+{
+  constexpr uint32_t kBinReaders = SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_PAIR_EVENTS | SC_TICK_PAIR_SHAPES |
+                                   SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS;
+  if (!(flags & SC_TICK_BROADPHASE) || (flags & kBinReaders) || !c->quietEnabled || !c->homeEnabled || !c->lazyEnabled) return false;
+  if (!c->n || c->sensors || c->neighbourMask || c->pairsStream || c->pairsPending) return false;
+  if (!c->homeValid || c->homeEpoch != c->topoEpoch) return false;      // (a learn tick is due: an append, a remove, a re-link, a layer upload)
+  return !worldCanPair(c);
+}
+
 int scTickRun(ScTickContext* c, uint32_t flags)
 {
   if (!c) return 0;
@@ -1779,6 +1808,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
     c->lastTickTail = false;
+    c->lastTickQuiet = false;
     HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
     return 1;
   }
@@ -1794,12 +1824,24 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if ((flags & SC_TICK_SORT_DRAWS) && !c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
   if ((flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)) && c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && c->pairsStream)
     return fail(c, "SC_TICK_RAY_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its rays are cast when the matrices may be the next tick's");
+  // (a quiet tick keeps the flag in lastFlags -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
+  const bool quiet = quietTick(c, flags);
+  const uint32_t run = quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
   TickParams p; uint32_t grid;
-  fillParams(c, flags, p, grid);
+  fillParams(c, run, p, grid);
+  if (quiet) p.parity = 0u;                            // (no kernel of it reads the word; its graph is one whatever parity the binning ticks have reached)
   c->lastFlags = flags;
+  c->lastTickQuiet = quiet;
   c->lastTickTail = (p.flags & kFlagTailOwnsDirty) != 0;
   c->lastTickLearn = false;
-  if ((flags & SC_TICK_XFORM) && !(flags & SC_TICK_BROADPHASE)) c->boxesTouched = true;      // matrices change, the bins do not follow
+  if ((run & SC_TICK_XFORM) && !(run & SC_TICK_BROADPHASE)) c->boxesTouched = true;      // matrices change, the bins do not follow
+  if (quiet) {
+    // the records go stale like on a transform-only tick: the next binning tick rewrites every always-written slot (cleanStay 0).  The bins'
+    // counters and layer summaries stay at homeCount / homeLayers, where the last pair role left them; the slots age on.
+    c->boxesTouched = true;
+    c->homeAge++;
+  }
+  flags = run;
   if ((flags & SC_TICK_BROADPHASE) && c->homeEnabled) {
     // home slots: a learn tick when nothing is remembered, the world's shape changed (entities, hierarchy, layers) or the
     // slots have aged; every bin copy must be idle and empty for it (a rare event: the streams are joined here)
@@ -1857,7 +1899,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     // whole-step capture (scTickTileStep on a tile with neighbours): the RCCL group and the pair half join the graph, so a
     // step of an in-order tile is ONE hipGraphLaunch
     const bool whole = c->captureWholeStep;
-    if (!replayGraph(c, c->stream, c->graph[q], p, whole, "hipStreamEndCapture", [&] {
+    if (!replayGraph(c, c->stream, c->graph[quiet ? kMaxParity : q], p, whole, "hipStreamEndCapture", [&] {
           enqueueStages(c, p, grid, true);
           if (!whole) return 1;
           if (!exchangeBorders(c, p.parity, c->stream, true)) return 0;
@@ -2173,7 +2215,7 @@ int scTickGetCounts(ScTickContext* c, ScTickCounts* out)
   out->renderables_total = k[6];
   out->visible = k[0];
   out->culled = k[1];
-  if (c->sectors && (c->lastFlags & SC_TICK_BROADPHASE) && !c->pairsPending) {
+  if (c->sectors && (c->lastFlags & SC_TICK_BROADPHASE) && !c->pairsPending && !c->lastTickQuiet) {      // (a quiet tick: 0 pairs by construction)
     TickParams pp{}; pp.maxPairs = c->maxPairs;
     launchGatherPairs(c->d, pp, resultSlot, c->dPairsOut, c->dPairTotal, c->stream);
     uint32_t tot[2] = {};
@@ -2311,6 +2353,7 @@ int scTickReadPairs(ScTickContext* c, uint32_t* pairs2, uint32_t cap, uint32_t* 
   if (!(c->lastFlags & SC_TICK_BROADPHASE)) return fail(c, "the last scTickRun did not request SC_TICK_BROADPHASE");
   if (c->pairsPending) return fail(c, "scTickRunPairs has not been called for the last tick");
   if (!joinPairs(c)) return 0;
+  if (c->lastTickQuiet) { *count = 0; return 1; }      // no two colliders of that tick's world could meet: the empty set, whatever the bins' copies hold
   // the pair list is kept in per-shard segments on the device; gather them into one list first
   TickParams pp{}; pp.maxPairs = c->maxPairs;
   const uint32_t slot = c->lastParity;
@@ -3116,7 +3159,7 @@ int scTickGetBinStats(ScTickContext* c, uint32_t stats[4])
   stats[0] = stats[1] = stats[2] = stats[3] = 0u;
   if (!bind(c)) return 0;
   if (!c->d.homeA || !c->n) return 1;
-  stats[2] = (c->lastTickLazy ? 1u : 0u) | (c->lastTickStay ? 2u : 0u) | (c->lastTickSweepOnly ? 4u : 0u); stats[3] = c->learnTicks;
+  stats[2] = (c->lastTickLazy ? 1u : 0u) | (c->lastTickStay ? 2u : 0u) | (c->lastTickSweepOnly ? 4u : 0u) | (c->lastTickQuiet ? 8u : 0u); stats[3] = c->learnTicks;
   if (!c->homeValid) return 1;
   if (!sync(c)) return 0;
   std::vector<uint32_t> a(c->n), b(c->n);

@@ -3036,10 +3036,11 @@ static uint32_t compactGroup(uint32_t grid, bool merged)
 {
   return (merged && grid >= 512u) ? 2u : 1u;
 }
-void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s)
+void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
   const uint32_t g = compactGroup(grid, false);
-  hipLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
+  if (evA) hipExtLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, evA, evB, 0, d, p, g);
+  else hipLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
 }
 // Pair-role geometry (round 4, second form): four pair workgroups for every CU -- the fifth resident workgroup of each CU is left to the
 // compaction role, which shares the launch and comes behind the pair role in index order -- and the run as long as that needs:

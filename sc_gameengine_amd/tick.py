@@ -532,11 +532,14 @@ class WorldTick:
         self._ok(self.lib.scTickSetWorldLayers(self.ctx, g, m, 1 if known else 0), "scTickSetWorldLayers")
 
     def bin_stats(self):
-        """how the broadphase bins are filled: remembered slots, those written on every tick, whether the last tick could leave slots unwritten, learn ticks"""
+        """how the broadphase bins are filled: remembered slots, those written on every tick, whether the last tick could leave slots unwritten, learn ticks;
+        quiet_last_tick: the last tick filled no bin at all (nothing reads them: scTickGetBinStats) -- the other flags then tell of the last tick that did"""
         st = np.zeros(4, np.uint32)
         self._ok(self.lib.scTickGetBinStats(self.ctx, _u(st)), "scTickGetBinStats")
-        return {"remembered_slots": int(st[0]), "written_every_tick": int(st[1]), "lazy_last_tick": bool(st[2] & 1),
-                "unchanged_records_stay": bool(st[2] & 2), "pair_role_sweep_only": bool(st[2] & 4), "learn_ticks": int(st[3])}
+        return {"remembered_slots": int(st[0]), "written_every_tick": int(st[1]), "lazy_last_tick": bool(st[2] & capi.BIN_LAZY),
+                "unchanged_records_stay": bool(st[2] & capi.BIN_STAY), "pair_role_sweep_only": bool(st[2] & capi.BIN_SWEEP_ONLY),
+                "quiet_last_tick": bool(st[2] & capi.BIN_QUIET),
+                "learn_ticks": int(st[3])}
 
     def tail_stats(self):
         """where the last tick ended: whether its fused kernel owned the dirty words (dirty clear and root nudge per span), and whether the
