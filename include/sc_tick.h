@@ -63,6 +63,7 @@ enum {
   SC_TICK_PAIR_EVENTS = 1u << 12,  /* with BROADPHASE: report which pairs begun and which ended since the last run with this flag (scTickSetPairEvents) */
   SC_TICK_BIND_RUNS   = 1u << 13,  /* with DRAWS | SORT_DRAWS: also the bind runs of the sorted list and the material touch set (scTickSetBindRuns) */
   SC_TICK_PAIR_SHAPES = 1u << 14,  /* with BROADPHASE: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes) */
+  SC_TICK_TOUCH_EVENTS = 1u << 15, /* with BROADPHASE: report which pairs begun and which ended TOUCHING since the last run with this flag (scTickSetTouchEvents) */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -949,6 +950,63 @@ int scTickSetPairShapes(ScTickContext* ctx, uint32_t max_touching);   /* 0 switc
 /* pairs2: [capacity][2] (a, b), may be NULL with capacity 0.  Synchronises; copies the 24 bytes of `info` and
  * min(touching, max_touching, capacity) pairs, nothing else. */
 int scTickReadPairShapes(ScTickContext* ctx, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info);
+
+/* ---- touch events: the tick-to-tick difference of the touching set ----
+ * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on
+ * every tick, with no memory.  A host that keeps a contact cache or fires trigger enter / exit wants begin / end of TOUCHING: two yawed
+ * vehicles in neighbouring lanes are an AABB pair that never touches, and a pedestrian capsule meets the bounding cube of a rotated prop
+ * metres before it meets the prop.  This build's OWN SPEC: the "pair events" text with "this tick's pair set" replaced by "this tick's
+ * touching set".
+ *   THE SET    The touching set of a tick is the set of distinct pairs (a, b), a < b, of this tick's pair list that the "touching pairs"
+ *              section does not prove apart: the same three routines, the same refinability rule, the same fp32 operation order.  A pair
+ *              with a member that is not refinable -- a BOUNDS proxy, a neighbour tile's border record, a degenerate matrix, any member
+ *              of a context without colliders -- is in the set on its AABB answer; so in a world without uploaded colliders touch events
+ *              equal pair events as sets.  A pair that the pair list names twice is in the set once.
+ *   The flag needs neither SC_TICK_PAIR_SHAPES nor scTickSetPairShapes, and max_touching does not limit it: a truncated touching LIST
+ *   (ScTickPairShapeInfo::truncated) loses no event.  With both flags in a run each pair is decided once, in one pass.
+ *   scTickSetTouchEvents(max_tracked_pairs, max_events) enables them (and sizes every buffer; (0, 0) switches them off and frees the
+ *   buffers).  The context then remembers the touching set of the last run that carried SC_TICK_TOUCH_EVENTS.  A run with the flag reports
+ *     begun   the pairs of this tick's touching set that are not in the remembered set
+ *     ended   the pairs of the remembered set that are not in this tick's touching set
+ *   and then remembers its own set.  Ids are rank << 24 | dense index, a < b.  The order inside a list is unspecified.  Runs without the
+ *   flag leave the remembered set alone.
+ *   RESYNC     begun = the whole touching set, ended = nothing, resync = 1: on the first flagged run, after scTickRemoveEntities, a
+ *              shrinking scTickSetEntityCount, scTickSetTile to another rank, and after an overflow tick -- exactly where pair events
+ *              resync; a rename between the halves of a split tick is forgotten again behind the pair half, as for pair events.
+ *              Appends force no resync, nor do topology, layer or COLLIDER uploads: their effect arrives as ordinary events -- a collider
+ *              that shrinks ends its touches, a type change is decided by the new shape.
+ *   OVERFLOW   the pair list was truncated (ScTickCounts::pairs_truncated), or this tick's touching set holds more than
+ *              max_tracked_pairs distinct pairs: overflow = 1, every count 0, both lists empty, the remembered set is dropped; the next
+ *              flagged run that fits is a resync tick.  It is the TOUCHING count that decides: a tick with 1 000 AABB pairs of which 40
+ *              touch fits max_tracked_pairs = 40.
+ *   TRUNCATED  more than max_events pairs begin, or end: begun / ended carry the true totals, each list holds max_events valid members,
+ *              events_truncated = 1.  The remembered set is whole all the same.
+ * Order behind the pair search, on its stream (after scTickRunPairs in a split flow): the narrow phase -- ONE pass for the touching list
+ * and / or the touch events -- then the pair events, which keep diffing the AABB set: their output is the same with touch events on or
+ * off.  No host round trip; the launches replay from a captured graph.  Device memory, as for pair events: two tables of slots x 8 bytes,
+ * slots = the power of two >= 2 x max_tracked_pairs (at least 64), plus slots / 4 bytes of marks, plus 2 x max_events x 8 bytes.
+ * scTickSetTouchEvents drops captured graphs, asks for no learn tick, and fails while scTickRunPairs is pending.  A context that never
+ * calls it allocates and launches exactly what it did before.
+ * scTickRun / scTickTileStep fail, with a last-error text and nothing changed, for SC_TICK_TOUCH_EVENTS without SC_TICK_BROADPHASE, without
+ * a prior scTickSetTouchEvents, or on a pipelined context (scTickSetPipelined / scTickSetPairsStream: its tick parities overlap in time,
+ * and by the time its pair half runs the matrices may be the next tick's).  In the caller-owned split flow the pending pair half reads
+ * matrices, colliders and dense indices as they stand, so between scTickRun(.. | SC_TICK_SPLIT_PAIRS | SC_TICK_TOUCH_EVENTS) and its
+ * scTickRunPairs the calls refused for a pending SC_TICK_PAIR_SHAPES tick are refused too: scTickUploadWorldMatrices,
+ * scTickUploadColliders, scTickRemoveEntities, scTickSetEntityCount, scTickRun with SC_TICK_XFORM.  scTickReadTouchEvents fails when the
+ * last run did not carry the flag and while scTickRunPairs is pending.
+ * Not covered: contacts (point, normal, depth), a neighbour tile's shapes (its records stay on their box answer), pipelined tiles. */
+typedef struct ScTickTouchEventInfo
+{
+  uint32_t begun, ended;       /* pairs that begun / ended touching this tick (true totals: may exceed max_events, and the caller's capacities) */
+  uint32_t tracked;            /* size of the remembered touching set after this tick */
+  uint32_t resync;             /* 1 = nothing was remembered: begun is this tick's whole touching set */
+  uint32_t overflow;           /* 1 = the set did not fit: nothing is listed, nothing is remembered */
+  uint32_t events_truncated;   /* 1 = begun or ended exceeds max_events */
+} ScTickTouchEventInfo;
+int scTickSetTouchEvents(ScTickContext* ctx, uint32_t max_tracked_pairs, uint32_t max_events);
+/* begun2 / ended2: [cap][2] (a, b), either may be NULL with capacity 0; min(count, max_events, capacity) pairs are written to each.
+ * Synchronises; copies the 24 bytes of `info` and the listed pairs, nothing else. */
+int scTickReadTouchEvents(ScTickContext* ctx, uint32_t* begun2, uint32_t begun_cap, uint32_t* ended2, uint32_t ended_cap, ScTickTouchEventInfo* info);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

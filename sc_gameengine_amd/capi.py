@@ -16,6 +16,7 @@ ANCHORED_RAYS = 1 << 11
 PAIR_EVENTS = 1 << 12         # SC_TICK_PAIR_EVENTS: which pairs begun / ended since the last run with this flag (scTickSetPairEvents)
 BIND_RUNS = 1 << 13           # SC_TICK_BIND_RUNS: with DRAWS | SORT_DRAWS, the bind runs of the sorted list and the material touch set (scTickSetBindRuns)
 PAIR_SHAPES = 1 << 14         # SC_TICK_PAIR_SHAPES: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes)
+TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended TOUCHING since the last run with this flag (scTickSetTouchEvents)
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 FULL = XFORM | CULL | BROADPHASE
@@ -65,6 +66,10 @@ class SweepHit(C.Structure):
 
 
 class PairEventInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("begun", "ended", "tracked", "resync", "overflow", "events_truncated")]
+
+
+class TouchEventInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("begun", "ended", "tracked", "resync", "overflow", "events_truncated")]
 
 
@@ -225,6 +230,8 @@ SYMBOLS = {
     "scTickGetRayShapes": (C.c_int, [_CTX, U32P]),
     "scTickSetPairEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "scTickReadPairEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairEventInfo)]),
+    "scTickSetTouchEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "scTickReadTouchEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(TouchEventInfo)]),
     "scTickSetPairShapes": (C.c_int, [_CTX, C.c_uint32]),
     "scTickReadPairShapes": (C.c_int, [_CTX, U32P, C.c_uint32, C.POINTER(PairShapeInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),

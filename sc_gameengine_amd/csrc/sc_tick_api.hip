@@ -123,6 +123,9 @@ struct ScTickContext
   PairEventState pairEvents{};
   void* pairEventSlab = nullptr; size_t pairEventSlabBytes = 0;
   bool pairEventsResyncAgain = false;      // ids were renamed between the halves of a split tick: forget again what its pair half remembers
+  // scTickSetTouchEvents: the same state a second time, for the touching set (filled by the narrow-phase kernel).  All null until the call.
+  PairEventState touchEvents{};
+  void* touchEventSlab = nullptr; size_t touchEventSlabBytes = 0;
   // scTickSetPairShapes: the touching list, its running counts and its report.  All null until the call: nothing is launched.
   PairShapeState pairShapes{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
@@ -650,6 +653,7 @@ const char* pendingShapeReader(const ScTickContext* c)
   if (c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)))
     return "casts rays in SC_TICK_RAY_SHAPES_EXACT mode";
   if (c->pendingParams.flags & SC_TICK_PAIR_SHAPES) return "lists the touching pairs (SC_TICK_PAIR_SHAPES)";
+  if (c->pendingParams.flags & SC_TICK_TOUCH_EVENTS) return "reports touch events (SC_TICK_TOUCH_EVENTS)";
   return nullptr;
 }
 #define REFUSE_WHILE_SHAPES_PENDING(c, what) \
@@ -657,15 +661,29 @@ const char* pendingShapeReader(const ScTickContext* c)
          return fail(c, (std::string(what " is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that ") + reads + \
                          ": its pair half reads the matrices and colliders as they stand").c_str()); } while (0)
 
+// (touch events remember pairs by the same ids: they are forgotten in the same places, by the same call)
 bool resyncPairEvents(ScTickContext* c)
 {
-  if (!c->pairEventSlab) return true;
-  const hipError_t e = hipMemsetAsync(c->pairEventSlab, 0, c->pairEventSlabBytes, c->stream);
-  if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair events)", e);
+  if (c->pairEventSlab) {
+    const hipError_t e = hipMemsetAsync(c->pairEventSlab, 0, c->pairEventSlabBytes, c->stream);
+    if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair events)", e);
+  }
+  if (c->touchEventSlab) {
+    const hipError_t e = hipMemsetAsync(c->touchEventSlab, 0, c->touchEventSlabBytes, c->stream);
+    if (e != hipSuccess) return fail(c, "hipMemsetAsync (touch events)", e);
+  }
   // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
   // the rename -- runPendingPairs forgets it again behind that half
-  if (c->pairsPending && (c->pendingParams.flags & SC_TICK_PAIR_EVENTS)) c->pairEventsResyncAgain = true;
+  if (c->pairsPending && (c->pendingParams.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS))) c->pairEventsResyncAgain = true;
   return true;
+}
+
+// the narrow phase of a tick: ONE launch of the pair-shape kernel whatever mix of SC_TICK_PAIR_SHAPES and SC_TICK_TOUCH_EVENTS the tick
+// carries (each pair is decided once), then the list's report and / or the touch state's sweep and finish.  Neither flag: nothing.
+void launchNarrowPhase(ScTickContext* c, const DeviceState& ds, const TickParams& p, hipStream_t s)
+{
+  if (!(p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))) return;
+  launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr, s);
 }
 
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
@@ -847,7 +865,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
-    if (flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, p, c->pairShapes, c->stream);      // the pair set is complete: which of its pairs touch
+    launchNarrowPhase(c, ds, p, c->stream);                                                  // the pair set is complete: which of its pairs touch
     if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // ... what begun, what ended
   } else {
     const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
@@ -878,7 +896,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       }
       else {
         { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
-        if (flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, p, c->pairShapes, c->stream);
+        launchNarrowPhase(c, ds, p, c->stream);
         if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);
       }
     }
@@ -1731,7 +1749,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);
   // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
-  if (pp.flags & SC_TICK_PAIR_SHAPES) launchPairShapes(ds, pp, c->pairShapes, ps);      // behind the pair search, on its stream
+  launchNarrowPhase(c, ds, pp, ps);                                                     // behind the pair search, on its stream
   if (pp.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, pp, c->pairEvents, ps);
   return rode;
 }
@@ -1770,7 +1788,7 @@ static bool worldCanPair(ScTickContext* c)
 static bool quietTick(ScTickContext* c, uint32_t flags)
 {
   constexpr uint32_t kBinReaders = SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_PAIR_EVENTS | SC_TICK_PAIR_SHAPES |
-                                   SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS;
+                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS;
   if (!(flags & SC_TICK_BROADPHASE) || (flags & kBinReaders) || !c->quietEnabled || !c->homeEnabled || !c->lazyEnabled) return false;
   if (!c->n || c->sensors || c->neighbourMask || c->pairsStream || c->pairsPending) return false;
   if (!c->homeValid || c->homeEpoch != c->topoEpoch) return false;      // (a learn tick is due: an append, a remove, a re-link, a layer upload)
@@ -1796,6 +1814,11 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_SHAPES needs SC_TICK_BROADPHASE in the same run (the touching pairs are those of this tick's pair list)");
     if (!c->pairShapes.ctl) return fail(c, "SC_TICK_PAIR_SHAPES needs scTickSetPairShapes first");
     if (c->pairsStream) return fail(c, "SC_TICK_PAIR_SHAPES cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its pair half runs when the matrices may be the next tick's");
+  }
+  if (flags & SC_TICK_TOUCH_EVENTS) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_TOUCH_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's touching set)");
+    if (!c->touchEvents.ctl) return fail(c, "SC_TICK_TOUCH_EVENTS needs scTickSetTouchEvents first");
+    if (c->pairsStream) return fail(c, "SC_TICK_TOUCH_EVENTS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its tick parities overlap in time, and its pair half runs when the matrices may be the next tick's");
   }
   if (flags & SC_TICK_BIND_RUNS) {
     if ((flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS)) != (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS))
@@ -2477,17 +2500,16 @@ int scTickReadSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, ui
                        c ? c->sweeps.hits : nullptr, c ? c->sweeps.count : 0u, hits, cap, count);
 }
 
-int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
+// pair events and touch events: one state each, allocated, read and freed alike (`what` names the feature in the error texts)
+static int setEventState(ScTickContext* c, PairEventState& e, void*& slabOut, size_t& slabBytes, const std::string& what, uint32_t maxTracked, uint32_t maxEvents)
 {
-  if (!c) return 0;
-  if ((maxTracked == 0u) != (maxEvents == 0u)) return fail(c, "pair events: max_tracked_pairs and max_events are both positive, or both 0 (off)");
+  if ((maxTracked == 0u) != (maxEvents == 0u)) return fail(c, (what + ": max_tracked_pairs and max_events are both positive, or both 0 (off)").c_str());
   if (maxTracked && !c->sectors) return fail(c, "the context has no broadphase");
-  if (maxTracked > (1u << 27) || maxEvents > (1u << 27)) return fail(c, "pair events: at most 2^27 tracked pairs and 2^27 events");
+  if (maxTracked > (1u << 27) || maxEvents > (1u << 27)) return fail(c, (what + ": at most 2^27 tracked pairs and 2^27 events").c_str());
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
-  PairEventState& e = c->pairEvents;
-  dfree(c, c->pairEventSlab); dfree(c, e.info); dfree(c, e.begun); dfree(c, e.ended);
-  e = PairEventState{}; c->pairEventSlab = nullptr; c->pairEventSlabBytes = 0;
+  dfree(c, slabOut); dfree(c, e.info); dfree(c, e.begun); dfree(c, e.ended);
+  e = PairEventState{}; slabOut = nullptr; slabBytes = 0;
   dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); the pair search itself is not concerned
   if (!maxTracked) return 1;
   uint32_t slots = 64u;
@@ -2497,7 +2519,7 @@ int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvent
   const size_t bytes = 2u * tableBytes + 2u * markBytes + kPeCtlWords * sizeof(uint32_t);
   char* slab = nullptr;
   if (!dalloc(c, slab, bytes)) return 0;
-  c->pairEventSlab = slab; c->pairEventSlabBytes = bytes;
+  slabOut = slab; slabBytes = bytes;
   if (!dalloc(c, e.info, kPeInfoWords) || !dalloc(c, e.begun, maxEvents, false) || !dalloc(c, e.ended, maxEvents, false)) return 0;
   e.table[0] = reinterpret_cast<unsigned long long*>(slab); e.table[1] = reinterpret_cast<unsigned long long*>(slab + tableBytes);
   e.marks[0] = reinterpret_cast<uint32_t*>(slab + 2u * tableBytes); e.marks[1] = reinterpret_cast<uint32_t*>(slab + 2u * tableBytes + markBytes);
@@ -2506,15 +2528,12 @@ int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvent
   return 1;
 }
 
-int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickPairEventInfo* info)
+// (the caller has checked the flag of the last run and that no pair half is pending)
+static int readEventState(ScTickContext* c, const PairEventState& e, const char* off, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap,
+                          ScTickPairEventInfo* info)
 {
   static_assert(sizeof(ScTickPairEventInfo) == 6u * sizeof(uint32_t) && kPeInfoWords >= 6u, "the device writes the report word by word");
-  if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_PAIR_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_EVENTS");
-  if (c->pairsPending) return fail(c, "pair events are ready after scTickRunPairs");
-  const PairEventState& e = c->pairEvents;
-  if (!e.ctl) return fail(c, "pair events were switched off since the last scTickRun");
+  if (!e.ctl) return fail(c, off);
   if (!joinPairs(c)) return 0;
   if (!d2h(c, info, e.info, sizeof *info) || !sync(c)) return 0;
   const uint32_t nb = std::min(std::min(info->begun, e.maxEvents), begun2 ? begunCap : 0u);
@@ -2523,6 +2542,39 @@ int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, 
   if (ne && !d2h(c, ended2, e.ended, (size_t)ne * sizeof(uint2))) return 0;
   if ((nb || ne) && !sync(c)) return 0;
   return 1;
+}
+
+int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
+{
+  if (!c) return 0;
+  return setEventState(c, c->pairEvents, c->pairEventSlab, c->pairEventSlabBytes, "pair events", maxTracked, maxEvents);
+}
+
+int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickPairEventInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_PAIR_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_EVENTS");
+  if (c->pairsPending) return fail(c, "pair events are ready after scTickRunPairs");
+  return readEventState(c, c->pairEvents, "pair events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap, info);
+}
+
+int scTickSetTouchEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
+{
+  if (!c) return 0;
+  return setEventState(c, c->touchEvents, c->touchEventSlab, c->touchEventSlabBytes, "touch events", maxTracked, maxEvents);
+}
+
+int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickTouchEventInfo* info)
+{
+  static_assert(sizeof(ScTickTouchEventInfo) == sizeof(ScTickPairEventInfo) && offsetof(ScTickTouchEventInfo, events_truncated) == offsetof(ScTickPairEventInfo, events_truncated),
+                "the two reports are the same six words");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_TOUCH_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_TOUCH_EVENTS");
+  if (c->pairsPending) return fail(c, "touch events are ready after scTickRunPairs");
+  return readEventState(c, c->touchEvents, "touch events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap,
+                        reinterpret_cast<ScTickPairEventInfo*>(info));
 }
 
 int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)

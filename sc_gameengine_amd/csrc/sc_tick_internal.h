@@ -355,6 +355,46 @@ struct PairEventState {
 constexpr uint32_t kPeCur = 0, kPeValid = 1, kPeBegun = 2, kPeEnded = 3, kPeTracked = 4, kPeOverflow = 5, kPeCtlWords = 16;
 constexpr uint32_t kPeInfoWords = 8;
 void launchPairEvents(const DeviceState& d, const TickParams& p, const PairEventState& e, hipStream_t s);
+// the sweep and the finish alone, for a state whose current table another kernel filled (touch events: the narrow-phase pass)
+void launchPairEventsTail(const PairEventState& e, hipStream_t s);
+#ifdef __HIPCC__
+__device__ __forceinline__ uint32_t pairHash(unsigned long long k)
+{
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;   // (MurmurHash3's 64-bit finaliser)
+  return (uint32_t)k;
+}
+// One pair (key = a << 32 | b, never 0) of this tick's set: it enters the CURRENT table -- `inserted`: by this lane; a pair met twice enters
+// once -- and a pair that entered is looked up in the PREVIOUS table: `found` and its slot marked, or not found: the pair has begun.
+// Both probe loops are bounded by the slot count; one that runs out raises the overflow word, it never spins.
+__device__ __forceinline__ void pairSetEnter(const PairEventState& e, unsigned long long* curT, const unsigned long long* prevT, uint32_t* prevM,
+                                             uint32_t mask, unsigned long long key, bool& inserted, bool& found)
+{
+  const uint32_t home = pairHash(key) & mask;
+  uint32_t pos = home;
+  bool placed = false;
+  for (uint32_t n = 0; n < e.slots; ++n) {
+    // (a slot only ever goes from empty to a key inside the entering kernel; the load is served past the L1, and a slot read as empty is
+    //  taken with a compare-and-swap, which answers with what is really there)
+    unsigned long long v = __hip_atomic_load(&curT[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v == 0ull) {
+      v = atomicCAS(&curT[pos], 0ull, key);
+      if (v == 0ull) { inserted = true; placed = true; break; }
+    }
+    if (v == key) { placed = true; break; }             // the pair list named it twice: it is in the set once
+    pos = (pos + 1u) & mask;
+  }
+  if (!placed) atomicOr(&e.ctl[kPeOverflow], 1u);       // every slot taken by other keys: cannot happen while the set fits
+  if (inserted) {
+    pos = home;
+    for (uint32_t n = 0; n < e.slots; ++n) {
+      const unsigned long long v = prevT[pos];
+      if (v == key) { atomicOr(&prevM[pos >> 5], 1u << (pos & 31u)); found = true; break; }
+      if (v == 0ull) break;
+      pos = (pos + 1u) & mask;
+    }
+  }
+}
+#endif
 // ---- touching pairs (sc_tick_pair_shapes.hip; include/sc_tick.h "touching pairs"): the pairs of this tick's list whose collider shapes
 // overlap, decided on the device behind the pair search from the resident collider records and this tick's matrix rows.  A kernel
 // argument of its own; the pass owns no per-entity state.
@@ -367,7 +407,11 @@ struct PairShapeState {
 constexpr uint32_t kPsTouching = 0, kPsRefined = 1, kPsKept = 2, kPsTested = 3, kPsPairsTruncated = 4, kPsCtlWords = 8;
 constexpr uint32_t kPsInfoWords = 8;
 constexpr float kPairShapesSatEps = 1e-6f;      // == SC_TICK_PAIR_SHAPES_SAT_EPS
-void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState& e, hipStream_t s);
+// ---- touch events (include/sc_tick.h "touch events"): the pair events' difference taken over the TOUCHING set.  A second PairEventState;
+// the narrow-phase kernel enters what it decides "not apart" into that state's current table (its <.., Events> instances), the pair
+// events' sweep and finish do the rest.  One narrow-phase launch per tick: `list` (SC_TICK_PAIR_SHAPES) and `touch`
+// (SC_TICK_TOUCH_EVENTS) may each be null, or not enabled (no ctl): then that half is not written.
+void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, hipStream_t s);
 // ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----
 struct BindRun24 { uint32_t first, count, pipeline, material, mesh, binds; };      // == ScTickBindRun
 // the report's words (== ScTickBindInfo)

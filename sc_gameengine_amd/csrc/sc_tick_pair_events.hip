@@ -23,12 +23,6 @@ namespace sctick {
 
 namespace {
 
-__device__ __forceinline__ uint32_t pairHash(unsigned long long k)
-{
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;   // (MurmurHash3's 64-bit finaliser)
-  return (uint32_t)k;
-}
-
 // One wave appends the pairs of its lanes with `yes` to a list of `cap` entries whose running count is *counter: one atomic per wave,
 // the count is the true total, entries beyond the capacity are not written.  Every lane of the wave must call.
 __device__ __forceinline__ void appendWave(bool yes, uint2 pr, uint32_t* counter, uint2* list, uint32_t cap)
@@ -84,32 +78,8 @@ __global__ __launch_bounds__(kTile) void k_pair_events_diff(const DeviceState d,
       for (uint32_t step = 32u; step; step >>= 1) if (prefix[s + step] <= i) s += step;
       pr = d.pairs[(size_t)s * shardCap + (i - prefix[s])];
       const unsigned long long key = ((unsigned long long)pr.x << 32) | pr.y;
-      if (key != 0ull) {                                      // (no pair has a == b == 0; the key is the tables' "empty")
-        const uint32_t home = pairHash(key) & mask;
-        uint32_t pos = home;
-        bool placed = false;
-        for (uint32_t n = 0; n < e.slots; ++n) {
-          // (a slot only ever goes from empty to a key inside this kernel; the load is served past the L1, and a slot read as empty is
-          //  taken with a compare-and-swap, which answers with what is really there)
-          unsigned long long v = __hip_atomic_load(&curT[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (v == 0ull) {
-            v = atomicCAS(&curT[pos], 0ull, key);
-            if (v == 0ull) { inserted = true; placed = true; break; }
-          }
-          if (v == key) { placed = true; break; }             // the pair list named it twice: it is in the set once
-          pos = (pos + 1u) & mask;
-        }
-        if (!placed) atomicOr(&e.ctl[kPeOverflow], 1u);       // every slot taken by other keys: cannot happen while the set fits
-        if (inserted) {
-          pos = home;
-          for (uint32_t n = 0; n < e.slots; ++n) {
-            const unsigned long long v = prevT[pos];
-            if (v == key) { atomicOr(&prevM[pos >> 5], 1u << (pos & 31u)); found = true; break; }
-            if (v == 0ull) break;
-            pos = (pos + 1u) & mask;
-          }
-        }
-      }
+      // (no pair has a == b == 0; the key is the tables' "empty")
+      if (key != 0ull) pairSetEnter(e, curT, prevT, prevM, mask, key, inserted, found);
     }
     const unsigned long long mt = ballot64(inserted);
     if (mt && lane == 0) atomicAdd(&e.ctl[kPeTracked], (uint32_t)__popcll(mt));
@@ -163,16 +133,22 @@ __global__ __launch_bounds__(64) void k_pair_events_finish(const PairEventState 
 
 } // namespace
 
+void launchPairEventsTail(const PairEventState& e, hipStream_t s)
+{
+  if (!e.ctl) return;
+  const uint32_t sweepBlocks = std::min(std::max(e.slots / kTile, 1u), 2048u);      // a thread per slot
+  hipLaunchKernelGGL(k_pair_events_sweep, dim3(sweepBlocks), dim3(kTile), 0, s, e);
+  hipLaunchKernelGGL(k_pair_events_finish, dim3(1), dim3(64), 0, s, e);
+}
+
 void launchPairEvents(const DeviceState& d, const TickParams& p, const PairEventState& e, hipStream_t s)
 {
   if (!e.ctl) return;
   // grids by capacities alone: a thread per pair the tables can take (grid-stride beyond that), a thread per slot
   const uint32_t most = std::min(p.maxPairs, e.maxTracked);
   const uint32_t diffBlocks = std::min(std::max((most + kTile - 1u) / kTile, 1u), 2048u);
-  const uint32_t sweepBlocks = std::min(std::max(e.slots / kTile, 1u), 2048u);
   hipLaunchKernelGGL(k_pair_events_diff, dim3(diffBlocks), dim3(kTile), 0, s, d, e, p.parity, p.maxPairs);
-  hipLaunchKernelGGL(k_pair_events_sweep, dim3(sweepBlocks), dim3(kTile), 0, s, e);
-  hipLaunchKernelGGL(k_pair_events_finish, dim3(1), dim3(64), 0, s, e);
+  launchPairEventsTail(e, s);
 }
 
 } // namespace sctick

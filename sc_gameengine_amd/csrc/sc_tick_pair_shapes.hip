@@ -6,10 +6,16 @@
 // are provably apart.  Two launches behind the pair search, on its stream, no host round trip; the grids are fixed by capacities and every
 // count is read on the device, so the launches replay unchanged from a captured graph.
 //
-//   k_pair_shapes          a thread per pair of this tick, read in place from the shard segments as k_pair_events_diff reads them: both
+//   k_pair_shapes<List, Events>
+//                          a thread per pair of this tick, read in place from the shard segments as k_pair_events_diff reads them: both
 //                          members' collider records and matrix rows, one of three routines (segment-segment distance, segment-box
 //                          distance, 15-axis separating-axis test), one append per wave to the touching list
 //   k_pair_shapes_finish   one thread: the tick's report (ScTickPairShapeInfo), the running counts back to zero
+//
+// Touch events (include/sc_tick.h "touch events") are the pair events' difference over the touching SET: the <.., Events> instances enter
+// every pair decided "not apart" into a second PairEventState's current table, probe its previous table and append to its `begun`, in
+// the lane that decided the pair; k_pair_events_sweep / _finish then run on that state unchanged (launchPairEventsTail).  <true, false>
+// is the kernel as it was; <false, true> writes no list; <true, true> decides each pair once for both.
 //
 // The filter only ever removes: a pair is dropped on a positive comparison alone, so a NaN keeps it, and a pair with a member that cannot
 // be refined (a Bounds proxy, a neighbour tile's record, a degenerate matrix) is listed on its AABB answer.  Every loop has a fixed trip
@@ -234,10 +240,15 @@ __device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
   return apart;
 }
 
-__global__ __launch_bounds__(kTile) void k_pair_shapes(const DeviceState d, const PairShapeState e, uint32_t parity, uint32_t maxPairs, uint32_t count,
-                                                       uint32_t rankBits)
+// List: the touching list and its report (SC_TICK_PAIR_SHAPES).  Events: every pair decided "not apart" enters the touch state's current
+// table in the same lane and the same pass, as k_pair_events_diff enters a pair of the pair list (SC_TICK_TOUCH_EVENTS); `e` is then
+// not looked at unless List is set too, and `t` is looked at only with Events.
+template <bool List, bool Events>
+__global__ __launch_bounds__(kTile) void k_pair_shapes(const DeviceState d, const PairShapeState e, const PairEventState t, uint32_t parity,
+                                                       uint32_t maxPairs, uint32_t count, uint32_t rankBits)
 {
   static_assert(kPairShards == 64, "one lane per shard counter");
+  static_assert(List || Events, "a pass with nothing to write");
   __shared__ uint32_t prefix[kPairShards + 1];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t shardCap = maxPairs / kPairShards;
@@ -255,12 +266,36 @@ __global__ __launch_bounds__(kTile) void k_pair_shapes(const DeviceState d, cons
   }
   __syncthreads();
   const uint32_t total = prefix[kPairShards];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {               // what the report needs besides the running counts
-    e.ctl[kPsTested] = total;
-    e.ctl[kPsPairsTruncated] = d.counters[kCtrPar + 8u * parity + kCtrPairs] != 0u ? 1u : 0u;      // pairs found after every segment was full
+  if constexpr (List) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {             // what the report needs besides the running counts
+      e.ctl[kPsTested] = total;
+      e.ctl[kPsPairsTruncated] = d.counters[kCtrPar + 8u * parity + kCtrPairs] != 0u ? 1u : 0u;      // pairs found after every segment was full
+    }
+  }
+  // touch events: a truncated pair list is an overflow tick -- the same answer in every workgroup, nothing is entered anywhere.  Whether
+  // the touching set fits is not known before the pairs are decided: the wave that counts itself past maxTracked raises the word.
+  bool enter = false;
+  unsigned long long* curT = nullptr;
+  const unsigned long long* prevT = nullptr;
+  uint32_t* prevM = nullptr;
+  uint32_t mask = 0u;
+  if constexpr (Events) {
+    enter = d.counters[kCtrPar + 8u * parity + kCtrPairs] == 0u;
+    if (!enter && blockIdx.x == 0 && threadIdx.x == 0) t.ctl[kPeOverflow] = 1u;
+    const uint32_t cur = t.ctl[kPeCur] & 1u;
+    curT = t.table[cur]; prevT = t.table[cur ^ 1u]; prevM = t.marks[cur ^ 1u];
+    mask = t.slots - 1u;
   }
   const uint32_t stride = gridDim.x * kTile;
   for (uint32_t base = blockIdx.x * kTile + (threadIdx.x & ~63u); base < total; base += stride) {      // (wave-uniform trip count)
+    if constexpr (Events) {
+      // an overflow tick lists and remembers nothing: stop entering once the word is up (one value for the wave: its first lane's)
+      if (enter) {
+        const uint32_t up = __hip_atomic_load(&t.ctl[kPeOverflow], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        enter = __builtin_amdgcn_readfirstlane(up) == 0u;
+      }
+      if (!List && !enter) break;                             // (wave-uniform: nothing is left for this wave to write)
+    }
     const uint32_t i = base + lane;
     bool touching = false, refined = false, kept = false;
     uint2 pr = make_uint2(0u, 0u);
@@ -282,12 +317,27 @@ __global__ __launch_bounds__(kTile) void k_pair_shapes(const DeviceState d, cons
         touching = !apart;
       }
     }
-    const unsigned long long mr = ballot64(refined), mk = ballot64(kept);
-    if (lane == 0) {
-      if (mr) atomicAdd(&e.ctl[kPsRefined], (uint32_t)__popcll(mr));
-      if (mk) atomicAdd(&e.ctl[kPsKept], (uint32_t)__popcll(mk));
+    if constexpr (List) {
+      const unsigned long long mr = ballot64(refined), mk = ballot64(kept);
+      if (lane == 0) {
+        if (mr) atomicAdd(&e.ctl[kPsRefined], (uint32_t)__popcll(mr));
+        if (mk) atomicAdd(&e.ctl[kPsKept], (uint32_t)__popcll(mk));
+      }
+      appendWave(touching, pr, &e.ctl[kPsTouching], e.list, e.maxTouching);
     }
-    appendWave(touching, pr, &e.ctl[kPsTouching], e.list, e.maxTouching);
+    if constexpr (Events) {
+      bool inserted = false, found = false;
+      const unsigned long long key = ((unsigned long long)pr.x << 32) | pr.y;
+      // (no pair has a == b == 0; the key is the tables' "empty")
+      if (enter && touching && key != 0ull) pairSetEnter(t, curT, prevT, prevM, mask, key, inserted, found);
+      const unsigned long long mt = ballot64(inserted);
+      if (mt && lane == 0) {
+        const uint32_t added = (uint32_t)__popcll(mt);
+        const uint32_t before = atomicAdd(&t.ctl[kPeTracked], added);
+        if (before + added > t.maxTracked) atomicOr(&t.ctl[kPeOverflow], 1u);      // the touching set does not fit
+      }
+      appendWave(inserted && !found, pr, &t.ctl[kPeBegun], t.begun, t.maxEvents);
+    }
   }
 }
 
@@ -302,13 +352,22 @@ __global__ __launch_bounds__(64) void k_pair_shapes_finish(const PairShapeState 
 
 } // namespace
 
-void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState& e, hipStream_t s)
+// One narrow-phase launch per tick, whatever mix of SC_TICK_PAIR_SHAPES (list) and SC_TICK_TOUCH_EVENTS (touch) the run carries: each
+// pair is decided once.  Behind it the list's report and / or the touch state's sweep and finish (k_pair_events_sweep / _finish, unchanged).
+void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, hipStream_t s)
 {
-  if (!e.ctl) return;
+  if (list && !list->ctl) list = nullptr;
+  if (touch && !touch->ctl) touch = nullptr;
+  if (!list && !touch) return;
   // the grid by the pair list's capacity alone: a thread per pair it can hold (grid-stride beyond that)
   const uint32_t blocks = std::min(std::max((p.maxPairs + kTile - 1u) / kTile, 1u), 2048u);
-  hipLaunchKernelGGL(k_pair_shapes, dim3(blocks), dim3(kTile), 0, s, d, e, p.parity, p.maxPairs, p.n, p.rankBits);
-  hipLaunchKernelGGL(k_pair_shapes_finish, dim3(1), dim3(64), 0, s, e);
+  const PairShapeState e = list ? *list : PairShapeState{};
+  const PairEventState t = touch ? *touch : PairEventState{};
+  if (list && touch) hipLaunchKernelGGL((k_pair_shapes<true, true>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
+  else if (list) hipLaunchKernelGGL((k_pair_shapes<true, false>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
+  else hipLaunchKernelGGL((k_pair_shapes<false, true>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
+  if (list) hipLaunchKernelGGL(k_pair_shapes_finish, dim3(1), dim3(64), 0, s, e);
+  if (touch) launchPairEventsTail(t, s);
 }
 
 } // namespace sctick

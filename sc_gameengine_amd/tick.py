@@ -750,6 +750,23 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairShapeInfo._fields_}
         return pairs[:min(out["touching"], cap)].copy(), out
 
+    # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
+    def set_touch_events(self, max_tracked, max_events):
+        """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report
+        its tick-to-tick difference on every run with capi.TOUCH_EVENTS (scTickSetTouchEvents): room for max_tracked pairs in the set and
+        max_events pairs in each list; (0, 0) switches it off.  Needs neither capi.PAIR_SHAPES nor set_pair_shapes."""
+        self._ok(self.lib.scTickSetTouchEvents(self.ctx, int(max_tracked), int(max_events)), "scTickSetTouchEvents")
+        self._max_touch_events = int(max_events)
+
+    def touch_events(self):
+        """(begun[k, 2], ended[m, 2], info) of the last run with capi.TOUCH_EVENTS, shaped as pair_events() returns them."""
+        cap = getattr(self, "_max_touch_events", 0)
+        b, e = np.zeros((max(cap, 1), 2), np.uint32), np.zeros((max(cap, 1), 2), np.uint32)
+        info = capi.TouchEventInfo()
+        self._ok(self.lib.scTickReadTouchEvents(self.ctx, _u(b), cap, _u(e), cap, C.byref(info)), "scTickReadTouchEvents")
+        out = {k: int(getattr(info, k)) for k, _ in capi.TouchEventInfo._fields_}
+        return b[:min(out["begun"], cap)].copy(), e[:min(out["ended"], cap)].copy(), out
+
     def draws(self):
         cnt = C.c_uint32()
         self._ok(self.lib.scTickReadDraws(self.ctx, None, 0, C.byref(cnt)), "scTickReadDraws")
