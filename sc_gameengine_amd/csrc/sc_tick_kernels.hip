@@ -91,6 +91,35 @@ __device__ __forceinline__ Aff loadLocal(const DeviceState& d, uint32_t j, uint3
   L.r2[0] = a20 * kx; L.r2[1] = r21 * ky; L.r2[2] = r22 * kz; L.r2[3] = ldF(d, kPZ, j);
   return L;
 }
+// loadLocal in two halves, for the pipelined tile loop (xformCullPipelined): the requests of several levels go out before the
+// first value is looked at.  The same loads under the same conditions and the same arithmetic in the same order: the same bits.
+struct LocalRaw { float sx, cx, sy, cy, sz, cz, kx, ky, kz, px, py, pz; };
+__device__ __forceinline__ LocalRaw requestLocal(const DeviceState& d, uint32_t j, uint32_t lkj)
+{
+  const uint32_t triv = lkj >> 29;                      // bit0 X, bit1 Y, bit2 Z
+  LocalRaw r;
+  r.sx = 0.0f; r.cx = 1.0f; r.sy = 0.0f; r.cy = 1.0f; r.sz = 0.0f; r.cz = 1.0f;
+  if (!(triv & 1u)) { r.sx = ldF(d, kRSX, j); r.cx = ldF(d, kRCX, j); }
+  if (!(triv & 2u)) { r.sy = ldF(d, kRSY, j); r.cy = ldF(d, kRCY, j); }
+  if (!(triv & 4u)) { r.sz = ldF(d, kRSZ, j); r.cz = ldF(d, kRCZ, j); }
+  r.kx = ldF(d, kSX, j); r.ky = ldF(d, kSY, j); r.kz = ldF(d, kSZ, j);
+  r.px = ldF(d, kPX, j); r.py = ldF(d, kPY, j); r.pz = ldF(d, kPZ, j);
+  return r;
+}
+__device__ __forceinline__ Aff buildLocal(const LocalRaw& q)
+{
+  const float a00 = q.cz * q.cy, a10 = q.sz * q.cy, a20 = -q.sy;
+  const float a01 = -q.sz,       a11 = q.cz;
+  const float a02 = q.cz * q.sy, a12 = q.sz * q.sy, a22 = q.cy;
+  const float nsx = -q.sx;
+  const float r01 = a01 * q.cx + a02 * q.sx, r11 = a11 * q.cx + a12 * q.sx, r21 = a22 * q.sx;
+  const float r02 = a01 * nsx + a02 * q.cx, r12 = a11 * nsx + a12 * q.cx, r22 = a22 * q.cx;
+  Aff L;
+  L.r0[0] = a00 * q.kx; L.r0[1] = r01 * q.ky; L.r0[2] = r02 * q.kz; L.r0[3] = q.px;
+  L.r1[0] = a10 * q.kx; L.r1[1] = r11 * q.ky; L.r1[2] = r12 * q.kz; L.r1[3] = q.py;
+  L.r2[0] = a20 * q.kx; L.r2[1] = r21 * q.ky; L.r2[2] = r22 * q.kz; L.r2[3] = q.pz;
+  return L;
+}
 
 // world = parent * local  (mat4_mul, sc_math.cpp:52-68): ((p0*l0 + p1*l1) + p2*l2) + p3*l3 with
 // l3 the local's last row (0,0,0,1): the fourth term is +-0 for columns 0..2 and p3 for column 3.
@@ -634,8 +663,209 @@ __device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams&
   for (uint32_t v = w + kTile; v < wEnd; v += kTile) d.dirty[v] = (d.dirty[v] & d.unreach[v]) | (produce ? d.rootMask[v] : 0u);   // spans wider than 8192 entities
 }
 
+// ------------------------------------------------------------------------------------------
+// The instances without binning (kAabb == false; the quiet tick of a world that cannot pair is one): the tile loop of
+// xformCullBody as a two-stage software pipeline.  Stage W, the walk, reads only link words and dirty words and gives a tile's
+// a[], rotFlags and top; stage X is everything else.  W of tile k + 1 is spread over X of tile k: its own link and dirty word
+// go out with X's requests, each ancestor level behind the next piece of X's work (the arithmetic, the stores, the sphere
+// test), so that a tile's kChain + 1 walk trips ride under the tile before.  X itself asks for the seed rows and for the locals
+// of every level it multiplies in one round trip (requestLocal / buildLocal) instead of one per level.  The same products in
+// the same order: the same bits.  No byte more from memory: X's loads keep their per-lane conditions; the walk's loads are
+// UNconditional -- a lane that has no ancestor at a level asks for its own words again, a lane past the end for the span's last
+// entity's (lines the tile holds anyway) -- and their results are selected afterwards.  That is deliberate: the compiler counts
+// outstanding loads per path, and a load whose use sits under a condition stays "outstanding" on the path around it; a walk
+// written with the conditions of xformCullBody waited for the next tile's link word at the head of the loop for that reason
+// alone.  With every walk trip looked at on every path, the wait at the bottom of the loop clears the
+// count for the next trip round.
+// No hazard: between launch and spanTail nothing in the kernel writes a link word or a dirty word, and the only rows read are
+// a clean seed's or a clean entity's own, which nobody writes this tick.  The trip count stays uniform over the workgroup; the
+// last tile of a span, which has no tile to walk ahead of, is a copy of the stage without the walk (kNext).
+// The price is registers -- the raw locals of every level and the next tile's walk in flight -- which these instances have:
+// a launch of at most 1536 spans needs six waves per SIMD, 80 VGPRs (profiles/r18; DESIGN.md sections 5 and 11.15).  The
+// binning instances have none to give and keep xformCullBody.
+// ------------------------------------------------------------------------------------------
+template <uint32_t kChain>
+struct TileWalk {
+  uint32_t lk;                       // own link word (the inactive word past n)
+  uint32_t a[kChain + 1];            // a[0]: own index, clamped into the span; ancestors; above the depth a[0] again
+  uint32_t rotFlags, cur;            // cur: link word of the level resolved last
+  int top;
+  uint32_t pendLink, pendDirty;      // requested for the level issued last and not looked at yet
+};
+// own link word and own dirty word: requested, not looked at.  `last`: the span's last entity (i is in the span or past it)
+template <uint32_t kChain>
+__device__ __forceinline__ void walkRequest(const DeviceState& d, TileWalk<kChain>& w, uint32_t i, uint32_t last)
+{
+  w.a[0] = i <= last ? i : last;
+  w.pendLink = ldU(d, kLINK, w.a[0]);
+  w.pendDirty = d.dirty[w.a[0] >> 5];
+}
+// look at what was requested for level `lev` (the first use of the loaded words: the wait sits here)
+template <uint32_t kChain>
+__device__ __forceinline__ void walkResolve(TileWalk<kChain>& w, uint32_t lev, uint32_t i, uint32_t last, bool doXform)
+{
+  // both words are wanted HERE, on every path: without this the compiler sinks the last level's rotation bits to their use,
+  // under the next tile's conditions, and the outstanding count is never cleared on the path around them
+  asm volatile("" : : "v"(w.pendLink), "v"(w.pendDirty));
+  if (lev == 0u) {
+    w.lk = i <= last ? w.pendLink : ((kUnreachable << kDepthShift) | kNoParent);
+    w.rotFlags = w.lk >> 29; w.cur = w.lk;
+    const bool walk = doXform && linkDepth(w.lk) <= kChain;
+    w.top = (walk && ((w.pendDirty >> (w.a[0] & 31u)) & 1u)) ? 0 : -1;
+  } else {
+    const uint32_t depth = linkDepth(w.lk);
+    const bool on = doXform && depth <= kChain && lev <= depth;
+    w.cur = on ? w.pendLink : w.cur;
+    w.rotFlags |= on ? (w.pendLink >> 29) << (3u * lev) : 0u;
+    w.top = (on && ((w.pendDirty >> (w.a[lev] & 31u)) & 1u)) ? (int)lev : w.top;
+  }
+}
+// ask for ancestor `lev`'s link word and dirty word (level lev - 1 is resolved)
+template <uint32_t kChain>
+__device__ __forceinline__ void walkIssue(const DeviceState& d, TileWalk<kChain>& w, uint32_t lev, bool doXform)
+{
+  const uint32_t depth = linkDepth(w.lk);
+  const bool on = doXform && depth <= kChain && lev <= depth;
+  w.a[lev] = on ? (w.cur & kParentMask) : w.a[0];
+  w.pendLink = ldU(d, kLINK, w.a[lev]);
+  w.pendDirty = d.dirty[w.a[lev] >> 5];
+}
+
+// kBatch: how many levels, from level kChain down, have their locals requested in one round trip with the seed rows; the levels
+// below are requested one by one as in xformCullBody (an instance whose registers do not hold every level: profiles/r18)
+template <bool kCull, uint32_t kChain, bool kTail, uint32_t kBatch = kChain + 1>
+__device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const TickParams& p)
+{
+  static_assert(kBatch >= 1 && kBatch <= kChain + 1, "levels requested together");
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t begin = blockIdx.x * p.span;
+  const uint32_t end = (begin + p.span < p.n) ? begin + p.span : p.n;
+  const bool doXform = (p.flags & SC_TICK_XFORM) != 0;
+  const bool wantCand = (p.flags & SC_TICK_CULLED_LIST) != 0;
+  const bool hasDeep = (p.flags & kFlagHasDeep) != 0;
+  uint32_t tailWave = 0;
+  if (kTail && !kCull) tailWave = __builtin_amdgcn_readfirstlane(wave);      // (scalar: see spanTail)
+
+  uint32_t visCount = 0, candCount = 0;      // wave-uniform running sums
+  TileWalk<kChain> w, nw;
+
+  // one tile: stage X on the walk `w`, and (hasNext) the walk of the tile behind it into `nw`, a trip at each seam of X
+  auto tile = [&](uint32_t base, auto hasNext) {
+    constexpr bool kNext = decltype(hasNext)::value;
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t last = end - 1u;
+    const bool active = i < p.n;
+    const uint32_t lk = w.lk;
+    const uint32_t depth = linkDepth(lk);
+    const int top = w.top;
+    const bool recompute = top >= 0;
+    const bool fromRoot = (uint32_t)top == depth;       // the chain's root itself is rebuilt: world = local
+
+    // ---- X: every request of the tile.  Rows: a clean entity's own, or the clean parent's of the top dirty ancestor (the seed)
+    uint32_t rows = i;
+#pragma unroll
+    for (uint32_t k = 0; k < kChain; ++k) if ((uint32_t)top == k) rows = w.a[k + 1];
+    Aff M;
+    if (recompute ? !fromRoot : (kCull && active)) M = loadRows(d, rows);
+    LocalRaw raw[kChain + 1];
+#pragma unroll
+    for (int lev = (int)kChain; lev > (int)kChain - (int)kBatch; --lev)
+      if (lev <= top) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
+    // ---- W, trip 1: behind X's requests in the queue and in flight with them
+    if (kNext) walkRequest(d, nw, i + kTile, last);
+
+    // ---- W, trip 2: under the arithmetic
+    if (kNext) { walkResolve(nw, 0u, i + kTile, last, doXform); if (kChain >= 1) walkIssue(d, nw, 1u, doXform); }
+
+    if (recompute) {
+#pragma unroll
+      for (int lev = (int)kChain; lev >= 0; --lev) {
+        if (lev <= top) {
+          if (lev <= (int)kChain - (int)kBatch) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
+          const Aff L = buildLocal(raw[lev]);
+          if (lev == top && fromRoot) M = L;
+          else M = mulAff(M, L);
+        }
+      }
+    }
+    // ---- W, trip 3: in flight together with the stores
+    if (kNext && kChain >= 2) { walkResolve(nw, 1u, i + kTile, last, doXform); walkIssue(d, nw, 2u, doXform); }
+    if (recompute) storeRows(d, i, M);
+
+    if (hasDeep) {
+      const unsigned long long rm = ballot64(recompute);
+      if (lane == 0 && (base + wave * 64u) < p.n) d.recomp[(base >> 6) + wave] = rm;
+    }
+    // ---- W, trip 4: under the sphere test
+    if (kNext && kChain >= 3) { walkResolve(nw, 2u, i + kTile, last, doXform); walkIssue(d, nw, 3u, doXform); }
+
+    if (kCull) {
+      const bool cand = active && (lk & kHasMesh);
+      const bool hb = active && (lk & kHasBounds);
+      // the wave-tile's class word, read here and not at the head of the tile
+      const uint32_t t = __builtin_amdgcn_readfirstlane((base >> 6) + wave);
+      ConstU tw = (ConstU)d.boundsPalette + (kPaletteCap * 8u + 2u * t);      // (== d.tileClass: one allocation, one pointer held in SGPRs)
+      const uint32_t cls = tw[0] & kClassMask;
+      BoundsCE b = {0, 0, 0, 0, 0, 0};
+      if (cls < kPaletteCap) b = paletteBounds((ConstF)d.boundsPalette + 8u * cls);      // (wave-uniform branch; a lane without Bounds never uses b)
+      else if (hb) b = loadBounds(d, i);
+
+      bool visible = cand;
+      if (cand && hb && !p.freeze && p.frustumValid) {
+        const float* fr = d.frustum;
+        asm volatile("" : "+s"(fr));                 // opaque: keeps the plane loads inside the loop, at their use
+        visible = sphereVisibleAt(M, b, (ConstF)fr);
+      }
+      // deeper entities get their matrix (and their bit) from the level kernels
+      if (doXform && depth > kChain && depth != kUnreachable) visible = false;
+      const unsigned long long vm = ballot64(visible);
+      const unsigned long long cm = ballot64(cand);
+      if (lane == 0 && (base + wave * 64u) < p.n) {
+        d.vis[(base >> 6) + wave] = vm;
+        if (wantCand) d.cand[(base >> 6) + wave] = cm;
+      }
+      visCount += (uint32_t)__popcll(vm);
+      candCount += (uint32_t)__popcll(cm);
+    }
+    // ---- W: the last trip, looked at on every path
+    if (kNext) { walkResolve(nw, kChain, i + kTile, last, doXform); w = nw; }
+  };
+
+  if (begin < end) {                                   // (uniform: false for the one workgroup of an empty world)
+    // prologue: the first tile's walk, trip by trip
+    const uint32_t i0 = begin + threadIdx.x, last = end - 1u;
+    walkRequest(d, w, i0, last);
+#pragma unroll
+    for (uint32_t k = 1; k <= kChain; ++k) { walkResolve(w, k - 1u, i0, last, doXform); walkIssue(d, w, k, doXform); }
+    walkResolve(w, kChain, i0, last, doXform);
+    uint32_t base = begin;
+    for (; base + kTile < end; base += kTile) tile(base, std::true_type{});
+    tile(base, std::false_type{});
+  }
+
+  if (kCull) {
+    __shared__ uint32_t sVis[kTile / 64], sCand[kTile / 64];
+    if (lane == 0) { sVis[wave] = visCount; sCand[wave] = candCount; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      d.blockVis[blockIdx.x] = sVis[0] + sVis[1] + sVis[2] + sVis[3];
+      d.blockCand[blockIdx.x] = sCand[0] + sCand[1] + sCand[2] + sCand[3];
+    }
+  }
+  if (kTail) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+}
+
+// every level's locals in one round trip, but for the chain-3 instance with culling: four levels and the sphere test's state
+// are 85 VGPRs, five waves per SIMD; with level 0 requested on its own, behind the product of level 1, it holds six
+constexpr uint32_t pipelinedBatch(bool cull, uint32_t chain) { return (cull && chain == 3u) ? 3u : chain + 1u; }
+
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
-__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome, false>(d, p); }
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p)
+{
+  if constexpr (kAabb) xformCullBody<kCull, kAabb, kChain, kHome, false>(d, p);
+  else xformCullPipelined<kCull, kChain, false, pipelinedBatch(kCull, kChain)>(d, p);
+}
 // The collider instances (kAabb only: without binning nothing reads a collider), launched once scTickUploadColliders was called:
 // kernels of their own name, so that a context that never made the call runs exactly the instances above.
 template <bool kCull, uint32_t kChain, uint32_t kHome>
@@ -643,7 +873,11 @@ __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders(con
 // The tail instances (kFlagTailOwnsDirty, spanTail), again under names of their own: behind a run-time flag in the instances above the tail
 // cost most of them a VGPR (profiles/r09), and a context that is never eligible launches exactly what it launched before.
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
-__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_tail(const DeviceState d, const TickParams p) { xformCullBody<kCull, kAabb, kChain, kHome, false, true>(d, p); }
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_tail(const DeviceState d, const TickParams p)
+{
+  if constexpr (kAabb) xformCullBody<kCull, kAabb, kChain, kHome, false, true>(d, p);
+  else xformCullPipelined<kCull, kChain, true, pipelinedBatch(kCull, kChain)>(d, p);
+}
 template <bool kCull, uint32_t kChain, uint32_t kHome>
 __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders_tail(const DeviceState d, const TickParams p) { xformCullBody<kCull, true, kChain, kHome, true, true>(d, p); }
 
