@@ -328,6 +328,17 @@ int scTickGetBinStats(ScTickContext* ctx, uint32_t stats[4]);
  * the current span.  Host-side, no read-back (flushes a pending re-link; the span-closed state is rescanned, O(n), only after the
  * entity count moved to another span). */
 int scTickGetTailStats(ScTickContext* ctx, uint32_t stats[2]);
+/* How the last scTickRun's compaction was cut into workgroups (diagnostics; no result depends on it).  The compaction (the ordered visible
+ * and culled lists, CullingStats' counters) is a role of the tick's end-of-tick launch.  Where that launch has nothing else to do -- a tick
+ * with SC_TICK_CULL and without a pair half, whose fused kernel owned the dirty words (above) or which has no SC_TICK_XFORM -- and a
+ * span holds at most 16384 entities, the launch takes its WIDE form: one workgroup takes several consecutive spans, one visibility word
+ * (64 entities) per thread, and scatters word by word.  Every other launch keeps one workgroup per span (two where the pair search shares
+ * the launch).  stats[0] workgroups of the compaction role, [1] spans per workgroup; 0 / 0 when the tick had no compaction (no
+ * SC_TICK_CULL and the dirty words owned by the fused kernel, or an empty context).  Host-side, no read-back, no synchronisation.
+ * A/B switches, read at creation: SC_TICK_VARIANT bit 4 (16) keeps one workgroup per span everywhere; SC_TICK_COMPACT_G=<n> fixes the
+ * spans per workgroup of the wide form (clamped to what one word per thread allows) instead of the library's rule.
+ * SC_TICK_VARIANT bits that remain: 1 (2) home slots off, 3 (8) quiet ticks off, 4 (16) wide compaction off, 5 (32) lazy records off. */
+int scTickGetCompactStats(ScTickContext* ctx, uint32_t stats[2]);
 /* stats[3] of the above alone: learn ticks so far.  Host-side, no read-back, no synchronisation (what a timed loop may ask). */
 int scTickGetLearnTicks(ScTickContext* ctx, uint32_t* learn_ticks);
 /* Bounds classes (diagnostics; no result depends on them).  The library keeps a table of the distinct local boxes it was given

@@ -175,6 +175,7 @@ SYMBOLS = {
     "scTickGetBinStats": (C.c_int, [_CTX, U32P]),
     "scTickGetLearnTicks": (C.c_int, [_CTX, U32P]),
     "scTickGetTailStats": (C.c_int, [_CTX, U32P]),
+    "scTickGetCompactStats": (C.c_int, [_CTX, U32P]),
     "scTickGetBoundsClassStats": (C.c_int, [_CTX, U32P]),
     "scTickSetWorldLayers": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int]),
     "scTickResetHostTimes": (C.c_int, [_CTX]),

@@ -32,6 +32,7 @@ struct CapturedGraph {
   hipGraphExec_t exec = nullptr;
   TickParams key{};
   uint64_t epoch = ~0ull;                              // ScTickContext::topoEpoch at capture
+  uint32_t compactG = 0;                               // ScTickContext::compactG at capture: which form of the end-of-tick kernel is inside
   bool rccl = false;                                   // the library's RCCL group is inside (captured in relaxed mode)
 };
 
@@ -98,6 +99,11 @@ struct ScTickContext
   bool tailEnabled = true;             // SC_TICK_TAIL=0 at creation: the end-of-tick kernel keeps the dirty clear and the producer (A/B switch)
   bool spanClosed = false; uint32_t closureSpan = 0;
   bool lastTickTail = false;           // the last tick's fused kernel owned the dirty words (scTickGetTailStats)
+  // The end-of-tick kernel's wide form (k_compact_wide): SC_TICK_VARIANT bit 4 (16) at creation keeps one workgroup per span (A/B switch);
+  // SC_TICK_COMPACT_G at creation fixes the spans per workgroup instead of compactWideGroup's rule (measurements, tests).  compactG: this
+  // tick's spans per workgroup, 0 = compactBody's form -- part of a captured graph's key; lastCompact: scTickGetCompactStats.
+  bool wideCompact = true; uint32_t compactForceG = 0, compactG = 0;
+  uint32_t lastCompact[2] = { 0u, 0u };
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
   uint32_t lastFlags = 0;
 
@@ -880,11 +886,11 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       // dispatch's own begin / end timestamps (whoever reads that slot sees what the tick's second launch cost, whichever it was)
       if (c->lastTickQuiet && timed(c, SC_TICK_K_PAIRS, timing)) {
         const EventPair ev = takeEvents(c);
-        launchCompact(ds, p, grid, c->stream, ev.a, ev.b);
+        launchCompact(ds, p, grid, c->compactG, c->stream, ev.a, ev.b);
         c->times[SC_TICK_K_PAIRS].push_back(ev);
       } else {
         Scoped s(c, SC_TICK_K_COMPACT, timing && !c->lastTickQuiet);
-        launchCompact(ds, p, grid, c->stream);
+        launchCompact(ds, p, grid, c->compactG, c->stream);
       }
     }
     if (flags & SC_TICK_BROADPHASE) {
@@ -949,13 +955,13 @@ void dropGraphs(CapturedGraph* g, uint32_t count)
 template <uint32_t N> void dropGraphs(CapturedGraph (&g)[N]) { dropGraphs(g, N); }
 
 // Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for other TickParams, another
-// topology epoch, or with / without the library's RCCL group inside (rccl: the group touches the communicator's own resources
-// during capture, so the capture is relaxed).  body() enqueues the work on s; it returns 0 on an error whose text it has set.
+// topology epoch, another form of the end-of-tick kernel (compactG), or with / without the library's RCCL group inside (rccl: the
+// group touches the communicator's own resources during capture, so the capture is relaxed).  body() enqueues the work on s; it returns 0 on an error whose text it has set.
 // what: the graph's name in the error texts.
 template <typename Body>
 int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickParams& key, bool rccl, const char* what, Body body)
 {
-  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl) {
+  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl || g.compactG != c->compactG) {
     dropGraphs(&g, 1);
     HIP_OK(c, hipStreamBeginCapture(s, rccl ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
     const int ok = body();
@@ -964,7 +970,7 @@ int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickPar
     if (ce != hipSuccess) return fail(c, what, ce);
     if (!g.graph) return fail(c, (std::string(what) + " returned no graph (the capture was invalidated)").c_str());
     HIP_OK(c, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl;
+    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl; g.compactG = c->compactG;
   }
   HIP_OK(c, hipGraphLaunch(g.exec, s));
   return 1;
@@ -994,10 +1000,10 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (e != hipSuccess || count <= 0) { fail(nullptr, "no HIP device available (libsc_tick needs an AMD GPU; there is no CPU fallback)", e); return nullptr; }
   if (desc->device_ordinal < 0 || desc->device_ordinal >= count) { fail(nullptr, "device ordinal out of range"); return nullptr; }
 
-  // SC_TICK_VARIANT: the three A/B switches that remain (include/sc_tick.h); any other bit names a retired experiment
+  // SC_TICK_VARIANT: the four A/B switches that remain (include/sc_tick.h); any other bit names a retired experiment
   const char* vs = std::getenv("SC_TICK_VARIANT");
   const uint32_t variant = vs ? (uint32_t)std::atoi(vs) : 0u;
-  if (variant & ~(2u | 8u | 32u)) { fail(nullptr, "SC_TICK_VARIANT: only bits 1 (2, home slots off) and 5 (32, lazy records off) and 3 (8, quiet ticks off) remain"); return nullptr; }
+  if (variant & ~(2u | 8u | 16u | 32u)) { fail(nullptr, "SC_TICK_VARIANT: only bits 1 (2, home slots off) and 5 (32, lazy records off) and 3 (8, quiet ticks off) and 4 (16, one compaction workgroup per span) remain"); return nullptr; }
 
   ScTickContext* c = new ScTickContext();
   c->desc = *desc;
@@ -1005,6 +1011,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (c->desc.sector_size <= 0.001f) c->desc.sector_size = 64.0f;     // WorldPartition::configure, sc_world_partition.cpp:222-223
   c->cap = ((desc->capacity + kTile - 1) / kTile) * kTile;
   if (const char* s = std::getenv("SC_TICK_SPANS")) { const int v = std::atoi(s); if (v > 0) c->spansWanted = (uint32_t)v; }
+  if (const char* s = std::getenv("SC_TICK_COMPACT_G")) { const int v = std::atoi(s); if (v > 0) c->compactForceG = (uint32_t)v; }
   if (const char* s = std::getenv("SC_TICK_TAIL")) c->tailEnabled = std::atoi(s) != 0;      // A/B switch: 0 keeps the dirty clear and the root nudge in the end-of-tick kernel
 
   bool ok = bind(c);
@@ -1096,6 +1103,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   }
   if (variant & 32u) c->lazyEnabled = false;            // SC_TICK_VARIANT bit 5: every remembered slot is written on every tick (A/B)
   if (variant & 2u) c->homeEnabled = false;             // SC_TICK_VARIANT bit 1: every record reserves its slot on every tick (A/B)
+  if (variant & 16u) c->wideCompact = false;            // SC_TICK_VARIANT bit 4: the end-of-tick kernel alone keeps one workgroup per span, compactBody's form (A/B)
   if (variant & 8u) c->quietEnabled = false;            // SC_TICK_VARIANT bit 3: a tick whose bins nobody reads fills and sweeps them all the same (A/B)
   if (const char* fp = std::getenv("SC_TICK_FAST_PAIRS")) c->fastPairs = std::atoi(fp) != 0;      // 0: every bin goes through the general pair search (A/B)
   if (const char* hp = std::getenv("SC_TICK_HOME_PERIOD")) { const int v = std::atoi(hp); if (v > 0) c->homePeriod = (uint32_t)v; }
@@ -1832,6 +1840,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     c->lastFlags = flags;
     c->lastTickTail = false;
     c->lastTickQuiet = false;
+    c->lastCompact[0] = c->lastCompact[1] = 0u;
     HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
     return 1;
   }
@@ -1914,6 +1923,16 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   }
   if (c->frustumStale && (flags & SC_TICK_CULL)) { launchSetFrustum(c->d, c->frustum, c->stream); c->frustumStale = false; }   // outside any graph
 
+  // the end-of-tick launch's shape (enqueueStages' rule for who carries the compaction role): the wide form only where the launch is
+  // the compaction's own
+  {
+    const bool needCompact = (p.flags & SC_TICK_CULL) != 0 || ((p.flags & SC_TICK_XFORM) && !(p.flags & kFlagTailOwnsDirty));
+    const bool pairsNow = (p.flags & SC_TICK_BROADPHASE) && !(p.flags & SC_TICK_SPLIT_PAIRS);
+    const bool alone = needCompact && !(p.flags & SC_TICK_BROADPHASE);
+    c->compactG = (alone && c->wideCompact) ? compactWideGroup(p, grid, c->compactForceG) : 0u;
+    c->lastCompact[0] = c->lastCompact[1] = 0u;
+    if (needCompact) compactLaunchShape(grid, pairsNow, c->compactG, c->lastCompact);
+  }
   const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
   c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
   waitParityFree(c, p);
@@ -3202,6 +3221,13 @@ int scTickGetTailStats(ScTickContext* c, uint32_t stats[2])
   if (span != c->closureSpan) deriveSpanClosed(c);
   stats[0] = c->lastTickTail ? 1u : 0u;
   stats[1] = c->spanClosed ? 1u : 0u;
+  return 1;
+}
+
+int scTickGetCompactStats(ScTickContext* c, uint32_t stats[2])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  stats[0] = c->lastCompact[0]; stats[1] = c->lastCompact[1];
   return 1;
 }
 

@@ -437,7 +437,10 @@ void launchOccupancy(const DeviceState& d, uint32_t n, const float4* q, uint32_t
 void launchXformCull(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
 void launchSnapshotHome(const DeviceState& d, uint32_t sectors, uint32_t n, uint32_t binSX, uint32_t binSZ, uint32_t vocabMode, uint32_t vocab, uint32_t ordered, hipStream_t s);
 void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* levelList, uint32_t count, hipStream_t s);
-void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
+// the end-of-tick kernel alone.  wideG: spans per workgroup of the wide form (compactWideGroup; 0: one workgroup per span, compactBody)
+uint32_t compactWideGroup(const TickParams& p, uint32_t grid, uint32_t forced);
+void compactLaunchShape(uint32_t grid, bool merged, uint32_t wideG, uint32_t shape[2]);
+void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, uint32_t wideG, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
 bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEvent_t done = nullptr);
 uint32_t pairRunFor(uint32_t sectors, uint32_t cus, bool sweepOnly);
 void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t compactGrid, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);

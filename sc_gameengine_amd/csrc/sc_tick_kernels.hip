@@ -1526,6 +1526,111 @@ __global__ __launch_bounds__(kTile) void k_compact(const DeviceState d, const Ti
   compactBody<false>(d, p, blockIdx.x, gridDim.x, group, scratch, moved, words);
 }
 
+// The WIDE form of the compaction, for a launch that has nothing but compaction left (launchCompact's rule: culling on, and the dirty
+// clear and the producer either owned by the fused kernel's tail or not part of the tick; no draw emission).  A kernel of its own, not
+// another flag in compactBody.  One workgroup takes `group` consecutive spans whose visibility words number at most kCompactWordsMax:
+// ONE WORD PER THREAD, dealt out round robin over the waves -- word j of the workgroup belongs to lane j / 4 of wave j % 4 -- so that every
+// wave scatters a quarter of them however few the workgroup has.  Requests first, as above (clamped indices, uniform conditions, select
+// afterwards): the thread's vis word, its cand word with SC_TICK_CULLED_LIST, and the predecessors' counts -- the last workgroup its own
+// spans' too.  The words' popcounts (visible | culled << 16) cross the waves through LDS ahead of blockSum4, whose pair of barriers
+// publishes them: two barriers in all.  Every wave then scans the same 64 row sums (a row: the four words of one lane index) and adds
+// the row's words of the waves before its own.  The scatter goes by word, not by entity: each wave takes a ballot of its non-empty words
+// and loops over the set bits only -- the word and its offsets come out of the owning lane's registers (readlane: the index is uniform),
+// lane b stores word * 64 + b at offset + popcount(mask below b).  An empty word costs nothing; a full one is one coalesced 256-byte
+// store.  LDS: blockSum4's scratch and one dword per thread.
+__global__ __launch_bounds__(kTile) void k_compact_wide(const DeviceState d, const TickParams p, uint32_t group)
+{
+  constexpr uint32_t kWaves = kTile / 64u;
+  static_assert(kWaves == 4u, "the round-robin deal below is written for four waves");
+  __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
+  __shared__ uint32_t wordCount[kWaves][64];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t bid = blockIdx.x, nblocks = gridDim.x;
+  const uint32_t width = p.span * group;
+  const uint32_t begin = bid * width;
+  const uint32_t end = (begin + width < p.n) ? begin + width : p.n;
+  const bool doCulled = (p.flags & SC_TICK_CULLED_LIST) != 0;
+  const bool some = begin < end;                       // (uniform; false only for the one workgroup of an empty world)
+
+  // ---- requests first
+  const uint32_t vBegin = begin >> 6, vEnd = (end + 63u) >> 6, vWords = vEnd - vBegin;      // (the launcher holds vWords <= kCompactWordsMax)
+  const uint32_t myWord = lane * kWaves + wave;        // of the workgroup's words
+  unsigned long long rawVis = 0ull, rawCand = 0ull;
+  const uint32_t visAt = vBegin + (myWord < vWords ? myWord : vWords - 1u);
+  if (some) {                                          // (uniform)
+    rawVis = d.vis[visAt];
+    if (doCulled) rawCand = d.cand[visAt];
+  }
+  constexpr uint32_t kPrefixBatch = 8;
+  const bool lastBlock = bid == nblocks - 1u;
+  const uint32_t pre = bid * group;
+  const uint32_t lim = lastBlock ? (p.n + p.span - 1u) / p.span : pre;
+  uint4 sums = make_uint4(0, 0, 0, 0);                 // predecessors' visible / candidates, own visible / candidates (last workgroup)
+  auto prefixBatch = [&](uint32_t j0) {
+    uint32_t bv[kPrefixBatch], bc[kPrefixBatch];
+#pragma unroll
+    for (uint32_t u = 0; u < kPrefixBatch; ++u) {
+      const uint32_t j = j0 + u * kTile + threadIdx.x;
+      const uint32_t at = j < lim ? j : 0u;
+      bv[u] = d.blockVis[at]; bc[u] = d.blockCand[at];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kPrefixBatch; ++u) {
+      const uint32_t j = j0 + u * kTile + threadIdx.x;
+      if (j < pre) { sums.x += bv[u]; sums.y += bc[u]; }
+      else if (j < lim) { sums.z += bv[u]; sums.w += bc[u]; }
+    }
+  };
+  if (lim) {
+    prefixBatch(0u);                                   // (the first batch outside the loop: a loop head waits for every load in flight)
+    for (uint32_t j0 = kPrefixBatch * kTile; j0 < lim; j0 += kPrefixBatch * kTile) prefixBatch(j0);
+  }
+
+  // ---- the words' popcounts cross the waves on blockSum4's barriers
+  const bool mine = some && myWord < vWords;
+  const unsigned long long myVis = mine ? rawVis : 0ull, myCul = (mine && doCulled) ? (rawCand & ~rawVis) : 0ull;
+  wordCount[wave][lane] = (uint32_t)__popcll(myVis) | ((uint32_t)__popcll(myCul) << 16);      // at most 64 of either
+  const uint4 tot = blockSum4(sums, scratch);
+  if (lastBlock && threadIdx.x == 0) {
+    const uint32_t tv = tot.x + tot.z, tc = tot.y + tot.w;
+    d.counters[0] = tv;            // CullingStats::visible
+    d.counters[1] = tc - tv;       // CullingStats::culled
+    d.counters[6] = tc;            // renderablesTotal
+  }
+  // exclusive scan over the words in index order, both lists in one dword: a row holds at most 4 x 64, a workgroup at most 16384 of either
+  const uint32_t c0 = wordCount[0][lane], c1 = wordCount[1][lane], c2 = wordCount[2][lane], c3 = wordCount[3][lane];
+  const uint32_t row = c0 + c1 + c2 + c3;
+  uint32_t incl = row;
+#pragma unroll
+  for (uint32_t o = 1; o < 64u; o <<= 1) {
+    const uint32_t up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  const uint32_t before = (incl - row) + (wave > 0u ? c0 : 0u) + (wave > 1u ? c1 : 0u) + (wave > 2u ? c2 : 0u);
+  const uint32_t offV = tot.x + (before & 0xFFFFu), offC = (tot.y - tot.x) + (before >> 16);
+
+  // ---- scatter by word
+  const uint32_t visLo = (uint32_t)myVis, visHi = (uint32_t)(myVis >> 32), culLo = (uint32_t)myCul, culHi = (uint32_t)(myCul >> 32);
+  const uint32_t firstOfWave = ((vBegin + wave) << 6) + lane;      // this lane's entity in the wave's first word; its k-th word lies k * kWaves words on
+  unsigned long long todo = (SC_DIAG_EOT & 2) ? 0ull : ballot64((myVis | myCul) != 0ull);
+  while (todo) {
+    const uint32_t k = (uint32_t)__builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const uint32_t i = firstOfWave + k * (kWaves * 64u);
+    const uint32_t mLo = (uint32_t)__builtin_amdgcn_readlane((int)visLo, (int)k), mHi = (uint32_t)__builtin_amdgcn_readlane((int)visHi, (int)k);
+    const uint32_t ov = (uint32_t)__builtin_amdgcn_readlane((int)offV, (int)k);
+    const unsigned long long m = ((unsigned long long)mHi << 32) | mLo;
+    if ((m >> lane) & 1ull) d.visibleIdx[ov + __builtin_amdgcn_mbcnt_hi(mHi, __builtin_amdgcn_mbcnt_lo(mLo, 0u))] = i;
+    if (doCulled) {
+      const uint32_t cLo = (uint32_t)__builtin_amdgcn_readlane((int)culLo, (int)k), cHi = (uint32_t)__builtin_amdgcn_readlane((int)culHi, (int)k);
+      const uint32_t oc = (uint32_t)__builtin_amdgcn_readlane((int)offC, (int)k);
+      const unsigned long long cm = ((unsigned long long)cHi << 32) | cLo;
+      if ((cm >> lane) & 1ull) d.culledIdx[oc + __builtin_amdgcn_mbcnt_hi(cHi, __builtin_amdgcn_mbcnt_lo(cLo, 0u))] = i;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // K3: pair search.  One wave per sector bin (grid-stride): the bin's <= 64 records become an LDS
 // tile (lane i stages record i), the n(n-1)/2 record pairs are spread over the 64 lanes, each lane
@@ -3262,19 +3367,50 @@ void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* 
   if (p.colliders) hipLaunchKernelGGL(k_deep_level_colliders, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
   else hipLaunchKernelGGL(k_deep_level, dim3((count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, list, count);
 }
-// spans of the fused kernel per compaction workgroup
-// Measured at 1M entities (1536 spans): alone, one span per workgroup is fastest (8.2 us; 9.2 / 10.9 with 2 / 4 -- the
-// tiles of a workgroup are walked one after the other); sharing the launch with the pair search, two spans per
-// workgroup win (10.5 us against 11.3 / 12.2 with 1 / 4): fewer workgroups leave room for the pair role's.
+// spans of the fused kernel per compaction workgroup, compactBody's form (k_compact while it has more than compaction to do, and the
+// compaction role of the shared launches)
+// Measured at 1M entities (1536 spans) when the role still ran the producer and walked its tiles entity by entity: alone, one span per
+// workgroup is fastest (8.2 us; 9.2 / 10.9 with 2 / 4 -- the tiles of a workgroup are walked one after the other); sharing the launch
+// with the pair search, two spans per workgroup win (10.5 us against 11.3 / 12.2 with 1 / 4): fewer workgroups leave room for the
+// pair role's.
 static uint32_t compactGroup(uint32_t grid, bool merged)
 {
   return (merged && grid >= 512u) ? 2u : 1u;
 }
-void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
+// spans per workgroup of the WIDE form (k_compact_wide); 0 = this launch keeps compactBody.  The wide form needs a launch with nothing
+// but compaction left -- culling on; the dirty clear and the producer owned by the fused kernel's tail, or no transform half in the
+// tick -- and a span whose words fit a workgroup.  The rule, as a function of span and grid:
+//   G = min(floor(kCompactWordsMax / (span / 64)), max(1, floor(kCompactWideWords / (span / 64))), grid)
+// i.e. as many spans as give a workgroup about kCompactWideWords visibility words, nine to a wave, never more than one per thread.
+// The grid enters only as the cap.  Measured at 1M entities, 1366 spans of 768 (end-of-tick slot, us; compactBody 5.9 / 6.5):
+//   G                       1     2     3     4     5     6    10    21
+//   4.3 k visible         4.3   4.1   4.2   4.2   4.2   4.0   4.2   4.2      flat from 683 workgroups down to 66; 1366 cost the STEP 1.2 us more
+//   everything visible    5.2   4.6   4.6   4.7   4.8   4.7   5.6   8.4      a wave's scatter loop is serial: its length is words / 4
+// so what G trades is the workgroup count (too many: G = 1) against the words one wave stores in turn (too many: G >= 10).
+// `forced` (SC_TICK_COMPACT_G at creation, measurements and tests): that many instead, under the same upper bound.
+constexpr uint32_t kCompactWideWords = 36u;
+uint32_t compactWideGroup(const TickParams& p, uint32_t grid, uint32_t forced)
 {
-  const uint32_t g = compactGroup(grid, false);
-  if (evA) hipExtLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, evA, evB, 0, d, p, g);
-  else hipLaunchKernelGGL(k_compact, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
+  const bool only = (p.flags & SC_TICK_CULL) && ((p.flags & kFlagTailOwnsDirty) || !(p.flags & SC_TICK_XFORM));
+  const uint32_t words = p.span / 64u;
+  if (!only || !words || words > kCompactWordsMax) return 0u;
+  const uint32_t upper = kCompactWordsMax / words;
+  const uint32_t g = forced ? forced : std::min(std::max(1u, kCompactWideWords / words), std::max(1u, grid));
+  return std::min(g, upper);
+}
+// {workgroups of the compaction role, spans per workgroup} of a launch; merged: the role shares its launch with the pair search
+void compactLaunchShape(uint32_t grid, bool merged, uint32_t wideG, uint32_t shape[2])
+{
+  const uint32_t g = wideG ? wideG : compactGroup(grid, merged);
+  shape[0] = (grid + g - 1u) / g; shape[1] = g;
+}
+// wideG: compactWideGroup()'s answer for this launch (0: compactBody's form)
+void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, uint32_t wideG, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
+{
+  const uint32_t g = wideG ? wideG : compactGroup(grid, false);
+  auto kernel = wideG ? k_compact_wide : k_compact;
+  if (evA) hipExtLaunchKernelGGL(kernel, dim3((grid + g - 1) / g), dim3(kTile), 0, s, evA, evB, 0, d, p, g);
+  else hipLaunchKernelGGL(kernel, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
 }
 // Pair-role geometry (round 4, second form): four pair workgroups for every CU -- the fifth resident workgroup of each CU is left to the
 // compaction role, which shares the launch and comes behind the pair role in index order -- and the run as long as that needs:

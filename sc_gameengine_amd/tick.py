@@ -548,6 +548,13 @@ class WorldTick:
         self._ok(self.lib.scTickGetTailStats(self.ctx, _u(st)), "scTickGetTailStats")
         return {"tail_owned_dirty": bool(st[0]), "span_closed": bool(st[1])}
 
+    def compact_stats(self):
+        """how the last tick's compaction was cut into workgroups: workgroups of the compaction role and spans per workgroup, 0 / 0 when
+        the tick had none (host-side: no read-back).  More than one span per workgroup on a launch of its own: the wide form ran"""
+        st = np.zeros(2, np.uint32)
+        self._ok(self.lib.scTickGetCompactStats(self.ctx, _u(st)), "scTickGetCompactStats")
+        return {"workgroups": int(st[0]), "spans_per_workgroup": int(st[1])}
+
     def learn_ticks(self):
         """learn ticks so far (host-side counter: no read-back)"""
         st = np.zeros(1, np.uint32)
