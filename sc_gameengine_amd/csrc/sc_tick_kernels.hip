@@ -21,6 +21,14 @@ namespace sctick {
 #ifndef SC_XFORM_OCC
 #define SC_XFORM_OCC      // (an occupancy attribute for the fused kernel, for experiments: seven and eight waves per SIMD by force both lost -- profiles/r03/ab_eight_waves.log, profiles/r04/ab_fused_kernel_slp_fma.log)
 #endif
+// Cache policy of the matrix-row stores of the instances without binning (xformCullPipelined), chosen at compile time:
+// 0 plain, 1 nt, 2 sc1, 3 sc0 sc1.  Plain and nt stores leave the line dirty in the XCD's L2, and a launch that writes more rows
+// than the L2s hold ends with the last of them still to be written back before the end-of-tick launch can start; sc1 and
+// sc0 sc1 stores write through and drop the line.  Measured on config 3 (DESIGN.md sections 5 and 11.17): sc1 and sc0 sc1 take
+// 0.8-1.5 us off the step and are not apart, nt and plain are not apart either.
+#ifndef SC_ROW_STORE_POLICY
+#define SC_ROW_STORE_POLICY 2
+#endif
 #ifndef SC_PAIR_OCC
 #define SC_PAIR_OCC __attribute__((amdgpu_waves_per_eu(5, 5)))
 #endif
@@ -50,16 +58,30 @@ __device__ __forceinline__ float4 ldRow(const DeviceState& d, uint32_t row, uint
   return *reinterpret_cast<const float4*>(d.rslab + (row * d.capBytes16 + i * 16u));
 }
 typedef float V4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void storeStream16(void* p, const float4& v)
-{
-  // written once per tick and not read again before the NEXT launch: a non-temporal store does not leave the line dirty in
-  // L2, which the following kernel boundary would otherwise have to write back before the end-of-tick kernel starts
-  V4f x = { v.x, v.y, v.z, v.w };
-  __builtin_nontemporal_store(x, reinterpret_cast<V4f*>(p));
-}
 __device__ __forceinline__ void stRow(const DeviceState& d, uint32_t row, uint32_t i, const float4& v)
 {
   *reinterpret_cast<float4*>(d.rslab + (row * d.capBytes16 + i * 16u)) = v;
+}
+// stRow under SC_ROW_STORE_POLICY, for rows that are written once per tick and not read again before the next launch.  Vector
+// stores only.  The compiler does not count a store written in asm in vmcnt; the hardware does, so a wait behind one can only
+// be longer than the compiler meant, never shorter, and nothing in the kernel reads a row it stored.
+__device__ __forceinline__ void stRowPolicy(const DeviceState& d, uint32_t row, uint32_t i, const float4& v)
+{
+#if SC_ROW_STORE_POLICY == 0
+  stRow(d, row, i, v);
+#else
+  const V4f x = { v.x, v.y, v.z, v.w };
+  const uint32_t off = row * d.capBytes16 + i * 16u;
+#if SC_ROW_STORE_POLICY == 1
+  __builtin_nontemporal_store(x, reinterpret_cast<V4f*>(d.rslab + off));
+#elif SC_ROW_STORE_POLICY == 2
+  asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(off), "v"(x), "s"(d.rslab) : "memory");
+#elif SC_ROW_STORE_POLICY == 3
+  asm volatile("global_store_dwordx4 %0, %1, %2 sc0 sc1" : : "v"(off), "v"(x), "s"(d.rslab) : "memory");
+#else
+#error "SC_ROW_STORE_POLICY: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1"
+#endif
+#endif
 }
 
 // local = T * (R * S) with R = (Rz * Ry) * Rx  (sc_math.cpp:100-142).
@@ -151,6 +173,12 @@ __device__ __forceinline__ void storeRows(const DeviceState& d, uint32_t j, cons
   stRow(d, 0, j, make_float4(M.r0[0], M.r0[1], M.r0[2], M.r0[3]));
   stRow(d, 1, j, make_float4(M.r1[0], M.r1[1], M.r1[2], M.r1[3]));
   stRow(d, 2, j, make_float4(M.r2[0], M.r2[1], M.r2[2], M.r2[3]));
+}
+__device__ __forceinline__ void storeRowsPolicy(const DeviceState& d, uint32_t j, const Aff& M)
+{
+  stRowPolicy(d, 0, j, make_float4(M.r0[0], M.r0[1], M.r0[2], M.r0[3]));
+  stRowPolicy(d, 1, j, make_float4(M.r1[0], M.r1[1], M.r1[2], M.r1[3]));
+  stRowPolicy(d, 2, j, make_float4(M.r2[0], M.r2[1], M.r2[2], M.r2[3]));
 }
 
 struct BoundsCE { float cx, cy, cz, ex, ey, ez; };
@@ -791,7 +819,7 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
     }
     // ---- W, trip 3: in flight together with the stores
     if (kNext && kChain >= 2) { walkResolve(nw, 1u, i + kTile, last, doXform); walkIssue(d, nw, 2u, doXform); }
-    if (recompute) storeRows(d, i, M);
+    if (recompute) storeRowsPolicy(d, i, M);             // (write-through: SC_ROW_STORE_POLICY)
 
     if (hasDeep) {
       const unsigned long long rm = ballot64(recompute);
