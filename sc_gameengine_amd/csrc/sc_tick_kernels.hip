@@ -29,6 +29,12 @@ namespace sctick {
 #ifndef SC_ROW_STORE_POLICY
 #define SC_ROW_STORE_POLICY 2
 #endif
+// Parent chains inside a wave-tile of the instances without binning (xformCullPipelined): 1 = a wave-tile whose every chain link stays
+// inside it multiplies once per lane and takes the parent's world matrix from the parent's lane (ds_bpermute) instead of rebuilding every
+// ancestor's matrix in every descendant's lane; 0 = every wave-tile rebuilds, the kernel as it was.  DESIGN.md section 11.18.
+#ifndef SC_WAVE_CHAINS
+#define SC_WAVE_CHAINS 1
+#endif
 #ifndef SC_PAIR_OCC
 #define SC_PAIR_OCC __attribute__((amdgpu_waves_per_eu(5, 5)))
 #endif
@@ -179,6 +185,17 @@ __device__ __forceinline__ void storeRowsPolicy(const DeviceState& d, uint32_t j
   stRowPolicy(d, 0, j, make_float4(M.r0[0], M.r0[1], M.r0[2], M.r0[3]));
   stRowPolicy(d, 1, j, make_float4(M.r1[0], M.r1[1], M.r1[2], M.r1[3]));
   stRowPolicy(d, 2, j, make_float4(M.r2[0], M.r2[1], M.r2[2], M.r2[3]));
+}
+
+// the twelve floats of lane (src4 >> 2)'s M, bits in and bits out.  Every lane of the wave has to be enabled (a switched-off source
+// lane gives 0): the caller sits outside any divergent branch, and a lane that wants nothing names itself.
+__device__ __forceinline__ float fromLane(int src4, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src4, __float_as_int(v))); }
+__device__ __forceinline__ Aff affFromLane(int src4, const Aff& M)
+{
+  Aff P;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) { P.r0[c] = fromLane(src4, M.r0[c]); P.r1[c] = fromLane(src4, M.r1[c]); P.r2[c] = fromLane(src4, M.r2[c]); }
+  return P;
 }
 
 struct BoundsCE { float cx, cy, cz, ex, ey, ez; };
@@ -625,7 +642,8 @@ __device__ __forceinline__ void binEntitySingle(const DeviceState& d, const Tick
 // ------------------------------------------------------------------------------------------
 // (Alternatives that were measured and dropped -- a wave-cooperative hierarchy resolve through ds_bpermute, bounds
 // loaded before the walk, binning with a single atomic round trip -- are in the history at 72ae167; all of
-// them lost to this form because they cost VGPRs, and this kernel is occupancy-bound.  DESIGN.md section 5.)
+// them lost to this form because they cost VGPRs, and this kernel is occupancy-bound.  DESIGN.md section 5.  That holds for the
+// binning instances, xformCullBody; the instances without binning do resolve chains in the wave-tile: SC_WAVE_CHAINS, section 11.18.)
 // The body is a device function taking the arguments by reference on purpose: written directly in the
 // __global__ function the same code allocates 84/91 VGPRs instead of 64/77 (hipcc, ROCm 7.2).
 // kChain = how many ancestors a lane may have to walk: min(deepest level in the world, kMaxChain), known to the
@@ -711,6 +729,9 @@ __device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams&
 // The price is registers -- the raw locals of every level and the next tile's walk in flight -- which these instances have:
 // a launch of at most 1536 spans needs six waves per SIMD, 80 VGPRs (profiles/r18; DESIGN.md sections 5 and 11.15).  The
 // binning instances have none to give and keep xformCullBody.
+// With SC_WAVE_CHAINS a wave-tile whose chain links all stay inside it does not rebuild its ancestors at all: every lane asks for its
+// own local only and takes its parent's finished matrix from the parent's lane (the cooperative form, in the tile lambda); the rebuild
+// described above is then the fallback of the other wave-tiles and asks level by level (pipelinedBatch).
 // ------------------------------------------------------------------------------------------
 template <uint32_t kChain>
 struct TileWalk {
@@ -795,25 +816,59 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
 #pragma unroll
     for (uint32_t k = 0; k < kChain; ++k) if ((uint32_t)top == k) rows = w.a[k + 1];
     Aff M;
-    if (recompute ? !fromRoot : (kCull && active)) M = loadRows(d, rows);
-    LocalRaw raw[kChain + 1];
+    // ---- W, trip 1: behind X's requests in the queue and in flight with them; trip 2: under the arithmetic
+    auto walkAhead = [&]() {
+      if (kNext) { walkRequest(d, nw, i + kTile, last); walkResolve(nw, 0u, i + kTile, last, doXform); if (kChain >= 1) walkIssue(d, nw, 1u, doXform); }
+    };
+#if SC_WAVE_CHAINS
+    // The cooperative form, chosen per wave-tile (uniform): every lane with a dirty ancestor above it has its parent in this wave-tile.
+    // That parent is level top - 1 of the same chain under the same top entity, so it recomputes in this trip, from the same seed, and
+    // what its lane ends with is what this lane would rebuild.  Only the own local is asked for, and only a top-0 lane asks for seed rows.
+    // Pass 0: every lane's own local; the top-0 lanes are done, a lane with top >= 1 keeps its local in M until its pass (no second
+    // matrix held across the passes).  Pass p: the lanes with top == p multiply their parent's finished matrix (a top-(p-1) lane,
+    // finished one pass earlier) by their local -- ((L_top * L_top-1) * ...) * L_0, the order of the rebuild below: the same bits.
+    // What a lane reads in a pass that is not its own is thrown away.  A pass nobody in the wave needs is skipped (uniform), and
+    // with it every later one.  The two forms are two arms of one branch, the walk's trips written in both: a value asked for in
+    // one form and used in the same form is then live in that arm only.
+    bool coop = false;
+    if (kChain >= 1) coop = ballot64(top >= 1 && (w.a[kChain >= 1 ? 1 : 0] >> 6) != (i >> 6)) == 0ull;
+    if (coop) {
+      LocalRaw own;
+      if (recompute ? (top == 0 && !fromRoot) : (kCull && active)) M = loadRows(d, rows);
+      if (recompute) own = requestLocal(d, w.a[0], w.rotFlags << 29);
+      walkAhead();
+      if (recompute) {
+        const Aff L = buildLocal(own);
+        if (top == 0 && !fromRoot) M = mulAff(M, L);
+        else M = L;
+      }
+      const int src4 = (int)((top >= 1 ? (w.a[kChain >= 1 ? 1 : 0] & 63u) : lane) << 2);
 #pragma unroll
-    for (int lev = (int)kChain; lev > (int)kChain - (int)kBatch; --lev)
-      if (lev <= top) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
-    // ---- W, trip 1: behind X's requests in the queue and in flight with them
-    if (kNext) walkRequest(d, nw, i + kTile, last);
-
-    // ---- W, trip 2: under the arithmetic
-    if (kNext) { walkResolve(nw, 0u, i + kTile, last, doXform); if (kChain >= 1) walkIssue(d, nw, 1u, doXform); }
-
-    if (recompute) {
+      for (int pass = 1; pass <= (int)kChain; ++pass) {
+        if (ballot64(top == pass) != 0ull) {
+          const Aff P = affFromLane(src4, M);
+          if (top == pass) M = mulAff(P, M);
+        }
+      }
+    } else
+#endif
+    {
+      if (recompute ? !fromRoot : (kCull && active)) M = loadRows(d, rows);
+      LocalRaw raw[kChain + 1];
 #pragma unroll
-      for (int lev = (int)kChain; lev >= 0; --lev) {
-        if (lev <= top) {
-          if (lev <= (int)kChain - (int)kBatch) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
-          const Aff L = buildLocal(raw[lev]);
-          if (lev == top && fromRoot) M = L;
-          else M = mulAff(M, L);
+      for (int lev = (int)kChain; lev > (int)kChain - (int)kBatch; --lev)
+        if (lev <= top) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
+      walkAhead();
+
+      if (recompute) {
+#pragma unroll
+        for (int lev = (int)kChain; lev >= 0; --lev) {
+          if (lev <= top) {
+            if (lev <= (int)kChain - (int)kBatch) raw[lev] = requestLocal(d, w.a[lev], (w.rotFlags >> (3 * lev)) << 29);
+            const Aff L = buildLocal(raw[lev]);
+            if (lev == top && fromRoot) M = L;
+            else M = mulAff(M, L);
+          }
         }
       }
     }
@@ -884,9 +939,16 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
   if (kTail) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 }
 
-// every level's locals in one round trip, but for the chain-3 instance with culling: four levels and the sphere test's state
-// are 85 VGPRs, five waves per SIMD; with level 0 requested on its own, behind the product of level 1, it holds six
+// Without SC_WAVE_CHAINS: every level's locals in one round trip, but for the chain-3 instance with culling: four levels and the sphere
+// test's state are 85 VGPRs, five waves per SIMD; with level 0 requested on its own, behind the product of level 1, it holds six.
+// With it the rebuild is the fallback of the wave-tiles whose chains leave them, and it asks level by level: both forms with the
+// batched requests are 83 / 73 / 85 VGPRs (chain 2 with culling / without / chain 3 without), a wave per SIMD fewer than the kernel had;
+// level by level they are 60 / 56 / 56, a wave more (profiles/r21/kernel_regs_*.txt).
+#if SC_WAVE_CHAINS
+constexpr uint32_t pipelinedBatch(bool, uint32_t) { return 1u; }
+#else
 constexpr uint32_t pipelinedBatch(bool cull, uint32_t chain) { return (cull && chain == 3u) ? 3u : chain + 1u; }
+#endif
 
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
 __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull(const DeviceState d, const TickParams p)
