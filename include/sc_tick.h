@@ -784,8 +784,8 @@ int scTickReadAnchoredRays(ScTickContext* ctx, uint32_t first, uint32_t count, u
  * diagonal and a sphere answers at the face of its bounding cube.  scTickSetRayShapes(SC_TICK_RAY_SHAPES_EXACT) makes the runs with
  * SC_TICK_RAYS and SC_TICK_ANCHORED_RAYS answer a candidate whose proxy comes from a typed collider (scTickUploadColliders: BOX, SPHERE,
  * CAPSULE) by the shape itself, taken through the entity's world matrix of this tick.  The AABB test stays as the pre-filter; the sector
- * walk, the filter, the skip rule, the tie rule and ScTickRayHit are what they were.  Capsule sweeps, the traffic AI's front rays,
- * scTickQueryOccupied and the pair search do not change: they see AABBs in either mode.
+ * walk, the filter, the skip rule, the tie rule and ScTickRayHit are what they were.  Capsule sweeps (which have a mode of their own: "exact shapes for capsule sweeps"),
+ * the traffic AI's front rays, scTickQueryOccupied and the pair search do not change: they see AABBs in either mode.
  * This build's OWN SPEC, like the rays.  All arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt;
  * dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
  * A candidate record passes the filter and the skip test, then the slab test against its AABB (dir: the normalised direction, L: max_dist).
@@ -1018,6 +1018,77 @@ int scTickSetTouchEvents(ScTickContext* ctx, uint32_t max_tracked_pairs, uint32_
 /* begun2 / ended2: [cap][2] (a, b), either may be NULL with capacity 0; min(count, max_events, capacity) pairs are written to each.
  * Synchronises; copies the 24 bytes of `info` and the listed pairs, nothing else. */
 int scTickReadTouchEvents(ScTickContext* ctx, uint32_t* begun2, uint32_t begun_cap, uint32_t* ended2, uint32_t ended_cap, ScTickTouchEventInfo* info);
+
+/* ---- exact shapes for capsule sweeps: sphere, capsule, oriented box ----
+ * The capsule sweeps answer from the broadphase's WORLD AABBs with the sweeper's own AABB: a pedestrian capsule walking past a prop yawed
+ * by 45 degrees is stopped by the corner of the prop's bounding square, and the sweeper itself has square corners.  The reference sweeps
+ * Bullet's rounded capsule through Bullet's exact shapes (convexSweepTest behind PhysicsWorld::sweepCapsule, sc_physics.cpp:779-810), an
+ * iterative convex cast.  scTickSetSweepShapes(SC_TICK_SWEEP_SHAPES_EXACT) makes the runs with SC_TICK_SWEEPS answer a candidate whose
+ * proxy comes from a typed collider (scTickUploadColliders: BOX, SPHERE, CAPSULE) by a conservative advancement of the capsule itself
+ * towards the shape itself, over the distance routines of the touching pairs.  The grown-AABB test stays as the pre-filter; the sector
+ * walk, the filter, the skip rule, the tie rule, ScTickSweepHit, scTickSetSweepQueries and scTickReadSweepHits are what they were.
+ * This build's OWN SPEC.  All arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt; dot as the rays define it.
+ * A candidate record passes the filter and the skip test, then the capsule sweeps' slab test against its grown AABB (sweeper e, segment
+ * (start, ndir, far) as defined there) -- a capsule lies inside its AABB and a collider's shape inside its world AABB, so the pre-filter
+ * loses nothing.
+ *   A grown-AABB miss: the candidate does not answer, in both modes.
+ *   A grown-AABB hit with entry time t0 (the slab test's t) in EXACT mode is REFINED when the box's id is refinable the way a member of
+ *   a touching pair is: colliders were uploaded, the id's rank is this context's, e = id & 0xFFFFFF is below the entity count, the collider
+ *   type of e is BOX, SPHERE or CAPSULE, and every n_k is finite and > 0.  Otherwise the grown-AABB answer stands, bit for bit as in AABB
+ *   mode: BOUNDS proxies, a neighbour tile's border records, degenerate matrices, a context without colliders.
+ * The sweeper at travel t is a ROUND in the sense of the touching pairs: centre c(t) = start + ndir*t per component, A = (0, hh, 0) with
+ * hh as the capsule sweeps define it -- not hh*hh > 0: A = (0, 0, 0), a sphere --, R = radius.  The target's round (A_t, R_t) or box frame
+ * (u_k, H_k, T) is what the touching pairs build from its matrix and record.
+ *   dist2(t)  SPHERE, CAPSULE: routine 1 of the touching pairs with p1 = c(t) - A, d1 = A + A, p2 = T - A_t, d2 = A_t + A_t: its
+ *             dot(v, v).  ps - pt below is that v.
+ *             BOX: routine 2 with w = c(t) - T: its fmin, together with the parameter it was found at -- at = 0 for F(0), and every later
+ *             evaluation of the fifteen, in the routine's order (F(1); then per interval i: F(ts), and for i < 6 F(hi)), takes over only
+ *             when strictly smaller.  ps = (c(t) - A) + (A + A)*at per component; z_k = the coordinate y0_k + dy_k*at clamped into the box,
+ *             lo = (y < -H_k) ? -H_k : y, z_k = (lo > H_k) ? H_k : lo;  pt_i = ((u_0[i]*z_0 + u_1[i]*z_1) + u_2[i]*z_2) + T_i.
+ *   Rs        R + R_t for a SPHERE or CAPSULE target, R for a BOX.     gap(t) = sqrt(dist2(t)) - Rs.
+ * gap is convex in t (the distance of two convex sets in linear relative motion) and ndir is a unit vector, so neither a step of gap(t)
+ * metres nor a step to the zero of the secant through two iterates left of the first contact passes that contact:
+ *   t = t0;  no previous iterate;  repeat SC_TICK_SWEEP_SHAPES_STEPS times:
+ *     d2 = dist2(t)
+ *     t == 0 and not d2 > Rs*Rs:   INSIDE: hit, t = +0, normal (0,1,0) -- the touching pairs' comparison: a NaN is inside
+ *     g = sqrt(d2) - Rs
+ *     g <= SC_TICK_SWEEP_SHAPES_TOL:   HIT at t
+ *     far == 0:   MISS (an overlap test makes one evaluation)
+ *     step = g;   with a previous iterate (tp, gp):  slope = (g - gp) / (t - tp);  not slope < 0: MISS (convex and not approaching: it
+ *                 never arrives);  sec = (-g) / slope;  sec > step: step = sec
+ *     (tp, gp) = (t, g);  t = t + step;  t > far: MISS
+ *   after the last repetition: HIT at the t reached, counted in `exhausted` -- a sweep never passes through what it ran out of steps for.
+ * A HIT's normal: v = ps - pt of the last evaluation made, vv = dot(v, v); vv > 0: v / sqrt(vv) per component, else (0,1,0).
+ * The rest of the hit: position = start + ndir*t (the capsule's centre), travel = t, distance = t / far (0 when far == 0), layer and id as in
+ * AABB mode.  Among candidates the smallest t wins -- refined or standing alike -- and equal t goes to the lower id.
+ * scTickGetSweepShapeInfo reports what the last run's sweeps did with their candidates.  A candidate is a box that passed the filter, the
+ * skip test and the grown-AABB test of one sweep; it is counted once for that sweep however many sectors hold a record of it, for the
+ * first SC_TICK_SWEEP_SHAPES_SEEN candidates of a sweep (beyond that a box met again in another sector counts again).  The words are
+ * zeroed and written on the device: a captured graph replays them.
+ * The mode is a property of the context and stays until it is changed (default AABB).  Setting it drops captured graphs and asks for no
+ * learn tick.  It fails on an unknown mode and while scTickRunPairs is pending.  A run with SC_TICK_SWEEPS in EXACT mode fails on a
+ * pipelined context (scTickSetPipelined / scTickSetPairsStream): by the time its sweeps are cast the matrices may be the next tick's.
+ * In-order tiles and the caller-owned split flow work, with the exact rays' restriction on the latter: between
+ * scTickRun(.. | SC_TICK_SPLIT_PAIRS | SC_TICK_SWEEPS) in EXACT mode and its scTickRunPairs, scTickUploadWorldMatrices,
+ * scTickUploadColliders, scTickRemoveEntities, scTickSetEntityCount and scTickRun with SC_TICK_XFORM fail and change nothing.  A context
+ * that never calls scTickSetSweepShapes allocates and launches exactly what it did before; AABB mode launches the kernel it always did.
+ * Not covered: rotated sweepers (the reference's is upright), contact points, a neighbour tile's shapes, pipelined tiles. */
+enum { SC_TICK_SWEEP_SHAPES_AABB = 0, SC_TICK_SWEEP_SHAPES_EXACT = 1 };
+#define SC_TICK_SWEEP_SHAPES_TOL   1e-3f   /* metres */
+#define SC_TICK_SWEEP_SHAPES_STEPS 12
+#define SC_TICK_SWEEP_SHAPES_SEEN  256u
+typedef struct ScTickSweepShapeInfo
+{
+  uint32_t refined;         /* candidates answered by their shape */
+  uint32_t kept_as_boxes;   /* candidates left on their grown-AABB answer */
+  uint32_t exhausted;       /* refined candidates that ran out of steps: reported as a hit at the travel reached */
+  uint32_t pad;             /* 0 */
+} ScTickSweepShapeInfo;
+int scTickSetSweepShapes(ScTickContext* ctx, uint32_t mode);   /* default SC_TICK_SWEEP_SHAPES_AABB */
+int scTickGetSweepShapes(ScTickContext* ctx, uint32_t* mode);
+/* of the last scTickRun(... | SC_TICK_SWEEPS) (after scTickRunPairs in a split flow); fails when that run did not carry the flag or swept
+ * in AABB mode.  Synchronises; copies the 16 bytes of `info`. */
+int scTickGetSweepShapeInfo(ScTickContext* ctx, ScTickSweepShapeInfo* info);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

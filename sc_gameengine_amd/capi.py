@@ -19,6 +19,8 @@ PAIR_SHAPES = 1 << 14         # SC_TICK_PAIR_SHAPES: also list the pairs of this
 TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended TOUCHING since the last run with this flag (scTickSetTouchEvents)
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
+SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*: what a capsule sweep's candidates are (scTickSetSweepShapes)
+SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 BIN_LAZY, BIN_STAY, BIN_SWEEP_ONLY, BIN_QUIET = 1, 2, 4, 8     # scTickGetBinStats stats[2]: what the last tick did with the bins (BIN_QUIET: nothing at all)
@@ -71,6 +73,10 @@ class PairEventInfo(C.Structure):
 
 class TouchEventInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("begun", "ended", "tracked", "resync", "overflow", "events_truncated")]
+
+
+class SweepShapeInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("refined", "kept_as_boxes", "exhausted", "pad")]
 
 
 class PairShapeInfo(C.Structure):
@@ -229,6 +235,9 @@ SYMBOLS = {
     "scTickReadAnchoredRays": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
     "scTickSetRayShapes": (C.c_int, [_CTX, C.c_uint32]),
     "scTickGetRayShapes": (C.c_int, [_CTX, U32P]),
+    "scTickSetSweepShapes": (C.c_int, [_CTX, C.c_uint32]),
+    "scTickGetSweepShapes": (C.c_int, [_CTX, U32P]),
+    "scTickGetSweepShapeInfo": (C.c_int, [_CTX, C.POINTER(SweepShapeInfo)]),
     "scTickSetPairEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "scTickReadPairEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairEventInfo)]),
     "scTickSetTouchEvents": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),

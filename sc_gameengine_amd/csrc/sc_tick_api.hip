@@ -123,6 +123,11 @@ struct ScTickContext
   // scTickSetRayShapes: SC_TICK_RAY_SHAPES_EXACT selects the exact-shape instances of the ray and anchored-ray kernels (launch time:
   // a captured graph holds the instance it was captured with, so a change drops the graphs)
   uint32_t rayShapes = SC_TICK_RAY_SHAPES_AABB;
+  // scTickSetSweepShapes: SC_TICK_SWEEP_SHAPES_EXACT selects the exact-shape instance of the sweep kernel, likewise; sweepInfo: the words of
+  // its report (== ScTickSweepShapeInfo), allocated by the first call that sets EXACT, zeroed on the stream before every launch
+  uint32_t sweepShapes = SC_TICK_SWEEP_SHAPES_AABB;
+  uint32_t* sweepInfo = nullptr;
+  bool lastSweepsExact = false;        // the last run with SC_TICK_SWEEPS ran them in EXACT mode (scTickGetSweepShapeInfo)
   std::vector<uint2> hAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
@@ -639,6 +644,9 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   p.colliders = c->d.colType ? 1u : 0u;         // (part of a captured graph's key: the instance choice follows it)
 }
 
+// the sweeps' instance: the report words of the exact-shape kernel, nullptr in AABB mode (launchSweepQueries chooses by it)
+uint32_t* exactSweepInfo(const ScTickContext* c) { return c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT ? c->sweepInfo : nullptr; }
+
 // the anchored rays as a tick of parity q sees them: its own copy of the snapshot
 AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
 {
@@ -658,6 +666,8 @@ const char* pendingShapeReader(const ScTickContext* c)
   if (!c->pairsPending) return nullptr;
   if (c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)))
     return "casts rays in SC_TICK_RAY_SHAPES_EXACT mode";
+  if (c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && (c->pendingParams.flags & SC_TICK_SWEEPS))
+    return "sweeps capsules in SC_TICK_SWEEP_SHAPES_EXACT mode";
   if (c->pendingParams.flags & SC_TICK_PAIR_SHAPES) return "lists the touching pairs (SC_TICK_PAIR_SHAPES)";
   if (c->pendingParams.flags & SC_TICK_TOUCH_EVENTS) return "reports touch events (SC_TICK_TOUCH_EVENTS)";
   return nullptr;
@@ -833,7 +843,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
-  if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, c->stream);
+  if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
@@ -1751,7 +1761,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   // (exact shapes: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
   if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, exactRays, ps);   // sees the neighbours' border boxes too
-  if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, ps);   // ... as do the capsule sweeps
+  if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, exactSweepInfo(c), ps);   // ... as do the capsule sweeps (exact shapes: as for the rays)
   if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), exactRays, ps);   // ... and the anchored rays, as the tick half resolved them
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
@@ -1856,6 +1866,9 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if ((flags & SC_TICK_SORT_DRAWS) && !c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
   if ((flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)) && c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && c->pairsStream)
     return fail(c, "SC_TICK_RAY_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its rays are cast when the matrices may be the next tick's");
+  if ((flags & SC_TICK_SWEEPS) && c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && c->pairsStream)
+    return fail(c, "SC_TICK_SWEEP_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its sweeps are cast when the matrices may be the next tick's");
+  if (flags & SC_TICK_SWEEPS) c->lastSweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
   // (a quiet tick keeps the flag in lastFlags -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
   const bool quiet = quietTick(c, flags);
   const uint32_t run = quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
@@ -2650,6 +2663,41 @@ int scTickGetRayShapes(ScTickContext* c, uint32_t* mode)
 {
   if (!c || !mode) return c ? fail(c, "null argument") : 0;
   *mode = c->rayShapes;
+  return 1;
+}
+
+int scTickSetSweepShapes(ScTickContext* c, uint32_t mode)
+{
+  static_assert(kSweepShapesTol == SC_TICK_SWEEP_SHAPES_TOL && kSweepShapesSteps == SC_TICK_SWEEP_SHAPES_STEPS && kSweepSeenCap == SC_TICK_SWEEP_SHAPES_SEEN,
+                "the sweep refinement's constants differ from the header's");
+  if (!c) return 0;
+  if (mode != SC_TICK_SWEEP_SHAPES_AABB && mode != SC_TICK_SWEEP_SHAPES_EXACT) return fail(c, "unknown sweep shape mode (SC_TICK_SWEEP_SHAPES_*)");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending (its sweeps are cast in the mode its tick half ran in)");
+  if (mode == c->sweepShapes) return 1;
+  if (!bind(c) || !sync(c)) return 0;
+  if (mode == SC_TICK_SWEEP_SHAPES_EXACT && !c->sweepInfo && !dalloc(c, c->sweepInfo, kSweepInfoWords)) return 0;
+  c->sweepShapes = mode;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
+  return 1;
+}
+
+int scTickGetSweepShapes(ScTickContext* c, uint32_t* mode)
+{
+  if (!c || !mode) return c ? fail(c, "null argument") : 0;
+  *mode = c->sweepShapes;
+  return 1;
+}
+
+int scTickGetSweepShapeInfo(ScTickContext* c, ScTickSweepShapeInfo* info)
+{
+  static_assert(sizeof(ScTickSweepShapeInfo) == kSweepInfoWords * sizeof(uint32_t), "the device writes the report word by word");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_SWEEPS)) return fail(c, "the last scTickRun did not request SC_TICK_SWEEPS");
+  if (!c->lastSweepsExact || !c->sweepInfo) return fail(c, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined");
+  if (c->pairsPending) return fail(c, "the sweep shape report is ready after scTickRunPairs");
+  if (!joinPairs(c)) return 0;
+  if (!d2h(c, info, c->sweepInfo, sizeof *info) || !sync(c)) return 0;
   return 1;
 }
 

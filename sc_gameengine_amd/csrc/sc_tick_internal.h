@@ -319,7 +319,13 @@ struct SweepQueryState {
   SweepHit48* hits;
   uint32_t count;
 };
-void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s);
+// exactInfo (scTickSetSweepShapes, SC_TICK_SWEEP_SHAPES_EXACT; nullptr: AABB mode): the instance that refines a grown-AABB hit of a refinable
+// collider by the shape itself -- chosen here, on the host -- and the words of its report (== ScTickSweepShapeInfo), zeroed before the launch
+constexpr float kSweepShapesTol = 1e-3f;        // == SC_TICK_SWEEP_SHAPES_TOL
+constexpr int kSweepShapesSteps = 12;           // == SC_TICK_SWEEP_SHAPES_STEPS
+constexpr uint32_t kSweepSeenCap = 256;         // == SC_TICK_SWEEP_SHAPES_SEEN: boxes one sweep counts once
+constexpr uint32_t kSweepInfoWords = 4;
+void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, uint32_t* exactInfo, hipStream_t s);
 // ---- entity-anchored rays (include/sc_tick.h "entity-anchored rays"): given in an entity's local frame, resolved against this tick's
 // world matrix of that entity by the kernel that casts them.  A kernel argument of their own, like the sweeps'. ----
 constexpr uint32_t kAnchorNone = 0xFFFFFFFFu;    // == SC_TICK_ANCHOR_NONE: origin and direction are world space
@@ -407,6 +413,159 @@ struct PairShapeState {
 constexpr uint32_t kPsTouching = 0, kPsRefined = 1, kPsKept = 2, kPsTested = 3, kPsPairsTruncated = 4, kPsCtlWords = 8;
 constexpr uint32_t kPsInfoWords = 8;
 constexpr float kPairShapesSatEps = 1e-6f;      // == SC_TICK_PAIR_SHAPES_SAT_EPS
+// The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
+// (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
+// fp32, unfused, left to right, as the header states it operation by operation.
+#ifdef __HIPCC__
+__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ float clamp01(float x) { const float c = (x > 0.0f) ? x : 0.0f; return (c < 1.0f) ? c : 1.0f; }   // (a NaN is 0)
+
+// a member of a pair as the routines take it: columns c[k], translation T, n[k] = dot(c[k], c[k]), the record (ex, ey, ez, radius)
+struct Member { float c[3][3]; float T[3]; float n[3]; float4 s; uint32_t type; bool ok; };
+
+// ok = the member can be refined: an own entity below the count with a typed collider and three finite, positive column norms
+__device__ __forceinline__ Member fetchMember(const DeviceState& d, uint32_t id, uint32_t count, uint32_t rankBits)
+{
+  Member m;
+  m.ok = false; m.type = kColliderBounds; m.s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { m.c[k][0] = m.c[k][1] = m.c[k][2] = 0.0f; m.T[k] = 0.0f; m.n[k] = 0.0f; }
+  const uint32_t e = id & 0x00FFFFFFu;
+  if (!d.colType || (id & 0xFF000000u) != rankBits || e >= count) return m;
+  m.type = d.colType[e];
+  if (m.type != kColliderBox && m.type != kColliderSphere && m.type != kColliderCapsule) return m;
+  m.s = d.colShape[e];
+  const float4 r0 = d.w0[e], r1 = d.w1[e], r2 = d.w2[e];
+  m.c[0][0] = r0.x; m.c[0][1] = r1.x; m.c[0][2] = r2.x;
+  m.c[1][0] = r0.y; m.c[1][1] = r1.y; m.c[1][2] = r2.y;
+  m.c[2][0] = r0.z; m.c[2][1] = r1.z; m.c[2][2] = r2.z;
+  m.T[0] = r0.w; m.T[1] = r1.w; m.T[2] = r2.w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) m.n[k] = dot3(m.c[k], m.c[k]);
+  m.ok = m.n[0] > 0.0f && m.n[1] > 0.0f && m.n[2] > 0.0f && isfinite(m.n[0]) && isfinite(m.n[1]) && isfinite(m.n[2]);
+  return m;
+}
+
+// a sphere or a capsule: the segment T - A .. T + A (A = 0: a point) and the radius around it
+struct Round { float A[3]; float R; };
+__device__ __forceinline__ Round roundOf(const Member& m)
+{
+  Round r;
+  if (m.type == kColliderSphere) {
+    const float nyz = (m.n[2] < m.n[1]) ? m.n[1] : m.n[2];
+    r.R = m.s.w * sqrtf((m.n[0] < nyz) ? nyz : m.n[0]);
+    r.A[0] = r.A[1] = r.A[2] = 0.0f;
+  } else {
+    r.R = m.s.w * sqrtf((m.n[0] < m.n[2]) ? m.n[2] : m.n[0]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r.A[i] = m.c[1][i] * m.s.y;
+    if (!(dot3(r.A, r.A) > 0.0f)) r.A[0] = r.A[1] = r.A[2] = 0.0f;      // no axis: the sphere of radius R
+  }
+  return r;
+}
+
+// a box in its own orthonormal frame: unit axes u[k], half lengths H[k]
+struct Frame { float u[3][3]; float H[3]; };
+__device__ __forceinline__ Frame frameOf(const Member& m)
+{
+  Frame f;
+  const float e[3] = { m.s.x, m.s.y, m.s.z };
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float q = sqrtf(m.n[k]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) f.u[k][i] = m.c[k][i] / q;
+    f.H[k] = e[k] * q;
+  }
+  return f;
+}
+
+__device__ __forceinline__ float boxDist2(const float y0[3], const float dy[3], const float H[3], float t)
+{
+  float g[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { const float x = fabsf(y0[k] + dy[k] * t) - H[k]; g[k] = (x > 0.0f) ? x : 0.0f; }
+  return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+}
+
+// The segment-segment core: the closest points of p1 + d1*[0, 1] and p2 + d2*[0, 1] by the clamped closed form -- their parameters s
+// and t, their difference v (first minus second) and its squared length
+struct SegSeg { float s, t, dist2; float v[3]; };
+__device__ __forceinline__ SegSeg segSegCore(const float p1[3], const float d1[3], const float p2[3], const float d2[3])
+{
+  float r[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r[i] = p1[i] - p2[i];
+  const float a = dot3(d1, d1), e = dot3(d2, d2), f = dot3(d2, r);
+  float s = 0.0f, t = 0.0f;
+  if (!(a > 0.0f)) { if (e > 0.0f) t = clamp01(f / e); }
+  else {
+    const float c = dot3(d1, r);
+    if (!(e > 0.0f)) s = clamp01((-c) / a);
+    else {
+      const float b = dot3(d1, d2);
+      const float den = a * e - b * b;
+      if (den > 0.0f) s = clamp01((b * f - c * e) / den);
+      t = (b * s + f) / e;
+      if (t < 0.0f) { t = 0.0f; s = clamp01((-c) / a); }
+      else if (t > 1.0f) { t = 1.0f; s = clamp01((b - c) / a); }
+    }
+  }
+  SegSeg o; o.s = s; o.t = t;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o.v[i] = (p1[i] + d1[i] * s) - (p2[i] + d2[i] * t);
+  o.dist2 = dot3(o.v, o.v);
+  return o;
+}
+
+// The segment-box core: the segment y0 + dy*[0, 1] in the box's frame.  F(t), the squared distance of its point t from the box, is convex
+// and piecewise quadratic with breakpoints where a coordinate crosses a face plane -- its minimum is F at a breakpoint, at an end, or at the
+// stationary point of one of the seven intervals between them: fifteen evaluations, the first strictly smaller one in their order keeps
+// its parameter.  segment false: a point (every dy is 0 and every F would be F(0) again) -- one evaluation.
+struct SegBox { float fmin, at; };
+__device__ __forceinline__ SegBox segBoxCore(const float y0[3], const float dy[3], const float H[3], bool segment)
+{
+  SegBox o;
+  o.fmin = boxDist2(y0, dy, H, 0.0f); o.at = 0.0f;
+  if (segment) {
+    float x = boxDist2(y0, dy, H, 1.0f);
+    if (x < o.fmin) { o.fmin = x; o.at = 1.0f; }
+    float b[8];
+    b[0] = 0.0f; b[7] = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      b[1 + 2 * k] = clamp01((H[k] - y0[k]) / dy[k]);
+      b[2 + 2 * k] = clamp01(((-H[k]) - y0[k]) / dy[k]);
+    }
+    // b[1..6] in ascending order: a fixed network of twelve compare-exchanges
+#define SC_CX(i, j) { const float lo = (b[j] < b[i]) ? b[j] : b[i], hi = (b[j] < b[i]) ? b[i] : b[j]; b[i] = lo; b[j] = hi; }
+    SC_CX(1, 6) SC_CX(2, 4) SC_CX(3, 5) SC_CX(2, 3) SC_CX(4, 5) SC_CX(1, 4) SC_CX(3, 6) SC_CX(1, 2) SC_CX(3, 4) SC_CX(5, 6) SC_CX(2, 3) SC_CX(4, 5)
+#undef SC_CX
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const float lo = b[i], hi = b[i + 1];
+      const float tm = (lo + hi) * 0.5f;
+      float num[3], den[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float y = y0[k] + dy[k] * tm;
+        const bool out = fabsf(y) - H[k] > 0.0f;
+        const float face = (y > 0.0f) ? H[k] : -H[k];
+        num[k] = out ? (y0[k] - face) * dy[k] : 0.0f;
+        den[k] = out ? dy[k] * dy[k] : 0.0f;
+      }
+      const float ns = (num[0] + num[1]) + num[2], ds = (den[0] + den[1]) + den[2];
+      float ts = (ds > 0.0f) ? (-ns) / ds : lo;
+      ts = (ts < lo) ? lo : ts;
+      ts = (ts > hi) ? hi : ts;
+      x = boxDist2(y0, dy, H, ts);
+      if (x < o.fmin) { o.fmin = x; o.at = ts; }
+      if (i < 6) { x = boxDist2(y0, dy, H, hi); if (x < o.fmin) { o.fmin = x; o.at = hi; } }
+    }
+  }
+  return o;
+}
+#endif
 // ---- touch events (include/sc_tick.h "touch events"): the pair events' difference taken over the TOUCHING set.  A second PairEventState;
 // the narrow-phase kernel enters what it decides "not apart" into that state's current table (its <.., Events> instances), the pair
 // events' sweep and finish do the rest.  One narrow-phase launch per tick: `list` (SC_TICK_PAIR_SHAPES) and `touch`

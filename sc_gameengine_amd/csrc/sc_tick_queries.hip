@@ -51,7 +51,7 @@ struct WaveRay { bool valid, hit; float t; uint32_t id, axis, layer; float dir[3
 // SC_TICK_RAY_SHAPES_EXACT: a candidate that passed the slab test against its AABB and whose proxy comes from a typed collider of this
 // context is answered by the shape itself, taken through the entity's world matrix of this tick.  All of it fp32, unfused, left to right;
 // every acceptance is a positive comparison, so a NaN is a miss.  c_k: column k of the matrix, T: its translation, q = o - T.
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+// (dot3: sc_tick_internal.h)
 // what a shape reports: never -0 (the wave's 64-bit min orders distances by their bit patterns)
 __device__ __forceinline__ float notNegative(float t) { return t > 0.0f ? t : 0.0f; }
 
@@ -145,15 +145,129 @@ __device__ __forceinline__ ShapeHit shapeHit(const DeviceState& d, uint32_t e, u
   return h;
 }
 
+// ---- exact collider shapes for capsule sweeps (own spec, include/sc_tick.h "exact shapes for capsule sweeps") ----------------------
+// SC_TICK_SWEEP_SHAPES_EXACT: a candidate whose grown AABB the segment met at t0 and that is refinable the way a member of a touching pair
+// is (fetchMember) is answered by a conservative advancement of the sweeper -- the round (o + dir*t, A = (0, ay, 0), radius) -- towards the
+// collider's shape: gap(t) = sqrt(dist2(t)) - Rs with dist2 from the touching pairs' distance cores, a step of `gap` metres or to the zero
+// of the secant through the last two iterates, whichever is further (gap is convex in t: neither passes the first contact).  The frame or
+// round of the target is built once, outside the step loop; the loop has a fixed trip count.  exhausted: the steps ran out (a hit at the
+// travel reached).
+__device__ __forceinline__ ShapeHit sweepShapeHit(const Member& m, const float o[3], const float dir[3], float far, float ay, float radius, float t0,
+                                                  bool& exhausted)
+{
+  ShapeHit h; h.kind = kShapeMiss; h.t = 0.0f; h.n[0] = 0.0f; h.n[1] = 1.0f; h.n[2] = 0.0f;
+  exhausted = false;
+  const bool box = m.type == kColliderBox;
+  const float A[3] = { 0.0f, ay, 0.0f };
+  const float d1[3] = { A[0] + A[0], A[1] + A[1], A[2] + A[2] };
+  float p2[3] = { 0.0f, 0.0f, 0.0f }, d2[3] = { 0.0f, 0.0f, 0.0f }, ya[3] = { 0.0f, 0.0f, 0.0f }, dy[3] = { 0.0f, 0.0f, 0.0f }, Rs = radius;
+  Frame fr;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { fr.u[k][0] = fr.u[k][1] = fr.u[k][2] = 0.0f; fr.H[k] = 0.0f; }
+  if (box) {
+    fr = frameOf(m);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { ya[k] = dot3(fr.u[k], A); dy[k] = ya[k] + ya[k]; }
+  } else {
+    const Round rt = roundOf(m);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { p2[i] = m.T[i] - rt.A[i]; d2[i] = rt.A[i] + rt.A[i]; }
+    Rs = radius + rt.R;
+  }
+  float t = t0, tp = 0.0f, gp = 0.0f, v[3] = { 0.0f, 0.0f, 0.0f };
+  bool prev = false, met = false;
+#pragma unroll 1
+  for (int it = 0; it < kSweepShapesSteps; ++it) {
+    float c[3], dist2;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c[i] = o[i] + dir[i] * t;
+    if (box) {
+      float w[3], y0[3], z[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) w[i] = c[i] - m.T[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) y0[k] = dot3(fr.u[k], w) - ya[k];
+      const SegBox sb = segBoxCore(y0, dy, fr.H, ay != 0.0f);
+      dist2 = sb.fmin;
+      // the two closest points: the segment's at the minimising parameter, and that point clamped into the box, back in world space
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float y = y0[k] + dy[k] * sb.at;
+        const float lo = (y < -fr.H[k]) ? -fr.H[k] : y;
+        z[k] = (lo > fr.H[k]) ? fr.H[k] : lo;
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float ps = (c[i] - A[i]) + d1[i] * sb.at;
+        const float pt = ((fr.u[0][i] * z[0] + fr.u[1][i] * z[1]) + fr.u[2][i] * z[2]) + m.T[i];
+        v[i] = ps - pt;
+      }
+    } else {
+      float p1[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) p1[i] = c[i] - A[i];
+      const SegSeg ss = segSegCore(p1, d1, p2, d2);
+      dist2 = ss.dist2;
+      v[0] = ss.v[0]; v[1] = ss.v[1]; v[2] = ss.v[2];
+    }
+    if (t == 0.0f && !(dist2 > Rs * Rs)) { h.kind = kShapeHit; return h; }      // inside (the touching pairs' comparison: a NaN is inside)
+    const float g = sqrtf(dist2) - Rs;
+    if (g <= kSweepShapesTol) { met = true; break; }
+    if (far == 0.0f) return h;                                                   // an overlap test: one evaluation
+    float step = g;
+    if (prev) {
+      const float slope = (g - gp) / (t - tp);
+      if (!(slope < 0.0f)) return h;                                             // convex and not approaching: it never arrives
+      const float sec = (-g) / slope;
+      if (sec > step) step = sec;
+    }
+    prev = true; tp = t; gp = g;
+    t = t + step;
+    if (t > far) return h;
+  }
+  exhausted = !met;
+  h.kind = kShapeHit; h.t = t;
+  const float vv = dot3(v, v);
+  if (vv > 0.0f) { const float q = sqrtf(vv); h.n[0] = v[0] / q; h.n[1] = v[1] / q; h.n[2] = v[2] / q; }
+  return h;
+}
+
+// What one sweep's wave counts for scTickGetSweepShapeInfo (wave-uniform).  A box lies in up to four sectors, and in the overflow list
+// besides: the wave remembers the ids it has counted (seen[], its own row of LDS) and counts a box once per sweep.  Beyond kSweepSeenCap
+// counted boxes per sweep nothing more is remembered and a box met again counts again.
+struct SweepTally { uint32_t* seen; uint32_t nSeen, refined, kept, exhausted; };
+enum : uint32_t { kTallyRefined = 1u, kTallyKept = 2u, kTallyExhausted = 4u };
+// every lane of the wave must call; kind 0: this lane has nothing to count
+__device__ __forceinline__ void sweepTally(SweepTally& tl, uint32_t kind, uint32_t id)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  unsigned long long m = ballot64(kind != 0u);
+  while (m) {                                                                      // (wave-uniform)
+    const int src = __ffsll((long long)m) - 1;
+    m &= m - 1ull;
+    const uint32_t bid = __shfl(id, src, 64), bk = __shfl(kind, src, 64);
+    bool dup = false;
+    for (uint32_t k = lane; k < tl.nSeen; k += 64u) dup = dup || tl.seen[k] == bid;
+    if (ballot64(dup)) continue;
+    if (tl.nSeen < kSweepSeenCap) { if (lane == 0) tl.seen[tl.nSeen] = bid; tl.nSeen++; }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    tl.refined += (bk & kTallyRefined) ? 1u : 0u; tl.kept += (bk & kTallyKept) ? 1u : 0u; tl.exhausted += (bk & kTallyExhausted) ? 1u : 0u;
+  }
+}
+
 // The segment o + dir * [0, maxDist] against this tick's records, by a whole wave; fills hit / t / id / axis / layer of `w`.
 // kSweep (capsule sweeps, k_sweep_queries): every candidate box is grown by `grow` per axis before the slab test, and the sector
 // walk reaches `reach` (the sweeper's xz half extent) further on every side.  The ray instance (kSweep false) takes neither and
 // is the routine the ray kernels always had.
 // kExact (the exact-shape instances of the ray kernels): an AABB hit of an own typed collider is refined by shapeHit, lanes keep the
 // normal instead of the face's axis, and the winner's normal travels with the other shuffles into wn[3] (w.axis is not filled).
+// kSweep && kExact (k_sweep_queries_exact): a grown-AABB hit of a refinable member is refined by sweepShapeHit -- ay: the sweeper's half
+// axis, grow[0] its radius -- and every candidate is counted once in `tally`.
 template <bool kSweep, bool kExact = false>
 __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d, const TickParams& p, const float o[3], const float dir[3], float maxDist,
-                                                uint32_t rayMask, uint32_t skipId, const float grow[3], float reach, float* wn = nullptr)
+                                                uint32_t rayMask, uint32_t skipId, const float grow[3], float reach, float* wn = nullptr,
+                                                float ay = 0.0f, SweepTally* tally = nullptr)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const float ex = o[0] + dir[0] * maxDist, ez = o[2] + dir[2] * maxDist;
@@ -161,6 +275,7 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
   // this lane's best so far
   float bt = INFINITY; uint32_t bid = 0xFFFFFFFFu, baxis = 3u, blayer = 0u;
   float bn0 = 0.0f, bn1 = 1.0f, bn2 = 0.0f;
+  uint32_t cKind = 0u, cId = 0u;                        // exact sweeps: what the last consider() leaves for sweepTally
   auto consider = [&](const float4& lo, const float4& hi) {
     const uint32_t lay = __float_as_uint(lo.w);
     // Bullet's needsCollision with the callback's group 0xFFFF: (proxy.group & mask) && (0xFFFF & proxy.mask)
@@ -181,6 +296,21 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
         n[0] = s.axis == 0u ? sgn : 0.0f; n[1] = s.axis == 1u ? sgn : 0.0f; n[2] = s.axis == 2u ? sgn : 0.0f;
       }
       // ... stands for Bounds proxies, a neighbour tile's records and a context without colliders
+      if constexpr (kSweep) {
+        // (... and for a degenerate matrix: the refinability rule of the touching pairs)
+        const Member m = fetchMember(d, id, p.n, p.rankBits);
+        cId = id;
+        if (!m.ok) cKind = kTallyKept;
+        else {
+          bool ranOut;
+          const ShapeHit h = sweepShapeHit(m, o, dir, maxDist, ay, grow[0], s.t, ranOut);
+          cKind = kTallyRefined | (ranOut ? kTallyExhausted : 0u);
+          if (h.kind == kShapeMiss) return;
+          t = h.t; n[0] = h.n[0]; n[1] = h.n[1]; n[2] = h.n[2];
+        }
+        if (t < bt || (t == bt && id < bid)) { bt = t; bid = id; blayer = lay & 0xFFFFu; bn0 = n[0]; bn1 = n[1]; bn2 = n[2]; }
+        return;
+      }
       const uint32_t e = id & 0x00FFFFFFu;
       if (d.colType && (id & 0x7F000000u) == p.rankBits && e < p.n) {
         const uint32_t type = d.colType[e];
@@ -226,14 +356,26 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
         const uint32_t s = gz * p.binSX + gx;
         uint32_t n = d.binCount[s];
         if (n > kBinCap) { n = kBinCap; anyOverflow = true; }
+        if (kSweep && kExact) cKind = 0u;
         if (lane < n) {
           const float4* rec = d.bins + 2u * ((size_t)s * kBinCap + lane);
           consider(rec[0], rec[1]);
         }
+        if constexpr (kSweep && kExact) sweepTally(*tally, cKind, cId);
       }
   }
   const uint32_t nbig = min(d.counters[kCtrPar + 8u * p.parity + kCtrBig], p.bigCap);
-  for (uint32_t b = lane; b < nbig; b += 64u) consider(d.bigList[2u * (size_t)b], d.bigList[2u * (size_t)b + 1u]);
+  if constexpr (kSweep && kExact) {
+    // (the same records in the same lanes; the trip count is the wave's, so that every lane reaches the tally)
+    for (uint32_t b0 = 0; b0 < nbig; b0 += 64u) {
+      const uint32_t b = b0 + lane;
+      cKind = 0u;
+      if (b < nbig) consider(d.bigList[2u * (size_t)b], d.bigList[2u * (size_t)b + 1u]);
+      sweepTally(*tally, cKind, cId);
+    }
+  } else {
+    for (uint32_t b = lane; b < nbig; b += 64u) consider(d.bigList[2u * (size_t)b], d.bigList[2u * (size_t)b + 1u]);
+  }
   // records that found their sector's bin full -- this tile's own boxes and a neighbour's border records (k_border_merge)
   // -- live only in the sector overflow list; they are this tile's to answer for like the records in the bins.  Duplicates
   // of a box that is also binned elsewhere are harmless: the same box gives the same distance and the id breaks the tie.
@@ -241,7 +383,16 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
   //  sector whose counter passed 64.)
   if (anyOverflow) {
     const uint32_t nspill = min(d.counters[kCtrPar + 8u * p.parity + kCtrSpill], p.ovfCap);
-    for (uint32_t e = lane; e < nspill; e += 64u) consider(d.spill[2u * (size_t)e], d.spill[2u * (size_t)e + 1u]);
+    if constexpr (kSweep && kExact) {
+      for (uint32_t e0 = 0; e0 < nspill; e0 += 64u) {
+        const uint32_t e = e0 + lane;
+        cKind = 0u;
+        if (e < nspill) consider(d.spill[2u * (size_t)e], d.spill[2u * (size_t)e + 1u]);
+        sweepTally(*tally, cKind, cId);
+      }
+    } else {
+      for (uint32_t e = lane; e < nspill; e += 64u) consider(d.spill[2u * (size_t)e], d.spill[2u * (size_t)e + 1u]);
+    }
   }
 
   // closest hit of the wave: distances are >= 0, so their bit patterns order like the values
@@ -466,6 +617,52 @@ __global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, co
   if (lane == 0) q.hits[r] = out;
 }
 
+// SC_TICK_SWEEP_SHAPES_EXACT: launched instead of the kernel above, never next to it.  The sweeper is the round (centre, A = (0, hh, 0),
+// radius) in the sense of the touching pairs' roundOf -- not dot(A, A) > 0: a sphere --; the grown-AABB test stays the pre-filter and the
+// winner brings its own normal.  info: the three running words of ScTickSweepShapeInfo, zeroed on the stream before the launch.
+__global__ __launch_bounds__(kTile) void k_sweep_queries_exact(const DeviceState d, const TickParams p, const SweepQueryState q, uint32_t* __restrict__ info)
+{
+  __shared__ uint32_t seen[kTile / 64u][kSweepSeenCap];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
+  if (r >= q.count) return;
+  const float4 a = q.start[r], b = q.end[r];
+  const uint2 f = q.filter[r];
+  const float o[3] = { a.x, a.y, a.z };
+  const float radius = a.w, hh = (b.w > 0.0f) ? b.w : 0.0f;
+  const float grow[3] = { radius, hh + radius, radius };
+  const float ay = (hh * hh > 0.0f) ? hh : 0.0f;       // (dot(A, A) of A = (0, hh, 0) is hh*hh to the bit)
+  const float dv[3] = { b.x - a.x, b.y - a.y, b.z - a.z };
+  const float lenSq = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];
+  float far = 0.0f, dir[3] = { 0.0f, 0.0f, 0.0f };
+  if (lenSq > 1e-6f) {
+    far = sqrtf(lenSq);
+    const float inv = 1.0f / far;
+    dir[0] = dv[0] * inv; dir[1] = dv[1] * inv; dir[2] = dv[2] * inv;
+  }
+  WaveRay w; w.valid = true; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u;
+  float wn[3] = { 0.0f, 1.0f, 0.0f };
+  SweepTally tally; tally.seen = seen[threadIdx.x >> 6]; tally.nSeen = 0u; tally.refined = 0u; tally.kept = 0u; tally.exhausted = 0u;
+  castSegmentWave<true, true>(w, d, p, o, dir, far, f.x, f.y, grow, radius, wn, ay, &tally);
+  SweepHit48 out;
+  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
+  out.position[0] = out.position[1] = out.position[2] = 0.0f;
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;
+  out.layer = 0u; out.travel = 0.0f; out.pad = 0u;
+  if (w.hit) {
+    out.hit = 1u; out.id = w.id; out.layer = w.layer; out.travel = w.t;
+    out.distance = far > 0.0f ? w.t / far : 0.0f;
+    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;
+    out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2];
+  }
+  if (lane == 0) {
+    q.hits[r] = out;
+    if (tally.refined) atomicAdd(&info[0], tally.refined);
+    if (tally.kept) atomicAdd(&info[1], tally.kept);
+    if (tally.exhausted) atomicAdd(&info[2], tally.exhausted);
+  }
+}
+
 // ---- the traffic AI's obstacle ray (src/engine/traffic/sc_traffic_ai.cpp:300-345) --------------------------------------------
 // Every agent of the OnRails tier casts one ray per step from 1.7 m ahead of its origin (0.6 m up) along its heading --
 // forward = normalize(sin(yaw), 0, cos(yaw)) with the yaw's sin / cos as the entity's rotation streams hold them (host libm) --
@@ -654,11 +851,13 @@ void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryS
   else hipLaunchKernelGGL(k_ray_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
-void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, hipStream_t s)
+void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, uint32_t* exactInfo, hipStream_t s)
 {
+  if (exactInfo) hipMemsetAsync(exactInfo, 0, kSweepInfoWords * sizeof(uint32_t), s);      // (an empty batch reports zeros)
   if (!q.count) return;
   const uint32_t perBlock = kTile / 64u;
-  hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  if (exactInfo) hipLaunchKernelGGL(k_sweep_queries_exact, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q, exactInfo);
+  else hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s)

@@ -265,6 +265,26 @@ class WorldTick:
         self._ok(self.lib.scTickGetRayShapes(self.ctx, C.byref(mode)), "scTickGetRayShapes")
         return int(mode.value)
 
+    # ---- exact collider shapes for the capsule sweeps (scTickSetSweepShapes) ----
+    def set_sweep_shapes(self, mode):
+        """capi.SWEEP_SHAPES_EXACT: the runs with capi.SWEEPS answer a candidate whose proxy comes from a typed collider (box, sphere,
+        capsule) by advancing the capsule itself towards the shape itself, through the entity's world matrix of that tick; the grown-AABB
+        test stays the pre-filter.  capi.SWEEP_SHAPES_AABB (the default): the capsule's box against the world AABBs.  A property of the
+        context; costs no learn tick (scTickSetSweepShapes)."""
+        self._ok(self.lib.scTickSetSweepShapes(self.ctx, int(mode)), "scTickSetSweepShapes")
+
+    def sweep_shapes(self):
+        mode = C.c_uint32()
+        self._ok(self.lib.scTickGetSweepShapes(self.ctx, C.byref(mode)), "scTickGetSweepShapes")
+        return int(mode.value)
+
+    def sweep_shape_info(self):
+        """What the last run's sweeps did with their candidates in capi.SWEEP_SHAPES_EXACT mode (scTickGetSweepShapeInfo): a dict with
+        refined, kept_as_boxes, exhausted."""
+        info = capi.SweepShapeInfo()
+        self._ok(self.lib.scTickGetSweepShapeInfo(self.ctx, C.byref(info)), "scTickGetSweepShapeInfo")
+        return {k: int(getattr(info, k)) for k, _ in capi.SweepShapeInfo._fields_ if k != "pad"}
+
     # ---- entity-anchored rays: given in an entity's local frame, resolved on the device every tick ----
     def set_anchored_rays(self, anchor, local_origin, local_dir, max_dist, mask, skip_self=None):
         """Rays in the local frame of the entities `anchor` (dense indices; capi.ANCHOR_NONE: a world-space ray), answered by every run
