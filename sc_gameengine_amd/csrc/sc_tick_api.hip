@@ -848,7 +848,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
   if (flags & SC_TICK_ANCHORED_RAYS) {
-    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), exactRays, c->stream);
+    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), false, exactRays, c->stream);
     else if (flags & SC_TICK_BROADPHASE) launchAnchoredRaySnapshot(ds, p, anchoredFor(c, p.parity), c->stream);
   }
   // Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
@@ -1762,7 +1762,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
   if (pp.flags & SC_TICK_RAYS) launchRayQueries(ds, pp, c->rays, exactRays, ps);   // sees the neighbours' border boxes too
   if (pp.flags & SC_TICK_SWEEPS) launchSweepQueries(ds, pp, c->sweeps, exactSweepInfo(c), ps);   // ... as do the capsule sweeps (exact shapes: as for the rays)
-  if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRaysFromSnapshot(ds, pp, anchoredFor(c, pp.parity), exactRays, ps);   // ... and the anchored rays, as the tick half resolved them
+  if (pp.flags & SC_TICK_ANCHORED_RAYS) launchAnchoredRays(ds, pp, anchoredFor(c, pp.parity), true, exactRays, ps);   // ... and the anchored rays, as the tick half resolved them
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);

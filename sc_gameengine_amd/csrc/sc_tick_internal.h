@@ -340,9 +340,8 @@ struct AnchoredRayState {
   float4* snapOrigin; float4* snapDir; uint32_t* snapSkip;
   uint32_t count;
 };
-void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s);              // resolve + cast
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool fromSnapshot, bool exact, hipStream_t s);   // resolve + cast; fromSnapshot (pair half): cast
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);      // tick half: resolve
-void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s); // pair half: cast
 // ---- pair begin / end events (sc_tick_pair_events.hip; include/sc_tick.h "pair events"): the difference between this tick's pair set and
 // the set of the last tick that ran with SC_TICK_PAIR_EVENTS, formed on the device behind the pair search.  A kernel argument of its own.
 // Two open-addressing tables of 64-bit keys a << 32 | b (0 = empty: a < b rules it out) are used in turn: the one holding the remembered

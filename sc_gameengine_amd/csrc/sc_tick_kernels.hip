@@ -224,38 +224,16 @@ __device__ __forceinline__ BoundsCE paletteBounds(ConstF e)
 
 // computeWorldBoundsSphere + sphereInFrustum (sc_world_partition.cpp:1105-1144).  All six planes
 // are evaluated; OR-ing "d < -radius" equals the reference's early-out (NaN compares false in both).
-__device__ __forceinline__ bool sphereVisible(const Aff& M, const BoundsCE& b, const Frustum6& fr,
-                                              float& c0, float& c1, float& c2)
-{
-  c0 = M.r0[0] * b.cx + M.r0[1] * b.cy + M.r0[2] * b.cz + M.r0[3];
-  c1 = M.r1[0] * b.cx + M.r1[1] * b.cy + M.r1[2] * b.cz + M.r1[3];
-  c2 = M.r2[0] * b.cx + M.r2[1] * b.cy + M.r2[2] * b.cz + M.r2[3];
-  // max of the three column norms (std::max(a,b) == (a<b)?b:a): the correctly rounded square root is monotone and keeps
-  // NaN, so selecting among the SQUARED norms with the same comparisons and taking one root gives the value the
-  // reference gets from three roots (equal roots of unequal squares are the same value either way)
-  const float nx = M.r0[0] * M.r0[0] + M.r1[0] * M.r1[0] + M.r2[0] * M.r2[0];
-  const float ny = M.r0[1] * M.r0[1] + M.r1[1] * M.r1[1] + M.r2[1] * M.r2[1];
-  const float nz = M.r0[2] * M.r0[2] + M.r1[2] * M.r1[2] + M.r2[2] * M.r2[2];
-  const float nyz = (ny < nz) ? nz : ny;
-  const float maxScale = sqrtf((nx < nyz) ? nyz : nx);
-  const float radius = sqrtf(b.ex * b.ex + b.ey * b.ey + b.ez * b.ez) * maxScale;
-  bool out = false;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const float dist = fr.p[k][0] * c0 + fr.p[k][1] * c1 + fr.p[k][2] * c2 + fr.p[k][3];
-    out = out || (dist < -radius);
-  }
-  return !out;
-}
-
-// Same test with the planes read through a uniform pointer into the constant address space: scalar loads at
+// The planes are read through a uniform pointer into the constant address space: scalar loads at
 // the point of use.  The fused kernel uses it so that the 24 coefficients are not held in SGPRs across the tile.
 __device__ __forceinline__ bool sphereVisibleAt(const Aff& M, const BoundsCE& b, ConstF fr)
 {
   const float c0 = M.r0[0] * b.cx + M.r0[1] * b.cy + M.r0[2] * b.cz + M.r0[3];
   const float c1 = M.r1[0] * b.cx + M.r1[1] * b.cy + M.r1[2] * b.cz + M.r1[3];
   const float c2 = M.r2[0] * b.cx + M.r2[1] * b.cy + M.r2[2] * b.cz + M.r2[3];
-  // (one root of the largest squared column norm instead of three roots: see sphereVisible)
+  // max of the three column norms (std::max(a,b) == (a<b)?b:a): the correctly rounded square root is monotone and keeps
+  // NaN, so selecting among the SQUARED norms with the same comparisons and taking one root gives the value the
+  // reference gets from three roots (equal roots of unequal squares are the same value either way)
   const float nx = M.r0[0] * M.r0[0] + M.r1[0] * M.r1[0] + M.r2[0] * M.r2[0];
   const float ny = M.r0[1] * M.r0[1] + M.r1[1] * M.r1[1] + M.r2[1] * M.r2[1];
   const float nz = M.r0[2] * M.r0[2] + M.r1[2] * M.r1[2] + M.r2[2] * M.r2[2];
@@ -288,7 +266,7 @@ __device__ __forceinline__ void worldAabb(const Aff& M, const BoundsCE& b, float
 // world AABB of a typed collider (kColliderBox / Sphere / Capsule), centred on the entity's origin:
 // c_r = M[r,3], h_r = ((|M[r,0]|*ex + |M[r,1]|*ey) + |M[r,2]|*ez) + pad with s = (ex, ey, ez, radius) as DeviceState::colShape holds
 // it; pad = 0 for a box, radius * sqrt(largest squared column norm) for a sphere (the three columns) and a capsule (columns 0
-// and 2: its round part lies in the local xz plane) -- the squared norms and their selection as sphereVisible forms them.
+// and 2: its round part lies in the local xz plane) -- the squared norms and their selection as sphereVisibleAt forms them.
 __device__ __forceinline__ void colliderAabb(const Aff& M, const float4& s, uint32_t type, float mn[3], float mx[3])
 {
   float pad = 0.0f;

@@ -47,6 +47,15 @@ __device__ __forceinline__ Slab rayBox(const float o[3], const float dir[3], flo
 // The result is wave-uniform.  skipId: a box that never answers (0xFFFFFFFF = none) -- an agent's own box for its front ray.
 struct WaveRay { bool valid, hit; float t; uint32_t id, axis, layer; float dir[3]; };
 
+// the outward normal of the axis-aligned face that a segment along `dir` entered through axis a (< 3); selects, not indexed
+// arrays: an index the compiler cannot resolve puts the array in LDS
+__device__ __forceinline__ float3 faceNormal(uint32_t a, const float dir[3])
+{
+  const float da = a == 0u ? dir[0] : (a == 1u ? dir[1] : dir[2]);
+  const float sgn = da > 0.0f ? -1.0f : 1.0f;
+  return make_float3(a == 0u ? sgn : 0.0f, a == 1u ? sgn : 0.0f, a == 2u ? sgn : 0.0f);
+}
+
 // ---- exact collider shapes (own spec, include/sc_tick.h "exact shapes for rays") ---------------------------------------------
 // SC_TICK_RAY_SHAPES_EXACT: a candidate that passed the slab test against its AABB and whose proxy comes from a typed collider of this
 // context is answered by the shape itself, taken through the entity's world matrix of this tick.  All of it fp32, unfused, left to right;
@@ -262,7 +271,7 @@ __device__ __forceinline__ void sweepTally(SweepTally& tl, uint32_t kind, uint32
 // is the routine the ray kernels always had.
 // kExact (the exact-shape instances of the ray kernels): an AABB hit of an own typed collider is refined by shapeHit, lanes keep the
 // normal instead of the face's axis, and the winner's normal travels with the other shuffles into wn[3] (w.axis is not filled).
-// kSweep && kExact (k_sweep_queries_exact): a grown-AABB hit of a refinable member is refined by sweepShapeHit -- ay: the sweeper's half
+// kSweep && kExact (k_sweep_queries<true>): a grown-AABB hit of a refinable member is refined by sweepShapeHit -- ay: the sweeper's half
 // axis, grow[0] its radius -- and every candidate is counted once in `tally`.
 template <bool kSweep, bool kExact = false>
 __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d, const TickParams& p, const float o[3], const float dir[3], float maxDist,
@@ -290,11 +299,7 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
     if (kExact) {
       // the AABB answer, as rayHitOf would report it ...
       float t = s.t, n[3] = { 0.0f, 1.0f, 0.0f };
-      if (s.axis < 3u) {
-        const float da = s.axis == 0u ? dir[0] : (s.axis == 1u ? dir[1] : dir[2]);
-        const float sgn = da > 0.0f ? -1.0f : 1.0f;
-        n[0] = s.axis == 0u ? sgn : 0.0f; n[1] = s.axis == 1u ? sgn : 0.0f; n[2] = s.axis == 2u ? sgn : 0.0f;
-      }
+      if (s.axis < 3u) { const float3 f = faceNormal(s.axis, dir); n[0] = f.x; n[1] = f.y; n[2] = f.z; }
       // ... stands for Bounds proxies, a neighbour tile's records and a context without colliders
       if constexpr (kSweep) {
         // (... and for a degenerate matrix: the refinability rule of the touching pairs)
@@ -431,7 +436,9 @@ __device__ __forceinline__ WaveRay castRayWave(const DeviceState& d, const TickP
 }
 
 // what a ray leaves for the host: RaycastHit{} (sc_physics.h:106-114) unless the wave found a box
-__device__ __forceinline__ RayHit48 rayHitOf(const WaveRay& w, const float o[3])
+// kExact: the winner brought its own normal (wn); otherwise the normal is the entered face's
+template <bool kExact>
+__device__ __forceinline__ RayHit48 rayHitOf(const WaveRay& w, const float o[3], const float wn[3])
 {
   RayHit48 out;
   out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
@@ -441,30 +448,17 @@ __device__ __forceinline__ RayHit48 rayHitOf(const WaveRay& w, const float o[3])
   if (w.hit) {
     out.hit = 1u; out.id = w.id; out.distance = w.t; out.layer = w.layer;
     out.position[0] = o[0] + w.dir[0] * w.t; out.position[1] = o[1] + w.dir[1] * w.t; out.position[2] = o[2] + w.dir[2] * w.t;
-    if (w.axis < 3u) {                                  // the face the ray entered through; a ray starting inside keeps (0,1,0)
-      out.normal[0] = out.normal[1] = out.normal[2] = 0.0f;
-      out.normal[w.axis] = w.dir[w.axis] > 0.0f ? -1.0f : 1.0f;
+    if constexpr (kExact) { out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2]; }
+    else if (w.axis < 3u) {                             // the face the ray entered through; a ray starting inside keeps (0,1,0)
+      const float3 f = faceNormal(w.axis, w.dir);
+      out.normal[0] = f.x; out.normal[1] = f.y; out.normal[2] = f.z;
     }
   }
   return out;
 }
 
-// the exact-shape instances: the winner brings its own normal (wn), everything else as above
-__device__ __forceinline__ RayHit48 rayHitExact(const WaveRay& w, const float o[3], const float wn[3])
-{
-  RayHit48 out;
-  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
-  out.position[0] = out.position[1] = out.position[2] = 0.0f;
-  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;
-  out.layer = 0u; out.pad = 0u; out.pad2 = 0u;
-  if (w.hit) {
-    out.hit = 1u; out.id = w.id; out.distance = w.t; out.layer = w.layer;
-    out.position[0] = o[0] + w.dir[0] * w.t; out.position[1] = o[1] + w.dir[1] * w.t; out.position[2] = o[2] + w.dir[2] * w.t;
-    out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2];
-  }
-  return out;
-}
-
+// kExact (SC_TICK_RAY_SHAPES_EXACT): the instance launched instead of the AABB one, never next to it
+template <bool kExact>
 __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, const TickParams p, const RayQueryState q)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -473,23 +467,9 @@ __global__ __launch_bounds__(kTile) void k_ray_queries(const DeviceState d, cons
   const float4 od = q.origin[r], dm = q.dir[r];
   const float o[3] = { od.x, od.y, od.z };
   const float dv[3] = { dm.x, dm.y, dm.z };
-  const WaveRay w = castRayWave(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu);
-  const RayHit48 out = rayHitOf(w, o);
-  if (lane == 0) q.hits[r] = out;
-}
-
-// SC_TICK_RAY_SHAPES_EXACT: launched instead of the kernel above, never next to it
-__global__ __launch_bounds__(kTile) void k_ray_queries_exact(const DeviceState d, const TickParams p, const RayQueryState q)
-{
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
-  if (r >= q.count) return;
-  const float4 od = q.origin[r], dm = q.dir[r];
-  const float o[3] = { od.x, od.y, od.z };
-  const float dv[3] = { dm.x, dm.y, dm.z };
   float wn[3] = { 0.0f, 1.0f, 0.0f };
-  const WaveRay w = castRayWave<true>(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu, wn);
-  const RayHit48 out = rayHitExact(w, o, wn);
+  const WaveRay w = castRayWave<kExact>(d, p, o, dv, od.w, __float_as_uint(dm.w), 0xFFFFFFFFu, wn);
+  const RayHit48 out = rayHitOf<kExact>(w, o, wn);
   if (lane == 0) q.hits[r] = out;
 }
 
@@ -525,42 +505,30 @@ __device__ __forceinline__ ResolvedRay resolveAnchoredRay(const DeviceState& d, 
   return r;
 }
 
+// ray r as k_anchored_ray_snapshot noted it
+__device__ __forceinline__ ResolvedRay snapshotRay(const AnchoredRayState& q, uint32_t r)
+{
+  const float4 a = q.snapOrigin[r], b = q.snapDir[r];
+  ResolvedRay ray;
+  ray.o[0] = a.x; ray.o[1] = a.y; ray.o[2] = a.z; ray.dv[0] = b.x; ray.dv[1] = b.y; ray.dv[2] = b.z;
+  ray.maxDist = a.w; ray.mask = __float_as_uint(b.w); ray.skipId = q.snapSkip[r];
+  return ray;
+}
+
 // One wave per ray, like k_ray_queries.  The ray index is made scalar, so the ray, its anchor word and the twelve words of the anchor's
 // matrix rows come through the scalar path: one fetch per wave, not one per lane.  kFromSnapshot (the pair half of a split flow): the
-// ray was resolved by k_anchored_ray_snapshot in the tick half and is cast as it stands there.
-template <bool kFromSnapshot>
+// ray was resolved by k_anchored_ray_snapshot in the tick half and is cast as it stands there.  kExact (SC_TICK_RAY_SHAPES_EXACT): as for
+// k_ray_queries; the snapshot holds the resolved ray, and the candidates are refined against the matrices as they stand.
+template <bool kFromSnapshot, bool kExact>
 __global__ __launch_bounds__(kTile) void k_anchored_rays(const DeviceState d, const TickParams p, const AnchoredRayState q)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
   if (r >= q.count) return;
-  ResolvedRay ray;
-  if (kFromSnapshot) {
-    const float4 a = q.snapOrigin[r], b = q.snapDir[r];
-    ray.o[0] = a.x; ray.o[1] = a.y; ray.o[2] = a.z; ray.dv[0] = b.x; ray.dv[1] = b.y; ray.dv[2] = b.z;
-    ray.maxDist = a.w; ray.mask = __float_as_uint(b.w); ray.skipId = q.snapSkip[r];
-  } else ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
-  const WaveRay w = castRayWave(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId);
-  const RayHit48 out = rayHitOf(w, ray.o);
-  if (lane == 0) q.hits[r] = out;
-}
-
-// SC_TICK_RAY_SHAPES_EXACT (the snapshot of a split flow holds the resolved ray; the candidates are refined against the matrices as they stand)
-template <bool kFromSnapshot>
-__global__ __launch_bounds__(kTile) void k_anchored_rays_exact(const DeviceState d, const TickParams p, const AnchoredRayState q)
-{
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
-  if (r >= q.count) return;
-  ResolvedRay ray;
-  if (kFromSnapshot) {
-    const float4 a = q.snapOrigin[r], b = q.snapDir[r];
-    ray.o[0] = a.x; ray.o[1] = a.y; ray.o[2] = a.z; ray.dv[0] = b.x; ray.dv[1] = b.y; ray.dv[2] = b.z;
-    ray.maxDist = a.w; ray.mask = __float_as_uint(b.w); ray.skipId = q.snapSkip[r];
-  } else ray = resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
+  const ResolvedRay ray = kFromSnapshot ? snapshotRay(q, r) : resolveAnchoredRay(d, p, q.origin[r], q.dir[r], q.anchor[r]);
   float wn[3] = { 0.0f, 1.0f, 0.0f };
-  const WaveRay w = castRayWave<true>(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId, wn);
-  const RayHit48 out = rayHitExact(w, ray.o, wn);
+  const WaveRay w = castRayWave<kExact>(d, p, ray.o, ray.dv, ray.maxDist, ray.mask, ray.skipId, wn);
+  const RayHit48 out = rayHitOf<kExact>(w, ray.o, wn);
   if (lane == 0) q.hits[r] = out;
 }
 
@@ -579,50 +547,15 @@ __global__ __launch_bounds__(kTile) void k_anchored_ray_snapshot(const DeviceSta
 // The sweeper is the upright capsule's own AABB, e = (radius, max(0, halfHeight) + radius, radius); a box swept against a box is the
 // segment against the box grown by e, so the test is rayBox again.  A segment of |d|^2 <= 1e-6 is an overlap test at `start`: direction
 // (0, 0, 0) and length 0 send every axis of the slab test through its containment branch.  One wave per sweep.
-__global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, const TickParams p, const SweepQueryState q)
+// kExact (SC_TICK_SWEEP_SHAPES_EXACT; the instance launched instead of the AABB one, never next to it): the sweeper is the round (centre,
+// A = (0, ay, 0), radius) in the sense of the touching pairs' roundOf -- not dot(A, A) > 0: a sphere --; the grown-AABB test stays the
+// pre-filter and the winner brings its own normal.
+// info (kExact): the three running words of ScTickSweepShapeInfo, zeroed on the stream before the launch
+// (Set-up and hit writer are written out in the one body, the face normal by its own selects and the cast as two calls: handing this
+//  kernel's local arrays to one more helper changes the order they become registers in -- DESIGN 11.20.)
+template <bool kExact>
+__global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, const TickParams p, const SweepQueryState q, uint32_t* __restrict__ info)
 {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
-  if (r >= q.count) return;
-  const float4 a = q.start[r], b = q.end[r];
-  const uint2 f = q.filter[r];
-  const float o[3] = { a.x, a.y, a.z };
-  const float radius = a.w, hh = (b.w > 0.0f) ? b.w : 0.0f;
-  const float grow[3] = { radius, hh + radius, radius };
-  const float dv[3] = { b.x - a.x, b.y - a.y, b.z - a.z };
-  const float lenSq = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];
-  float far = 0.0f, dir[3] = { 0.0f, 0.0f, 0.0f };
-  if (lenSq > 1e-6f) {
-    far = sqrtf(lenSq);
-    const float inv = 1.0f / far;
-    dir[0] = dv[0] * inv; dir[1] = dv[1] * inv; dir[2] = dv[2] * inv;
-  }
-  WaveRay w; w.valid = true; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u;
-  castSegmentWave<true>(w, d, p, o, dir, far, f.x, f.y, grow, radius);
-  SweepHit48 out;
-  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
-  out.position[0] = out.position[1] = out.position[2] = 0.0f;
-  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;           // SweepHit{} (sc_physics.h:116)
-  out.layer = 0u; out.travel = 0.0f; out.pad = 0u;
-  if (w.hit) {
-    out.hit = 1u; out.id = w.id; out.layer = w.layer; out.travel = w.t;
-    out.distance = far > 0.0f ? w.t / far : 0.0f;                              // the hit FRACTION (m_closestHitFraction, :801)
-    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;   // the capsule's centre
-    if (w.axis < 3u) {                                  // the face entered; a sweep that starts in overlap keeps (0,1,0)
-      const float dn = w.axis == 0u ? dir[0] : (w.axis == 1u ? dir[1] : dir[2]);
-      const float sgn = dn > 0.0f ? -1.0f : 1.0f;
-      out.normal[0] = w.axis == 0u ? sgn : 0.0f; out.normal[1] = w.axis == 1u ? sgn : 0.0f; out.normal[2] = w.axis == 2u ? sgn : 0.0f;
-    }
-  }
-  if (lane == 0) q.hits[r] = out;
-}
-
-// SC_TICK_SWEEP_SHAPES_EXACT: launched instead of the kernel above, never next to it.  The sweeper is the round (centre, A = (0, hh, 0),
-// radius) in the sense of the touching pairs' roundOf -- not dot(A, A) > 0: a sphere --; the grown-AABB test stays the pre-filter and the
-// winner brings its own normal.  info: the three running words of ScTickSweepShapeInfo, zeroed on the stream before the launch.
-__global__ __launch_bounds__(kTile) void k_sweep_queries_exact(const DeviceState d, const TickParams p, const SweepQueryState q, uint32_t* __restrict__ info)
-{
-  __shared__ uint32_t seen[kTile / 64u][kSweepSeenCap];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6);
   if (r >= q.count) return;
@@ -642,24 +575,37 @@ __global__ __launch_bounds__(kTile) void k_sweep_queries_exact(const DeviceState
   }
   WaveRay w; w.valid = true; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u;
   float wn[3] = { 0.0f, 1.0f, 0.0f };
-  SweepTally tally; tally.seen = seen[threadIdx.x >> 6]; tally.nSeen = 0u; tally.refined = 0u; tally.kept = 0u; tally.exhausted = 0u;
-  castSegmentWave<true, true>(w, d, p, o, dir, far, f.x, f.y, grow, radius, wn, ay, &tally);
+  uint32_t* seenRow = nullptr;
+  if constexpr (kExact) {
+    __shared__ uint32_t seen[kTile / 64u][kSweepSeenCap];
+    seenRow = seen[threadIdx.x >> 6];
+  }
+  SweepTally tally; tally.seen = seenRow; tally.nSeen = 0u; tally.refined = 0u; tally.kept = 0u; tally.exhausted = 0u;
+  if constexpr (kExact) castSegmentWave<true, true>(w, d, p, o, dir, far, f.x, f.y, grow, radius, wn, ay, &tally);
+  else castSegmentWave<true>(w, d, p, o, dir, far, f.x, f.y, grow, radius);
   SweepHit48 out;
   out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
   out.position[0] = out.position[1] = out.position[2] = 0.0f;
-  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;           // SweepHit{} (sc_physics.h:116)
   out.layer = 0u; out.travel = 0.0f; out.pad = 0u;
   if (w.hit) {
     out.hit = 1u; out.id = w.id; out.layer = w.layer; out.travel = w.t;
-    out.distance = far > 0.0f ? w.t / far : 0.0f;
-    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;
-    out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2];
+    out.distance = far > 0.0f ? w.t / far : 0.0f;                              // the hit FRACTION (m_closestHitFraction, :801)
+    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;   // the capsule's centre
+    if constexpr (kExact) { out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2]; }
+    else if (w.axis < 3u) {                             // the face entered; a sweep that starts in overlap keeps (0,1,0)
+      const float dn = w.axis == 0u ? dir[0] : (w.axis == 1u ? dir[1] : dir[2]);
+      const float sgn = dn > 0.0f ? -1.0f : 1.0f;
+      out.normal[0] = w.axis == 0u ? sgn : 0.0f; out.normal[1] = w.axis == 1u ? sgn : 0.0f; out.normal[2] = w.axis == 2u ? sgn : 0.0f;
+    }
   }
   if (lane == 0) {
     q.hits[r] = out;
-    if (tally.refined) atomicAdd(&info[0], tally.refined);
-    if (tally.kept) atomicAdd(&info[1], tally.kept);
-    if (tally.exhausted) atomicAdd(&info[2], tally.exhausted);
+    if constexpr (kExact) {
+      if (tally.refined) atomicAdd(&info[0], tally.refined);
+      if (tally.kept) atomicAdd(&info[1], tally.kept);
+      if (tally.exhausted) atomicAdd(&info[2], tally.exhausted);
+    }
   }
 }
 
@@ -671,24 +617,13 @@ __global__ __launch_bounds__(kTile) void k_sweep_queries_exact(const DeviceState
 // of this tick's bins (own spec: Bullet is absent); the agent's own box never answers (Bullet does not report a convex shape a
 // ray starts inside, and the reference discards a self hit: :322-325, :336).  The brake waits in aBrake[] for the on-rails
 // step that produces the next frame.
+//
+// The OnRails agents of this tick, listed.  kWithRays (tiled world, in-order step): the rays are cast in the PAIR half, behind the border
+// merge, so that an agent near a tile edge sees the neighbour tile's boxes too (the halo section of the border messages puts them in
+// the ring bins).  The tick half only lists the agents and notes each one's ray as it stands -- the frame producer fused into the
+// end-of-tick kernel moves the agents on before the pair half runs.
+template <bool kWithRays>
 __global__ __launch_bounds__(kTile) void k_list_onrails_agents(const DeviceState d, uint32_t n)
-{
-  const uint32_t i = blockIdx.x * kTile + threadIdx.x;
-  const bool agent = i < n && d.moverKind[i] == kMoverTraffic && d.aMode[i] == kTierOnRails;
-  const unsigned long long m = ballot64(agent);
-  if (!m) return;
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t base = 0;
-  if (lane == 0) base = atomicAdd(d.agentCount, (uint32_t)__popcll(m));
-  base = __shfl(base, 0, 64);
-  if (agent) d.agentList[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
-}
-
-// Tiled world, in-order step: the rays are cast in the PAIR half, behind the border merge, so that an agent near a tile edge sees the
-// neighbour tile's boxes too (the halo section of the border messages puts them in the ring bins).  The tick half only lists the agents
-// and notes each one's ray as it stands -- the frame producer fused into the end-of-tick kernel moves the agents on before the pair
-// half runs.  Same arithmetic as k_agent_front_rays.
-__global__ __launch_bounds__(kTile) void k_list_onrails_agents_with_rays(const DeviceState d, uint32_t n)
 {
   const uint32_t i = blockIdx.x * kTile + threadIdx.x;
   const bool agent = i < n && d.moverKind[i] == kMoverTraffic && d.aMode[i] == kTierOnRails;
@@ -701,41 +636,12 @@ __global__ __launch_bounds__(kTile) void k_list_onrails_agents_with_rays(const D
   if (agent) {
     const uint32_t k = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     d.agentList[k] = i;
-    float forward[3] = { d.rsy[i], 0.0f, d.rcy[i] };
-    const float len = sqrtf(forward[0] * forward[0] + forward[1] * forward[1] + forward[2] * forward[2]);
-    if (len > 1e-6f) { const float inv = 1.0f / len; forward[0] *= inv; forward[1] *= inv; forward[2] *= inv; }
-    d.agentRays[2u * k] = make_float4(d.px[i] + forward[0] * 1.7f, d.py[i] + 0.6f, d.pz[i] + forward[2] * 1.7f, d.aRayLen[i]);
-    d.agentRays[2u * k + 1u] = make_float4(forward[0], forward[2], d.aSafe[i], 0.0f);
-  }
-}
-
-__global__ __launch_bounds__(kTile) void k_agent_front_rays_from_snapshot(const DeviceState d, const TickParams p)
-{
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t count = *d.agentCount;
-  const uint32_t waves = gridDim.x * (kTile / 64u);
-  for (uint32_t k = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6); k < count; k += waves) {
-    const uint32_t i = d.agentList[k];
-    const float4 a = d.agentRays[2u * k], b = d.agentRays[2u * k + 1u];
-    const float origin[3] = { a.x, a.y, a.z }, forward[3] = { b.x, 0.0f, b.y };
-    const float rayLen = a.w, safe = b.z;
-    const WaveRay w = castRayWave(d, p, origin, forward, rayLen, 1u, i | p.rankBits);
-    float brake = 0.0f;
-    if (w.hit && safe > 1e-3f && w.t < safe) {
-      const float v = (safe - w.t) / safe;
-      const float m = (1.0f < v) ? 1.0f : v;
-      brake = (0.0f < m) ? m : 0.0f;
-    }
-    if (lane == 0) {
-      d.aBrake[i] = brake;
-      d.aHitDist[i] = w.hit ? w.t : rayLen;
-      uint32_t kind = 0u;
-      if (w.hit) {
-        const bool own = (w.id & 0x7F000000u) == p.rankBits;
-        const uint32_t mk = own ? d.moverKind[w.id & 0x00FFFFFFu] : 0u;
-        kind = own ? ((mk == 1u || mk == kMoverTraffic) ? 2u : 3u) : ((w.layer & 1u) ? 2u : 3u);
-      }
-      d.aHitType[i] = kind;
+    if constexpr (kWithRays) {
+      float forward[3] = { d.rsy[i], 0.0f, d.rcy[i] };               // (the arithmetic of k_agent_front_rays<false>, where the citations are)
+      const float len = sqrtf(forward[0] * forward[0] + forward[1] * forward[1] + forward[2] * forward[2]);
+      if (len > 1e-6f) { const float inv = 1.0f / len; forward[0] *= inv; forward[1] *= inv; forward[2] *= inv; }
+      d.agentRays[2u * k] = make_float4(d.px[i] + forward[0] * 1.7f, d.py[i] + 0.6f, d.pz[i] + forward[2] * 1.7f, d.aRayLen[i]);
+      d.agentRays[2u * k + 1u] = make_float4(forward[0], forward[2], d.aSafe[i], 0.0f);
     }
   }
 }
@@ -751,6 +657,30 @@ __global__ __launch_bounds__(kTile) void k_fill_sensors(const DeviceState d, uin
 //  vehicle by its mover kind (a traffic agent or a SynthWorld vehicle: what carries a VehicleComponent, :327), World otherwise;
 //  a box that arrived from a neighbour tile has no mover kind here: Vehicle when its group has the dynamic bit; without a hit the
 //  ray's length and None)
+// What agent i's ray leaves: the brake for the on-rails step, the hit's distance and kind for the host.  Every lane calls; lane 0 writes.
+__device__ __forceinline__ void writeAgentSensor(const DeviceState& d, const TickParams& p, uint32_t i, const WaveRay& w, float rayLen, float safe, uint32_t lane)
+{
+  float brake = 0.0f;
+  if (w.hit && safe > 1e-3f && w.t < safe) {
+    const float v = (safe - w.t) / safe;                            // clamp01 = std::max(0, std::min(v, 1)), :16-24
+    const float m = (1.0f < v) ? 1.0f : v;
+    brake = (0.0f < m) ? m : 0.0f;
+  }
+  if (lane == 0) {
+    d.aBrake[i] = brake;
+    d.aHitDist[i] = w.hit ? w.t : rayLen;                           // :319-322, :341-345
+    uint32_t kind = 0u;
+    if (w.hit) {
+      const bool own = (w.id & 0x7F000000u) == p.rankBits;
+      const uint32_t mk = own ? d.moverKind[w.id & 0x00FFFFFFu] : 0u;
+      kind = own ? ((mk == 1u || mk == kMoverTraffic) ? 2u : 3u) : ((w.layer & 1u) ? 2u : 3u);
+    }
+    d.aHitType[i] = kind;
+  }
+}
+
+// A wave per agent of the list.  kFromSnapshot: the pair half casts the rays that k_list_onrails_agents<true> noted in the tick half.
+template <bool kFromSnapshot>
 __global__ __launch_bounds__(kTile) void k_agent_front_rays(const DeviceState d, const TickParams p)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -758,29 +688,20 @@ __global__ __launch_bounds__(kTile) void k_agent_front_rays(const DeviceState d,
   const uint32_t waves = gridDim.x * (kTile / 64u);
   for (uint32_t k = blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6); k < count; k += waves) {
     const uint32_t i = d.agentList[k];
-    float forward[3] = { d.rsy[i], 0.0f, d.rcy[i] };                 // { sin(currentYaw), 0, cos(currentYaw) }, :304
-    const float len = sqrtf(forward[0] * forward[0] + forward[1] * forward[1] + forward[2] * forward[2]);      // normalize3, :38-48
-    if (len > 1e-6f) { const float inv = 1.0f / len; forward[0] *= inv; forward[1] *= inv; forward[2] *= inv; }
-    const float origin[3] = { d.px[i] + forward[0] * 1.7f, d.py[i] + 0.6f, d.pz[i] + forward[2] * 1.7f };       // :311-315
-    const float rayLen = d.aRayLen[i], safe = d.aSafe[i];            // :306-308
+    float origin[3], forward[3], rayLen, safe;
+    if constexpr (kFromSnapshot) {
+      const float4 a = d.agentRays[2u * k], b = d.agentRays[2u * k + 1u];
+      origin[0] = a.x; origin[1] = a.y; origin[2] = a.z; forward[0] = b.x; forward[1] = 0.0f; forward[2] = b.y;
+      rayLen = a.w; safe = b.z;
+    } else {
+      forward[0] = d.rsy[i]; forward[1] = 0.0f; forward[2] = d.rcy[i];                                         // { sin(currentYaw), 0, cos(currentYaw) }, :304
+      const float len = sqrtf(forward[0] * forward[0] + forward[1] * forward[1] + forward[2] * forward[2]);      // normalize3, :38-48
+      if (len > 1e-6f) { const float inv = 1.0f / len; forward[0] *= inv; forward[1] *= inv; forward[2] *= inv; }
+      origin[0] = d.px[i] + forward[0] * 1.7f; origin[1] = d.py[i] + 0.6f; origin[2] = d.pz[i] + forward[2] * 1.7f;   // :311-315
+      rayLen = d.aRayLen[i]; safe = d.aSafe[i];                       // :306-308
+    }
     const WaveRay w = castRayWave(d, p, origin, forward, rayLen, 1u, i | p.rankBits);
-    float brake = 0.0f;
-    if (w.hit && safe > 1e-3f && w.t < safe) {
-      const float v = (safe - w.t) / safe;                            // clamp01 = std::max(0, std::min(v, 1)), :16-24
-      const float m = (1.0f < v) ? 1.0f : v;
-      brake = (0.0f < m) ? m : 0.0f;
-    }
-    if (lane == 0) {
-      d.aBrake[i] = brake;
-      d.aHitDist[i] = w.hit ? w.t : rayLen;                           // :319-322, :341-345
-      uint32_t kind = 0u;
-      if (w.hit) {
-        const bool own = (w.id & 0x7F000000u) == p.rankBits;
-        const uint32_t mk = own ? d.moverKind[w.id & 0x00FFFFFFu] : 0u;
-        kind = own ? ((mk == 1u || mk == kMoverTraffic) ? 2u : 3u) : ((w.layer & 1u) ? 2u : 3u);
-      }
-      d.aHitType[i] = kind;
-    }
+    writeAgentSensor(d, p, i, w, rayLen, safe, lane);
   }
 }
 
@@ -825,61 +746,53 @@ void launchAgentFrontRays(const DeviceState& d, const TickParams& p, hipStream_t
 {
   if (!p.n || !d.aLane || !d.aBrake) return;
   hipMemsetAsync(d.agentCount, 0, sizeof(uint32_t), s);
-  hipLaunchKernelGGL(k_list_onrails_agents, dim3((p.n + kTile - 1) / kTile), dim3(kTile), 0, s, d, p.n);
+  hipLaunchKernelGGL(k_list_onrails_agents<false>, dim3((p.n + kTile - 1) / kTile), dim3(kTile), 0, s, d, p.n);
   const uint32_t blocks = std::min((p.n + 3u) / 4u, 8192u);          // (a wave per agent, wave-strided over the list the kernel above wrote)
-  hipLaunchKernelGGL(k_agent_front_rays, dim3(std::max(blocks, 1u)), dim3(kTile), 0, s, d, p);
+  hipLaunchKernelGGL(k_agent_front_rays<false>, dim3(std::max(blocks, 1u)), dim3(kTile), 0, s, d, p);
 }
 
 void launchAgentRaySnapshot(const DeviceState& d, const TickParams& p, hipStream_t s)
 {
   if (!p.n || !d.aLane || !d.aBrake || !d.agentRays) return;
   hipMemsetAsync(d.agentCount, 0, sizeof(uint32_t), s);
-  hipLaunchKernelGGL(k_list_onrails_agents_with_rays, dim3((p.n + kTile - 1) / kTile), dim3(kTile), 0, s, d, p.n);
+  hipLaunchKernelGGL(k_list_onrails_agents<true>, dim3((p.n + kTile - 1) / kTile), dim3(kTile), 0, s, d, p.n);
 }
 void launchAgentFrontRaysFromSnapshot(const DeviceState& d, const TickParams& p, hipStream_t s)
 {
   if (!p.n || !d.aLane || !d.aBrake || !d.agentRays) return;
   const uint32_t blocks = std::min((p.n + 3u) / 4u, 8192u);
-  hipLaunchKernelGGL(k_agent_front_rays_from_snapshot, dim3(std::max(blocks, 1u)), dim3(kTile), 0, s, d, p);
+  hipLaunchKernelGGL(k_agent_front_rays<true>, dim3(std::max(blocks, 1u)), dim3(kTile), 0, s, d, p);
+}
+
+// a wave per query, kTile / 64 queries a workgroup; an empty batch launches nothing
+template <typename... Params, typename... Args>
+static void launchWavePerQuery(void (*kernel)(Params...), uint32_t count, hipStream_t s, const Args&... args)
+{
+  const uint32_t perBlock = kTile / 64u;
+  if (count) hipLaunchKernelGGL(kernel, dim3((count + perBlock - 1) / perBlock), dim3(kTile), 0, s, args...);
 }
 
 void launchRayQueries(const DeviceState& d, const TickParams& p, const RayQueryState& q, bool exact, hipStream_t s)
 {
-  if (!q.count) return;
-  const uint32_t perBlock = kTile / 64u;
-  if (exact) hipLaunchKernelGGL(k_ray_queries_exact, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
-  else hipLaunchKernelGGL(k_ray_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  launchWavePerQuery(exact ? k_ray_queries<true> : k_ray_queries<false>, q.count, s, d, p, q);
 }
 
 void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, uint32_t* exactInfo, hipStream_t s)
 {
   if (exactInfo) hipMemsetAsync(exactInfo, 0, kSweepInfoWords * sizeof(uint32_t), s);      // (an empty batch reports zeros)
-  if (!q.count) return;
-  const uint32_t perBlock = kTile / 64u;
-  if (exactInfo) hipLaunchKernelGGL(k_sweep_queries_exact, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q, exactInfo);
-  else hipLaunchKernelGGL(k_sweep_queries, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  launchWavePerQuery(exactInfo ? k_sweep_queries<true> : k_sweep_queries<false>, q.count, s, d, p, q, exactInfo);
 }
 
-void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s)
+void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool fromSnapshot, bool exact, hipStream_t s)
 {
-  if (!q.count) return;
-  const uint32_t perBlock = kTile / 64u;
-  if (exact) hipLaunchKernelGGL(k_anchored_rays_exact<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
-  else hipLaunchKernelGGL(k_anchored_rays<false>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
+  launchWavePerQuery(fromSnapshot ? (exact ? k_anchored_rays<true, true> : k_anchored_rays<true, false>)
+                                  : (exact ? k_anchored_rays<false, true> : k_anchored_rays<false, false>), q.count, s, d, p, q);
 }
 
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s)
 {
   if (!q.count) return;
   hipLaunchKernelGGL(k_anchored_ray_snapshot, dim3((q.count + kTile - 1) / kTile), dim3(kTile), 0, s, d, p, q);
-}
-
-void launchAnchoredRaysFromSnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool exact, hipStream_t s)
-{
-  if (!q.count) return;
-  const uint32_t perBlock = kTile / 64u;
-  if (exact) hipLaunchKernelGGL(k_anchored_rays_exact<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
-  else hipLaunchKernelGGL(k_anchored_rays<true>, dim3((q.count + perBlock - 1) / perBlock), dim3(kTile), 0, s, d, p, q);
 }
 
 } // namespace sctick

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What SC_TICK_SWEEP_SHAPES_EXACT costs: one leg of the comparison per process, meant to run under
-rocprofv3 --kernel-trace --stats, whose kernel table gives k_sweep_queries / k_sweep_queries_exact in microseconds per launch.
+rocprofv3 --kernel-trace --stats, whose kernel table gives k_sweep_queries<false> / k_sweep_queries<true> in microseconds per launch.
 
     SC_TICK_LIB=<libsc_tick.so of the build under test> python tools/sweep_shapes_cost.py --mode aabb|exact [--ticks 200]
 
