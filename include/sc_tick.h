@@ -885,8 +885,8 @@ int scTickReadPairEvents(ScTickContext* ctx, uint32_t* begun2, uint32_t begun_ca
  * The pair search reports pairs of WORLD AABBs: a 4.4 m x 2 m vehicle box yawed by 45 degrees is a 4.5 m square to it, and two cars
  * passing in neighbouring lanes are a pair.  What Bullet's narrow phase answers in the reference (behind sc_physics.cpp:218-225) is whether
  * the shapes themselves touch.  A run with SC_TICK_PAIR_SHAPES also lists the pairs of this tick's pair list whose collider shapes
- * (scTickUploadColliders: BOX, SPHERE, CAPSULE) overlap, taken through the members' world matrices of this tick.  The result is boolean:
- * no contact point, normal or depth.  This build's OWN SPEC, like the exact shapes for rays, whose frame conventions it shares.  All
+ * (scTickUploadColliders: BOX, SPHERE, CAPSULE) overlap, taken through the members' world matrices of this tick.  The list is boolean:
+ * contact point, normal and depth are the "pair contacts" below, opt-in.  This build's OWN SPEC, like the exact shapes for rays, whose frame conventions it shares.  All
  * arithmetic is fp32, unfused, left to right, with correctly rounded / and sqrt; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z;
  * clamp01(x) = (c < 1) ? c : 1 with c = (x > 0) ? x : 0 (a NaN is 0).
  *   scTickSetPairShapes(max_touching) enables the pass and sizes its list (0 switches it off and frees the buffers).
@@ -961,6 +961,104 @@ int scTickSetPairShapes(ScTickContext* ctx, uint32_t max_touching);   /* 0 switc
 /* pairs2: [capacity][2] (a, b), may be NULL with capacity 0.  Synchronises; copies the 24 bytes of `info` and
  * min(touching, max_touching, capacity) pairs, nothing else. */
 int scTickReadPairShapes(ScTickContext* ctx, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info);
+
+/* ---- pair contacts: point, normal and depth of every touching pair ----
+ * The touching list is boolean.  A host that pushes a character out of a wall, places a decal or feeds a solver needs what Bullet's narrow
+ * phase hands the reference with the pair (sc_physics.cpp:218-225): where the shapes meet, in which direction, how deep.  While pair
+ * contacts are enabled, every run with SC_TICK_PAIR_SHAPES also writes one ScTickPairContact per entry of the touching list: record i
+ * belongs to entry i of the list scTickReadPairShapes returns for the same tick.  There is no run flag of its own.  This build's OWN SPEC,
+ * over the "touching pairs" text above: the same fp32 arithmetic (unfused, left to right, correctly rounded / and sqrt), the same dot and
+ * clamp01, the same REFINABLE rule, the same SPHERE / CAPSULE (A, R) and BOX (u_k, H_k, T) construction, the same routines 1 - 3 with
+ * their intermediate values.  sign(x) = (x < 0) ? -1 : +1 (so sign(0) = sign(NaN) = +1); clamp(x, h) = (c > h) ? h : c with
+ * c = (x < -h) ? -h : x; a sum over three axes of a frame is (x_0*u_0 + x_1*u_1) + x_2*u_2 per component, and "the world image" of frame
+ * coordinates x is T + that sum.
+ *   normal  a unit vector from member a to member b of the listed pair (a < b as listed);
+ *   depth   >= 0: how far b must move along normal for the two features to just touch;
+ *   point   on the contact line (through the closest feature points, along normal): the middle of the stretch of that line that lies
+ *           in both shapes -- the midpoint between the two surfaces unless one shape reaches right through the other;
+ *   kind    which routine answered, SC_TICK_CONTACT_*, with the DEEP and DEGENERATE bits.
+ * NOT REFINED: a pair with a member that is not refinable (kept_as_boxes) gets SC_TICK_CONTACT_NONE and all floats 0.
+ * 1. ROUND - ROUND (kind ROUND_ROUND): p1, d1, p2, d2, s, t, v as in routine 1; d2v = dot(v, v); Pa = p1 + d1*s.
+ *      d2v > 0:  dist = sqrt(d2v); depth = (Ra + Rb) - dist; normal = (-v) / dist per component.  On the line Pa + normal*x, a is
+ *                [-Ra, Ra] and b is [dist - Rb, dist + Rb]:  far = dist + Rb; hi = (far < Ra) ? far : Ra;  near = dist - Rb;
+ *                lo = (near < -Ra) ? -Ra : near;  mid = (lo + hi) * 0.5;  point = Pa + normal*mid per component.
+ *      otherwise (coincident centre lines, or a NaN): DEGENERATE; normal = (0, 1, 0); depth = Ra + Rb; point = Pa.
+ * 2. ROUND - BOX (kind ROUND_BOX): y0, dy, F and fmin as in routine 2, and `at`, the parameter at which fmin was found: 0 for F(0), and
+ *      each later candidate (F(1), then per interval F(ts) and F(hi), in that order) replaces it only when strictly smaller.
+ *      y_k = y0_k + dy_k*at; q_k = clamp(y_k, H_k); m_k = H_k - |y_k|; k' = the first k with the smallest m_k (strict <);
+ *      sg = sign(y_k'); dist = sqrt(fmin); e_k = (y_k - q_k) / dist; ell_k = (H_k + H_k) / |e_k|; l = the least ell_k (ell_0, then each
+ *      later one when strictly smaller).  On the line y + nBox*x the round is [-R, R].
+ *      fmin > 0 (shallow): nb_k = e_k; depth = R - dist.  The box is [-(dist + l), -dist]:  far = dist + l;
+ *                hi = (far < R) ? far : R;  mid = -((dist + hi) * 0.5).
+ *      otherwise (DEEP: the centre-line point is inside the box): nb_k = (k == k') ? sg : 0;
+ *                e0 = sg*y0_k'; e1 = sg*(y0_k' + dy_k'); low = (e1 < e0) ? e1 : e0; depth = R + (H_k' - low): the overlap of the whole
+ *                round along that face's normal (a sphere: low = |y_k'|, so depth = R + m_k').  The box is [m_k' - 2H_k', m_k']:
+ *                back = m_k' - (H_k' + H_k'); lo = (back < -R) ? -R : back; hi = (m_k' < R) ? m_k' : R; mid = (lo + hi) * 0.5.
+ *      nBox = the sum of nb_k u_k; point = (the world image of y) + nBox*mid per component; normal = -nBox when the round is a, else
+ *      nBox.
+ * 3. BOX - BOX: R_ij, Q_ij, t_i as in routine 3, and the fifteen axes in its order.  Overlap o and signed projection tl per axis:
+ *        a's axis i:    o = (Ha_i + ((Hb_0*Q_i0 + Hb_1*Q_i1) + Hb_2*Q_i2)) - |t_i|;  tl = t_i;  L = ua_i.
+ *        b's axis j:    tl = (t_0*R_0j + t_1*R_1j) + t_2*R_2j;  o = (((Ha_0*Q_0j + Ha_1*Q_1j) + Ha_2*Q_2j) + Hb_j) - |tl|;  L = ub_j.
+ *        ua_i x ub_j:   l2 = 1 - R_ij*R_ij; skipped when l2 < SC_TICK_PAIR_CONTACTS_EDGE_EPS (parallel edges add nothing to the face axes);
+ *                       tl = t_i2*R_i1j - t_i1*R_i2j;  o = (((Ha_i1*Q_i2j + Ha_i2*Q_i1j) + (Hb_j1*Q_ij2 + Hb_j2*Q_ij1)) - |tl|) / sqrt(l2);
+ *                       L = R_i1j*ua_i2 - R_i2j*ua_i1 per component.
+ *      The first axis starts as the best; a later one replaces it only when its o is strictly smaller: ties stay with the earlier axis,
+ *      faces come before edges.  depth = (o < 0) ? 0 : o (a pair inside the separating-axis epsilon); sg = sign(tl);
+ *      normal = sg * L for a face axis, sg * (L / sqrt(dot(L, L))) for an edge axis.  h = depth * 0.5.
+ *      BOX_FACE_A (a's axis i):  g_j = sign(dot(normal, ub_j)) * Hb_j;  p = Tb - the sum of g_j ub_j  (b's vertex furthest against the
+ *                       normal);  r = p - Ta;  x_k = dot(r, ua_k), and for the two k other than i x_k = clamp(x_k, Ha_k);
+ *                       point = (the world image of x in a's frame) + normal*h.
+ *      BOX_FACE_B (b's axis j):  g_k = -sign(dot(normal, ua_k)) * Ha_k;  p = Ta - the sum of g_k ua_k  (a's vertex furthest along the
+ *                       normal);  r = p - Tb;  x_k = dot(r, ub_k), clamped for the two k other than j;
+ *                       point = (the world image of x in b's frame) - normal*h.
+ *      BOX_EDGE (i, j): ga_k = (k == i) ? 0 : sign(dot(normal, ua_k)) * Ha_k;  gb_k = (k == j) ? 0 : (-sign(dot(normal, ub_k))) * Hb_k;
+ *                       ea, eb = the world images of ga in a's frame and gb in b's;  va = ua_i * Ha_i;  vb = ub_j * Hb_j;
+ *                       p1 = ea - va; d1 = va + va; p2 = eb - vb; d2 = vb + vb;  s, t by routine 1's closed form;
+ *                       point = ((p1 + d1*s) + (p2 + d2*t)) * 0.5.
+ * LIMITS: one point per pair, no manifold.  A DEEP capsule reports the face nearest to the centre-line point routine 2 stopped at, with
+ * the capsule's overlap along that face's normal, which need not be the capsule's minimum translation; point stays on the line through
+ * that centre-line point.  A sheared matrix gives the shape in the frame these formulas define.  A neighbour
+ * tile's shapes are unknown (NONE).  A pipelined context already refuses the flag.
+ *   scTickSetPairContacts(enable) needs a prior scTickSetPairShapes(max_touching > 0) -- otherwise it fails with a last-error text and
+ *   nothing changes -- and allocates max_touching records of 32 bytes, 8 control words and 8 report words; 0 frees them.  Like
+ *   scTickSetPairShapes it drops captured graphs, asks for no learn tick and fails while scTickRunPairs is pending.
+ *   scTickSetPairShapes(0) switches contacts off too; scTickSetPairShapes(another size) re-sizes their buffer.
+ * The pass is two more launches behind the narrow-phase pass, on its stream -- a thread per entry of the list, then one thread for the
+ * report --, the entry count read on the device, so they replay from a captured graph.  A context that never enables it launches exactly what it did before.
+ * scTickReadPairContacts synchronises like scTickReadPairShapes and copies the 32 bytes of `info` and min(touching, max_touching,
+ * capacity) records, nothing else.  It fails when the last run did not carry SC_TICK_PAIR_SHAPES, when contacts were not enabled at that
+ * run, and while scTickRunPairs is pending. */
+#define SC_TICK_PAIR_CONTACTS_EDGE_EPS 1e-4f
+#define SC_TICK_CONTACT_NONE        0u      /* the pair was kept on its AABB answer: all floats are 0 */
+#define SC_TICK_CONTACT_ROUND_ROUND 1u
+#define SC_TICK_CONTACT_ROUND_BOX   2u
+#define SC_TICK_CONTACT_BOX_FACE_A  3u
+#define SC_TICK_CONTACT_BOX_FACE_B  4u
+#define SC_TICK_CONTACT_BOX_EDGE    5u
+#define SC_TICK_CONTACT_DEEP        (1u << 8)   /* ROUND_BOX: the round's centre line is inside the box */
+#define SC_TICK_CONTACT_DEGENERATE  (1u << 9)   /* no direction could be formed: the fallback normal (0, 1, 0) */
+typedef struct ScTickPairContact
+{
+  float point[3];
+  float depth;
+  float normal[3];
+  uint32_t kind;            /* SC_TICK_CONTACT_* in the low byte, DEEP / DEGENERATE above it */
+} ScTickPairContact;
+typedef struct ScTickPairContactInfo          /* counts over the records written, not over the true touching total */
+{
+  uint32_t written;         /* min(touching, max_touching) */
+  uint32_t round_round;
+  uint32_t round_box;
+  uint32_t box_box;         /* BOX_FACE_A, BOX_FACE_B and BOX_EDGE */
+  uint32_t unrefined;       /* SC_TICK_CONTACT_NONE */
+  uint32_t deep;
+  uint32_t degenerate;
+  uint32_t reserved;        /* 0 */
+} ScTickPairContactInfo;
+int scTickSetPairContacts(ScTickContext* ctx, uint32_t enable);
+int scTickGetPairContacts(ScTickContext* ctx, uint32_t* enabled);
+/* out: [capacity] records, may be NULL with capacity 0 */
+int scTickReadPairContacts(ScTickContext* ctx, ScTickPairContact* out, uint32_t capacity, ScTickPairContactInfo* info);
 
 /* ---- touch events: the tick-to-tick difference of the touching set ----
  * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on

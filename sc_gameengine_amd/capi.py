@@ -20,6 +20,9 @@ TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended 
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*: what a capsule sweep's candidates are (scTickSetSweepShapes)
+# SC_TICK_CONTACT_*: ScTickPairContact::kind (scTickSetPairContacts)
+CONTACT_NONE, CONTACT_ROUND_ROUND, CONTACT_ROUND_BOX, CONTACT_BOX_FACE_A, CONTACT_BOX_FACE_B, CONTACT_BOX_EDGE = 0, 1, 2, 3, 4, 5
+CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
@@ -81,6 +84,14 @@ class SweepShapeInfo(C.Structure):
 
 class PairShapeInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("tested", "touching", "refined", "kept_as_boxes", "truncated", "pairs_truncated")]
+
+
+class PairContact(C.Structure):                          # ScTickPairContact: 32 bytes
+    _fields_ = [("point", C.c_float * 3), ("depth", C.c_float), ("normal", C.c_float * 3), ("kind", C.c_uint32)]
+
+
+class PairContactInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("written", "round_round", "round_box", "box_box", "unrefined", "deep", "degenerate", "reserved")]
 
 
 class Frame(C.Structure):
@@ -244,6 +255,9 @@ SYMBOLS = {
     "scTickReadTouchEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(TouchEventInfo)]),
     "scTickSetPairShapes": (C.c_int, [_CTX, C.c_uint32]),
     "scTickReadPairShapes": (C.c_int, [_CTX, U32P, C.c_uint32, C.POINTER(PairShapeInfo)]),
+    "scTickSetPairContacts": (C.c_int, [_CTX, C.c_uint32]),
+    "scTickGetPairContacts": (C.c_int, [_CTX, U32P]),
+    "scTickReadPairContacts": (C.c_int, [_CTX, C.POINTER(PairContact), C.c_uint32, C.POINTER(PairContactInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

@@ -139,6 +139,10 @@ struct ScTickContext
   void* touchEventSlab = nullptr; size_t touchEventSlabBytes = 0;
   // scTickSetPairShapes: the touching list, its running counts and its report.  All null until the call: nothing is launched.
   PairShapeState pairShapes{};
+  // scTickSetPairContacts: one record per entry of the touching list, the kind counts and their report.  All null until the call: nothing
+  // is launched.  lastPairContacts: the last run with SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts).
+  PairContactState pairContacts{};
+  bool lastPairContacts = false;
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched); what the
@@ -699,7 +703,8 @@ bool resyncPairEvents(ScTickContext* c)
 void launchNarrowPhase(ScTickContext* c, const DeviceState& ds, const TickParams& p, hipStream_t s)
 {
   if (!(p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))) return;
-  launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr, s);
+  launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
+                   &c->pairContacts, s);
 }
 
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
@@ -1869,6 +1874,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if ((flags & SC_TICK_SWEEPS) && c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && c->pairsStream)
     return fail(c, "SC_TICK_SWEEP_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its sweeps are cast when the matrices may be the next tick's");
   if (flags & SC_TICK_SWEEPS) c->lastSweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
+  if (flags & SC_TICK_PAIR_SHAPES) c->lastPairContacts = c->pairContacts.ctl != nullptr;
   // (a quiet tick keeps the flag in lastFlags -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
   const bool quiet = quietTick(c, flags);
   const uint32_t run = quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
@@ -2609,6 +2615,8 @@ int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap,
                         reinterpret_cast<ScTickPairEventInfo*>(info));
 }
 
+static bool sizePairContacts(ScTickContext* c, uint32_t maxTouching);
+
 int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
 {
   if (!c) return 0;
@@ -2620,13 +2628,71 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
   e = PairShapeState{};
   dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  if (!maxTouching) return 1;
+  const bool contacts = c->pairContacts.ctl != nullptr;   // pair contacts follow the list: off with it, re-sized with it
+  if (!maxTouching) { sizePairContacts(c, 0u); return 1; }
   if (!dalloc(c, e.ctl, kPsCtlWords) || !dalloc(c, e.info, kPsInfoWords) || !dalloc(c, e.list, maxTouching, false)) {
     dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
     e = PairShapeState{};
+    sizePairContacts(c, 0u);
     return 0;
   }
   e.maxTouching = maxTouching;
+  if (contacts && !sizePairContacts(c, maxTouching)) return 0;
+  return 1;
+}
+
+// the contact buffers for a touching list of maxTouching entries; 0 frees them
+static bool sizePairContacts(ScTickContext* c, uint32_t maxTouching)
+{
+  PairContactState& k = c->pairContacts;
+  dfree(c, k.rec); dfree(c, k.ctl); dfree(c, k.info);
+  k = PairContactState{};
+  if (!maxTouching) return true;
+  if (!dalloc(c, k.ctl, kPcCtlWords) || !dalloc(c, k.info, kPcInfoWords) || !dalloc(c, k.rec, 2u * (size_t)maxTouching, false)) {
+    dfree(c, k.rec); dfree(c, k.ctl); dfree(c, k.info);
+    k = PairContactState{};
+    return false;
+  }
+  k.maxTouching = maxTouching;
+  return true;
+}
+
+int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
+{
+  static_assert(sizeof(ScTickPairContact) == 2u * sizeof(float4) && offsetof(ScTickPairContact, normal) == sizeof(float4), "the device writes a record as two float4");
+  static_assert(kPairContactsEdgeEps == SC_TICK_PAIR_CONTACTS_EDGE_EPS, "the edge-axis epsilon differs from the header's");
+  static_assert(kContactNone == SC_TICK_CONTACT_NONE && kContactRoundRound == SC_TICK_CONTACT_ROUND_ROUND && kContactRoundBox == SC_TICK_CONTACT_ROUND_BOX &&
+                kContactBoxFaceA == SC_TICK_CONTACT_BOX_FACE_A && kContactBoxFaceB == SC_TICK_CONTACT_BOX_FACE_B && kContactBoxEdge == SC_TICK_CONTACT_BOX_EDGE &&
+                kContactDeep == SC_TICK_CONTACT_DEEP && kContactDegenerate == SC_TICK_CONTACT_DEGENERATE, "the contact kinds differ from the header's");
+  if (!c) return 0;
+  if (enable && !c->pairShapes.ctl) return fail(c, "scTickSetPairContacts needs scTickSetPairShapes(max_touching > 0) first");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  return sizePairContacts(c, enable ? c->pairShapes.maxTouching : 0u) ? 1 : 0;
+}
+
+int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
+{
+  if (!c || !enabled) return c ? fail(c, "null argument") : 0;
+  *enabled = c->pairContacts.ctl ? 1u : 0u;
+  return 1;
+}
+
+int scTickReadPairContacts(ScTickContext* c, ScTickPairContact* out, uint32_t capacity, ScTickPairContactInfo* info)
+{
+  static_assert(sizeof(ScTickPairContactInfo) == kPcInfoWords * sizeof(uint32_t), "the device writes the report word by word");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
+  if (!c->lastPairContacts) return fail(c, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)");
+  if (c->pairsPending) return fail(c, "pair contacts are ready after scTickRunPairs");
+  const PairContactState& k = c->pairContacts;
+  if (!k.ctl) return fail(c, "pair contacts were switched off since the last scTickRun");
+  if (!joinPairs(c)) return 0;
+  if (!d2h(c, info, k.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t m = std::min(std::min(info->written, k.maxTouching), out ? capacity : 0u);
+  if (m && (!d2h(c, out, k.rec, (size_t)m * sizeof(ScTickPairContact)) || !sync(c))) return 0;
   return 1;
 }
 

@@ -412,6 +412,20 @@ struct PairShapeState {
 constexpr uint32_t kPsTouching = 0, kPsRefined = 1, kPsKept = 2, kPsTested = 3, kPsPairsTruncated = 4, kPsCtlWords = 8;
 constexpr uint32_t kPsInfoWords = 8;
 constexpr float kPairShapesSatEps = 1e-6f;      // == SC_TICK_PAIR_SHAPES_SAT_EPS
+// ---- pair contacts (k_pair_contacts, sc_tick_pair_shapes.hip; include/sc_tick.h "pair contacts"): one record per entry of the touching
+// list -- point, depth, normal, kind -- written behind the narrow-phase pass while the list's running count is still up.  All null
+// until scTickSetPairContacts: nothing is launched.
+struct PairContactState {
+  float4* rec;                    // [2 * maxTouching]: record i = (point, depth), (normal, kind) of list entry i (== ScTickPairContact)
+  uint32_t* ctl;                  // kPc* words below: the tick's running kind counts
+  uint32_t* info;                 // what the last tick with contacts reports (== ScTickPairContactInfo)
+  uint32_t maxTouching;           // the touching list's
+};
+constexpr uint32_t kPcRoundRound = 0, kPcRoundBox = 1, kPcBoxBox = 2, kPcUnrefined = 3, kPcDeep = 4, kPcDegenerate = 5, kPcCtlWords = 8;
+constexpr uint32_t kPcInfoWords = 8;
+constexpr uint32_t kContactNone = 0, kContactRoundRound = 1, kContactRoundBox = 2, kContactBoxFaceA = 3, kContactBoxFaceB = 4, kContactBoxEdge = 5,
+                   kContactDeep = 1u << 8, kContactDegenerate = 1u << 9;      // == SC_TICK_CONTACT_*
+constexpr float kPairContactsEdgeEps = 1e-4f;   // == SC_TICK_PAIR_CONTACTS_EDGE_EPS
 // The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
 // (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
 // fp32, unfused, left to right, as the header states it operation by operation.
@@ -569,7 +583,9 @@ __device__ __forceinline__ SegBox segBoxCore(const float y0[3], const float dy[3
 // the narrow-phase kernel enters what it decides "not apart" into that state's current table (its <.., Events> instances), the pair
 // events' sweep and finish do the rest.  One narrow-phase launch per tick: `list` (SC_TICK_PAIR_SHAPES) and `touch`
 // (SC_TICK_TOUCH_EVENTS) may each be null, or not enabled (no ctl): then that half is not written.
-void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, hipStream_t s);
+// `contacts` (scTickSetPairContacts; null or not enabled: nothing more is launched) adds k_pair_contacts between the pass and the list's report.
+void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
+                      hipStream_t s);
 // ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----
 struct BindRun24 { uint32_t first, count, pipeline, material, mesh, binds; };      // == ScTickBindRun
 // the report's words (== ScTickBindInfo)

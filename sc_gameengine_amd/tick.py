@@ -777,6 +777,30 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairShapeInfo._fields_}
         return pairs[:min(out["touching"], cap)].copy(), out
 
+    # ---- pair contacts: point, depth, normal and kind of every entry of the touching list ----
+    CONTACT_DTYPE = np.dtype([("point", np.float32, 3), ("depth", np.float32), ("normal", np.float32, 3), ("kind", np.uint32)])
+
+    def set_pair_contacts(self, on):
+        """Write, on every run with capi.PAIR_SHAPES, one contact record per entry of the touching list (scTickSetPairContacts); needs
+        set_pair_shapes(max_touching > 0) first.  Drops captured graphs, costs no learn tick."""
+        self._ok(self.lib.scTickSetPairContacts(self.ctx, 1 if on else 0), "scTickSetPairContacts")
+
+    def pair_contacts_enabled(self):
+        on = C.c_uint32()
+        self._ok(self.lib.scTickGetPairContacts(self.ctx, C.byref(on)), "scTickGetPairContacts")
+        return bool(on.value)
+
+    def read_pair_contacts(self):
+        """(records[n], info) of the last run with capi.PAIR_SHAPES while contacts were enabled: a structured array (point[3], depth,
+        normal[3], kind), record i for entry i of read_pair_shapes()'s list; info is a dict (written, round_round, round_box, box_box,
+        unrefined, deep, degenerate, reserved) over the records written."""
+        cap = getattr(self, "_max_touching", 0)
+        rec = np.zeros(max(cap, 1), self.CONTACT_DTYPE)
+        info = capi.PairContactInfo()
+        self._ok(self.lib.scTickReadPairContacts(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairContact)), cap, C.byref(info)), "scTickReadPairContacts")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairContactInfo._fields_}
+        return rec[:min(out["written"], cap)].copy(), out
+
     # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
     def set_touch_events(self, max_tracked, max_events):
         """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report
