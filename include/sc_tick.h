@@ -450,7 +450,10 @@ int scTickSetTrafficSensors(ScTickContext* ctx, int enable, float front_ray_leng
 int scTickReadTrafficBrakes(ScTickContext* ctx, uint32_t first, uint32_t count, float* obstacle_brake);
 /* Per-agent TrafficSensors (src/engine/traffic/sc_traffic_common.h:46-53; the AI reads frontRayLength / safeDistance of the agent's own
  * component, sc_traffic_ai.cpp:306-308): scTickSetTrafficSensors gives every entity the two defaults, scTickUploadTrafficSensors
- * overrides them for a range (they travel with their entity through scTickRemoveEntities).  What the AI leaves in the component
+ * overrides them for a range.  The whole component travels with its entity through scTickRemoveEntities, as the reference's pool
+ * swap-removes it (sc_ecs.h:240-262): the two values, lastHitDistance / lastHitType, and the brake -- so a scTickAdvanceMovers between a
+ * removal and the next ray tick scales a relocated agent's speed by its own last brake.  An entity appended later starts with the
+ * defaults and empty last-hit values (scTickAppendEntities).  What the AI leaves in the component
  * (:339-345, read by the debug state :420-421, :479-480) comes back through scTickReadTrafficSensors: lastHitDistance -- the hit's
  * distance, or the agent's ray length without a hit -- and lastHitType -- 0 None, 2 Vehicle, 3 World; own spec like the rays:
  * Vehicle = the hit entity is a vehicle by its mover kind (a traffic agent, or a kind-1 mover: what carries a VehicleComponent,
@@ -652,7 +655,10 @@ uint32_t scTickSectorPath(const char* world_root, int32_t x, int32_t z, char* ou
  * created at the END of the Transform pool's dense order (ComponentPool::add, sc_ecs.h:203-221) with setLocal
  * (dirty), a RenderMesh, Bounds (NULL min/max = the unit cube kUnitCubeBounds, :27) and collision layers (NULL =
  * group/mask all).  parent = NULL: all roots, nothing else is touched (O(count) work); otherwise dense indices
- * (earlier entities or this batch) and the hierarchy is re-linked.  *first_index = dense index of the first one. */
+ * (earlier entities or this batch) and the hierarchy is re-linked.  *first_index = dense index of the first one.
+ * An appended entity is no mover and no traffic agent, whoever held its slot before; once scTickSetTrafficSensors has been called
+ * its TrafficSensors are a new component's (sc_traffic_common.h:46-53): the context's defaults for front_ray_length / safe_distance,
+ * lastHitDistance 0, lastHitType None, brake 0 -- also while the sensors are switched off. */
 int scTickAppendEntities(ScTickContext* ctx, uint32_t count, const float* pos3, const float* rot3, const float* scale3,
                          const float* bounds_min3, const float* bounds_max3,
                          const uint32_t* mesh_id, const uint32_t* material_id,

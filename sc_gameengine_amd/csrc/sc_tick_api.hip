@@ -1423,6 +1423,13 @@ int scTickAppendEntities(ScTickContext* c, uint32_t count, const float* pos3, co
     const hipError_t e = hipMemsetAsync(c->d.moverKind + first, 0, (size_t)count * 4u, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync", e);
   }
+  if (c->d.aHitType) {        // ... and a new entity's TrafficSensors are the context's defaults with nothing hit yet (sc_traffic_common.h:46-53), not the slot's last occupant's
+    launchFillSensors(c->d, first, count, c->sensorRay, c->sensorSafe, c->stream);
+    hipError_t e = hipMemsetAsync(c->d.aHitDist + first, 0, (size_t)count * 4u, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d.aHitType + first, 0, (size_t)count * 4u, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d.aBrake + first, 0, (size_t)count * 4u, c->stream);
+    if (e != hipSuccess) return fail(c, "hipMemsetAsync", e);
+  }
 
   if (parent || wasStale) {
     if (parent) std::copy(parent, parent + count, c->hParent.begin() + first);

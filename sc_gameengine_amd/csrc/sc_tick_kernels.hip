@@ -3161,7 +3161,7 @@ __global__ __launch_bounds__(kTile) void k_gather_rows(const DeviceState d, cons
 // Swap-remove relocations (ComponentPool::remove, sc_ecs.h:240-262, applied to every per-entity array at
 // once): entity src[k] moves to slot dst[k].  The host guarantees every src lies at or beyond the new
 // entity count and every dst below it, so no slot is both read and written.  One thread per (move, array).
-constexpr uint32_t kMoveSlots = 42;     // 22 streams, 3 matrix rows, the dirty bit, 7 mover arrays, 5 traffic-agent arrays, 2 sensor arrays, 2 collider arrays
+constexpr uint32_t kMoveSlots = 45;     // 22 streams, 3 matrix rows, the dirty bit, 7 mover arrays, 5 traffic-agent arrays, 2 sensor arrays, 2 collider arrays, 3 last-hit arrays
 __global__ __launch_bounds__(kTile) void k_move_entities(const DeviceState d, const uint32_t* __restrict__ src,
                                                          const uint32_t* __restrict__ dst, uint32_t moves)
 {
@@ -3194,6 +3194,13 @@ __global__ __launch_bounds__(kTile) void k_move_entities(const DeviceState d, co
     a[to] = a[from];
   } else if (d.colType && slot == kStreamCount + 18u) d.colShape[to] = d.colShape[from];      // a collider travels with its entity
   else if (d.colType && slot == kStreamCount + 19u) d.colType[to] = d.colType[from];
+  else if (d.aHitType && slot >= kStreamCount + 20u && slot < kStreamCount + 23u) {
+    // ... and so does what the AI left in the component (the whole TrafficSensors is swap-removed) and the brake, which a step
+    // without a ray tick in between scales the speed by
+    uint32_t* arrays[3] = { reinterpret_cast<uint32_t*>(d.aHitDist), d.aHitType, reinterpret_cast<uint32_t*>(d.aBrake) };
+    uint32_t* a = arrays[slot - kStreamCount - 20u];
+    a[to] = a[from];
+  }
 }
 
 // Children of a relocated entity: pairs (entity, new parent index); depth and flags are untouched.
