@@ -1021,7 +1021,7 @@ int scTickReadPairShapes(ScTickContext* ctx, uint32_t* pairs2, uint32_t capacity
  *                       ea, eb = the world images of ga in a's frame and gb in b's;  va = ua_i * Ha_i;  vb = ub_j * Hb_j;
  *                       p1 = ea - va; d1 = va + va; p2 = eb - vb; d2 = vb + vb;  s, t by routine 1's closed form;
  *                       point = ((p1 + d1*s) + (p2 + d2*t)) * 0.5.
- * LIMITS: one point per pair, no manifold.  A DEEP capsule reports the face nearest to the centre-line point routine 2 stopped at, with
+ * LIMITS: one point per pair (more of them: the "pair manifolds" below).  A DEEP capsule reports the face nearest to the centre-line point routine 2 stopped at, with
  * the capsule's overlap along that face's normal, which need not be the capsule's minimum translation; point stays on the line through
  * that centre-line point.  A sheared matrix gives the shape in the frame these formulas define.  A neighbour
  * tile's shapes are unknown (NONE).  A pipelined context already refuses the flag.
@@ -1065,6 +1065,105 @@ int scTickSetPairContacts(ScTickContext* ctx, uint32_t enable);
 int scTickGetPairContacts(ScTickContext* ctx, uint32_t* enabled);
 /* out: [capacity] records, may be NULL with capacity 0 */
 int scTickReadPairContacts(ScTickContext* ctx, ScTickPairContact* out, uint32_t capacity, ScTickPairContactInfo* info);
+
+/* ---- pair manifolds: up to four contact points per touching pair ----
+ * One point cannot describe a resting contact: a box on a slab touches over an area, a capsule lying on a floor along a line.  While pair
+ * manifolds are enabled, every run with SC_TICK_PAIR_SHAPES also writes one ScTickPairManifold per entry of the touching list: record i
+ * belongs to entry i of the list and to contact record i of the same tick, whose normal it shares (it is not repeated here).  No run flag
+ * of its own.  This build's OWN SPEC, over the "pair contacts" text above: the same fp32 arithmetic, dot, sign, clamp, clamp01, frame sums
+ * and world image, and the intermediate values routines 1 - 3 and the contact rules name.  Ties go to the earlier index.  Every point is
+ * halfway between the two surfaces along the face's or the pair's own direction; depth[i] >= 0 belongs to point[i].
+ * NONE: the contact is SC_TICK_CONTACT_NONE: count 0, all words 0.
+ * SINGLE: count 1, point[0] and depth[0] are the contact's, bit for bit.  Every contact that no rule below replaces: one with a sphere
+ *      (A = 0) in it, BOX_EDGE, any DEGENERATE contact, a shallow ROUND_BOX whose closest box feature is an edge or a vertex (more than
+ *      one k with y_k != q_k, that is, a non-zero e_k), and a SEGMENT or FACE rule that keeps no point.
+ * SEGMENT, a capsule on a box face: a ROUND_BOX contact whose round has A != 0 and that is DEEP (k' and sg as the contact rule has them)
+ *      or shallow with exactly one k with y_k != q_k (that k is k'; sg = sign(y_k')).
+ *      lo = 0, hi = 1; for the two k other than k', ascending:  dy_k != 0:  b0 = (H_k - y0_k) / dy_k; b1 = ((-H_k) - y0_k) / dy_k (routine
+ *      2's breakpoints before clamp01); tl = (b1 < b0) ? b1 : b0; th = (b1 < b0) ? b0 : b1; lo = (tl > lo) ? tl : lo; hi = (th < hi) ? th : hi.
+ *      dy_k == 0: the clip is empty when |y0_k| > H_k.  Empty, or not lo <= hi (rounding alone can do it): SINGLE.
+ *      The ends t_0 = lo, t_1 = hi; t_1 is left out when hi == lo.  Per end: yk = y0_k' + dy_k'*t; up = sg*yk; pen = R - (up - H_k'); kept
+ *      when pen >= 0, l <= h (below: the round reaches the box at that end) and the line through the end along the face's normal leaves
+ *      the round at R: dd = (dy_0*dy_0 + dy_1*dy_1) + dy_2*dy_2 and R*(dy_k'*dy_k') <= SC_TICK_MANIFOLD_FLAT*dd (the centre line lies flat
+ *      on the face), or the end is a true end of the centre line that the normal leaves on the far side (t_0 == 0 and sg*dy_k' >= 0;
+ *      t_1 == 1 and sg*dy_k' <= 0).  On the line through the centre-line point along the face's normal the round is [-R, R] and the box
+ *      [least - 2H_k', least]: least = H_k' - up; back = least - (H_k' + H_k'); l = (back < -R) ? -R : back; h = (least < R) ? least : R;
+ *      mid = (l + h) * 0.5;  x_k' = yk + sg*mid and x_k = y0_k + dy_k*t for the other two;  point = the world image of x in the box's
+ *      frame;  depth = pen.  The kept ends fill the slots in their order.
+ * SEGMENT, capsule on capsule: a ROUND_ROUND contact, not DEGENERATE, both rounds with A != 0.  p1, d1, p2, d2 as in routine 1;
+ *      a = dot(d1, d1); e = dot(d2, d2).  Two candidates, c = 0, 1:  g = p2 (c = 0) or p2 + d2 (c = 1);  s_c = clamp01(dot(g - p1, d1) / a);
+ *      Pa = p1 + d1*s_c;  the partner Pb is g itself when clamp01 left the quotient as it was (the end projects into segment 1), else
+ *      p2 + d2*t with t = clamp01(dot(Pa - p2, d2) / e): every candidate pairs an end of one segment with its closest point on the
+ *      other.  v = Pa - Pb;  d2v = dot(v, v);  dist = sqrt(d2v);
+ *      pen = (Ra + Rb) - dist;  w = (-v) / dist per component;  kept when pen >= 0, d2v > 0, the candidate's own direction is the contact's
+ *      -- (Ra + Rb) * dot(w - normal, w - normal) <= SC_TICK_MANIFOLD_FLAT -- and the line through the pair leaves either round at its
+ *      radius: c1 = dot(w, d1): s_c == 0 and c1 <= 0, or s_c == 1 and c1 >= 0, or Ra*(c1*c1) <= SC_TICK_MANIFOLD_FLAT*a;  c2 = dot(w, d2),
+ *      tp = the partner's parameter (0 or 1 for g itself, else t): tp == 0 and c2 >= 0, or tp == 1 and c2 <= 0, or
+ *      Rb*(c2*c2) <= SC_TICK_MANIFOLD_FLAT*e.  Candidate 1 is left out when s_1 == s_0.  far, near, hi, lo, mid as in
+ *      contact rule 1 with this dist;  point = Pa + w*mid per component;  depth = pen.  None kept: SINGLE.
+ *      Neither SEGMENT rule has a parallelism threshold: a crossing pair keeps no end, a lying pair keeps both.
+ * FACE: BOX_FACE_A or BOX_FACE_B.  The reference box o is the axis's owner (a, axis i; or b, axis j), the other box is t.  ax = that
+ *      axis, a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;  sg = sign(tl) of the contact rule;  sr = sg for FACE_A, -sg for FACE_B: the reference
+ *      face lies at sr * Ho_ax along uo_ax.  The incident face: c_k = dot(normal, ut_k); m = the first k with the largest |c_k| (strict >);
+ *      sm = +1 when (c_m < 0) differs from "FACE_B", else -1; m1 = (m + 1) % 3, m2 = (m + 2) % 3.  Its vertices j = 0..3 have the signs
+ *      (s1, s2) = (+, +), (-, +), (-, -), (+, -):  g_m = sm*Ht_m, g_m1 = s1*Ht_m1, g_m2 = s2*Ht_m2;  V = the world image of g in t's frame;
+ *      r = V - To;  x_k = dot(r, uo_k);  the vertex is (p, q, z) = (x_a1, x_a2, sr*x_ax).
+ *      Clip (Sutherland-Hodgman) against p <= Ho_a1, p >= -Ho_a1, q <= Ho_a2, q >= -Ho_a2, in that order; per plane with bound h on
+ *      coordinate x: walk the vertices in order, each with its predecessor (the first with the last): when exactly one of the two is
+ *      inside, emit prev + (cur - prev) * ((h - x_prev) / (x_cur - x_prev)) per component (all three); then emit cur when it is inside.
+ *      A vertex beyond the eighth is not emitted.
+ *      The point of a vertex is the world image in o's frame of x_a1 = p, x_a2 = q, x_ax = sr * (z + pen*0.5) with pen = Ho_ax - z, its
+ *      depth pen.  A vertex is kept when pen >= 0, z >= -Ho_ax (it is not below the reference box) and the point lies within
+ *      SC_TICK_MANIFOLD_SKIN of the other box: r = point - Tt and |dot(r, ut_k)| - Ht_k <= SC_TICK_MANIFOLD_SKIN for k = 0, 1, 2.  Nothing kept: SINGLE.  Up to four: the slots in polygon order.  More: REDUCED, and the
+ *      slots are: the deepest (largest pen); the one farthest from it by dp*dp + dq*dq; with (ex, ey) the in-face vector from the first to
+ *      the second, area = ex*(q - q_first) - ey*(p - p_first): the largest area above 0, left out when none is; the smallest area below
+ *      0, left out when none is.  Each of the four searches takes the first vertex and then each later one that is strictly better.
+ * WHAT THE EXTRA CONDITIONS BUY: every point lies in both shapes, to within a millimetre, and its depth is the two shapes' overlap on the
+ * line through it along the contact's normal -- on a box resting a few centimetres deep as on shapes a metre inside each other at random
+ * angles, where an inclined capsule's end or the vertex of a steeply leaning face would otherwise report a feature's depth under a point
+ * outside one shape.  What they drop falls back towards SINGLE.
+ * LIMITS: BOX_EDGE and edge or vertex features give one point.  A DEEP capsule uses the face its contact reports.  A sheared matrix gives
+ * the shape in the frame these formulas define.  A neighbour tile's shapes give NONE.  A pipelined context already refuses the flag.
+ * Bullet's btBoxBoxDetector culls to the deepest point plus an angular spread around the centroid; this rule goes by extent instead.
+ *   scTickSetPairManifolds(enable) needs pair contacts enabled -- otherwise it fails with a last-error text and nothing changes -- and
+ *   allocates max_touching records of 80 bytes, 8 control words and 8 report words; 0 frees them.  It drops captured graphs, asks for no
+ *   learn tick and fails while scTickRunPairs is pending.  scTickSetPairContacts(0) and scTickSetPairShapes(0) switch manifolds off too;
+ *   scTickSetPairShapes(another size) re-sizes their buffer.
+ * The pass is two more launches behind the contacts' -- a thread per entry of the list, then one thread for the report --, the entry
+ * count read on the device, so they replay from a captured graph.  A context that never enables it launches exactly what it did before.
+ * scTickReadPairManifolds synchronises like scTickReadPairContacts and copies the 32 bytes of `info` and min(touching, max_touching,
+ * capacity) records, nothing else.  It fails when the last run did not carry SC_TICK_PAIR_SHAPES, when manifolds were not enabled at that
+ * run, when they were switched off since, and while scTickRunPairs is pending. */
+#define SC_TICK_MANIFOLD_SKIN     2.5e-4f   /* metres: how far outside the other box a FACE point may lie (a leaning edge) */
+#define SC_TICK_MANIFOLD_FLAT     1e-3f     /* metres: R * cos^2 of the angle a round's centre line may make with the line its depth is measured on */
+#define SC_TICK_MANIFOLD_NONE     0u   /* the pair's contact is SC_TICK_CONTACT_NONE: count 0, all words 0 */
+#define SC_TICK_MANIFOLD_SINGLE   1u   /* the contact's own point and depth, count 1 */
+#define SC_TICK_MANIFOLD_SEGMENT  2u   /* ends of a capsule's contact stretch, count 1..2 */
+#define SC_TICK_MANIFOLD_FACE     3u   /* incident face clipped to the reference face, count 1..4 */
+#define SC_TICK_MANIFOLD_REDUCED  (1u << 8)  /* FACE: more than four vertices were kept, four were chosen */
+typedef struct ScTickPairManifold       /* 80 bytes: five 16-byte stores */
+{
+  float    point[4][3];
+  float    depth[4];
+  uint32_t count;                       /* 0..4; slots >= count are +0 */
+  uint32_t kind;                        /* SC_TICK_MANIFOLD_* in the low byte, REDUCED above it */
+  uint32_t reserved[2];                 /* 0 */
+} ScTickPairManifold;
+typedef struct ScTickPairManifoldInfo   /* 32 bytes, over the records written */
+{
+  uint32_t written;         /* min(touching, max_touching) */
+  uint32_t points;          /* the sum of count */
+  uint32_t with_one;
+  uint32_t with_two;
+  uint32_t with_three;
+  uint32_t with_four;
+  uint32_t face;            /* SC_TICK_MANIFOLD_FACE, REDUCED or not */
+  uint32_t reduced;
+} ScTickPairManifoldInfo;
+int scTickSetPairManifolds(ScTickContext* ctx, uint32_t enable);
+int scTickGetPairManifolds(ScTickContext* ctx, uint32_t* enabled);
+/* out: [capacity] records, may be NULL with capacity 0 */
+int scTickReadPairManifolds(ScTickContext* ctx, ScTickPairManifold* out, uint32_t capacity, ScTickPairManifoldInfo* info);
 
 /* ---- touch events: the tick-to-tick difference of the touching set ----
  * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on

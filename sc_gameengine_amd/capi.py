@@ -23,6 +23,9 @@ SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*:
 # SC_TICK_CONTACT_*: ScTickPairContact::kind (scTickSetPairContacts)
 CONTACT_NONE, CONTACT_ROUND_ROUND, CONTACT_ROUND_BOX, CONTACT_BOX_FACE_A, CONTACT_BOX_FACE_B, CONTACT_BOX_EDGE = 0, 1, 2, 3, 4, 5
 CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
+# SC_TICK_MANIFOLD_*: ScTickPairManifold::kind (scTickSetPairManifolds)
+MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
+MANIFOLD_REDUCED = 1 << 8
 SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
@@ -92,6 +95,14 @@ class PairContact(C.Structure):                          # ScTickPairContact: 32
 
 class PairContactInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("written", "round_round", "round_box", "box_box", "unrefined", "deep", "degenerate", "reserved")]
+
+
+class PairManifold(C.Structure):                         # ScTickPairManifold: 80 bytes
+    _fields_ = [("point", (C.c_float * 3) * 4), ("depth", C.c_float * 4), ("count", C.c_uint32), ("kind", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PairManifoldInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("written", "points", "with_one", "with_two", "with_three", "with_four", "face", "reduced")]
 
 
 class Frame(C.Structure):
@@ -258,6 +269,9 @@ SYMBOLS = {
     "scTickSetPairContacts": (C.c_int, [_CTX, C.c_uint32]),
     "scTickGetPairContacts": (C.c_int, [_CTX, U32P]),
     "scTickReadPairContacts": (C.c_int, [_CTX, C.POINTER(PairContact), C.c_uint32, C.POINTER(PairContactInfo)]),
+    "scTickSetPairManifolds": (C.c_int, [_CTX, C.c_uint32]),
+    "scTickGetPairManifolds": (C.c_int, [_CTX, U32P]),
+    "scTickReadPairManifolds": (C.c_int, [_CTX, C.POINTER(PairManifold), C.c_uint32, C.POINTER(PairManifoldInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

@@ -143,6 +143,9 @@ struct ScTickContext
   // is launched.  lastPairContacts: the last run with SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts).
   PairContactState pairContacts{};
   bool lastPairContacts = false;
+  // scTickSetPairManifolds: the same a level up -- five float4 per entry of the touching list, the counts and their report
+  PairManifoldState pairManifolds{};
+  bool lastPairManifolds = false;
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched); what the
@@ -704,7 +707,7 @@ void launchNarrowPhase(ScTickContext* c, const DeviceState& ds, const TickParams
 {
   if (!(p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))) return;
   launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                   &c->pairContacts, s);
+                   &c->pairContacts, &c->pairManifolds, s);
 }
 
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
@@ -1882,6 +1885,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     return fail(c, "SC_TICK_SWEEP_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its sweeps are cast when the matrices may be the next tick's");
   if (flags & SC_TICK_SWEEPS) c->lastSweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
   if (flags & SC_TICK_PAIR_SHAPES) c->lastPairContacts = c->pairContacts.ctl != nullptr;
+  if (flags & SC_TICK_PAIR_SHAPES) c->lastPairManifolds = c->pairManifolds.ctl != nullptr;
   // (a quiet tick keeps the flag in lastFlags -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
   const bool quiet = quietTick(c, flags);
   const uint32_t run = quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
@@ -2623,6 +2627,7 @@ int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap,
 }
 
 static bool sizePairContacts(ScTickContext* c, uint32_t maxTouching);
+static bool sizePairManifolds(ScTickContext* c, uint32_t maxTouching);
 
 int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
 {
@@ -2636,15 +2641,18 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   e = PairShapeState{};
   dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   const bool contacts = c->pairContacts.ctl != nullptr;   // pair contacts follow the list: off with it, re-sized with it
-  if (!maxTouching) { sizePairContacts(c, 0u); return 1; }
+  const bool manifolds = c->pairManifolds.ctl != nullptr; // ... and pair manifolds follow the contacts
+  if (!maxTouching) { sizePairContacts(c, 0u); sizePairManifolds(c, 0u); return 1; }
   if (!dalloc(c, e.ctl, kPsCtlWords) || !dalloc(c, e.info, kPsInfoWords) || !dalloc(c, e.list, maxTouching, false)) {
     dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
     e = PairShapeState{};
     sizePairContacts(c, 0u);
+    sizePairManifolds(c, 0u);
     return 0;
   }
   e.maxTouching = maxTouching;
-  if (contacts && !sizePairContacts(c, maxTouching)) return 0;
+  if (contacts && !sizePairContacts(c, maxTouching)) { sizePairManifolds(c, 0u); return 0; }
+  if (manifolds && !sizePairManifolds(c, maxTouching)) return 0;
   return 1;
 }
 
@@ -2676,6 +2684,7 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  if (!enable) sizePairManifolds(c, 0u);                 // pair manifolds need the contacts: off with them
   return sizePairContacts(c, enable ? c->pairShapes.maxTouching : 0u) ? 1 : 0;
 }
 
@@ -2700,6 +2709,61 @@ int scTickReadPairContacts(ScTickContext* c, ScTickPairContact* out, uint32_t ca
   if (!d2h(c, info, k.info, sizeof *info) || !sync(c)) return 0;
   const uint32_t m = std::min(std::min(info->written, k.maxTouching), out ? capacity : 0u);
   if (m && (!d2h(c, out, k.rec, (size_t)m * sizeof(ScTickPairContact)) || !sync(c))) return 0;
+  return 1;
+}
+
+// the manifold buffers for a touching list of maxTouching entries; 0 frees them
+static bool sizePairManifolds(ScTickContext* c, uint32_t maxTouching)
+{
+  PairManifoldState& f = c->pairManifolds;
+  dfree(c, f.rec); dfree(c, f.ctl); dfree(c, f.info);
+  f = PairManifoldState{};
+  if (!maxTouching) return true;
+  if (!dalloc(c, f.ctl, kPmCtlWords) || !dalloc(c, f.info, kPmInfoWords) || !dalloc(c, f.rec, 5u * (size_t)maxTouching, false)) {
+    dfree(c, f.rec); dfree(c, f.ctl); dfree(c, f.info);
+    f = PairManifoldState{};
+    return false;
+  }
+  f.maxTouching = maxTouching;
+  return true;
+}
+
+int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
+{
+  static_assert(sizeof(ScTickPairManifold) == 5u * sizeof(float4) && offsetof(ScTickPairManifold, depth) == 3u * sizeof(float4) &&
+                offsetof(ScTickPairManifold, count) == 4u * sizeof(float4), "the device writes a record as five float4");
+  static_assert(kManifoldNone == SC_TICK_MANIFOLD_NONE && kManifoldSingle == SC_TICK_MANIFOLD_SINGLE && kManifoldSegment == SC_TICK_MANIFOLD_SEGMENT &&
+                kManifoldFace == SC_TICK_MANIFOLD_FACE && kManifoldReduced == SC_TICK_MANIFOLD_REDUCED, "the manifold kinds differ from the header's");
+  static_assert(kManifoldSkin == SC_TICK_MANIFOLD_SKIN && kManifoldFlat == SC_TICK_MANIFOLD_FLAT, "the manifold tolerances differ from the header's");
+  if (!c) return 0;
+  if (enable && !c->pairContacts.ctl) return fail(c, "scTickSetPairManifolds needs scTickSetPairContacts(1) first");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  return sizePairManifolds(c, enable ? c->pairShapes.maxTouching : 0u) ? 1 : 0;
+}
+
+int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
+{
+  if (!c || !enabled) return c ? fail(c, "null argument") : 0;
+  *enabled = c->pairManifolds.ctl ? 1u : 0u;
+  return 1;
+}
+
+int scTickReadPairManifolds(ScTickContext* c, ScTickPairManifold* out, uint32_t capacity, ScTickPairManifoldInfo* info)
+{
+  static_assert(sizeof(ScTickPairManifoldInfo) == kPmInfoWords * sizeof(uint32_t), "the device writes the report word by word");
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!bind(c)) return 0;
+  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
+  if (!c->lastPairManifolds) return fail(c, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)");
+  if (c->pairsPending) return fail(c, "pair manifolds are ready after scTickRunPairs");
+  const PairManifoldState& f = c->pairManifolds;
+  if (!f.ctl) return fail(c, "pair manifolds were switched off since the last scTickRun");
+  if (!joinPairs(c)) return 0;
+  if (!d2h(c, info, f.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t m = std::min(std::min(info->written, f.maxTouching), out ? capacity : 0u);
+  if (m && (!d2h(c, out, f.rec, (size_t)m * sizeof(ScTickPairManifold)) || !sync(c))) return 0;
   return 1;
 }
 

@@ -426,6 +426,20 @@ constexpr uint32_t kPcInfoWords = 8;
 constexpr uint32_t kContactNone = 0, kContactRoundRound = 1, kContactRoundBox = 2, kContactBoxFaceA = 3, kContactBoxFaceB = 4, kContactBoxEdge = 5,
                    kContactDeep = 1u << 8, kContactDegenerate = 1u << 9;      // == SC_TICK_CONTACT_*
 constexpr float kPairContactsEdgeEps = 1e-4f;   // == SC_TICK_PAIR_CONTACTS_EDGE_EPS
+// ---- pair manifolds (k_pair_manifolds, sc_tick_pair_shapes.hip; include/sc_tick.h "pair manifolds"): up to four points per entry of the
+// touching list, written behind the contact records while the list's running count is still up.  All null until scTickSetPairManifolds:
+// nothing is launched.
+struct PairManifoldState {
+  float4* rec;                    // [5 * maxTouching]: record i = five float4 of list entry i (== ScTickPairManifold)
+  uint32_t* ctl;                  // kPm* words below: the tick's running counts
+  uint32_t* info;                 // what the last tick with manifolds reports (== ScTickPairManifoldInfo)
+  uint32_t maxTouching;           // the touching list's
+};
+constexpr uint32_t kPmOne = 0, kPmTwo = 1, kPmThree = 2, kPmFour = 3, kPmFace = 4, kPmReduced = 5, kPmCtlWords = 8;
+constexpr uint32_t kPmInfoWords = 8;
+constexpr uint32_t kManifoldNone = 0, kManifoldSingle = 1, kManifoldSegment = 2, kManifoldFace = 3, kManifoldReduced = 1u << 8;      // == SC_TICK_MANIFOLD_*
+constexpr float kManifoldSkin = 2.5e-4f, kManifoldFlat = 1e-3f;      // == SC_TICK_MANIFOLD_SKIN, SC_TICK_MANIFOLD_FLAT
+constexpr uint32_t kManifoldWave = 64;          // threads per workgroup of k_pair_manifolds: one wave, its clip polygons in LDS
 // The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
 // (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
 // fp32, unfused, left to right, as the header states it operation by operation.
@@ -584,8 +598,11 @@ __device__ __forceinline__ SegBox segBoxCore(const float y0[3], const float dy[3
 // events' sweep and finish do the rest.  One narrow-phase launch per tick: `list` (SC_TICK_PAIR_SHAPES) and `touch`
 // (SC_TICK_TOUCH_EVENTS) may each be null, or not enabled (no ctl): then that half is not written.
 // `contacts` (scTickSetPairContacts; null or not enabled: nothing more is launched) adds k_pair_contacts between the pass and the list's report.
+// `manifolds` (scTickSetPairManifolds; the same) adds k_pair_manifolds behind the contacts' report.
 void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      hipStream_t s);
+                      const PairManifoldState* manifolds, hipStream_t s);
+// k_pair_manifolds and its report (sc_tick_pair_manifolds.hip), launched by launchPairShapes between the contacts' report and the list's
+void launchPairManifolds(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairManifoldState& manifolds, hipStream_t s);
 // ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----
 struct BindRun24 { uint32_t first, count, pipeline, material, mesh, binds; };      // == ScTickBindRun
 // the report's words (== ScTickBindInfo)

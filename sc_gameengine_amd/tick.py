@@ -801,6 +801,31 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairContactInfo._fields_}
         return rec[:min(out["written"], cap)].copy(), out
 
+    # ---- pair manifolds: up to four points and depths of every entry of the touching list ----
+    MANIFOLD_DTYPE = np.dtype([("point", np.float32, (4, 3)), ("depth", np.float32, 4), ("count", np.uint32), ("kind", np.uint32),
+                               ("reserved", np.uint32, 2)])
+
+    def set_pair_manifolds(self, on):
+        """Write, on every run with capi.PAIR_SHAPES, one manifold record per entry of the touching list (scTickSetPairManifolds); needs
+        set_pair_contacts(True) first.  Drops captured graphs, costs no learn tick."""
+        self._ok(self.lib.scTickSetPairManifolds(self.ctx, 1 if on else 0), "scTickSetPairManifolds")
+
+    def pair_manifolds_enabled(self):
+        on = C.c_uint32()
+        self._ok(self.lib.scTickGetPairManifolds(self.ctx, C.byref(on)), "scTickGetPairManifolds")
+        return bool(on.value)
+
+    def read_pair_manifolds(self):
+        """(records[n], info) of the last run with capi.PAIR_SHAPES while manifolds were enabled: a structured array (point[4][3],
+        depth[4], count, kind, reserved[2]), record i for entry i of read_pair_shapes()'s list and record i of read_pair_contacts(); info
+        is a dict (written, points, with_one, with_two, with_three, with_four, face, reduced) over the records written."""
+        cap = getattr(self, "_max_touching", 0)
+        rec = np.zeros(max(cap, 1), self.MANIFOLD_DTYPE)
+        info = capi.PairManifoldInfo()
+        self._ok(self.lib.scTickReadPairManifolds(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairManifold)), cap, C.byref(info)), "scTickReadPairManifolds")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairManifoldInfo._fields_}
+        return rec[:min(out["written"], cap)].copy(), out
+
     # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
     def set_touch_events(self, max_tracked, max_events):
         """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report

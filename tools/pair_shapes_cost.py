@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""What SC_TICK_PAIR_SHAPES costs, and pair contacts on top of it, in one process on one device.
+"""What SC_TICK_PAIR_SHAPES costs, and pair contacts and pair manifolds on top of it, in one process on one device.
 
     SC_TICK_LAX_BIND=1 python tools/pair_shapes_cost.py [--workload config5|config3dyn] [--parent libsc_tick_parent.so]
 
 The caller-owned split flow -- scTickRun(FULL | PRODUCE_NEXT | SPLIT_PAIRS [| PAIR_SHAPES]) then scTickRunPairs -- whose
 SC_TICK_K_PAIRS event slot brackets the pair half.  Every entity gets a collider first: leg "box" a BOX of its bounds' half extents
 (SynthWorld's bounds are centred: the world AABBs and the pair set stay what they were), leg "mixed" BOX / SPHERE / CAPSULE by index
-modulo 3 with sizes from the same half extents (another pair set: its size is printed).  Per leg up to five contexts on the same world --
-a build of the parent commit (--parent) without and with the flag, this build without the flag, with it, and with it and pair contacts
-(scTickSetPairContacts) -- are timed in interleaved rounds: the wall
+modulo 3 with sizes from the same half extents (another pair set: its size is printed).  Per leg up to six contexts on the same world --
+a build of the parent commit (--parent) without and with the flag, this build without the flag, with it, with it and pair contacts
+(scTickSetPairContacts), and with manifolds on top of those (scTickSetPairManifolds) -- are timed in interleaved rounds: the wall
 time of a burst of steps ending in a synchronise, then on a separate profiled burst the K_PAIRS slot alone."""
 import argparse
 import json
@@ -54,7 +54,7 @@ def colliders(leg):
     return typ, he, radius, np.maximum(he[:, 1] - radius, 0).astype(np.float32)
 
 
-def context(lib, leg, flagged, contacts=False):
+def context(lib, leg, flagged, contacts=False, manifolds=False):
     capi._LIB = None
     capi.LIB_PATH = os.path.abspath(lib)
     t = WorldTick.from_world(w, broadphase=True)
@@ -66,6 +66,8 @@ def context(lib, leg, flagged, contacts=False):
         t.set_pair_shapes(max(int(t.max_pairs), 1))
     if contacts:
         t.set_pair_contacts(True)
+    if manifolds:
+        t.set_pair_manifolds(True)
     return t
 
 
@@ -77,12 +79,12 @@ def step(t, flags):
 for leg in ("box", "mixed"):
     legs = []
     if args.parent:
-        legs += [("parent, flag off", args.parent, False, False), ("parent, flag on", args.parent, True, False)]
-    legs += [("this build, flag off", this_lib, False, False), ("this build, flag on", this_lib, True, False),
-             ("this build, flag on, contacts on", this_lib, True, True)]
+        legs += [("parent, flag off", args.parent, False, False, False), ("parent, flag on", args.parent, True, False, False)]
+    legs += [("this build, flag off", this_lib, False, False, False), ("this build, flag on", this_lib, True, False, False),
+             ("this build, flag on, contacts on", this_lib, True, True, False), ("this build, flag on, contacts on, manifolds on", this_lib, True, True, True)]
     if args.this_first:
         legs.reverse()
-    ctxs = {name: (context(lib, leg, flagged, contacts), SPLIT | (capi.PAIR_SHAPES if flagged else 0)) for name, lib, flagged, contacts in legs}
+    ctxs = {name: (context(lib, leg, flagged, contacts, manifolds), SPLIT | (capi.PAIR_SHAPES if flagged else 0)) for name, lib, flagged, contacts, manifolds in legs}
     for t, flags in ctxs.values():
         for _ in range(30):
             step(t, flags)
@@ -113,8 +115,10 @@ for leg in ("box", "mixed"):
                "pair_half_us_max": round(float(np.max(r["pair_half_us"])), 2)}
         if flags & capi.PAIR_SHAPES:
             out["info"] = t.read_pair_shapes()[1]
-        if name.endswith("contacts on"):
+        if "contacts on" in name:
             out["contacts"] = t.read_pair_contacts()[1]
+        if name.endswith("manifolds on"):
+            out["manifolds"] = t.read_pair_manifolds()[1]
         print(json.dumps(out), flush=True)
     for t, _ in ctxs.values():
         t.close()
