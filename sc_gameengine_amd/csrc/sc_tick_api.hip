@@ -971,6 +971,8 @@ void dropGraphs(CapturedGraph* g, uint32_t count)
   }
 }
 template <uint32_t N> void dropGraphs(CapturedGraph (&g)[N]) { dropGraphs(g, N); }
+// ... every capture of the context: the tick's graphs and the pair half's (a pipelined tile's)
+void dropCaptures(ScTickContext* c) { dropGraphs(c->graph); dropGraphs(c->pairGraph); }
 
 // Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for other TickParams, another
 // topology epoch, another form of the end-of-tick kernel (compactG), or with / without the library's RCCL group inside (rccl: the
@@ -999,6 +1001,92 @@ void rowsToMat4(const float* r12, float* m16)
   // rows -> column-major Mat4 (m[c*4+r]); last row (0,0,0,1)
   for (int r = 0; r < 3; ++r) for (int col = 0; col < 4; ++col) m16[col * 4 + r] = r12[r * 4 + col];
   m16[3] = 0.0f; m16[7] = 0.0f; m16[11] = 0.0f; m16[15] = 1.0f;
+}
+
+// ---- shared steps of the C ABI's pair-half calls: one gate and one copy for the readers, one grow rule, one owner of the narrow-phase buffers ----
+// The gate of every call that reads a result of the last scTickRun's pair half, in one order: that run carried `flag`; the feature was
+// enabled at that run (enabledThen; features without such a state pass true); its pair half is not pending; the feature's buffers are
+// still there (onNow; likewise); then the pairs stream is joined.  The call site passes the texts (nullptr where the check cannot fail).
+bool lastRunResult(ScTickContext* c, uint32_t flag, const char* notRequested, bool enabledThen, const char* notEnabled, const char* pending,
+                   bool onNow, const char* switchedOff)
+{
+  if (!(c->lastFlags & flag)) return fail(c, notRequested);
+  if (!enabledThen) return fail(c, notEnabled);
+  if (c->pairsPending) return fail(c, pending);
+  if (!onNow) return fail(c, switchedOff);
+  return joinPairs(c);
+}
+
+// ... and what most of them do next: the report, then the first min(the report's count, what the device keeps, the caller's room) records
+template <typename Info>
+bool readReportAndRecords(ScTickContext* c, Info* info, const uint32_t* devInfo, uint32_t Info::*count, uint32_t kept, const void* devRec,
+                          size_t recBytes, void* out, uint32_t capacity)
+{
+  if (!d2h(c, info, devInfo, sizeof *info) || !sync(c)) return false;
+  const uint32_t m = std::min(std::min(info->*count, kept), out ? capacity : 0u);
+  return !m || (d2h(c, out, devRec, (size_t)m * recBytes) && sync(c));
+}
+
+// One array of a query batch: the state's pointer to it, its elements per query, whether it starts out as zeros.
+template <typename T> struct BatchArray { T*& p; size_t per; bool zero; };
+template <typename T> BatchArray<T> batchArray(T*& p, bool zero = false, size_t per = 1) { return { p, per, zero }; }
+
+// The grow rule of the query batches (rays, sweeps, anchored rays), for a batch of `count` queries behind a sync.  A count within the
+// capacity keeps the arrays; a larger one frees every array and allocates them anew for max(count, 1 024) queries.  One failure path: the
+// batch is left empty (held 0) with capacity 0, the epoch where it was.  A call that succeeds moves the epoch whether it grew the arrays
+// or not: a captured frame holds the old batch size -- and the next broadphase tick is a learn tick.
+template <typename... T>
+bool growBatch(ScTickContext* c, uint32_t& cap, uint32_t& held, uint32_t count, BatchArray<T>... arrays)
+{
+  if (count > cap) {
+    auto drop = [&](auto& a) { dfree(c, const_cast<void*>(static_cast<const void*>(a.p))); a.p = nullptr; };      // (inputs are pointers to const)
+    (drop(arrays), ...);
+    cap = 0; held = 0;
+    const uint32_t want = std::max(count, 1024u);
+    if (!(dalloc(c, arrays.p, want * arrays.per, arrays.zero) && ...)) { (drop(arrays), ...); return false; }
+    cap = want;
+  }
+  held = count;
+  c->topoEpoch++;
+  return true;
+}
+
+// The narrow-phase buffers are a chain -- the touching list, a contact record per entry of it, a manifold record per entry -- and this is
+// the one place that sizes them.  One level: its control words, its report and recsPer records per entry; 0 entries: freed, all null.
+template <typename State, typename Rec>
+bool sizeNarrowLevel(ScTickContext* c, State& s, Rec* State::*rec, uint32_t ctlWords, uint32_t infoWords, uint32_t recsPer, uint32_t entries)
+{
+  dfree(c, s.*rec); dfree(c, s.ctl); dfree(c, s.info);
+  s = State{};
+  if (!entries) return true;
+  if (!dalloc(c, s.ctl, ctlWords) || !dalloc(c, s.info, infoWords) || !dalloc(c, s.*rec, (size_t)recsPer * entries, false)) return false;
+  s.maxTouching = entries;
+  return true;
+}
+
+// The chain for a list of maxTouching entries (0: everything off), with contacts and manifolds where wanted: contacts need the list,
+// manifolds the contacts.  `set` is the level the calling setter sets.  A failed allocation leaves all three off (the allocator's text
+// stands): nothing is ever on without what it needs, or sized for another list.
+enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds };
+bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds)
+{
+  const uint32_t contactEntries = contacts ? maxTouching : 0u;
+  const uint32_t manifoldEntries = (contacts && manifolds) ? maxTouching : 0u;
+  // a level is allocated afresh when the setter sets it or the list under it is allocated afresh, freed when it has to be off, and
+  // otherwise stays as it is (scTickSetPairContacts(1) leaves the list and the manifolds alone)
+  const bool doList = set == kNarrowList;
+  const bool doContacts = doList || set == kNarrowContacts || !contactEntries;
+  const bool doManifolds = doList || set == kNarrowManifolds || !manifoldEntries;
+  bool ok = true;
+  if (doList) ok = sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, maxTouching);
+  if (ok && doContacts) ok = sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, contactEntries);
+  if (ok && doManifolds) ok = sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, manifoldEntries);
+  if (!ok) {      // everything off (0 entries: a level is freed, nothing is allocated)
+    sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, 0u);
+    sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, 0u);
+    sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, 0u);
+  }
+  return ok;
 }
 
 } // namespace
@@ -1152,7 +1240,7 @@ void scTickDestroyContext(ScTickContext* c)
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->pairsStream) hipStreamSynchronize(c->pairsStream);
   c->stream = c->ownStream;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);
+  dropGraphs(c->graph); dropGraphs(c->pairGraph);      // (teardown keeps its text word for word, this line included: DESIGN.md section 6)
   for (auto& v : c->times) for (auto& p : v) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto& p : c->eventPool) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (uint32_t k = 0; k < kMaxParity; ++k) { if (c->packed[k]) hipEventDestroy(c->packed[k]); if (c->pairsDone[k]) hipEventDestroy(c->pairsDone[k]); }
@@ -2105,7 +2193,7 @@ int scTickSetBorderCapacity(ScTickContext* c, uint32_t recordsPerRingSector)
     for (auto& a : c->alt) a.borderSend[d] = a.borderRecv[d] = nullptr;
     for (uint32_t q = 0; q < kMaxParity; ++q) for (int k = 0; k < 2; ++k) if (c->ownBorder[q][d][k]) { dfree(c, c->ownBorder[q][d][k]); c->ownBorder[q][d][k] = nullptr; }
   }
-  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
+  dropCaptures(c); c->topoEpoch++;
   return 1;
 }
 
@@ -2422,9 +2510,8 @@ int scTickReadPairs(ScTickContext* c, uint32_t* pairs2, uint32_t cap, uint32_t* 
 {
   if (!c || !count) return c ? fail(c, "null argument") : 0;
   if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_BROADPHASE)) return fail(c, "the last scTickRun did not request SC_TICK_BROADPHASE");
-  if (c->pairsPending) return fail(c, "scTickRunPairs has not been called for the last tick");
-  if (!joinPairs(c)) return 0;
+  if (!lastRunResult(c, SC_TICK_BROADPHASE, "the last scTickRun did not request SC_TICK_BROADPHASE", true, nullptr,
+                     "scTickRunPairs has not been called for the last tick", true, nullptr)) return 0;
   if (c->lastTickQuiet) { *count = 0; return 1; }      // no two colliders of that tick's world could meet: the empty set, whatever the bins' copies hold
   // the pair list is kept in per-shard segments on the device; gather them into one list first
   TickParams pp{}; pp.maxPairs = c->maxPairs;
@@ -2463,10 +2550,7 @@ static int readQueryHits(ScTickContext* c, uint32_t flag, const char* notRequest
                          void* hits, uint32_t cap, uint32_t* count)
 {
   if (!c || !count) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & flag)) return fail(c, notRequested);
-  if (c->pairsPending) return fail(c, pending);
-  if (!joinPairs(c)) return 0;
+  if (!bind(c) || !lastRunResult(c, flag, notRequested, true, nullptr, pending, true, nullptr)) return 0;
   *count = have;
   const uint32_t take = std::min(have, cap);
   if (take && hits) { if (!d2h(c, hits, src, (size_t)take * sizeof(RayHit48)) || !sync(c)) return 0; }
@@ -2478,16 +2562,7 @@ int scTickSetRayQueries(ScTickContext* c, uint32_t count, const float* origin3, 
   if (!c) return 0;
   if (count && (!origin3 || !dir3 || !maxDist || !mask)) return fail(c, "null argument");
   if (!bind(c) || !sync(c)) return 0;
-  if (count > c->rayCap) {
-    dfree(c, const_cast<float4*>(c->rays.origin)); dfree(c, const_cast<float4*>(c->rays.dir)); dfree(c, c->rays.hits);
-    c->rays = RayQueryState{}; c->rayCap = 0;
-    const uint32_t want = std::max(count, 1024u);
-    float4 *o = nullptr, *dd = nullptr; RayHit48* h = nullptr;
-    if (!dalloc(c, o, want, false) || !dalloc(c, dd, want, false) || !dalloc(c, h, want)) return 0;
-    c->rays.origin = o; c->rays.dir = dd; c->rays.hits = h; c->rayCap = want;
-  }
-  c->rays.count = count;
-  c->topoEpoch++;                      // a captured frame holds the old batch size
+  if (!growBatch(c, c->rayCap, c->rays.count, count, batchArray(c->rays.origin), batchArray(c->rays.dir), batchArray(c->rays.hits, true))) return 0;
   if (!count) return 1;
   std::vector<float4> o(count), dd(count);
   for (uint32_t i = 0; i < count; ++i) {
@@ -2525,16 +2600,8 @@ int scTickSetSweepQueries(ScTickContext* c, uint32_t count, const float* start3,
     if (!std::isfinite((dx * dx + dy * dy) + dz * dz)) return fail(c, "sweep queries: the segment's squared length overflows fp32");
   }
   if (!bind(c) || !sync(c)) return 0;
-  if (count > c->sweepCap) {
-    dfree(c, const_cast<float4*>(c->sweeps.start)); dfree(c, const_cast<float4*>(c->sweeps.end)); dfree(c, const_cast<uint2*>(c->sweeps.filter)); dfree(c, c->sweeps.hits);
-    c->sweeps = SweepQueryState{}; c->sweepCap = 0;
-    const uint32_t want = std::max(count, 1024u);
-    float4 *st = nullptr, *en = nullptr; uint2* fl = nullptr; SweepHit48* h = nullptr;
-    if (!dalloc(c, st, want, false) || !dalloc(c, en, want, false) || !dalloc(c, fl, want, false) || !dalloc(c, h, want)) return 0;
-    c->sweeps.start = st; c->sweeps.end = en; c->sweeps.filter = fl; c->sweeps.hits = h; c->sweepCap = want;
-  }
-  c->sweeps.count = count;
-  c->topoEpoch++;                      // a captured frame holds the old batch size
+  if (!growBatch(c, c->sweepCap, c->sweeps.count, count, batchArray(c->sweeps.start), batchArray(c->sweeps.end), batchArray(c->sweeps.filter),
+                 batchArray(c->sweeps.hits, true))) return 0;
   if (!count) return 1;
   if (!h2d(c, const_cast<float4*>(c->sweeps.start), a.data(), (size_t)count * 16u) ||
       !h2d(c, const_cast<float4*>(c->sweeps.end), b.data(), (size_t)count * 16u) ||
@@ -2559,7 +2626,7 @@ static int setEventState(ScTickContext* c, PairEventState& e, void*& slabOut, si
   if (!bind(c) || !sync(c)) return 0;
   dfree(c, slabOut); dfree(c, e.info); dfree(c, e.begun); dfree(c, e.ended);
   e = PairEventState{}; slabOut = nullptr; slabBytes = 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); the pair search itself is not concerned
+  dropCaptures(c);       // a captured tick holds the old buffers (or none); the pair search itself is not concerned
   if (!maxTracked) return 1;
   uint32_t slots = 64u;
   while (slots < 2u * maxTracked) slots <<= 1;
@@ -2577,13 +2644,12 @@ static int setEventState(ScTickContext* c, PairEventState& e, void*& slabOut, si
   return 1;
 }
 
-// (the caller has checked the flag of the last run and that no pair half is pending)
-static int readEventState(ScTickContext* c, const PairEventState& e, const char* off, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap,
-                          ScTickPairEventInfo* info)
+static int readEventState(ScTickContext* c, const PairEventState& e, uint32_t flag, const char* notRequested, const char* pending, const char* off,
+                          uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickPairEventInfo* info)
 {
   static_assert(sizeof(ScTickPairEventInfo) == 6u * sizeof(uint32_t) && kPeInfoWords >= 6u, "the device writes the report word by word");
-  if (!e.ctl) return fail(c, off);
-  if (!joinPairs(c)) return 0;
+  if (!info) return fail(c, "null argument");      // (the callers have checked c)
+  if (!bind(c) || !lastRunResult(c, flag, notRequested, true, nullptr, pending, e.ctl != nullptr, off)) return 0;
   if (!d2h(c, info, e.info, sizeof *info) || !sync(c)) return 0;
   const uint32_t nb = std::min(std::min(info->begun, e.maxEvents), begun2 ? begunCap : 0u);
   const uint32_t ne = std::min(std::min(info->ended, e.maxEvents), ended2 ? endedCap : 0u);
@@ -2601,11 +2667,9 @@ int scTickSetPairEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvent
 
 int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickPairEventInfo* info)
 {
-  if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_PAIR_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_EVENTS");
-  if (c->pairsPending) return fail(c, "pair events are ready after scTickRunPairs");
-  return readEventState(c, c->pairEvents, "pair events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap, info);
+  if (!c) return 0;
+  return readEventState(c, c->pairEvents, SC_TICK_PAIR_EVENTS, "the last scTickRun did not request SC_TICK_PAIR_EVENTS", "pair events are ready after scTickRunPairs",
+                        "pair events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap, info);
 }
 
 int scTickSetTouchEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
@@ -2618,16 +2682,10 @@ int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap,
 {
   static_assert(sizeof(ScTickTouchEventInfo) == sizeof(ScTickPairEventInfo) && offsetof(ScTickTouchEventInfo, events_truncated) == offsetof(ScTickPairEventInfo, events_truncated),
                 "the two reports are the same six words");
-  if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_TOUCH_EVENTS)) return fail(c, "the last scTickRun did not request SC_TICK_TOUCH_EVENTS");
-  if (c->pairsPending) return fail(c, "touch events are ready after scTickRunPairs");
-  return readEventState(c, c->touchEvents, "touch events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap,
-                        reinterpret_cast<ScTickPairEventInfo*>(info));
+  if (!c) return 0;
+  return readEventState(c, c->touchEvents, SC_TICK_TOUCH_EVENTS, "the last scTickRun did not request SC_TICK_TOUCH_EVENTS", "touch events are ready after scTickRunPairs",
+                        "touch events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap, reinterpret_cast<ScTickPairEventInfo*>(info));
 }
-
-static bool sizePairContacts(ScTickContext* c, uint32_t maxTouching);
-static bool sizePairManifolds(ScTickContext* c, uint32_t maxTouching);
 
 int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
 {
@@ -2636,40 +2694,9 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   if (maxTouching > (1u << 27)) return fail(c, "touching pairs: at most 2^27 listed pairs");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
-  PairShapeState& e = c->pairShapes;
-  dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
-  e = PairShapeState{};
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  const bool contacts = c->pairContacts.ctl != nullptr;   // pair contacts follow the list: off with it, re-sized with it
-  const bool manifolds = c->pairManifolds.ctl != nullptr; // ... and pair manifolds follow the contacts
-  if (!maxTouching) { sizePairContacts(c, 0u); sizePairManifolds(c, 0u); return 1; }
-  if (!dalloc(c, e.ctl, kPsCtlWords) || !dalloc(c, e.info, kPsInfoWords) || !dalloc(c, e.list, maxTouching, false)) {
-    dfree(c, e.list); dfree(c, e.ctl); dfree(c, e.info);
-    e = PairShapeState{};
-    sizePairContacts(c, 0u);
-    sizePairManifolds(c, 0u);
-    return 0;
-  }
-  e.maxTouching = maxTouching;
-  if (contacts && !sizePairContacts(c, maxTouching)) { sizePairManifolds(c, 0u); return 0; }
-  if (manifolds && !sizePairManifolds(c, maxTouching)) return 0;
-  return 1;
-}
-
-// the contact buffers for a touching list of maxTouching entries; 0 frees them
-static bool sizePairContacts(ScTickContext* c, uint32_t maxTouching)
-{
-  PairContactState& k = c->pairContacts;
-  dfree(c, k.rec); dfree(c, k.ctl); dfree(c, k.info);
-  k = PairContactState{};
-  if (!maxTouching) return true;
-  if (!dalloc(c, k.ctl, kPcCtlWords) || !dalloc(c, k.info, kPcInfoWords) || !dalloc(c, k.rec, 2u * (size_t)maxTouching, false)) {
-    dfree(c, k.rec); dfree(c, k.ctl); dfree(c, k.info);
-    k = PairContactState{};
-    return false;
-  }
-  k.maxTouching = maxTouching;
-  return true;
+  dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  // (pair contacts follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
+  return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
@@ -2683,9 +2710,9 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
   if (enable && !c->pairShapes.ctl) return fail(c, "scTickSetPairContacts needs scTickSetPairShapes(max_touching > 0) first");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  if (!enable) sizePairManifolds(c, 0u);                 // pair manifolds need the contacts: off with them
-  return sizePairContacts(c, enable ? c->pairShapes.maxTouching : 0u) ? 1 : 0;
+  dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  // (pair manifolds need the contacts: off with them)
+  return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
@@ -2699,33 +2726,11 @@ int scTickReadPairContacts(ScTickContext* c, ScTickPairContact* out, uint32_t ca
 {
   static_assert(sizeof(ScTickPairContactInfo) == kPcInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
-  if (!c->lastPairContacts) return fail(c, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)");
-  if (c->pairsPending) return fail(c, "pair contacts are ready after scTickRunPairs");
   const PairContactState& k = c->pairContacts;
-  if (!k.ctl) return fail(c, "pair contacts were switched off since the last scTickRun");
-  if (!joinPairs(c)) return 0;
-  if (!d2h(c, info, k.info, sizeof *info) || !sync(c)) return 0;
-  const uint32_t m = std::min(std::min(info->written, k.maxTouching), out ? capacity : 0u);
-  if (m && (!d2h(c, out, k.rec, (size_t)m * sizeof(ScTickPairContact)) || !sync(c))) return 0;
-  return 1;
-}
-
-// the manifold buffers for a touching list of maxTouching entries; 0 frees them
-static bool sizePairManifolds(ScTickContext* c, uint32_t maxTouching)
-{
-  PairManifoldState& f = c->pairManifolds;
-  dfree(c, f.rec); dfree(c, f.ctl); dfree(c, f.info);
-  f = PairManifoldState{};
-  if (!maxTouching) return true;
-  if (!dalloc(c, f.ctl, kPmCtlWords) || !dalloc(c, f.info, kPmInfoWords) || !dalloc(c, f.rec, 5u * (size_t)maxTouching, false)) {
-    dfree(c, f.rec); dfree(c, f.ctl); dfree(c, f.info);
-    f = PairManifoldState{};
-    return false;
-  }
-  f.maxTouching = maxTouching;
-  return true;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                 c->lastPairContacts, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)",
+                                 "pair contacts are ready after scTickRunPairs", k.ctl != nullptr, "pair contacts were switched off since the last scTickRun")) return 0;
+  return readReportAndRecords(c, info, k.info, &ScTickPairContactInfo::written, k.maxTouching, k.rec, sizeof(ScTickPairContact), out, capacity) ? 1 : 0;
 }
 
 int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
@@ -2739,8 +2744,8 @@ int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
   if (enable && !c->pairContacts.ctl) return fail(c, "scTickSetPairManifolds needs scTickSetPairContacts(1) first");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  return sizePairManifolds(c, enable ? c->pairShapes.maxTouching : 0u) ? 1 : 0;
+  dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u) ? 1 : 0;
 }
 
 int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
@@ -2754,17 +2759,11 @@ int scTickReadPairManifolds(ScTickContext* c, ScTickPairManifold* out, uint32_t 
 {
   static_assert(sizeof(ScTickPairManifoldInfo) == kPmInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
-  if (!c->lastPairManifolds) return fail(c, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)");
-  if (c->pairsPending) return fail(c, "pair manifolds are ready after scTickRunPairs");
   const PairManifoldState& f = c->pairManifolds;
-  if (!f.ctl) return fail(c, "pair manifolds were switched off since the last scTickRun");
-  if (!joinPairs(c)) return 0;
-  if (!d2h(c, info, f.info, sizeof *info) || !sync(c)) return 0;
-  const uint32_t m = std::min(std::min(info->written, f.maxTouching), out ? capacity : 0u);
-  if (m && (!d2h(c, out, f.rec, (size_t)m * sizeof(ScTickPairManifold)) || !sync(c))) return 0;
-  return 1;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                 c->lastPairManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)",
+                                 "pair manifolds are ready after scTickRunPairs", f.ctl != nullptr, "pair manifolds were switched off since the last scTickRun")) return 0;
+  return readReportAndRecords(c, info, f.info, &ScTickPairManifoldInfo::written, f.maxTouching, f.rec, sizeof(ScTickPairManifold), out, capacity) ? 1 : 0;
 }
 
 int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info)
@@ -2772,16 +2771,10 @@ int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, 
   static_assert(sizeof(ScTickPairShapeInfo) == 6u * sizeof(uint32_t) && kPsInfoWords >= 6u, "the device writes the report word by word");
   static_assert(kPairShapesSatEps == SC_TICK_PAIR_SHAPES_SAT_EPS, "the separating-axis epsilon differs from the header's");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_PAIR_SHAPES)) return fail(c, "the last scTickRun did not request SC_TICK_PAIR_SHAPES");
-  if (c->pairsPending) return fail(c, "touching pairs are ready after scTickRunPairs");
   const PairShapeState& e = c->pairShapes;
-  if (!e.ctl) return fail(c, "touching pairs were switched off since the last scTickRun");
-  if (!joinPairs(c)) return 0;
-  if (!d2h(c, info, e.info, sizeof *info) || !sync(c)) return 0;
-  const uint32_t k = std::min(std::min(info->touching, e.maxTouching), pairs2 ? capacity : 0u);
-  if (k && (!d2h(c, pairs2, e.list, (size_t)k * sizeof(uint2)) || !sync(c))) return 0;
-  return 1;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES", true, nullptr,
+                                 "touching pairs are ready after scTickRunPairs", e.ctl != nullptr, "touching pairs were switched off since the last scTickRun")) return 0;
+  return readReportAndRecords(c, info, e.info, &ScTickPairShapeInfo::touching, e.maxTouching, e.list, sizeof(uint2), pairs2, capacity) ? 1 : 0;
 }
 
 int scTickSetRayShapes(ScTickContext* c, uint32_t mode)
@@ -2792,7 +2785,7 @@ int scTickSetRayShapes(ScTickContext* c, uint32_t mode)
   if (mode == c->rayShapes) return 1;
   if (!bind(c) || !sync(c)) return 0;
   c->rayShapes = mode;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
+  dropCaptures(c);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
   return 1;
 }
 
@@ -2814,7 +2807,7 @@ int scTickSetSweepShapes(ScTickContext* c, uint32_t mode)
   if (!bind(c) || !sync(c)) return 0;
   if (mode == SC_TICK_SWEEP_SHAPES_EXACT && !c->sweepInfo && !dalloc(c, c->sweepInfo, kSweepInfoWords)) return 0;
   c->sweepShapes = mode;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
+  dropCaptures(c);       // a captured tick holds the other instance; no epoch bump: the bins are not concerned
   return 1;
 }
 
@@ -2829,11 +2822,9 @@ int scTickGetSweepShapeInfo(ScTickContext* c, ScTickSweepShapeInfo* info)
 {
   static_assert(sizeof(ScTickSweepShapeInfo) == kSweepInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_SWEEPS)) return fail(c, "the last scTickRun did not request SC_TICK_SWEEPS");
-  if (!c->lastSweepsExact || !c->sweepInfo) return fail(c, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined");
-  if (c->pairsPending) return fail(c, "the sweep shape report is ready after scTickRunPairs");
-  if (!joinPairs(c)) return 0;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS",
+                                 c->lastSweepsExact && c->sweepInfo, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined",
+                                 "the sweep shape report is ready after scTickRunPairs", true, nullptr)) return 0;
   if (!d2h(c, info, c->sweepInfo, sizeof *info) || !sync(c)) return 0;
   return 1;
 }
@@ -2860,20 +2851,9 @@ int scTickSetAnchoredRays(ScTickContext* c, uint32_t count, const uint32_t* anch
   // The same count as the current set: only the device arrays are rewritten, behind whatever is queued on the tick stream (the pair
   // half of a split flow reads the snapshot, never these arrays) -- no epoch bump, so no learn tick, and a captured graph stays valid.
   if (count != c->anchored.count) {
-    if (!sync(c)) return 0;
-    if (count > c->anchoredCap) {
-      AnchoredRayState& a = c->anchored;
-      dfree(c, const_cast<float4*>(a.origin)); dfree(c, const_cast<float4*>(a.dir)); dfree(c, const_cast<uint2*>(a.anchor)); dfree(c, a.hits);
-      dfree(c, a.snapOrigin); dfree(c, a.snapDir); dfree(c, a.snapSkip);
-      a = AnchoredRayState{}; c->anchoredCap = 0;
-      const uint32_t want = std::max(count, 1024u);
-      float4 *lo = nullptr, *lv = nullptr, *so = nullptr, *sd = nullptr; uint2* w = nullptr; uint32_t* ss = nullptr; RayHit48* h = nullptr;
-      if (!dalloc(c, lo, want, false) || !dalloc(c, lv, want, false) || !dalloc(c, w, want, false) || !dalloc(c, h, want) ||
-          !dalloc(c, so, (size_t)want * kMaxParity) || !dalloc(c, sd, (size_t)want * kMaxParity) || !dalloc(c, ss, (size_t)want * kMaxParity)) return 0;
-      a.origin = lo; a.dir = lv; a.anchor = w; a.hits = h; a.snapOrigin = so; a.snapDir = sd; a.snapSkip = ss; c->anchoredCap = want;
-    }
-    c->anchored.count = count;
-    c->topoEpoch++;                    // a captured frame holds the old batch size
+    AnchoredRayState& a = c->anchored;
+    if (!sync(c) || !growBatch(c, c->anchoredCap, a.count, count, batchArray(a.origin), batchArray(a.dir), batchArray(a.anchor), batchArray(a.hits, true),
+                               batchArray(a.snapOrigin, true, kMaxParity), batchArray(a.snapDir, true, kMaxParity), batchArray(a.snapSkip, true, kMaxParity))) return 0;
   }
   c->hAnchor = an;
   if (!count) return 1;
@@ -2962,7 +2942,7 @@ int scTickSetGraphMode(ScTickContext* c, int enable)
   if (!c) return 0;
   if (!bind(c)) return 0;
   c->graphMode = enable != 0;
-  if (!enable) { sync(c); dropGraphs(c->graph); dropGraphs(c->pairGraph); }
+  if (!enable) { sync(c); dropCaptures(c); }
   return 1;
 }
 
@@ -3034,7 +3014,7 @@ int scTickSetBindRuns(ScTickContext* c, uint32_t maxRuns)
   if (maxRuns && !c->sort.pipeline) return fail(c, "scTickSetBindRuns needs scTickSetDrawSortTable first (the touch bitmap is sized by its material_count)");
   if (maxRuns > c->cap) return fail(c, "max_runs exceeds the context's capacity (a list has at most one run per draw)");
   if (!bind(c) || !sync(c)) return 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph);       // a captured tick holds the old buffers (or none)
+  dropCaptures(c);       // a captured tick holds the old buffers (or none)
   return reallocBindRuns(c, maxRuns) ? 1 : 0;
 }
 
@@ -3214,7 +3194,7 @@ int scTickSetTrafficSensors(ScTickContext* c, int enable, float frontRayLength, 
     c->halo = wantHalo;
   }
   c->sensors = enable != 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
+  dropCaptures(c); c->topoEpoch++;
   return 1;
 }
 
@@ -3476,7 +3456,7 @@ int scTickCommDestroy(ScTickContext* c)
   sync(c);
   const RcclApi* r = needRccl(c);
   // captured steps hold ncclSend / ncclRecv nodes bound to this communicator and to the peers' ranks
-  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;
+  dropCaptures(c); c->topoEpoch++;
   if (r) r->CommDestroy(c->comm);
   c->comm = nullptr; c->commSize = 0; c->commRank = 0;
   return 1;
@@ -3486,7 +3466,7 @@ int scTickCommSetPeers(ScTickContext* c, const int32_t peerRank[8])
 {
   if (!c || !peerRank) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !sync(c)) return 0;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;       // a captured exchange names the old ranks
+  dropCaptures(c); c->topoEpoch++;       // a captured exchange names the old ranks
   for (int d = 0; d < 8; ++d) c->peer[d] = peerRank[d];
   c->peersSet = true;
   return 1;
@@ -3517,7 +3497,7 @@ int scTickCommInit(ScTickContext* c, const uint8_t id[SC_TICK_COMM_ID_BYTES], ui
   std::memcpy(&u, id, sizeof u);
   if (!ncclOk(c, r, r->CommInitRank(&c->comm, (int)worldSize, u, (int)rank), "ncclCommInitRank")) { c->comm = nullptr; return 0; }
   c->commSize = worldSize; c->commRank = rank;
-  dropGraphs(c->graph); dropGraphs(c->pairGraph); c->topoEpoch++;       // (a graph captured against an earlier communicator must not be replayed)
+  dropCaptures(c); c->topoEpoch++;       // (a graph captured against an earlier communicator must not be replayed)
   // the messages of both tick parities live in buffers of the library's own (a caller that runs its own transport binds
   // its buffers with scTickBindBorderBuffers instead and never comes here)
   for (uint32_t q = 0; q < kMaxParity; ++q)

@@ -426,7 +426,7 @@ constexpr uint32_t kPcInfoWords = 8;
 constexpr uint32_t kContactNone = 0, kContactRoundRound = 1, kContactRoundBox = 2, kContactBoxFaceA = 3, kContactBoxFaceB = 4, kContactBoxEdge = 5,
                    kContactDeep = 1u << 8, kContactDegenerate = 1u << 9;      // == SC_TICK_CONTACT_*
 constexpr float kPairContactsEdgeEps = 1e-4f;   // == SC_TICK_PAIR_CONTACTS_EDGE_EPS
-// ---- pair manifolds (k_pair_manifolds, sc_tick_pair_shapes.hip; include/sc_tick.h "pair manifolds"): up to four points per entry of the
+// ---- pair manifolds (k_pair_manifolds, sc_tick_pair_manifolds.hip; include/sc_tick.h "pair manifolds"): up to four points per entry of the
 // touching list, written behind the contact records while the list's running count is still up.  All null until scTickSetPairManifolds:
 // nothing is launched.
 struct PairManifoldState {

@@ -463,6 +463,11 @@ def test_anchored_ray_api_errors(oracle):
         t.anchored_ray_hits()
     t.run(ANCH)                                                                  # an empty set is fine
     assert len(t.anchored_ray_hits()) == 0 and len(t.anchored_ray_anchors()) == 0
+    t.run(ANCH | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="anchored ray hits are ready after scTickRunPairs"):
+        t.anchored_ray_hits()
+    t.run_pairs()
+    assert len(t.anchored_ray_hits()) == 0
     rng = np.random.default_rng(113)
     k = 64
     q = [rng.integers(0, w.n, k).astype(np.uint32), *local_rays(rng, k)]

@@ -308,6 +308,10 @@ def test_pair_contact_api_errors_and_sizes(oracle):
     t.run(SHAPES)
     with pytest.raises(capi.ScTickError, match="pair contacts were not enabled"):
         t.read_pair_contacts()
+    t.run(SHAPES | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="pair contacts were not enabled"):      # ... which is said before the pending half is
+        t.read_pair_contacts()
+    t.run_pairs()
     t.set_pair_contacts(True)
     with pytest.raises(capi.ScTickError, match="pair contacts were not enabled"):      # enabled since: the last run still wrote none
         t.read_pair_contacts()

@@ -278,6 +278,18 @@ def test_refusals_carry_the_librarys_message(oracle):
     t.run(EV)                                             # (switching the pipeline off again leaves the events usable)
     check_pairs(t, sets[0])
     t.set_pair_events(0, 0)
+    with pytest.raises(capi.ScTickError, match="pair events were switched off since the last scTickRun"):
+        t.pair_events()
     with pytest.raises(capi.ScTickError, match="needs scTickSetPairEvents first"):
         t.run(EV)
+    t.set_pair_events(64, 64)
+    t.run(FLAGS | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_PAIR_EVENTS"):      # the missing flag is named before the pending half
+        t.pair_events()
+    t.run_pairs()
+    t.run(EV | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="pair events are ready after scTickRunPairs"):
+        t.pair_events()
+    t.run_pairs()
+    t.pair_events()                                       # ... and readable behind it
     t.close()

@@ -283,6 +283,10 @@ def test_pair_manifold_api_errors_and_sizes(oracle):
     t.run(SHAPES)
     with pytest.raises(capi.ScTickError, match="pair manifolds were not enabled"):
         t.read_pair_manifolds()
+    t.run(SHAPES | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="pair manifolds were not enabled"):      # ... which is said before the pending half is
+        t.read_pair_manifolds()
+    t.run_pairs()
     t.set_pair_manifolds(True)
     with pytest.raises(capi.ScTickError, match="pair manifolds were not enabled"):      # enabled since: the last run still wrote none
         t.read_pair_manifolds()

@@ -352,9 +352,15 @@ def test_pair_shape_api_errors(oracle):
     t.run(SHAPES)
     check(t, col, 64)
     t.set_pair_shapes(0)
+    with pytest.raises(capi.ScTickError, match="touching pairs were switched off since the last scTickRun"):
+        t.read_pair_shapes()
     with pytest.raises(capi.ScTickError, match="needs scTickSetPairShapes first"):
         t.run(SHAPES)
     t.run(FLAGS)
+    t.run(FLAGS | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_PAIR_SHAPES"):      # the missing flag is named before the pending half
+        t.read_pair_shapes()
+    t.run_pairs()
     t.close()
     # a context without a broadphase cannot enable the pass; one without colliders lists every pair on its AABB answer
     t = WorldTick.from_world(w, broadphase=False)

@@ -442,7 +442,14 @@ def test_ray_shape_api_errors(oracle):
     with pytest.raises(capi.ScTickError, match="scTickRunPairs is pending"):
         t.set_ray_shapes(AABB)
     assert t.ray_shapes() == EXACT
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_RAYS"):      # the missing flag is named before the pending half
+        t.ray_hits()
     t.run_pairs()
+    t.run(RAYS | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="ray hits are ready after scTickRunPairs"):
+        t.ray_hits()
+    t.run_pairs()
+    assert len(t.ray_hits()) == 0
     t.set_ray_shapes(AABB)
     assert t.ray_shapes() == AABB
     # EXACT mode on a context without colliders: nothing is refined, the answers are the AABB mode's

@@ -374,7 +374,23 @@ def test_sweep_shape_api_errors(oracle):
     with pytest.raises(capi.ScTickError, match="scTickRunPairs is pending"):
         t.set_sweep_shapes(AABB)
     assert t.sweep_shapes() == EXACT
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_SWEEPS"):      # the missing flag is named before the pending half
+        t.sweep_shape_info()
+    with pytest.raises(capi.ScTickError, match="did not request SC_TICK_SWEEPS"):
+        t.sweep_hits()
     t.run_pairs()
+    t.run(SWEEPS | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="the sweep shape report is ready after scTickRunPairs"):
+        t.sweep_shape_info()
+    with pytest.raises(capi.ScTickError, match="sweep hits are ready after scTickRunPairs"):
+        t.sweep_hits()
+    t.run_pairs()
+    t.set_sweep_shapes(AABB)
+    t.run(SWEEPS | capi.SPLIT_PAIRS)
+    with pytest.raises(capi.ScTickError, match="SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined"):      # ... and so is the mode of that run
+        t.sweep_shape_info()
+    t.run_pairs()
+    t.set_sweep_shapes(EXACT)
     # EXACT mode on a context without colliders: nothing is refined, the answers are the AABB mode's
     set_queries(t, q)
     t.run(SWEEPS)

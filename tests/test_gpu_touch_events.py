@@ -530,6 +530,8 @@ def test_refusals_carry_the_librarys_message(oracle):
     t.run(TE)                                               # (switching the pipeline off again leaves the events usable)
     assert t.touch_events()[2] == dict(begun=0, ended=0, tracked=1, resync=0, overflow=0, events_truncated=0)
     t.set_touch_events(0, 0)                                # frees the buffers: the flag is refused again
+    with pytest.raises(capi.ScTickError, match="touch events were switched off since the last scTickRun"):
+        t.touch_events()
     with pytest.raises(capi.ScTickError, match="needs scTickSetTouchEvents first"):
         t.run(TE)
     t.run(FLAGS)
