@@ -191,7 +191,9 @@ int scTickSetFrustumPlanes(ScTickContext* ctx, const float planes24[24], int val
 int scTickGetFrustumPlanes(ScTickContext* ctx, float planes24[24], int* valid);
 /* CullingState::freezeCulling (sc_world_partition.cpp:1227-1233) */
 int scTickSetFreezeCulling(ScTickContext* ctx, int freeze);
-/* WorldStreamingBudgets::maxDrawsBudget for the next SC_TICK_DRAWS (overrides the create-time value; 0 = unlimited) */
+/* WorldStreamingBudgets::maxDrawsBudget for the next SC_TICK_DRAWS (overrides the create-time value; 0 = unlimited).  May be
+ * called between any two runs, with graph replay on too: a changed budget re-captures the next run (a captured tick holds the
+ * budget by value); an unchanged one costs nothing. */
 int scTickSetDrawBudget(ScTickContext* ctx, uint32_t max_draws);
 
 /* ---- the tick ---- */
@@ -228,7 +230,11 @@ int scTickSetTileGrid(ScTickContext* ctx, uint32_t tile_x, uint32_t tile_z, uint
 int scTickSetBorderCapacity(ScTickContext* ctx, uint32_t records_per_ring_sector);
 /* size in bytes of the fixed-capacity border message of direction d (same on both sides of an edge) */
 uint32_t scTickBorderBytes(ScTickContext* ctx, uint32_t direction);
-/* caller-owned device buffers (e.g. torch tensors) of at least scTickBorderBytes(d) bytes each */
+/* caller-owned device buffers (e.g. torch tensors) of at least scTickBorderBytes(d) bytes each.  scTickBindBorderBuffers and
+ * scTickBindBorderBuffersParity may be called again between two steps with other buffers, with graph replay on too: while
+ * captured graphs exist, a changed address waits for the work in flight and re-captures
+ * the next tick half and pair half (a captured pack or merge holds the addresses by value); the same addresses cost nothing.
+ * The buffers bound before must stay allocated until that call returns. */
 int scTickBindBorderBuffers(ScTickContext* ctx, uint32_t direction, void* send_device_ptr, void* recv_device_ptr);
 int scTickRunPairs(ScTickContext* ctx);
 /* Pipelined tiles.  With a pairs stream set (hipStream_t; NULL switches it off), scTickRunPairs queues the merge, the ray
@@ -1311,7 +1317,10 @@ int scTickSetProfilingKernels(ScTickContext* ctx, uint32_t mask);
 int scTickGetKernelTimes(ScTickContext* ctx, uint32_t kernel, float* ms, uint32_t capacity, uint32_t* count);
 /* capture the current stage sequence into a hipGraph and replay it on scTickRun (0 = eager launches).  scTickTileStep on
  * an in-order tile replays the whole step (RCCL group included) as one graph; on a pipelined tile each half of the step is
- * a graph of its own, on its own stream.  Not combinable with the frame read-back. */
+ * a graph of its own, on its own stream.  Not combinable with the frame read-back.
+ * Every setter of this header may be called between two runs while graph replay is on.  The next run re-captures where a
+ * captured graph would hold a stale value -- a count, a budget, a mode, a buffer address -- and replays where nothing it holds
+ * changed (tests/test_gpu_graph_setters.py; DESIGN.md section 6, "what invalidates a capture"). */
 int scTickSetGraphMode(ScTickContext* ctx, int enable);
 /* native stream handle (hipStream_t) for callers that order their own work against the tick */
 void* scTickGetStream(ScTickContext* ctx);

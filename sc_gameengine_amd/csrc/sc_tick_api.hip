@@ -1781,6 +1781,9 @@ int scTickSetDrawSortTable(ScTickContext* c, const uint8_t* pipelineOfMaterial, 
 int scTickSetDrawBudget(ScTickContext* c, uint32_t maxDraws)
 {
   if (!c) return 0;
+  if (maxDraws == c->desc.max_draws_budget) return 1;
+  // a captured tick holds the budget by value (the folded emission, the emission and sort launches, the run table's bound): not in the key
+  if (c->graphMode) { if (!bind(c) || !sync(c)) return 0; dropGraphs(c->graph); }
   c->desc.max_draws_budget = maxDraws;
   return 1;
 }
@@ -2197,9 +2200,25 @@ int scTickSetBorderCapacity(ScTickContext* c, uint32_t recordsPerRingSector)
   return 1;
 }
 
+// a captured tick half (the pack), pair half (the merge) or whole step holds the message buffers' addresses by value: a changed binding
+// drops every capture, behind a sync where one exists (a graph in flight still reads the old buffers)
+static bool forgetBorderCaptures(ScTickContext* c)
+{
+  bool any = false;
+  for (const CapturedGraph& g : c->graph) any = any || g.exec;
+  for (const CapturedGraph& g : c->pairGraph) any = any || g.exec;
+  if (!any) return true;
+  if (!bind(c) || !sync(c)) return false;
+  dropCaptures(c);
+  return true;
+}
+
 int scTickBindBorderBuffers(ScTickContext* c, uint32_t dir, void* send, void* recv)
 {
   if (!c || dir > 7u) return c ? fail(c, "bad direction") : 0;
+  bool same = c->d.borderSend[dir] == send && c->d.borderRecv[dir] == recv;
+  for (auto& a : c->alt) same = same && a.borderSend[dir] == send && a.borderRecv[dir] == recv;
+  if (!same && !forgetBorderCaptures(c)) return 0;
   c->d.borderSend[dir] = static_cast<uint32_t*>(send);
   c->d.borderRecv[dir] = static_cast<uint32_t*>(recv);
   for (auto& a : c->alt) { a.borderSend[dir] = static_cast<uint32_t*>(send); a.borderRecv[dir] = static_cast<uint32_t*>(recv); }
@@ -2210,6 +2229,9 @@ int scTickBindBorderBuffersParity(ScTickContext* c, uint32_t parity, uint32_t di
 {
   if (!c) return 0;
   if (dir > 7 || parity >= kMaxParity) return fail(c, "direction must be 0..7 and parity 0..3");
+  uint32_t* const oldSend = parity == 0 ? c->d.borderSend[dir] : c->alt[parity - 1u].borderSend[dir];
+  uint32_t* const oldRecv = parity == 0 ? c->d.borderRecv[dir] : c->alt[parity - 1u].borderRecv[dir];
+  if ((oldSend != send || oldRecv != recv) && !forgetBorderCaptures(c)) return 0;
   if (parity == 0) { c->d.borderSend[dir] = static_cast<uint32_t*>(send); c->d.borderRecv[dir] = static_cast<uint32_t*>(recv); }
   else { c->alt[parity - 1u].borderSend[dir] = static_cast<uint32_t*>(send); c->alt[parity - 1u].borderRecv[dir] = static_cast<uint32_t*>(recv); }
   return 1;
