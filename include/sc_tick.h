@@ -688,7 +688,9 @@ int scTickRemoveEntities(ScTickContext* ctx, const uint32_t* dense_indices, uint
  * candidates are the world AABBs of the broadphase, tested with the reference's own slab arithmetic
  * (intersectRayAABB, tools/world_editor/editor_core/editor_core.cpp:438-470); equal distances go to the lower id.
  * On a tiled world a context answers for the boxes registered in its own sectors, which includes the neighbours' boxes
- * that reach into them (the queries run after the border merge); the part of a ray beyond the tile is the neighbour's. */
+ * that reach into them (the queries run after the border merge); the part of a ray beyond the tile is the neighbour's.
+ * The answer equals brute force over every registered box with that slab test, hits at t == max_dist included: the sector walk
+ * is padded by the roundings of the segment's end, so a box whose face lies an ulp past it, across a sector boundary, is found. */
 typedef struct ScTickRayHit     /* RaycastHit, sc_physics.h:106-114 */
 {
   uint32_t hit;                /* 0 / 1 */
@@ -699,7 +701,9 @@ typedef struct ScTickRayHit     /* RaycastHit, sc_physics.h:106-114 */
   uint32_t layer;              /* the box's collision group */
   uint32_t pad[2];
 } ScTickRayHit;
-/* origin3 / dir3: [count][3]; max_dist, mask: [count].  The set stays until it is replaced (count 0 clears it). */
+/* origin3 / dir3: [count][3]; max_dist, mask: [count].  The set stays until it is replaced (count 0 clears it).  Fails -- and leaves
+ * the previous set in place -- when an origin, a direction or a max_dist is not finite, or a direction's squared length
+ * (x*x + y*y) + z*z overflows fp32.  A negative max_dist and a direction of |dir|^2 <= 1e-6 are accepted and answered with a miss. */
 int scTickSetRayQueries(ScTickContext* ctx, uint32_t count, const float* origin3, const float* dir3,
                         const float* max_dist, const uint32_t* mask);
 /* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_RAYS) (after scTickRunPairs on a tiled world) */
@@ -722,7 +726,9 @@ int scTickReadRayHits(ScTickContext* ctx, ScTickRayHit* hits, uint32_t capacity,
  *   test        lo' = lo - e, hi' = hi + e per component, then the rays' slab test of (start, ndir, far) against (lo', hi');
  *               the smallest t wins, equal t goes to the lower id
  * On a tiled world the rays' rule holds: a context answers for the boxes registered in its own sectors (the neighbours' boxes that
- * reach into them included); the part of a sweep beyond the tile is the neighbour's.  A pipelined tile sees what its rays see. */
+ * reach into them included); the part of a sweep beyond the tile is the neighbour's.  A pipelined tile sees what its rays see.
+ * The answer equals brute force over every registered box with that test, hits at t == far and the closed containment of an overlap
+ * test included: the sector walk reaches the sweeper's radius and the roundings of the segment's end beyond the segment. */
 typedef struct ScTickSweepHit   /* SweepHit, sc_physics.h:116; laid out like ScTickRayHit */
 {
   uint32_t hit;                /* 0 / 1 */

@@ -2583,15 +2583,20 @@ int scTickSetRayQueries(ScTickContext* c, uint32_t count, const float* origin3, 
 {
   if (!c) return 0;
   if (count && (!origin3 || !dir3 || !maxDist || !mask)) return fail(c, "null argument");
-  if (!bind(c) || !sync(c)) return 0;
-  if (!growBatch(c, c->rayCap, c->rays.count, count, batchArray(c->rays.origin), batchArray(c->rays.dir), batchArray(c->rays.hits, true))) return 0;
-  if (!count) return 1;
+  // the kernel never sees a value it has no answer for: checked before anything changes, so a refused call leaves the previous set in place
+  // (a negative max_dist and a direction of |dir|^2 <= 1e-6 have an answer: a miss)
   std::vector<float4> o(count), dd(count);
   for (uint32_t i = 0; i < count; ++i) {
     o[i] = make_float4(origin3[3 * i], origin3[3 * i + 1], origin3[3 * i + 2], maxDist[i]);
     float w; std::memcpy(&w, &mask[i], 4);
     dd[i] = make_float4(dir3[3 * i], dir3[3 * i + 1], dir3[3 * i + 2], w);
+    const float v[7] = { o[i].x, o[i].y, o[i].z, o[i].w, dd[i].x, dd[i].y, dd[i].z };
+    for (float x : v) if (!std::isfinite(x)) return fail(c, "ray queries: origin, dir and max_dist must be finite");
+    if (!std::isfinite((dd[i].x * dd[i].x + dd[i].y * dd[i].y) + dd[i].z * dd[i].z)) return fail(c, "ray queries: the direction's squared length overflows fp32");
   }
+  if (!bind(c) || !sync(c)) return 0;
+  if (!growBatch(c, c->rayCap, c->rays.count, count, batchArray(c->rays.origin), batchArray(c->rays.dir), batchArray(c->rays.hits, true))) return 0;
+  if (!count) return 1;
   if (!h2d(c, const_cast<float4*>(c->rays.origin), o.data(), (size_t)count * 16u) ||
       !h2d(c, const_cast<float4*>(c->rays.dir), dd.data(), (size_t)count * 16u)) return 0;
   return sync(c) ? 1 : 0;

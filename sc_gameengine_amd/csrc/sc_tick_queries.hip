@@ -335,14 +335,21 @@ __device__ __forceinline__ void castSegmentWave(WaveRay& w, const DeviceState& d
   // Sweeps: the extent grown by `reach` on every side.  That suffices: a box whose grown form the segment meets has a point within
   // `reach` (per axis, in x and z) of a point of the segment; that point of the box lies in a sector of the grown extent, and a box is
   // registered in every sector it overlaps -- or is in the big list.  The long-segment skip test below grows by the same amount.
-  float fx0, fx1, fz0, fz1;
-  if (kSweep) {
-    fx0 = floorf(((o[0] < ex ? o[0] : ex) - reach) * p.invSector) - p.binOx; fx1 = floorf(((o[0] < ex ? ex : o[0]) + reach) * p.invSector) - p.binOx;
-    fz0 = floorf(((o[2] < ez ? o[2] : ez) - reach) * p.invSector) - p.binOz; fz1 = floorf(((o[2] < ez ? ez : o[2]) + reach) * p.invSector) - p.binOz;
-  } else {
-    fx0 = floorf((o[0] < ex ? o[0] : ex) * p.invSector) - p.binOx; fx1 = floorf((o[0] < ex ? ex : o[0]) * p.invSector) - p.binOx;
-    fz0 = floorf((o[2] < ez ? o[2] : ez) * p.invSector) - p.binOz; fz1 = floorf((o[2] < ez ? ez : o[2]) * p.invSector) - p.binOz;
-  }
+  //
+  // The extent must hold every box the CLOSED slab test can accept, and the two are rounded independently.  With u = 2^-24 and dir.x > 0
+  // (the other signs and z alike), rayBox accepts a box only if t1 = fl(fl(mn.x - o.x) * fl(1 / dir.x)) <= maxDist -- three roundings:
+  // mn.x - o.x <= dir.x * maxDist * (1 + 3.1u) -- while the end is ex = fl(o.x + fl(dir.x * maxDist)) >= o.x + dir.x * maxDist - u * (maxDist
+  // + |ex|).  So mn.x <= ex + 4.1u * maxDist + u * |ex|: a face a few ulps of max(|o|, |ex|, maxDist) PAST the rounded end is still hit at
+  // t == maxDist, and when a sector boundary lies in between, the box is registered only beyond it.  A sweep adds the roundings of the grown
+  // face fl(mn.x - grow) and of fl(ex + reach), each below u * (|ex| + reach); a zero-length sweep is the same with maxDist = 0.  (On the
+  // origin's side nothing is lost: fl(mx.x - o.x) >= 0 exactly when mx.x >= o.x, and floorf(x * invSector) is monotone.)  All of it stays
+  // below 7u * (|o| + |ex| + maxDist + reach) per axis; the extent is padded by 16u of that sum, taken over both axes, on every side and
+  // before the clamp to the grid.  The pad is 1 m where the sum is 2^20 m (1 049 km): below that the long-segment skip test's metre covers
+  // the same roundings, so the skip test stays as it was.  An infinite sum pads to the whole grid; a NaN visits no bin, as before.
+  const float ax = fabsf(o[0]) > fabsf(ex) ? fabsf(o[0]) : fabsf(ex), az = fabsf(o[2]) > fabsf(ez) ? fabsf(o[2]) : fabsf(ez);
+  const float padded = reach + 0x1p-20f * ((ax > az ? ax : az) + maxDist + reach);
+  const float fx0 = floorf(((o[0] < ex ? o[0] : ex) - padded) * p.invSector) - p.binOx, fx1 = floorf(((o[0] < ex ? ex : o[0]) + padded) * p.invSector) - p.binOx;
+  const float fz0 = floorf(((o[2] < ez ? o[2] : ez) - padded) * p.invSector) - p.binOz, fz1 = floorf(((o[2] < ez ? ez : o[2]) + padded) * p.invSector) - p.binOz;
   const float gridX = (float)p.binSX - 1.0f, gridZ = (float)p.binSZ - 1.0f;
   bool anyOverflow = false;
   if (p.binSX && fx1 >= 0.0f && fz1 >= 0.0f && fx0 <= gridX && fz0 <= gridZ) {

@@ -163,6 +163,62 @@ def test_ray_api_errors():
     t.close()
 
 
+REFUSED_RAYS = [(0, (3, 0), np.nan, "finite"), (0, (5, 2), np.inf, "finite"), (0, (0, 1), -np.inf, "finite"),
+                (1, (7, 0), np.nan, "finite"), (1, (2, 1), np.inf, "finite"), (1, (9, 2), -np.inf, "finite"),
+                (2, (4,), np.nan, "finite"), (2, (6,), np.inf, "finite"), (2, (8,), -np.inf, "finite"),
+                (1, (1, 0), 2e19, "overflows fp32"), (1, (11, 2), -1.9e19, "overflows fp32")]
+
+
+def _refusal_world(oracle):
+    w = worlds.random_world(300, seed=63, spread=60.0)
+    ow = worlds.oracle_world(oracle, w, camera=False); ow.transform_system()
+    mn, mx = ow.world_aabbs(); ow.close()
+    rng = np.random.default_rng(64)
+    o, d, md, mask = random_rays(rng, 64, 70.0)
+    mask[:] = 0xFFFFFFFF
+    return w, mn, mx, [o, d, md, mask]
+
+
+@pytest.mark.parametrize("arg,idx,bad,msg", REFUSED_RAYS)
+def test_ray_queries_refuse_what_the_kernel_has_no_answer_for(oracle, arg, idx, bad, msg):
+    """a non-finite origin, direction or max_dist, and a direction whose squared length (x*x + y*y) + z*z overflows fp32: refused with
+    a last-error text, like the sweeps and the anchored rays refuse them"""
+    w, mn, mx, rays = _refusal_world(oracle)
+    t = WorldTick.from_world(w, broadphase=True)
+    broken = [x.copy() for x in rays]
+    broken[arg][idx] = bad
+    with pytest.raises(capi.ScTickError, match=msg):
+        t.set_ray_queries(*broken)
+    assert msg.encode() in t.lib.scTickGetLastError(t.ctx)
+    t.close()
+
+
+def test_a_refused_ray_set_leaves_the_old_set_answering(oracle):
+    w, mn, mx, rays = _refusal_world(oracle)
+    want = oracle.raycast_boxes(mn, mx, w.group, w.mask, *rays)
+    assert 5 < want["hit"].sum() < len(want)
+    t = WorldTick.from_world(w, broadphase=True)
+    t.set_ray_queries(*rays)
+    t.run(FLAGS)
+    compare(t.ray_hits(), want)
+    for arg, idx, bad, msg in REFUSED_RAYS:
+        broken = [x[:40].copy() for x in rays]                                  # (another count: a refusal after the buffers moved would show)
+        broken[arg][idx] = bad
+        with pytest.raises(capi.ScTickError, match=msg):
+            t.set_ray_queries(*broken)
+    t.run(FLAGS)
+    compare(t.ray_hits(), want)
+    # what stays accepted, and a miss: a negative max_dist, a direction of |dir|^2 <= 1e-6, the largest finite max_dist
+    odd = [x.copy() for x in rays]
+    odd[2][0] = -1.0; odd[1][1] = np.float32([1e-4, 0, 1e-4]); odd[2][2] = np.finfo(np.float32).max
+    t.set_ray_queries(*odd)
+    t.run(FLAGS)
+    got = t.ray_hits()
+    compare(got, oracle.raycast_boxes(mn, mx, w.group, w.mask, *odd))
+    assert got["hit"][0] == 0 and got["hit"][1] == 0
+    t.close()
+
+
 def test_occupancy_queries_match_is_occupied_world(oracle):
     """scTickQueryOccupied against the oracle's isOccupiedWorld (sc_traffic_spawner.cpp:93-116) on a config-5 world whose
     vehicles keep moving: points on, near and far from agents, radii around the decision boundary, strict '<'."""
