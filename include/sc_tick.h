@@ -64,6 +64,7 @@ enum {
   SC_TICK_BIND_RUNS   = 1u << 13,  /* with DRAWS | SORT_DRAWS: also the bind runs of the sorted list and the material touch set (scTickSetBindRuns) */
   SC_TICK_PAIR_SHAPES = 1u << 14,  /* with BROADPHASE: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes) */
   SC_TICK_TOUCH_EVENTS = 1u << 15, /* with BROADPHASE: report which pairs begun and which ended TOUCHING since the last run with this flag (scTickSetTouchEvents) */
+  SC_TICK_OVERLAPS    = 0x00010000u, /* bit 16.  With BROADPHASE: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -1304,6 +1305,78 @@ int scTickGetSweepShapes(ScTickContext* ctx, uint32_t* mode);
 /* of the last scTickRun(... | SC_TICK_SWEEPS) (after scTickRunPairs in a split flow); fails when that run did not carry the flag or swept
  * in AABB mode.  Synchronises; copies the 16 bytes of `info`. */
 int scTickGetSweepShapeInfo(ScTickContext* ctx, ScTickSweepShapeInfo* info);
+
+/* ---- overlap queries: collider volumes answered from this tick's boxes ----
+ * "Which entities are inside this volume": a trigger zone, a blast radius, a spawn-clearance box, an editor's box select, what a
+ * kinematic body stands in.  The rays and the sweeps answer "what does this segment meet first", the pair search "which boxes meet each
+ * other"; an overlap query is a COLLIDER WITHOUT AN ENTITY, tested against the world exactly as the touching pairs test a pair.  Answered
+ * where the rays are: after the bins are filled and before the pair search consumes them.
+ * This build's OWN SPEC, like the rays, the sweeps and the touching pairs.  All arithmetic is fp32, unfused, left to right, with correctly
+ * rounded / and sqrt; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   volume q    a collider type (SC_TICK_COLLIDER_BOX, _SPHERE or _CAPSULE), its values stored as scTickUploadColliders stores them -- the
+ *               record (ex, ey, ez, radius) is a box's half extents and 0, (0, 0, 0, radius) for a sphere, (0, max(0, half_height), 0,
+ *               radius) for a capsule --, an affine world matrix (mat16, column-major like scTickUploadWorldMatrices; its last row is
+ *               not read), a mask and a skip_id (NULL: 0xFFFFFFFF, none)
+ *   volume box  the collider box rule (scTickUploadColliders) applied to the volume's matrix M: n_k = (M[0,k]^2 + M[1,k]^2) + M[2,k]^2;
+ *               pad = 0 for a box, radius * sqrt(max(n_0, n_1, n_2)) for a sphere -- m = (n_2 < n_1) ? n_1 : n_2, then (n_0 < m) ? m : n_0 --
+ *               and radius * sqrt((n_0 < n_2) ? n_2 : n_0) for a capsule; h_r = ((|M[r,0]|*ex + |M[r,1]|*ey) + |M[r,2]|*ez) + pad;
+ *               min_r = M[r,3] - h_r, max_r = M[r,3] + h_r
+ *   candidates  every record the ray queries see -- this tick's bins, big list and sector overflow list.  A record passes when
+ *               (group & mask) != 0 and the proxy's own mask is not empty (the rays' filter), its id is not skip_id, and its box meets the
+ *               volume's box under the pair search's rule: closed intervals on all three axes, box.min <= volume.max and volume.min <=
+ *               box.max, positive comparisons only.  A NaN in the volume's box therefore meets nothing: zero hits, reported, not an error.
+ *   SC_TICK_OVERLAP_SHAPES_AABB   every candidate is a hit.
+ *   SC_TICK_OVERLAP_SHAPES_EXACT  a candidate whose entity is refinable as a member of a touching pair is -- colliders were uploaded, the
+ *               id's rank is this context's, e = id & 0xFFFFFF is below the entity count, the collider type of e is BOX, SPHERE or
+ *               CAPSULE, and the three n_k of e's world matrix of this tick are finite and positive -- is a hit unless the touching pairs'
+ *               routine for the two types says "apart" ("touching pairs": round-round, round-box, box-box), with the ENTITY AS MEMBER A
+ *               AND THE VOLUME AS MEMBER B -- the order a pair (i, j), i < j, has when the volume is given the id n + q.  A candidate that
+ *               cannot be refined (a BOUNDS proxy, a degenerate matrix, a context without colliders) stays a hit on its box answer, and so
+ *               does every candidate of a volume whose own n_k are not all finite and positive.
+ *   output      per volume the TRUE number of hits and up to max_hits ids (rank << 24 | dense index, as a ray hit carries them) in
+ *               unspecified order.  An entity appears at most once however many sectors hold a record of its box.  When the count exceeds
+ *               max_hits the slots hold max_hits distinct members of the true set, which ones is unspecified, and the volume counts as
+ *               truncated.
+ * The walk: the sectors floorf(min * invSector) .. floorf(max * invSector) of the volume's box in x and z, clamped to the grid.  Two closed
+ * intervals that meet share a point and a box is registered in every sector of that same range of its own, so the answer equals brute
+ * force over every registered box; a box in several sectors is reported from the one that holds the low corner of the two boxes'
+ * intersection, as a pair is.  The cost is linear in the sectors the volume's box covers: a volume over the whole grid reads every bin.
+ * scTickSetOverlapQueries: type [count]; mat16 [count][16]; half_extents3 [count][3]; radius, half_height, mask [count]; skip_id [count]
+ * or NULL.  Every array but skip_id is required whatever the types.  The set stays until it is replaced; count 0 clears it.  It fails --
+ * and leaves the previous set in place -- on a non-finite matrix entry (the twelve that are read), half extent, radius or half_height, a
+ * type other than BOX, SPHERE, CAPSULE, max_hits == 0 with count > 0, a count * max_hits beyond 2^30 - 1 id slots, and an unknown
+ * mode.  A call with THE SAME count, max_hits and mode as the current set only rewrites the volumes, behind
+ * whatever is queued: no learn tick, and a captured graph stays valid.  Anything else re-sizes the set (the query batches' grow rule),
+ * costs a learn tick and a fresh capture.
+ * skip_id is an id like any other the caller holds: scTickRemoveEntities does NOT rename it when the entity it names is relocated.
+ * A run with SC_TICK_OVERLAPS fails, with a last-error text, without SC_TICK_BROADPHASE, without a set (count 0 or never set), together
+ * with SC_TICK_SPLIT_PAIRS, on a context with neighbours (scTickSetTile with a non-zero mask) and on a pipelined context: tiles are not
+ * covered.  The flag makes the tick fill every bin (no quiet tick, no lazy records), like the rays. */
+enum { SC_TICK_OVERLAP_SHAPES_AABB = 0, SC_TICK_OVERLAP_SHAPES_EXACT = 1 };
+typedef struct ScTickOverlapInfo
+{
+  uint32_t queries;            /* volumes of the set the run answered */
+  uint32_t max_hits;           /* id slots per volume */
+  uint32_t hits;               /* sum of the true counts */
+  uint32_t truncated_queries;  /* volumes whose count exceeds max_hits */
+  uint32_t refined;            /* EXACT: candidates decided by a shape routine (hits or not); 0 in AABB mode */
+  uint32_t kept_as_boxes;      /* EXACT: hits left on their box answer; 0 in AABB mode */
+  uint32_t shapes;             /* the mode the run answered in */
+  uint32_t pad;                /* 0 */
+} ScTickOverlapInfo;
+#ifdef __cplusplus
+static_assert(sizeof(ScTickOverlapInfo) == 32, "ScTickOverlapInfo is 32 bytes");
+#else
+_Static_assert(sizeof(ScTickOverlapInfo) == 32, "ScTickOverlapInfo is 32 bytes");
+#endif
+int scTickSetOverlapQueries(ScTickContext* ctx, uint32_t count, const uint8_t* type, const float* mat16, const float* half_extents3,
+                            const float* radius, const float* half_height, const uint32_t* mask, const uint32_t* skip_id,
+                            uint32_t max_hits, uint32_t shapes);
+/* results of the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_OVERLAPS): counts [query_capacity], ids [query_capacity][max_hits] (row
+ * q: the first min(counts[q], max_hits) slots), for the first min(queries, query_capacity) volumes; `info` alone (counts and ids NULL)
+ * gives the sizes.  Each of counts, ids and info may be NULL.  Synchronises; the report's sums are formed by this call from the per-volume
+ * words the device wrote (saturating at 2^32 - 1). */
+int scTickReadOverlapHits(ScTickContext* ctx, uint32_t* counts, uint32_t* ids, uint32_t query_capacity, ScTickOverlapInfo* info);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

@@ -17,9 +17,11 @@ PAIR_EVENTS = 1 << 12         # SC_TICK_PAIR_EVENTS: which pairs begun / ended s
 BIND_RUNS = 1 << 13           # SC_TICK_BIND_RUNS: with DRAWS | SORT_DRAWS, the bind runs of the sorted list and the material touch set (scTickSetBindRuns)
 PAIR_SHAPES = 1 << 14         # SC_TICK_PAIR_SHAPES: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes)
 TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended TOUCHING since the last run with this flag (scTickSetTouchEvents)
+OVERLAPS = 1 << 16            # SC_TICK_OVERLAPS: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*: what a capsule sweep's candidates are (scTickSetSweepShapes)
+OVERLAP_SHAPES_AABB, OVERLAP_SHAPES_EXACT = 0, 1       # SC_TICK_OVERLAP_SHAPES_*: what an overlap query's hits are (scTickSetOverlapQueries)
 # SC_TICK_CONTACT_*: ScTickPairContact::kind (scTickSetPairContacts)
 CONTACT_NONE, CONTACT_ROUND_ROUND, CONTACT_ROUND_BOX, CONTACT_BOX_FACE_A, CONTACT_BOX_FACE_B, CONTACT_BOX_EDGE = 0, 1, 2, 3, 4, 5
 CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
@@ -83,6 +85,10 @@ class TouchEventInfo(C.Structure):
 
 class SweepShapeInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("refined", "kept_as_boxes", "exhausted", "pad")]
+
+
+class OverlapInfo(C.Structure):                          # ScTickOverlapInfo: 32 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("queries", "max_hits", "hits", "truncated_queries", "refined", "kept_as_boxes", "shapes", "pad")]
 
 
 class PairShapeInfo(C.Structure):
@@ -272,6 +278,8 @@ SYMBOLS = {
     "scTickSetPairManifolds": (C.c_int, [_CTX, C.c_uint32]),
     "scTickGetPairManifolds": (C.c_int, [_CTX, U32P]),
     "scTickReadPairManifolds": (C.c_int, [_CTX, C.POINTER(PairManifold), C.c_uint32, C.POINTER(PairManifoldInfo)]),
+    "scTickSetOverlapQueries": (C.c_int, [_CTX, C.c_uint32, U8P, F32P, F32P, F32P, F32P, U32P, U32P, C.c_uint32, C.c_uint32]),
+    "scTickReadOverlapHits": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(OverlapInfo)]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

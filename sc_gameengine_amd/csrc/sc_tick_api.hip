@@ -128,6 +128,13 @@ struct ScTickContext
   uint32_t sweepShapes = SC_TICK_SWEEP_SHAPES_AABB;
   uint32_t* sweepInfo = nullptr;
   bool lastSweepsExact = false;        // the last run with SC_TICK_SWEEPS ran them in EXACT mode (scTickGetSweepShapeInfo)
+  // scTickSetOverlapQueries: the volumes, the count and id rows and the report's running words; overlapCap: volumes the per-volume arrays
+  // hold, overlapIdCap: id slots.  overlapShapes selects the kernel instance at launch time, like the modes above.  lastOverlap*: what the
+  // last run with SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
+  OverlapQueryState overlaps{};
+  uint32_t overlapCap = 0; size_t overlapIdCap = 0;
+  uint32_t overlapShapes = SC_TICK_OVERLAP_SHAPES_AABB;
+  uint32_t lastOverlapCount = 0, lastOverlapMaxHits = 0, lastOverlapShapes = 0;
   std::vector<uint2> hAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
@@ -616,6 +623,7 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   computeSpan(c, p.span, grid);
   p.flags = flags & 0xFFFFu;        // SC_TICK_DENSE_AABBS == kFlagDenseAabbs
   if (c->levelOffsets.size() > 1 && (flags & SC_TICK_XFORM)) p.flags |= kFlagHasDeep;
+  if (flags & SC_TICK_OVERLAPS) p.flags |= kFlagOverlaps;      // (the public bit is one of the internal ones' positions: it travels as a bit of its own)
   // The fused kernel's workgroups end the tick for their own spans (spanTail) when the world is span-closed, no level kernel reads `dirty`
   // behind the fused kernel, and the tick's producer is none or the root nudge.  The movers' producer stays in the end-of-tick kernel
   // (the agents' front rays are cast between the two kernels against this frame's positions), and so does the nudge while traffic
@@ -852,6 +860,8 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
   if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
+  // (overlap queries: scTickRun refuses them in a split flow, so this is their one launch site -- the pair half never sees the flag)
+  if (pairsNow && (flags & kFlagOverlaps)) launchOverlapQueries(ds, p, c->overlaps, c->overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
@@ -1912,7 +1922,7 @@ static bool worldCanPair(ScTickContext* c)
 static bool quietTick(ScTickContext* c, uint32_t flags)
 {
   constexpr uint32_t kBinReaders = SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_PAIR_EVENTS | SC_TICK_PAIR_SHAPES |
-                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS;
+                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS | SC_TICK_OVERLAPS;
   if (!(flags & SC_TICK_BROADPHASE) || (flags & kBinReaders) || !c->quietEnabled || !c->homeEnabled || !c->lazyEnabled) return false;
   if (!c->n || c->sensors || c->neighbourMask || c->pairsStream || c->pairsPending) return false;
   if (!c->homeValid || c->homeEpoch != c->topoEpoch) return false;      // (a learn tick is due: an append, a remove, a re-link, a layer upload)
@@ -1951,6 +1961,14 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (!c->bind.info) return fail(c, "SC_TICK_BIND_RUNS needs scTickSetBindRuns first");
     c->bindLastTouchWords = c->bind.touchWords;
     c->bindLastEmpty = c->n == 0 && !(flags & SC_TICK_BROADPHASE);
+  }
+  if (flags & SC_TICK_OVERLAPS) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_OVERLAPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
+    if (!c->overlaps.count) return fail(c, "SC_TICK_OVERLAPS needs scTickSetOverlapQueries first (the set is empty)");
+    if (c->neighbourMask) return fail(c, "SC_TICK_OVERLAPS cannot run on a context with neighbours (scTickSetTile): overlap queries do not cover tiles");
+    if (c->pairsStream) return fail(c, "SC_TICK_OVERLAPS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): overlap queries do not cover tiles");
+    if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_OVERLAPS cannot run with SC_TICK_SPLIT_PAIRS: overlap queries do not cover tiles");
+    c->lastOverlapCount = c->overlaps.count; c->lastOverlapMaxHits = c->overlaps.maxHits; c->lastOverlapShapes = c->overlapShapes;
   }
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
@@ -2025,7 +2043,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
     const bool hostBetweenHalves = (flags & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
     c->lastTickLazy = p.lazy != 0u;
@@ -2641,6 +2659,89 @@ int scTickReadSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, ui
   static_assert(sizeof(ScTickSweepHit) == sizeof(SweepHit48) && offsetof(ScTickSweepHit, travel) == offsetof(SweepHit48, travel), "sweep hit layouts differ");
   return readQueryHits(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS", "sweep hits are ready after scTickRunPairs",
                        c ? c->sweeps.hits : nullptr, c ? c->sweeps.count : 0u, hits, cap, count);
+}
+
+int scTickSetOverlapQueries(ScTickContext* c, uint32_t count, const uint8_t* type, const float* mat16, const float* halfExtents3, const float* radius,
+                            const float* halfHeight, const uint32_t* mask, const uint32_t* skipId, uint32_t maxHits, uint32_t shapes)
+{
+  static_assert(sizeof(ScTickOverlapInfo) == 8u * sizeof(uint32_t), "ScTickOverlapInfo is eight words");
+  if (!c) return 0;
+  if (count && (!type || !mat16 || !halfExtents3 || !radius || !halfHeight || !mask)) return fail(c, "null argument");
+  if (shapes != SC_TICK_OVERLAP_SHAPES_AABB && shapes != SC_TICK_OVERLAP_SHAPES_EXACT) return fail(c, "unknown overlap shape mode (SC_TICK_OVERLAP_SHAPES_*)");
+  if (count && !maxHits) return fail(c, "overlap queries: max_hits must be at least 1");
+  if ((uint64_t)count * maxHits > 0x3FFFFFFFull) return fail(c, "overlap queries: count * max_hits does not fit (at most 2^30 - 1 id slots)");
+  // the kernel never sees a value it has no answer for: checked before anything changes, so a refused call leaves the previous set in place
+  std::vector<float4> v((size_t)count * kOverlapVolumeWords);
+  for (uint32_t i = 0; i < count; ++i) {
+    const float* m = mat16 + 16u * (size_t)i;                 // column-major: m[col * 4 + row]
+    const uint8_t t = type[i];
+    if (t != SC_TICK_COLLIDER_BOX && t != SC_TICK_COLLIDER_SPHERE && t != SC_TICK_COLLIDER_CAPSULE)
+      return fail(c, "overlap queries: a volume's type is SC_TICK_COLLIDER_BOX, _SPHERE or _CAPSULE");
+    const float he[3] = { halfExtents3[3 * (size_t)i], halfExtents3[3 * (size_t)i + 1], halfExtents3[3 * (size_t)i + 2] };
+    const float values[5] = { he[0], he[1], he[2], radius[i], halfHeight[i] };
+    bool finite = true;
+    for (float x : values) finite = finite && std::isfinite(x);
+    for (int col = 0; col < 4; ++col) for (int row = 0; row < 3; ++row) finite = finite && std::isfinite(m[col * 4 + row]);
+    if (!finite) return fail(c, "overlap queries: mat16, half_extents, radius and half_height must be finite");
+    float4* q = &v[(size_t)i * kOverlapVolumeWords];
+    for (int row = 0; row < 3; ++row) q[row] = make_float4(m[row], m[4 + row], m[8 + row], m[12 + row]);
+    // the record as scTickUploadColliders stores it
+    const float hh = halfHeight[i] < 0.0f ? 0.0f : halfHeight[i];
+    q[3] = t == SC_TICK_COLLIDER_BOX ? make_float4(he[0], he[1], he[2], 0.0f)
+         : t == SC_TICK_COLLIDER_SPHERE ? make_float4(0.0f, 0.0f, 0.0f, radius[i]) : make_float4(0.0f, hh, 0.0f, radius[i]);
+    const uint32_t words[4] = { t, mask[i], skipId ? skipId[i] : 0xFFFFFFFFu, 0u };
+    std::memcpy(&q[4], words, sizeof words);
+  }
+  if (!bind(c)) return 0;
+  OverlapQueryState& o = c->overlaps;
+  // The same count, max_hits and mode as the current set: only the volumes are rewritten, behind whatever is queued -- no epoch bump, so no
+  // learn tick, and a captured graph (which holds the buffers, the two sizes and the kernel instance) stays valid.
+  const uint32_t perVolume = count ? maxHits : 0u;             // (a cleared set holds no slots whatever max_hits says)
+  if (count != o.count || perVolume != o.maxHits || shapes != c->overlapShapes) {
+    if (!sync(c)) return 0;
+    const size_t slots = (size_t)count * perVolume;
+    auto empty = [&] { dfree(c, o.ids); o.ids = nullptr; c->overlapIdCap = 0; o.count = 0; o.maxHits = 0; };
+    if (slots > c->overlapIdCap) {                             // the id rows: kept within their capacity, allocated anew beyond it
+      empty();
+      if (!dalloc(c, o.ids, std::max<size_t>(slots, 1024u))) return 0;
+      c->overlapIdCap = std::max<size_t>(slots, 1024u);
+    }
+    if (!growBatch(c, c->overlapCap, o.count, count, batchArray(o.volume, false, kOverlapVolumeWords), batchArray(o.counts, true), batchArray(o.tally, true))) { empty(); return 0; }
+    o.maxHits = perVolume;
+    c->overlapShapes = shapes;
+  }
+  if (!count) return 1;
+  if (!h2d(c, const_cast<float4*>(o.volume), v.data(), v.size() * sizeof(float4))) return 0;
+  return sync(c) ? 1 : 0;
+}
+
+int scTickReadOverlapHits(ScTickContext* c, uint32_t* counts, uint32_t* ids, uint32_t queryCapacity, ScTickOverlapInfo* info)
+{
+  if (!c) return 0;
+  // the set is as the run left it while count and max_hits are what that run answered (a same-size call only rewrites volumes)
+  const bool stands = c->overlaps.count == c->lastOverlapCount && c->overlaps.maxHits == c->lastOverlapMaxHits;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_OVERLAPS, "the last scTickRun did not request SC_TICK_OVERLAPS", true, nullptr,
+                                 "overlap hits are ready after scTickRunPairs", stands, "the overlap set was re-sized since the last run with SC_TICK_OVERLAPS: its results are gone")) return 0;
+  const OverlapQueryState& o = c->overlaps;
+  // the report's sums are formed here, from the per-volume words the waves wrote: no wave adds to a shared word
+  const bool exact = c->lastOverlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT;
+  std::vector<uint32_t> perVolume(o.count);
+  std::vector<uint2> tally(exact ? o.count : 0u);
+  if (!d2h(c, perVolume.data(), o.counts, (size_t)o.count * sizeof(uint32_t))) return 0;
+  if (exact && !d2h(c, tally.data(), o.tally, (size_t)o.count * sizeof(uint2))) return 0;
+  const uint32_t take = std::min(o.count, queryCapacity);
+  if (take && ids && !d2h(c, ids, o.ids, (size_t)take * o.maxHits * sizeof(uint32_t))) return 0;
+  if (!sync(c)) return 0;
+  if (take && counts) std::memcpy(counts, perVolume.data(), (size_t)take * sizeof(uint32_t));
+  if (info) {
+    uint64_t hits = 0, refined = 0, kept = 0; uint32_t truncated = 0;
+    for (uint32_t n : perVolume) { hits += n; truncated += n > o.maxHits ? 1u : 0u; }
+    for (const uint2& t : tally) { refined += t.x; kept += t.y; }
+    info->queries = o.count; info->max_hits = o.maxHits; info->hits = (uint32_t)std::min<uint64_t>(hits, 0xFFFFFFFFull);
+    info->truncated_queries = truncated; info->refined = (uint32_t)std::min<uint64_t>(refined, 0xFFFFFFFFull);
+    info->kept_as_boxes = (uint32_t)std::min<uint64_t>(kept, 0xFFFFFFFFull); info->shapes = c->lastOverlapShapes; info->pad = 0u;
+  }
+  return 1;
 }
 
 // pair events and touch events: one state each, allocated, read and freed alike (`what` names the feature in the error texts)

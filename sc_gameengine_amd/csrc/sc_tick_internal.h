@@ -281,6 +281,8 @@ constexpr uint32_t kFlagHasDeep = 1u << 16;   // write recomp bits for the level
 constexpr uint32_t kFlagDeferredReset = 1u << 17;   // pipelined tiles: a pair kernel never clears the other parity's counters / big bits; a small kernel
                                                     // behind it on the pairs stream snapshots the results and clears its OWN parity
 constexpr uint32_t kFlagDenseAabbs = 1u << 5; // == SC_TICK_DENSE_AABBS
+constexpr uint32_t kFlagOverlaps = 1u << 19;    // SC_TICK_OVERLAPS as TickParams::flags carries it: the public flag is bit 16, kFlagHasDeep's position, and only
+                                                // the low 16 public bits are copied into the word (fillParams) -- no kernel looks at this bit, the launch list does
 constexpr uint32_t kFlagTailOwnsDirty = 1u << 18;   // span-closed world: every workgroup of the fused kernel ends the tick for its own span (dirty clear, and the
                                                     // root nudge with SC_TICK_PRODUCE_NEXT: spanTail); the end-of-tick kernel then touches neither
 
@@ -326,6 +328,20 @@ constexpr int kSweepShapesSteps = 12;           // == SC_TICK_SWEEP_SHAPES_STEPS
 constexpr uint32_t kSweepSeenCap = 256;         // == SC_TICK_SWEEP_SHAPES_SEEN: boxes one sweep counts once
 constexpr uint32_t kSweepInfoWords = 4;
 void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQueryState& q, uint32_t* exactInfo, hipStream_t s);
+// ---- overlap queries (include/sc_tick.h "overlap queries"): collider volumes without an entity, answered from this tick's records.  A kernel
+// argument of their own, like the sweeps'.  Volume q is five 16-byte words: rows 0..2 of its world matrix (x, y, z, translation), its
+// collider record (ex, ey, ez, radius) as DeviceState::colShape would hold it, and the bit patterns (type, mask, skip id, 0).
+constexpr uint32_t kOverlapVolumeWords = 5;
+struct OverlapQueryState {
+  const float4* volume;     // [count][kOverlapVolumeWords]
+  uint32_t* counts;         // [count] the true number of hits per volume
+  uint32_t* ids;            // [count][maxHits]: the first min(counts[q], maxHits) slots of row q hold distinct ids of its hits
+  uint2* tally;             // [count] EXACT mode: (candidates decided by a shape routine, hits left on their box answer) per volume.  The report's
+                            // sums are the READER's (scTickReadOverlapHits): one word all 4 096 waves add to takes ~88 additions per microsecond
+  uint32_t count, maxHits;
+};
+// exact (SC_TICK_OVERLAP_SHAPES_EXACT): the instance that asks the touching pairs' routines about a refinable candidate -- chosen on the host
+void launchOverlapQueries(const DeviceState& d, const TickParams& p, const OverlapQueryState& q, bool exact, hipStream_t s);
 // ---- entity-anchored rays (include/sc_tick.h "entity-anchored rays"): given in an entity's local frame, resolved against this tick's
 // world matrix of that entity by the kernel that casts them.  A kernel argument of their own, like the sweeps'. ----
 constexpr uint32_t kAnchorNone = 0xFFFFFFFFu;    // == SC_TICK_ANCHOR_NONE: origin and direction are world space
@@ -591,6 +607,80 @@ __device__ __forceinline__ SegBox segBoxCore(const float y0[3], const float dy[3
     }
   }
   return o;
+}
+
+// The three routines of the touching pairs (include/sc_tick.h "touching pairs"), shared with the overlap queries (sc_tick_queries.hip):
+// true = the two shapes are provably apart.  A positive comparison alone says so: a NaN keeps the pair.
+// 1. round - round: the squared distance between two segments by the clamped closed form; apart when it exceeds (Ra + Rb)^2
+__device__ __forceinline__ bool roundRoundApart(const Member& ma, const Member& mb)
+{
+  const Round ra = roundOf(ma), rb = roundOf(mb);
+  float p1[3], d1[3], p2[3], d2[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    p1[i] = ma.T[i] - ra.A[i]; d1[i] = ra.A[i] + ra.A[i];
+    p2[i] = mb.T[i] - rb.A[i]; d2[i] = rb.A[i] + rb.A[i];
+  }
+  const SegSeg c = segSegCore(p1, d1, p2, d2);
+  const float sum = ra.R + rb.R;
+  return c.dist2 > sum * sum;
+}
+
+// 2. round - box: the segment in the box's frame; apart when the minimum of F (segBoxCore) exceeds R^2
+__device__ __forceinline__ bool roundBoxApart(const Member& mr, const Member& mx)
+{
+  const Round rd = roundOf(mr);
+  const Frame fr = frameOf(mx);
+  float w[3], y0[3], dy[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = mr.T[i] - mx.T[i];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float yc = dot3(fr.u[k], w), ya = dot3(fr.u[k], rd.A);
+    y0[k] = yc - ya; dy[k] = ya + ya;
+  }
+  const SegBox c = segBoxCore(y0, dy, fr.H, rd.A[0] != 0.0f || rd.A[1] != 0.0f || rd.A[2] != 0.0f);
+  return c.fmin > rd.R * rd.R;
+}
+
+// 3. box - box: the 15-axis separating-axis test in A's frame; apart when some axis has |t . L| > ra + rb
+__device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
+{
+  const Frame fa = frameOf(ma), fb = frameOf(mb);
+  float Rm[3][3], Ab[3][3], w[3], t[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) w[i] = mb.T[i] - ma.T[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = dot3(w, fa.u[i]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { Rm[i][j] = dot3(fa.u[i], fb.u[j]); Ab[i][j] = fabsf(Rm[i][j]) + kPairShapesSatEps; }
+  }
+  bool apart = false;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                            // L = A's axis i
+    const float rb = (fb.H[0] * Ab[i][0] + fb.H[1] * Ab[i][1]) + fb.H[2] * Ab[i][2];
+    apart = apart || (fabsf(t[i]) > fa.H[i] + rb);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {                            // L = B's axis j
+    const float ra = (fa.H[0] * Ab[0][j] + fa.H[1] * Ab[1][j]) + fa.H[2] * Ab[2][j];
+    const float tl = (t[0] * Rm[0][j] + t[1] * Rm[1][j]) + t[2] * Rm[2][j];
+    apart = apart || (fabsf(tl) > ra + fb.H[j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                            // L = A's axis i x B's axis j
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      const float ra = fa.H[i1] * Ab[i2][j] + fa.H[i2] * Ab[i1][j];
+      const float rb = fb.H[j1] * Ab[i][j2] + fb.H[j2] * Ab[i][j1];
+      const float tl = t[i2] * Rm[i1][j] - t[i1] * Rm[i2][j];
+      apart = apart || (fabsf(tl) > ra + rb);
+    }
+  }
+  return apart;
 }
 #endif
 // ---- touch events (include/sc_tick.h "touch events"): the pair events' difference taken over the TOUCHING set.  A second PairEventState;

@@ -48,78 +48,8 @@ __device__ __forceinline__ void appendWave(bool yes, uint2 pr, uint32_t* counter
   if (yes && at < cap) list[at] = pr;
 }
 
-// (Member / fetchMember, Round / roundOf, Frame / frameOf, boxDist2 and the two distance cores: sc_tick_internal.h, shared with the sweeps)
-// 1. round - round: the squared distance between two segments by the clamped closed form; apart when it exceeds (Ra + Rb)^2
-__device__ __forceinline__ bool roundRoundApart(const Member& ma, const Member& mb)
-{
-  const Round ra = roundOf(ma), rb = roundOf(mb);
-  float p1[3], d1[3], p2[3], d2[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    p1[i] = ma.T[i] - ra.A[i]; d1[i] = ra.A[i] + ra.A[i];
-    p2[i] = mb.T[i] - rb.A[i]; d2[i] = rb.A[i] + rb.A[i];
-  }
-  const SegSeg c = segSegCore(p1, d1, p2, d2);
-  const float sum = ra.R + rb.R;
-  return c.dist2 > sum * sum;
-}
-
-// 2. round - box: the segment in the box's frame; apart when the minimum of F (segBoxCore) exceeds R^2
-__device__ __forceinline__ bool roundBoxApart(const Member& mr, const Member& mx)
-{
-  const Round rd = roundOf(mr);
-  const Frame fr = frameOf(mx);
-  float w[3], y0[3], dy[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) w[i] = mr.T[i] - mx.T[i];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float yc = dot3(fr.u[k], w), ya = dot3(fr.u[k], rd.A);
-    y0[k] = yc - ya; dy[k] = ya + ya;
-  }
-  const SegBox c = segBoxCore(y0, dy, fr.H, rd.A[0] != 0.0f || rd.A[1] != 0.0f || rd.A[2] != 0.0f);
-  return c.fmin > rd.R * rd.R;
-}
-
-// 3. box - box: the 15-axis separating-axis test in A's frame; apart when some axis has |t . L| > ra + rb
-__device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
-{
-  const Frame fa = frameOf(ma), fb = frameOf(mb);
-  float Rm[3][3], Ab[3][3], w[3], t[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) w[i] = mb.T[i] - ma.T[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    t[i] = dot3(w, fa.u[i]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { Rm[i][j] = dot3(fa.u[i], fb.u[j]); Ab[i][j] = fabsf(Rm[i][j]) + kPairShapesSatEps; }
-  }
-  bool apart = false;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {                            // L = A's axis i
-    const float rb = (fb.H[0] * Ab[i][0] + fb.H[1] * Ab[i][1]) + fb.H[2] * Ab[i][2];
-    apart = apart || (fabsf(t[i]) > fa.H[i] + rb);
-  }
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {                            // L = B's axis j
-    const float ra = (fa.H[0] * Ab[0][j] + fa.H[1] * Ab[1][j]) + fa.H[2] * Ab[2][j];
-    const float tl = (t[0] * Rm[0][j] + t[1] * Rm[1][j]) + t[2] * Rm[2][j];
-    apart = apart || (fabsf(tl) > ra + fb.H[j]);
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {                            // L = A's axis i x B's axis j
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-      const float ra = fa.H[i1] * Ab[i2][j] + fa.H[i2] * Ab[i1][j];
-      const float rb = fb.H[j1] * Ab[i][j2] + fb.H[j2] * Ab[i][j1];
-      const float tl = t[i2] * Rm[i1][j] - t[i1] * Rm[i2][j];
-      apart = apart || (fabsf(tl) > ra + rb);
-    }
-  }
-  return apart;
-}
+// (Member / fetchMember, Round / roundOf, Frame / frameOf, boxDist2, the two distance cores and the three routines roundRoundApart, roundBoxApart
+//  and boxBoxApart: sc_tick_internal.h, shared with the sweeps and the overlap queries)
 
 // List: the touching list and its report (SC_TICK_PAIR_SHAPES).  Events: every pair decided "not apart" enters the touch state's current
 // table in the same lane and the same pass, as k_pair_events_diff enters a pair of the pair list (SC_TICK_TOUCH_EVENTS); `e` is then

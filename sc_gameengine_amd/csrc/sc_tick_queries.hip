@@ -616,6 +616,145 @@ __global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, co
   }
 }
 
+// ---- overlap queries (own spec, include/sc_tick.h "overlap queries") ---------------------------------------------------------
+// "Which entities are inside this volume": a collider without an entity -- type, record and world matrix as an entity's would be --
+// tested against the world exactly as the touching pairs test a pair.  The volume's box is the collider box rule (colliderAabb,
+// sc_tick_kernels.hip) over its matrix, stated here over a Member: n_k are the squared column norms as that rule forms them, and the half
+// extent is ((|M[r,0]|*ex + |M[r,1]|*ey) + |M[r,2]|*ez) + pad, the same operations in the same order.
+__device__ __forceinline__ void memberAabb(const Member& m, float mn[3], float mx[3])
+{
+  float pad = 0.0f;
+  if (m.type != kColliderBox) {
+    const float nyz = (m.type == kColliderSphere && m.n[2] < m.n[1]) ? m.n[1] : m.n[2];      // sphere: max(n1, n2); capsule: n2
+    pad = m.s.w * sqrtf((m.n[0] < nyz) ? nyz : m.n[0]);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const float h = fabsf(m.c[0][r]) * m.s.x + fabsf(m.c[1][r]) * m.s.y + fabsf(m.c[2][r]) * m.s.z + pad;
+    mn[r] = m.T[r] - h; mx[r] = m.T[r] + h;
+  }
+}
+
+// One wave per volume, one lane per record.  The wave takes the records it has to look at in CHUNKS of up to 64, in one loop: the bins
+// of the rectangle floorf(min * invSector) .. floorf(max * invSector) of the volume's box, clamped to the grid, sector after sector; then
+// the big list; then -- only when a sector of the rectangle held more than its bin -- the sector overflow list.  No pad: two closed
+// intervals that meet share a point, floorf(x * invSector) is monotone, and planBins registers a box in every sector of that same
+// range of its own.  The cost is linear in the sectors the rectangle covers; a volume over the whole grid reads every bin.
+//   A box lies in up to four sectors.  As in the pair search, a (volume, record) hit counts only in the sector that holds the low corner
+// of the two boxes' intersection, floorf(max(box.min, volume.min) * invSector) in x and z: that sector is in the box's own range and in
+// the rectangle, so exactly one of the box's records reports it.  A record of the overflow list belongs to the sector it is tagged
+// with; a box of the big list has one record.
+//   The wave owns row r of the id buffer and word r of the counts: ballot, prefix popcount and a running count -- no atomics at all (the
+// report's sums are formed by the reader), vector stores, every index below count * maxHits.  The loop's trip count is the wave's (the volume is wave-uniform: it comes through the scalar path).
+// kExact (SC_TICK_OVERLAP_SHAPES_EXACT; the instance launched instead of the AABB one): a hit whose entity is refinable (fetchMember) is
+// dropped when the touching pairs' routine for the two types says "apart", the entity as member A and the volume as member B; a
+// candidate that cannot be refined, and every candidate of a volume with a degenerate matrix, stays a hit on its box answer.
+template <bool kExact>
+__global__ __launch_bounds__(kTile) void k_overlap_queries(const DeviceState d, const TickParams p, const OverlapQueryState q)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
+  if (r >= q.count) return;
+  const float4* vol = q.volume + (size_t)kOverlapVolumeWords * r;
+  const float4 r0 = vol[0], r1 = vol[1], r2 = vol[2], word = vol[4];
+  Member mv;
+  mv.s = vol[3]; mv.type = __float_as_uint(word.x);
+  mv.c[0][0] = r0.x; mv.c[0][1] = r1.x; mv.c[0][2] = r2.x;
+  mv.c[1][0] = r0.y; mv.c[1][1] = r1.y; mv.c[1][2] = r2.y;
+  mv.c[2][0] = r0.z; mv.c[2][1] = r1.z; mv.c[2][2] = r2.z;
+  mv.T[0] = r0.w; mv.T[1] = r1.w; mv.T[2] = r2.w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) mv.n[k] = dot3(mv.c[k], mv.c[k]);
+  mv.ok = mv.n[0] > 0.0f && mv.n[1] > 0.0f && mv.n[2] > 0.0f && isfinite(mv.n[0]) && isfinite(mv.n[1]) && isfinite(mv.n[2]);
+  const uint32_t mask = __float_as_uint(word.y), skipId = __float_as_uint(word.z);
+  float vmn[3], vmx[3];
+  memberAabb(mv, vmn, vmx);
+
+  // the rectangle (a NaN box compares false everywhere: no sector, and no record meets it)
+  const float fx0 = floorf(vmn[0] * p.invSector) - p.binOx, fx1 = floorf(vmx[0] * p.invSector) - p.binOx;
+  const float fz0 = floorf(vmn[2] * p.invSector) - p.binOz, fz1 = floorf(vmx[2] * p.invSector) - p.binOz;
+  const float gridX = (float)p.binSX - 1.0f, gridZ = (float)p.binSZ - 1.0f;
+  uint32_t gx0 = 0u, gz0 = 0u, width = 0u, nSec = 0u;
+  if (p.binSX && fx1 >= 0.0f && fz1 >= 0.0f && fx0 <= gridX && fz0 <= gridZ) {
+    gx0 = (uint32_t)(fx0 < 0.0f ? 0.0f : fx0); gz0 = (uint32_t)(fz0 < 0.0f ? 0.0f : fz0);
+    const uint32_t gx1 = (uint32_t)(fx1 > gridX ? gridX : fx1), gz1 = (uint32_t)(fz1 > gridZ ? gridZ : fz1);
+    width = gx1 - gx0 + 1u;
+    nSec = width * (gz1 - gz0 + 1u);
+  }
+  const uint32_t ctr = kCtrPar + 8u * p.parity;
+  const uint32_t nbig = min(d.counters[ctr + kCtrBig], p.bigCap), nspill = min(d.counters[ctr + kCtrSpill], p.ovfCap);
+  const uint32_t bigEnd = nSec + (nbig + 63u) / 64u, spillChunks = (nspill + 63u) / 64u;
+  bool anyOverflow = false;
+  uint32_t total = 0u, refined = 0u, kept = 0u;      // (wave-uniform)
+  uint32_t gx = gx0, gz = gz0;                          // the sector of chunk k while k < nSec
+  uint32_t* row = q.ids + (size_t)r * q.maxHits;
+  // (anyOverflow is final once the sectors are through, before it can matter)
+  for (uint32_t k = 0; k < bigEnd + (anyOverflow ? spillChunks : 0u); ++k) {
+    float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = lo;
+    bool have = false, bySector = false;
+    uint32_t sx = 0u, sz = 0u;                          // bySector: the sector this record is registered in
+    if (k < nSec) {
+      const uint32_t s = gz * p.binSX + gx;
+      uint32_t n = d.binCount[s];
+      if (n > kBinCap) { n = kBinCap; anyOverflow = true; }
+      have = lane < n; bySector = true; sx = gx; sz = gz;
+      if (have) { const float4* rec = d.bins + 2u * ((size_t)s * kBinCap + lane); lo = rec[0]; hi = rec[1]; }
+      if (++gx == gx0 + width) { gx = gx0; ++gz; }
+    } else if (k < bigEnd) {
+      const uint32_t b = (k - nSec) * 64u + lane;
+      have = b < nbig;
+      if (have) { lo = d.bigList[2u * (size_t)b]; hi = d.bigList[2u * (size_t)b + 1u]; }
+    } else {
+      const uint32_t e = (k - bigEnd) * 64u + lane;
+      have = e < nspill; bySector = true;
+      if (have) {
+        lo = d.spill[2u * (size_t)e]; hi = d.spill[2u * (size_t)e + 1u];
+        const uint32_t s = d.spillSector[e];
+        sx = s % p.binSX; sz = s / p.binSX;
+      }
+    }
+    // the rays' filter, the skip id, the pair rule's closed intervals (positive comparisons: a NaN meets nothing), the low corner
+    const uint32_t lay = __float_as_uint(lo.w);
+    const uint32_t id = __float_as_uint(hi.w) & ~kPrimary;
+    bool hit = have && ((lay & 0xFFFFu) & mask) != 0u && (lay >> 16) != 0u && id != skipId &&
+               lo.x <= vmx[0] && vmn[0] <= hi.x && lo.y <= vmx[1] && vmn[1] <= hi.y && lo.z <= vmx[2] && vmn[2] <= hi.z;
+    if (bySector) {
+      const float lx = lo.x > vmn[0] ? lo.x : vmn[0], lz = lo.z > vmn[2] ? lo.z : vmn[2];
+      hit = hit && (floorf(lx * p.invSector) - p.binOx) == (float)sx && (floorf(lz * p.invSector) - p.binOz) == (float)sz;
+    }
+    if constexpr (kExact) {
+      bool refine = false;
+      if (hit) {
+        const Member m = fetchMember(d, id, p.n, p.rankBits);
+        refine = m.ok && mv.ok;
+        if (refine) {
+          const bool boxA = m.type == kColliderBox, boxB = mv.type == kColliderBox;
+          bool apart;
+          if (boxA && boxB) apart = boxBoxApart(m, mv);
+          else if (boxA) apart = roundBoxApart(mv, m);
+          else if (boxB) apart = roundBoxApart(m, mv);
+          else apart = roundRoundApart(m, mv);
+          hit = !apart;
+        }
+      }
+      // refined: decided by a routine; kept: a hit that stands on its box answer
+      const unsigned long long mr = ballot64(refine);
+      refined += (uint32_t)__popcll(mr);
+      kept += (uint32_t)__popcll(ballot64(hit) & ~mr);
+    }
+    const unsigned long long m = ballot64(hit);
+    if (hit) {
+      const uint32_t at = total + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (at < q.maxHits) row[at] = id;
+    }
+    total += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) {
+    q.counts[r] = total;
+    if constexpr (kExact) q.tally[r] = make_uint2(refined, kept);
+  }
+}
+
 // ---- the traffic AI's obstacle ray (src/engine/traffic/sc_traffic_ai.cpp:300-345) --------------------------------------------
 // Every agent of the OnRails tier casts one ray per step from 1.7 m ahead of its origin (0.6 m up) along its heading --
 // forward = normalize(sin(yaw), 0, cos(yaw)) with the yaw's sin / cos as the entity's rotation streams hold them (host libm) --
@@ -788,6 +927,11 @@ void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQu
 {
   if (exactInfo) hipMemsetAsync(exactInfo, 0, kSweepInfoWords * sizeof(uint32_t), s);      // (an empty batch reports zeros)
   launchWavePerQuery(exactInfo ? k_sweep_queries<true> : k_sweep_queries<false>, q.count, s, d, p, q, exactInfo);
+}
+
+void launchOverlapQueries(const DeviceState& d, const TickParams& p, const OverlapQueryState& q, bool exact, hipStream_t s)
+{
+  launchWavePerQuery(exact ? k_overlap_queries<true> : k_overlap_queries<false>, q.count, s, d, p, q);
 }
 
 void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool fromSnapshot, bool exact, hipStream_t s)

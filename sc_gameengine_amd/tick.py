@@ -337,6 +337,41 @@ class WorldTick:
             self._ok(self.lib.scTickReadSweepHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadSweepHits")
         return np.frombuffer(buf, dtype=SWEEP_HIT_DTYPE, count=n.value).copy()
 
+    # ---- overlap queries: collider volumes answered from this tick's boxes ----
+    def overlap_queries(self, type, matrices, half_extents, radius, half_height, mask, skip_id=None, max_hits=64,
+                        shapes=capi.OVERLAP_SHAPES_AABB):
+        """Volumes -- a collider type (capi.COLLIDER_BOX / _SPHERE / _CAPSULE), its values and a world matrix (column-major [k, 16]) each --
+        answered by every run with capi.OVERLAPS: which boxes of that tick meet the volume's box (capi.OVERLAP_SHAPES_AABB), or which
+        collider shapes meet the volume itself (capi.OVERLAP_SHAPES_EXACT).  skip_id: per volume, a box id that never answers (None:
+        none); max_hits: id slots per volume.  A call with the same count, max_hits and mode as the current set costs no learn tick
+        and no graph capture (scTickSetOverlapQueries)."""
+        t = np.ascontiguousarray(type, np.uint8).reshape(-1)
+        k = len(t)
+        m, he = _c32(matrices).reshape(-1, 16), _c32(half_extents).reshape(-1, 3)
+        r, hh = _c32(radius).reshape(-1), _c32(half_height).reshape(-1)
+        mk = np.ascontiguousarray(mask, np.uint32).reshape(-1)
+        sk = None if skip_id is None else np.ascontiguousarray(skip_id, np.uint32).reshape(-1)
+        assert len(m) == k and len(he) == k and len(r) == k and len(hh) == k and len(mk) == k and (sk is None or len(sk) == k)
+        self._ok(self.lib.scTickSetOverlapQueries(self.ctx, k, t.ctypes.data_as(capi.U8P), _f(m), _f(he), _f(r), _f(hh), _u(mk),
+                                                  None if sk is None else _u(sk), int(max_hits), int(shapes)), "scTickSetOverlapQueries")
+
+    def overlap_info(self):
+        """What the last run's overlap queries found (scTickReadOverlapHits): a dict with queries, max_hits, hits, truncated_queries,
+        refined, kept_as_boxes, shapes."""
+        info = capi.OverlapInfo()
+        self._ok(self.lib.scTickReadOverlapHits(self.ctx, None, None, 0, C.byref(info)), "scTickReadOverlapHits")
+        return {k: int(getattr(info, k)) for k, _ in capi.OverlapInfo._fields_ if k != "pad"}
+
+    def overlap_hits(self):
+        """(counts [k], ids [k, max_hits]) of the last run's overlap queries: counts[q] is the true number of hits of volume q, the first
+        min(counts[q], max_hits) slots of ids[q] hold distinct ids (rank << 24 | dense index) of them, in no particular order."""
+        info = self.overlap_info()
+        k, mh = info["queries"], info["max_hits"]
+        counts, ids = np.zeros(max(k, 1), np.uint32), np.zeros((max(k, 1), max(mh, 1)), np.uint32)
+        if k:
+            self._ok(self.lib.scTickReadOverlapHits(self.ctx, _u(counts), _u(ids), k, None), "scTickReadOverlapHits")
+        return counts[:k].copy(), ids[:k, :mh].copy()
+
     def occupied(self, pos, radius, mask):
         """isOccupiedWorld for a batch of points (sc_traffic_spawner.cpp:93-116); returns a uint8 array."""
         p, r = _c32(pos).reshape(-1, 3), _c32(radius).reshape(-1)
