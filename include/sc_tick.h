@@ -524,7 +524,10 @@ int scTickReadDraws(ScTickContext* ctx, ScTickDrawItem* items, uint32_t capacity
  * scTickAcquireFrame(frames_back) waits for the copy of ONE frame -- 0: the most recently queued, 1: the one before, which
  * is how a host overlaps: queue tick t+1, then take frame t -- and for nothing queued after it, and hands out pointers into
  * the pinned buffer; they stay valid until the second scTickRun after the one that produced the frame.
- * (0, 0) switches it off.  Not combinable with graph replay. */
+ * (0, 0) switches it off; any other call restarts the tick index at 0 and drops both frames.  Not combinable with graph replay.
+ * max_visible is taken as given: visible_in_buffer never exceeds it (the block pads its index area to a multiple of four entries, so
+ * that the items stay 16-byte aligned; the padding is never reported).  EVERY scTickRun ends with a frame: a run on an empty context
+ * without SC_TICK_BROADPHASE, which launches nothing, leaves a frame of zeros under the next tick index. */
 typedef struct ScTickFrame
 {
   uint64_t tick;                   /* index of the scTickRun that produced it (counted from the first one after switching on) */
@@ -537,6 +540,26 @@ typedef struct ScTickFrame
 } ScTickFrame;
 int scTickSetFrameReadback(ScTickContext* ctx, uint32_t max_visible, uint32_t max_draws);
 int scTickAcquireFrame(ScTickContext* ctx, uint32_t frames_back, ScTickFrame* out);
+/* Which code wrote the last scTickRun's frame (diagnostics; no result depends on it -- every writer produces the same items and the same
+ * block).  stats[0]: who wrote the draw items, stats[1]: who staged the read-back block.  Host-side: no read-back, no synchronisation.
+ * The rule: a plain draw list rides in the compaction role of the combined end-of-tick launch when the tick has one
+ * (SC_TICK_BROADPHASE with its pair search in the same run, SC_TICK_CULL) -- into the draw buffer, or, with the read-back on and
+ * 0 < draw budget <= max_draws, straight into the block, header included; with the read-back on and such a budget but no combined launch
+ * (no broadphase, a quiet tick, SC_TICK_SPLIT_PAIRS) one emission kernel writes items and block; otherwise the emission kernel or the
+ * sort writes the draw buffer and a staging kernel copies its head into the block.  An empty context without SC_TICK_BROADPHASE launches
+ * nothing: the library writes that frame -- zeros under the next tick index -- itself. */
+#define SC_TICK_FRAME_ITEMS_NONE 0u          /* the run had no SC_TICK_DRAWS, or launched nothing (an empty context, below) */
+#define SC_TICK_FRAME_ITEMS_EOT_BUFFER 1u    /* compaction role of the end-of-tick launch, into the draw buffer */
+#define SC_TICK_FRAME_ITEMS_EOT_BLOCK 2u     /* ... into the read-back block */
+#define SC_TICK_FRAME_ITEMS_EMIT 3u          /* the emission kernel, into the draw buffer */
+#define SC_TICK_FRAME_ITEMS_EMIT_STAGED 4u   /* the staged emission kernel, into the read-back block */
+#define SC_TICK_FRAME_ITEMS_SORT 5u          /* SC_TICK_SORT_DRAWS: the sort, into the draw buffer */
+#define SC_TICK_FRAME_BLOCK_NONE 0u          /* the read-back is off */
+#define SC_TICK_FRAME_BLOCK_EOT 1u           /* compaction role of the end-of-tick launch */
+#define SC_TICK_FRAME_BLOCK_EMIT_STAGED 2u   /* the staged emission kernel */
+#define SC_TICK_FRAME_BLOCK_STAGE 3u         /* the staging kernel */
+#define SC_TICK_FRAME_BLOCK_HOST 4u          /* an empty context: no launch, the library wrote the zero frame */
+int scTickGetFrameStats(ScTickContext* ctx, uint32_t stats[2]);
 
 /* ---- bind runs of the sorted draw list, and the material touch set ----
  * What a renderer does with the sorted list, found on the device behind the sort.  The specification is the reference's own loop and

@@ -32,6 +32,9 @@ SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
 BIN_LAZY, BIN_STAY, BIN_SWEEP_ONLY, BIN_QUIET = 1, 2, 4, 8     # scTickGetBinStats stats[2]: what the last tick did with the bins (BIN_QUIET: nothing at all)
+# scTickGetFrameStats: who wrote the last tick's draw items (SC_TICK_FRAME_ITEMS_*) / staged its read-back block (SC_TICK_FRAME_BLOCK_*)
+FRAME_ITEMS_NONE, FRAME_ITEMS_EOT_BUFFER, FRAME_ITEMS_EOT_BLOCK, FRAME_ITEMS_EMIT, FRAME_ITEMS_EMIT_STAGED, FRAME_ITEMS_SORT = 0, 1, 2, 3, 4, 5
+FRAME_BLOCK_NONE, FRAME_BLOCK_EOT, FRAME_BLOCK_EMIT_STAGED, FRAME_BLOCK_STAGE, FRAME_BLOCK_HOST = 0, 1, 2, 3, 4
 NO_PARENT = -1
 # collider types (SC_TICK_COLLIDER_*): what an entity's broadphase proxy is formed from
 COLLIDER_BOUNDS, COLLIDER_NONE, COLLIDER_BOX, COLLIDER_SPHERE, COLLIDER_CAPSULE = 0, 1, 2, 3, 4
@@ -210,6 +213,7 @@ SYMBOLS = {
     "scTickGetLearnTicks": (C.c_int, [_CTX, U32P]),
     "scTickGetTailStats": (C.c_int, [_CTX, U32P]),
     "scTickGetCompactStats": (C.c_int, [_CTX, U32P]),
+    "scTickGetFrameStats": (C.c_int, [_CTX, U32P]),
     "scTickGetBoundsClassStats": (C.c_int, [_CTX, U32P]),
     "scTickSetWorldLayers": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int]),
     "scTickResetHostTimes": (C.c_int, [_CTX]),

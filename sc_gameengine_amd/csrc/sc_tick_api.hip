@@ -104,6 +104,7 @@ struct ScTickContext
   // tick's spans per workgroup, 0 = compactBody's form -- part of a captured graph's key; lastCompact: scTickGetCompactStats.
   bool wideCompact = true; uint32_t compactForceG = 0, compactG = 0;
   uint32_t lastCompact[2] = { 0u, 0u };
+  uint32_t lastFrame[2] = { 0u, 0u };  // who wrote the last tick's draw items / staged its read-back block (scTickGetFrameStats; framePathFor)
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
   uint32_t lastFlags = 0;
 
@@ -808,6 +809,34 @@ void waitFrameBlock(ScTickContext* c)
   (void)hipGetLastError();
 }
 
+// Which code writes the frame -- the draw items and the read-back block -- on a tick with these TickParams::flags: the one rule behind
+// enqueueStages' launches and scTickGetFrameStats' report.
+//   stagedEmit   the read-back is on and a plain draw list's budget fits the block: the items go straight into the block
+//   foldEmit     the combined end-of-tick launch runs (compaction and pair search): its compaction role writes the items
+//   stagedByEot  both: that role writes the whole block, header included
+struct FramePath {
+  bool needCompact, pairsNow, stagedEmit, foldEmit, stagedByEot;
+  uint32_t items, block;               // SC_TICK_FRAME_ITEMS_* / SC_TICK_FRAME_BLOCK_*
+};
+FramePath framePathFor(const ScTickContext* c, uint32_t flags)
+{
+  FramePath f;
+  // (kFlagTailOwnsDirty: the transform half left nothing for the end-of-tick kernel -- without culling there is no compaction role to launch)
+  f.needCompact = (flags & SC_TICK_CULL) != 0 || ((flags & SC_TICK_XFORM) && !(flags & kFlagTailOwnsDirty));
+  f.pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
+  const uint32_t drawBudget = c->desc.max_draws_budget;
+  f.stagedEmit = c->rb.bytes && (flags & SC_TICK_DRAWS) && !(flags & SC_TICK_SORT_DRAWS) && drawBudget && drawBudget <= c->rb.maxDraws;
+  f.foldEmit = f.needCompact && f.pairsNow && (flags & SC_TICK_CULL) && (flags & SC_TICK_DRAWS) &&
+               !(flags & SC_TICK_SORT_DRAWS) && (f.stagedEmit || !c->rb.bytes);
+  f.stagedByEot = f.foldEmit && f.stagedEmit;
+  f.items = !(flags & SC_TICK_DRAWS) ? SC_TICK_FRAME_ITEMS_NONE : (flags & SC_TICK_SORT_DRAWS) ? SC_TICK_FRAME_ITEMS_SORT
+          : f.stagedByEot ? SC_TICK_FRAME_ITEMS_EOT_BLOCK : f.foldEmit ? SC_TICK_FRAME_ITEMS_EOT_BUFFER
+          : f.stagedEmit ? SC_TICK_FRAME_ITEMS_EMIT_STAGED : SC_TICK_FRAME_ITEMS_EMIT;
+  f.block = !c->rb.bytes ? SC_TICK_FRAME_BLOCK_NONE : f.stagedByEot ? SC_TICK_FRAME_BLOCK_EOT
+          : f.stagedEmit ? SC_TICK_FRAME_BLOCK_EMIT_STAGED : SC_TICK_FRAME_BLOCK_STAGE;
+  return f;
+}
+
 // the tick's launches on c->stream, nothing else: safe inside a stream capture (the callers put waitParityFree before
 // and publishPacked behind it).  Launches are timed only on an eager, sampled tick (scTickRun sets lastTickSampled first).
 void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool inCapture)
@@ -854,9 +883,8 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
     else launchAgentFrontRays(ds, p, c->stream);
   }
   if ((flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_DENSE_AABBS)) launchDenseAabbs(ds, c->n, c->stream);   // read-back aid, off the hot path
-  // (kFlagTailOwnsDirty: the transform half left nothing for the end-of-tick kernel -- without culling there is no compaction role to launch)
-  const bool needCompact = (flags & SC_TICK_CULL) != 0 || ((flags & SC_TICK_XFORM) && !(flags & kFlagTailOwnsDirty));
-  const bool pairsNow = (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS);
+  const FramePath path = framePathFor(c, flags);
+  const bool needCompact = path.needCompact, pairsNow = path.pairsNow;
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
   if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
   if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
@@ -873,10 +901,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
   // entity's place in the list, i.e. its draw item (emitVisible).  With the frame read-back on (and a budget that fits the block)
   // the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
   const uint32_t drawBudget = c->desc.max_draws_budget;
-  const bool stagedEmit = c->rb.bytes && (flags & SC_TICK_DRAWS) && !(flags & SC_TICK_SORT_DRAWS) && drawBudget && drawBudget <= c->rb.maxDraws;
-  const bool foldEmit = needCompact && pairsNow && (flags & SC_TICK_CULL) && (flags & SC_TICK_DRAWS) &&
-                        !(flags & SC_TICK_SORT_DRAWS) && (stagedEmit || !c->rb.bytes);
-  const bool stagedByEot = foldEmit && stagedEmit;
+  const bool stagedEmit = path.stagedEmit, foldEmit = path.foldEmit, stagedByEot = path.stagedByEot;      // (framePathFor: the rule)
   if (needCompact && pairsNow) {
     TickParams pe = p;
     hipEvent_t done = nullptr;
@@ -952,10 +977,10 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
     if (!stagedByEot) waitFrameBlock(c);                  // (the end-of-tick kernel's launch waited already)
     const uint32_t drawMode = (flags & SC_TICK_DRAWS) ? ((flags & SC_TICK_SORT_DRAWS) ? 2u : 1u) : 0u;
     rb.bindsStaged[f] = false;
-    if (stagedByEot) c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + rb.maxVisible;       // the end-of-tick kernel wrote the block
+    if (stagedByEot) c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + frameVisibleWords(rb.maxVisible);       // the end-of-tick kernel wrote the block
     else if (stagedEmit) {
       launchEmitDrawsStaged(ds, drawBudget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);
-      c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + rb.maxVisible;       // what scTickReadDraws returns for this tick
+      c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + frameVisibleWords(rb.maxVisible);       // what scTickReadDraws returns for this tick
     } else {
       // (a flagged run is a sorted one, so it comes through here: its bind block is staged ahead of the frame's, whose `staged` covers both)
       rb.bindsStaged[f] = rb.bindBytes && (flags & SC_TICK_BIND_RUNS);
@@ -1970,12 +1995,29 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_OVERLAPS cannot run with SC_TICK_SPLIT_PAIRS: overlap queries do not cover tiles");
     c->lastOverlapCount = c->overlaps.count; c->lastOverlapMaxHits = c->overlaps.maxHits; c->lastOverlapShapes = c->overlapShapes;
   }
+  if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");      // (an empty context's run stages a frame too)
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
     c->lastTickTail = false;
     c->lastTickQuiet = false;
     c->lastCompact[0] = c->lastCompact[1] = 0u;
+    c->lastFrame[0] = c->lastFrame[1] = 0u;
+    c->lastDraws = c->dDraws;
     HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
+    if (c->rb.bytes) {
+      // every scTickRun ends with a frame: this one is all zeros under the next tick index, written by the host into the pinned block
+      // (nothing is launched and nothing copied; the block's copy of two frames ago is waited for on the host -- a rare tick)
+      ScTickContext::FrameReadback& rb = c->rb;
+      const uint32_t f = (uint32_t)(rb.frames & 1u);
+      if (rb.inFlight[f]) HIP_OK(c, hipEventSynchronize(rb.copied[f]));
+      std::memset(rb.hBlock[f], 0, (size_t)kFrameHeaderWords * 4u);
+      rb.hBlock[f][6] = (uint32_t)rb.frames; rb.hBlock[f][7] = (uint32_t)(rb.frames >> 32);
+      rb.bindsStaged[f] = false;
+      HIP_OK(c, hipEventRecord(rb.copied[f], rb.copyStream));      // (what scTickAcquireFrame waits on)
+      rb.inFlight[f] = true;
+      rb.frames++;
+      c->lastFrame[1] = SC_TICK_FRAME_BLOCK_HOST;
+    }
     return 1;
   }
   if (flags & SC_TICK_PRODUCE_NEXT) {
@@ -1983,7 +2025,6 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (!c->producerKind) return fail(c, "SC_TICK_PRODUCE_NEXT needs scTickSetFrameProducer first");
   }
   if (c->pairsStream && (flags & SC_TICK_BROADPHASE) && !(flags & SC_TICK_SPLIT_PAIRS)) return fail(c, "a pairs stream is set: run the broadphase with SC_TICK_SPLIT_PAIRS + scTickRunPairs");
-  if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");
   if ((flags & SC_TICK_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_SWEEPS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_SWEEPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
   if ((flags & SC_TICK_ANCHORED_RAYS) && !(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_ANCHORED_RAYS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
@@ -2071,6 +2112,8 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     c->compactG = (alone && c->wideCompact) ? compactWideGroup(p, grid, c->compactForceG) : 0u;
     c->lastCompact[0] = c->lastCompact[1] = 0u;
     if (needCompact) compactLaunchShape(grid, pairsNow, c->compactG, c->lastCompact);
+    const FramePath path = framePathFor(c, p.flags);       // (here, not in enqueueStages: a replayed graph enqueues nothing)
+    c->lastFrame[0] = path.items; c->lastFrame[1] = path.block;
   }
   const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
   c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
@@ -3087,8 +3130,9 @@ int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDr
   rb.bytes = 0; rb.frames = 0; rb.maxVisible = rb.maxDraws = 0;
   if (!maxVisible && !maxDraws) return reallocBindBlocks(c) ? 1 : 0;      // (the bind runs lose their staging blocks)
   if (maxVisible > c->cap || maxDraws > c->cap) return fail(c, "read-back sizes exceed the context's capacity");
-  maxVisible = (maxVisible + 3u) & ~3u;                        // keeps the draw items 16-byte aligned inside the block
-  const size_t bytes = (size_t)kFrameHeaderWords * 4u + (size_t)maxVisible * 4u + (size_t)maxDraws * sizeof(ScTickDrawItem);
+  // (the block keeps frameVisibleWords(maxVisible) words for the indices -- the items behind them stay 16-byte aligned --; the clamp of
+  //  visible_in_buffer is maxVisible as it was asked for)
+  const size_t bytes = (size_t)kFrameHeaderWords * 4u + (size_t)frameVisibleWords(maxVisible) * 4u + (size_t)maxDraws * sizeof(ScTickDrawItem);
   if (!rb.copyStream) {
     HIP_OK(c, hipStreamCreateWithFlags(&rb.copyStream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
@@ -3125,7 +3169,7 @@ int scTickAcquireFrame(ScTickContext* c, uint32_t framesBack, ScTickFrame* out)
   out->draws_emitted = h[3]; out->draws_dropped = h[4]; out->draws_sorted = h[5];
   out->visible_in_buffer = h[8]; out->draws_in_buffer = h[9];
   out->visible_indices = h + kFrameHeaderWords;
-  out->draws = reinterpret_cast<const ScTickDrawItem*>(h + kFrameHeaderWords + rb.maxVisible);
+  out->draws = reinterpret_cast<const ScTickDrawItem*>(h + kFrameHeaderWords + frameVisibleWords(rb.maxVisible));
   return 1;
 }
 
@@ -3521,6 +3565,13 @@ int scTickGetCompactStats(ScTickContext* c, uint32_t stats[2])
 {
   if (!c || !stats) return c ? fail(c, "null argument") : 0;
   stats[0] = c->lastCompact[0]; stats[1] = c->lastCompact[1];
+  return 1;
+}
+
+int scTickGetFrameStats(ScTickContext* c, uint32_t stats[2])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  stats[0] = c->lastFrame[0]; stats[1] = c->lastFrame[1];
   return 1;
 }
 

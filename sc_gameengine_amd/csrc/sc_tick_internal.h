@@ -747,6 +747,9 @@ void launchGatherRows(const DeviceState& d, const uint32_t* idx, uint32_t count,
 void launchEmitDraws(const DeviceState& d, uint32_t budget, void* items, hipStream_t s);
 // frame read-back block: header (kFrameHeaderWords), visible indices, draw items
 constexpr uint32_t kFrameHeaderWords = 16;
+// words the block keeps for the visible indices: max_visible rounded up to four, so that the draw items behind them stay 16-byte
+// aligned.  The writers take max_visible as the caller gave it -- the clamp of visible_in_buffer -- and find the items through this.
+__host__ __device__ inline uint32_t frameVisibleWords(uint32_t maxVisible) { return (maxVisible + 3u) & ~3u; }
 void launchEmitDrawsStaged(const DeviceState& d, uint32_t budget, uint32_t* block, uint32_t maxVisible, uint64_t tick, hipStream_t s, hipEvent_t done = nullptr);
 void launchStageFrame(const DeviceState& d, uint32_t* block, uint32_t maxVisible, uint32_t maxDraws, const void* items, uint32_t drawMode /*0 none, 1 plain, 2 sorted*/,
                       uint64_t tick, hipStream_t s, hipEvent_t done = nullptr);

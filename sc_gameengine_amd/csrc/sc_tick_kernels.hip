@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void emitVisible(const DeviceState& d, const TickPara
   float4* items = reinterpret_cast<float4*>(p.emitTarget);
   if (p.emitMode == 2u) {
     if (off < p.emitMaxVisible) p.emitTarget[kFrameHeaderWords + off] = j;
-    items = reinterpret_cast<float4*>(p.emitTarget + kFrameHeaderWords + p.emitMaxVisible);      // (emitMaxVisible is a multiple of 4: 16-byte aligned)
+    items = reinterpret_cast<float4*>(p.emitTarget + kFrameHeaderWords + frameVisibleWords(p.emitMaxVisible));      // (16-byte aligned; emitMaxVisible itself is the clamp)
   }
   if (p.emitBudget == 0u || off < p.emitBudget) {
     const float4 a = ldRow(d, 0, j), b = ldRow(d, 1, j), c = ldRow(d, 2, j);
@@ -3247,7 +3247,7 @@ __global__ __launch_bounds__(kTile) void k_stage_frame(const DeviceState d, uint
   }
   uint32_t* vis = block + kFrameHeaderWords;
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < nv; t += gridDim.x * kTile) vis[t] = d.visibleIdx[t];
-  uint4* out = reinterpret_cast<uint4*>(block + kFrameHeaderWords + maxVisible);      // (maxVisible is a multiple of 4: 16-byte aligned)
+  uint4* out = reinterpret_cast<uint4*>(block + kFrameHeaderWords + frameVisibleWords(maxVisible));      // (16-byte aligned; maxVisible itself is the clamp)
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < nd * 5u; t += gridDim.x * kTile) out[t] = items[t];
 }
 
@@ -3265,7 +3265,7 @@ __global__ __launch_bounds__(kTile) void k_emit_draws_staged(const DeviceState d
     block[threadIdx.x] = h[threadIdx.x];
   }
   uint32_t* vis = block + kFrameHeaderWords;
-  DrawItem80* items = reinterpret_cast<DrawItem80*>(block + kFrameHeaderWords + maxVisible);
+  DrawItem80* items = reinterpret_cast<DrawItem80*>(block + kFrameHeaderWords + frameVisibleWords(maxVisible));
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < (emitted > nv ? emitted : nv); t += gridDim.x * kTile) {
     const uint32_t j = d.visibleIdx[t];
     if (t < nv) vis[t] = j;

@@ -610,6 +610,13 @@ class WorldTick:
         self._ok(self.lib.scTickGetCompactStats(self.ctx, _u(st)), "scTickGetCompactStats")
         return {"workgroups": int(st[0]), "spans_per_workgroup": int(st[1])}
 
+    def frame_stats(self):
+        """which code wrote the last tick's frame: (who wrote the draw items, who staged the read-back block) as capi.FRAME_ITEMS_* /
+        capi.FRAME_BLOCK_* (host-side: no read-back, no synchronisation; scTickGetFrameStats)"""
+        st = np.zeros(2, np.uint32)
+        self._ok(self.lib.scTickGetFrameStats(self.ctx, _u(st)), "scTickGetFrameStats")
+        return int(st[0]), int(st[1])
+
     def learn_ticks(self):
         """learn ticks so far (host-side counter: no read-back)"""
         st = np.zeros(1, np.uint32)

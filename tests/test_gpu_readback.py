@@ -71,6 +71,13 @@ def test_truncation_and_switching_off():
     t.run(capi.XFORM | capi.CULL)
     fr, vis, draws = t.acquire_frame()
     assert fr.visible == w.n and fr.visible_in_buffer == 100 and np.array_equal(vis, np.arange(100, dtype=np.uint32)) and len(draws) == 0
+    # a capacity that is no multiple of four: the block pads its index area, the count it reports is still min(visible, max_visible)
+    # (each of the three writers of the block, against the oracle: the capacity rows of tests/frame_cases.py)
+    t.set_frame_readback(5, 3)
+    t.run(capi.XFORM | capi.CULL | capi.DRAWS)
+    fr, vis, draws = t.acquire_frame()
+    assert fr.tick == 0 and fr.visible == w.n and fr.visible_in_buffer == 5 and np.array_equal(vis, np.arange(5, dtype=np.uint32))
+    assert fr.draws_emitted == w.n and fr.draws_in_buffer == 3 and np.array_equal(draws[:, 0:4].copy().view(np.uint32).ravel(), np.arange(3, dtype=np.uint32))
     t.set_frame_readback(0, 0)
     t.run(capi.XFORM | capi.CULL)
     with pytest.raises(capi.ScTickError, match="scTickSetFrameReadback first"):
