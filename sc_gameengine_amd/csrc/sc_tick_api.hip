@@ -798,19 +798,30 @@ bool reallocBindRuns(ScTickContext* c, uint32_t maxRuns)
   return reallocBindBlocks(c);
 }
 
-// frame read-back: the block of this frame may still be read by the copy of two frames ago; the tick stream waits for it
+// frame read-back: this tick's slot of the two blocks, which the copy of two frames ago may still read; the tick stream waits for it
+uint32_t frameSlot(const ScTickContext::FrameReadback& rb) { return (uint32_t)(rb.frames & 1u); }
 // (asked first: a satisfied wait costs a bubble too)
 void waitFrameBlock(ScTickContext* c)
 {
   ScTickContext::FrameReadback& rb = c->rb;
-  const uint32_t f = (uint32_t)(rb.frames & 1u);
+  const uint32_t f = frameSlot(rb);
   if (!rb.inFlight[f]) return;
   if (hipEventQuery(rb.copied[f]) != hipSuccess) hipStreamWaitEvent(c->stream, rb.copied[f], 0);
   (void)hipGetLastError();
 }
 
+// this tick's frame is on its way to the host (or, on an emptied context, already there): `copied` is what scTickAcquireFrame waits on
+hipError_t publishFrame(ScTickContext* c, bool bindsStaged)
+{
+  ScTickContext::FrameReadback& rb = c->rb;
+  const uint32_t f = frameSlot(rb);
+  rb.bindsStaged[f] = bindsStaged; rb.inFlight[f] = true;
+  rb.frames++;
+  return hipEventRecord(rb.copied[f], rb.copyStream);
+}
+
 // Which code writes the frame -- the draw items and the read-back block -- on a tick with these TickParams::flags: the one rule behind
-// enqueueStages' launches and scTickGetFrameStats' report.
+// enqueueStages' launches and scTickGetFrameStats' report; scTickRun asks once per tick.
 //   stagedEmit   the read-back is on and a plain draw list's budget fits the block: the items go straight into the block
 //   foldEmit     the combined end-of-tick launch runs (compaction and pair search): its compaction role writes the items
 //   stagedByEot  both: that role writes the whole block, header included
@@ -837,9 +848,60 @@ FramePath framePathFor(const ScTickContext* c, uint32_t flags)
   return f;
 }
 
+// path.foldEmit.  Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
+// entity's place in the list, i.e. its draw item (emitVisible).  With the frame read-back on (and a budget that fits the block)
+// the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
+// Fills the launch's `pe`; returns the event it records (the block's `staged`), or null.
+hipEvent_t fillFoldEmit(ScTickContext* c, const FramePath& path, TickParams& pe)
+{
+  pe.emitBudget = c->desc.max_draws_budget;
+  if (!path.stagedByEot) { pe.emitMode = 1u; pe.emitTarget = reinterpret_cast<uint32_t*>(c->dDraws); return nullptr; }
+  ScTickContext::FrameReadback& rb = c->rb;
+  const uint32_t f = frameSlot(rb);
+  waitFrameBlock(c);
+  pe.emitMode = 2u; pe.emitTarget = rb.dBlock[f]; pe.emitMaxVisible = rb.maxVisible;
+  pe.emitTickLo = (uint32_t)rb.frames; pe.emitTickHi = (uint32_t)(rb.frames >> 32);
+  return rb.staged[f];
+}
+
+// The frame behind the end-of-tick launches: what they did not fold -- sorted draws, split flows, a budget beyond the block -- is emitted here (read-back on,
+// plain order and a budget that fits the block: emission and staging are one launch; else emission or sort, bind runs, staging); the block is copied and published.
+void enqueueFrame(ScTickContext* c, const DeviceState& ds, uint32_t flags, const FramePath& path)
+{
+  const uint32_t budget = c->desc.max_draws_budget;
+  c->lastDraws = c->dDraws;
+  if ((flags & SC_TICK_DRAWS) && !path.stagedEmit && !path.foldEmit) {
+    const uint32_t bound = (budget && budget < c->n) ? budget : c->n;
+    if (flags & SC_TICK_SORT_DRAWS) {
+      launchSortedDraws(ds, c->sort, budget, bound, c->dDraws, c->stream);
+      if (flags & SC_TICK_BIND_RUNS) launchBindRuns(ds, c->sort, c->bind, bound, c->stream);      // the sorted keys are still in place
+    } else launchEmitDraws(ds, budget, c->dDraws, c->stream);
+  }
+  if (!c->rb.bytes) return;
+  ScTickContext::FrameReadback& rb = c->rb;
+  const uint32_t f = frameSlot(rb);
+  if (!path.stagedByEot) waitFrameBlock(c);             // (the end-of-tick kernel's launch waited already)
+  bool binds = false;
+  if (path.stagedEmit) {                                // (stagedByEot: the end-of-tick kernel wrote the block)
+    if (!path.stagedByEot) launchEmitDrawsStaged(ds, budget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);
+    c->lastDraws = frameItems(rb.dBlock[f], rb.maxVisible);      // what scTickReadDraws returns for this tick
+  } else {
+    // (a flagged run is a sorted one, so it comes through here: its bind block is staged ahead of the frame's, whose `staged` covers both)
+    binds = rb.bindBytes && (flags & SC_TICK_BIND_RUNS);
+    if (binds) launchStageBinds(c->bind, rb.dBinds[f], c->stream);
+    const uint32_t drawMode = (flags & SC_TICK_DRAWS) ? ((flags & SC_TICK_SORT_DRAWS) ? 2u : 1u) : 0u;
+    launchStageFrame(ds, rb.dBlock[f], rb.maxVisible, rb.maxDraws, c->dDraws, drawMode, rb.frames, c->stream, rb.staged[f]);
+  }
+  // (`staged` rides on the staging dispatch: its completion signal, no marker packet on the tick queue)
+  hipStreamWaitEvent(rb.copyStream, rb.staged[f], 0);
+  hipMemcpyAsync(rb.hBlock[f], rb.dBlock[f], rb.bytes, hipMemcpyDeviceToHost, rb.copyStream);
+  if (binds) hipMemcpyAsync(rb.hBinds[f], rb.dBinds[f], rb.bindBytes, hipMemcpyDeviceToHost, rb.copyStream);      // before `copied`
+  publishFrame(c, binds);
+}
+
 // the tick's launches on c->stream, nothing else: safe inside a stream capture (the callers put waitParityFree before
-// and publishPacked behind it).  Launches are timed only on an eager, sampled tick (scTickRun sets lastTickSampled first).
-void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool inCapture)
+// and publishPacked behind it).  Launches are timed only on an eager, sampled tick (scTickRun sets lastTickSampled first, and asks for `path`).
+void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path, uint32_t grid, bool inCapture)
 {
   const uint32_t flags = p.flags;
   const DeviceState ds = stateFor(c, p.parity);
@@ -883,39 +945,21 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
     else launchAgentFrontRays(ds, p, c->stream);
   }
   if ((flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_DENSE_AABBS)) launchDenseAabbs(ds, c->n, c->stream);   // read-back aid, off the hot path
-  const FramePath path = framePathFor(c, flags);
-  const bool needCompact = path.needCompact, pairsNow = path.pairsNow;
   const bool exactRays = c->rayShapes == SC_TICK_RAY_SHAPES_EXACT;
-  if (pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
-  if (pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
+  if (path.pairsNow && (flags & SC_TICK_RAYS)) launchRayQueries(ds, p, c->rays, exactRays, c->stream);      // the bins are full, not yet consumed
+  if (path.pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
   // (overlap queries: scTickRun refuses them in a split flow, so this is their one launch site -- the pair half never sees the flag)
-  if (pairsNow && (flags & kFlagOverlaps)) launchOverlapQueries(ds, p, c->overlaps, c->overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
+  if (path.pairsNow && (flags & kFlagOverlaps)) launchOverlapQueries(ds, p, c->overlaps, c->overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
   if (flags & SC_TICK_ANCHORED_RAYS) {
-    if (pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), false, exactRays, c->stream);
+    if (path.pairsNow) launchAnchoredRays(ds, p, anchoredFor(c, p.parity), false, exactRays, c->stream);
     else if (flags & SC_TICK_BROADPHASE) launchAnchoredRaySnapshot(ds, p, anchoredFor(c, p.parity), c->stream);
   }
-  // Draw emission rides in the end-of-tick kernel when the order is the plain one: the compaction role knows every visible
-  // entity's place in the list, i.e. its draw item (emitVisible).  With the frame read-back on (and a budget that fits the block)
-  // the items, the head of the visible list and the header go straight into the block -- no emission kernel, no staging kernel.
-  const uint32_t drawBudget = c->desc.max_draws_budget;
-  const bool stagedEmit = path.stagedEmit, foldEmit = path.foldEmit, stagedByEot = path.stagedByEot;      // (framePathFor: the rule)
-  if (needCompact && pairsNow) {
+  if (path.needCompact && path.pairsNow) {
     TickParams pe = p;
-    hipEvent_t done = nullptr;
-    if (foldEmit) {
-      pe.emitBudget = drawBudget;
-      if (stagedByEot) {
-        ScTickContext::FrameReadback& rb = c->rb;
-        const uint32_t f = (uint32_t)(rb.frames & 1u);
-        waitFrameBlock(c);
-        pe.emitMode = 2u; pe.emitTarget = rb.dBlock[f]; pe.emitMaxVisible = rb.maxVisible;
-        pe.emitTickLo = (uint32_t)rb.frames; pe.emitTickHi = (uint32_t)(rb.frames >> 32);
-        done = rb.staged[f];
-      } else { pe.emitMode = 1u; pe.emitTarget = reinterpret_cast<uint32_t*>(c->dDraws); }
-    }
+    const hipEvent_t done = path.foldEmit ? fillFoldEmit(c, path, pe) : nullptr;
     // both depend only on the fused kernel: one launch, workgroups split by role (timed as K_PAIRS, by the dispatch's own
     // begin / end timestamps like the fused kernel: no marker packets on the queue)
     if (timed(c, SC_TICK_K_PAIRS, timing)) {
@@ -927,14 +971,14 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
     launchNarrowPhase(c, ds, p, c->stream);                                                  // the pair set is complete: which of its pairs touch
     if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // ... what begun, what ended
   } else {
-    const bool packToo = needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
+    const bool packToo = path.needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
       Scoped s(c, SC_TICK_K_COMPACT, timing);
       // pipelined tile, eager: the `packed` event rides on the dispatch (publishPacked then only makes the pairs stream wait)
       const bool ride = c->pairsStream && !inCapture && !s.on;
       launchCompactPack(ds, p, grid, c->stream, ride ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
       c->packedRides = ride;
-    } else if (needCompact) {
+    } else if (path.needCompact) {
       // a quiet tick's end-of-tick kernel: timed in the slot of a broadphase tick's end-of-tick kernel, SC_TICK_K_PAIRS, and like it by the
       // dispatch's own begin / end timestamps (whoever reads that slot sees what the tick's second launch cost, whichever it was)
       if (c->lastTickQuiet && timed(c, SC_TICK_K_PAIRS, timing)) {
@@ -960,41 +1004,7 @@ void enqueueStages(ScTickContext* c, const TickParams& p, uint32_t grid, bool in
       }
     }
   }
-  // (not folded -- sorted draws, split flows, a budget beyond the block: with the frame read-back on and a plain draw list whose
-  //  budget fits the block, emission and staging are one launch; else emission, then staging)
-  c->lastDraws = c->dDraws;
-  if ((flags & SC_TICK_DRAWS) && !stagedEmit && !foldEmit) {
-    const uint32_t budget = drawBudget;
-    const uint32_t bound = (budget && budget < c->n) ? budget : c->n;
-    if (flags & SC_TICK_SORT_DRAWS) {
-      launchSortedDraws(ds, c->sort, budget, bound, c->dDraws, c->stream);
-      if (flags & SC_TICK_BIND_RUNS) launchBindRuns(ds, c->sort, c->bind, bound, c->stream);      // the sorted keys are still in place
-    } else launchEmitDraws(ds, budget, c->dDraws, c->stream);
-  }
-  if (c->rb.bytes) {
-    ScTickContext::FrameReadback& rb = c->rb;
-    const uint32_t f = (uint32_t)(rb.frames & 1u);
-    if (!stagedByEot) waitFrameBlock(c);                  // (the end-of-tick kernel's launch waited already)
-    const uint32_t drawMode = (flags & SC_TICK_DRAWS) ? ((flags & SC_TICK_SORT_DRAWS) ? 2u : 1u) : 0u;
-    rb.bindsStaged[f] = false;
-    if (stagedByEot) c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + frameVisibleWords(rb.maxVisible);       // the end-of-tick kernel wrote the block
-    else if (stagedEmit) {
-      launchEmitDrawsStaged(ds, drawBudget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);
-      c->lastDraws = rb.dBlock[f] + kFrameHeaderWords + frameVisibleWords(rb.maxVisible);       // what scTickReadDraws returns for this tick
-    } else {
-      // (a flagged run is a sorted one, so it comes through here: its bind block is staged ahead of the frame's, whose `staged` covers both)
-      rb.bindsStaged[f] = rb.bindBytes && (flags & SC_TICK_BIND_RUNS);
-      if (rb.bindsStaged[f]) launchStageBinds(c->bind, rb.dBinds[f], c->stream);
-      launchStageFrame(ds, rb.dBlock[f], rb.maxVisible, rb.maxDraws, c->dDraws, drawMode, rb.frames, c->stream, rb.staged[f]);
-    }
-    // (`staged` rides on the staging dispatch: its completion signal, no marker packet on the tick queue)
-    hipStreamWaitEvent(rb.copyStream, rb.staged[f], 0);
-    hipMemcpyAsync(rb.hBlock[f], rb.dBlock[f], rb.bytes, hipMemcpyDeviceToHost, rb.copyStream);
-    if (rb.bindsStaged[f]) hipMemcpyAsync(rb.hBinds[f], rb.dBinds[f], rb.bindBytes, hipMemcpyDeviceToHost, rb.copyStream);      // before `copied`
-    hipEventRecord(rb.copied[f], rb.copyStream);
-    rb.inFlight[f] = true;
-    rb.frames++;
-  }
+  enqueueFrame(c, ds, flags, path);
 }
 
 // drop captured graphs: every one of the array (the tick's: the quiet tick's too)
@@ -2008,14 +2018,11 @@ int scTickRun(ScTickContext* c, uint32_t flags)
       // every scTickRun ends with a frame: this one is all zeros under the next tick index, written by the host into the pinned block
       // (nothing is launched and nothing copied; the block's copy of two frames ago is waited for on the host -- a rare tick)
       ScTickContext::FrameReadback& rb = c->rb;
-      const uint32_t f = (uint32_t)(rb.frames & 1u);
+      const uint32_t f = frameSlot(rb);
       if (rb.inFlight[f]) HIP_OK(c, hipEventSynchronize(rb.copied[f]));
-      std::memset(rb.hBlock[f], 0, (size_t)kFrameHeaderWords * 4u);
-      rb.hBlock[f][6] = (uint32_t)rb.frames; rb.hBlock[f][7] = (uint32_t)(rb.frames >> 32);
-      rb.bindsStaged[f] = false;
-      HIP_OK(c, hipEventRecord(rb.copied[f], rb.copyStream));      // (what scTickAcquireFrame waits on)
-      rb.inFlight[f] = true;
-      rb.frames++;
+      const FrameHeader h = frameHeader(0u, 0u, 0u, 0u, 0u, 0u, (uint32_t)rb.frames, (uint32_t)(rb.frames >> 32), 0u, 0u);
+      std::memcpy(rb.hBlock[f], h.w, sizeof h.w);
+      HIP_OK(c, publishFrame(c, false));
       c->lastFrame[1] = SC_TICK_FRAME_BLOCK_HOST;
     }
     return 1;
@@ -2105,16 +2112,12 @@ int scTickRun(ScTickContext* c, uint32_t flags)
 
   // the end-of-tick launch's shape (enqueueStages' rule for who carries the compaction role): the wide form only where the launch is
   // the compaction's own
-  {
-    const bool needCompact = (p.flags & SC_TICK_CULL) != 0 || ((p.flags & SC_TICK_XFORM) && !(p.flags & kFlagTailOwnsDirty));
-    const bool pairsNow = (p.flags & SC_TICK_BROADPHASE) && !(p.flags & SC_TICK_SPLIT_PAIRS);
-    const bool alone = needCompact && !(p.flags & SC_TICK_BROADPHASE);
-    c->compactG = (alone && c->wideCompact) ? compactWideGroup(p, grid, c->compactForceG) : 0u;
-    c->lastCompact[0] = c->lastCompact[1] = 0u;
-    if (needCompact) compactLaunchShape(grid, pairsNow, c->compactG, c->lastCompact);
-    const FramePath path = framePathFor(c, p.flags);       // (here, not in enqueueStages: a replayed graph enqueues nothing)
-    c->lastFrame[0] = path.items; c->lastFrame[1] = path.block;
-  }
+  const FramePath path = framePathFor(c, p.flags);         // once per tick (here, not in enqueueStages: a replayed graph enqueues nothing)
+  const bool alone = path.needCompact && !(p.flags & SC_TICK_BROADPHASE);
+  c->compactG = (alone && c->wideCompact) ? compactWideGroup(p, grid, c->compactForceG) : 0u;
+  c->lastCompact[0] = c->lastCompact[1] = 0u;
+  if (path.needCompact) compactLaunchShape(grid, path.pairsNow, c->compactG, c->lastCompact);
+  c->lastFrame[0] = path.items; c->lastFrame[1] = path.block;
   const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
   c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
   waitParityFree(c, p);
@@ -2124,14 +2127,14 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     // step of an in-order tile is ONE hipGraphLaunch
     const bool whole = c->captureWholeStep;
     if (!replayGraph(c, c->stream, c->graph[quiet ? kMaxParity : q], p, whole, "hipStreamEndCapture", [&] {
-          enqueueStages(c, p, grid, true);
+          enqueueStages(c, p, path, grid, true);
           if (!whole) return 1;
           if (!exchangeBorders(c, p.parity, c->stream, true)) return 0;
           enqueuePairHalf(c, p, c->stream);
           return 1;
         })) return 0;
   } else {
-    enqueueStages(c, p, grid, false);
+    enqueueStages(c, p, path, grid, false);
   }
   publishPacked(c, p);
   if (flags & SC_TICK_BROADPHASE) {
@@ -3130,9 +3133,8 @@ int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDr
   rb.bytes = 0; rb.frames = 0; rb.maxVisible = rb.maxDraws = 0;
   if (!maxVisible && !maxDraws) return reallocBindBlocks(c) ? 1 : 0;      // (the bind runs lose their staging blocks)
   if (maxVisible > c->cap || maxDraws > c->cap) return fail(c, "read-back sizes exceed the context's capacity");
-  // (the block keeps frameVisibleWords(maxVisible) words for the indices -- the items behind them stay 16-byte aligned --; the clamp of
-  //  visible_in_buffer is maxVisible as it was asked for)
-  const size_t bytes = (size_t)kFrameHeaderWords * 4u + (size_t)frameVisibleWords(maxVisible) * 4u + (size_t)maxDraws * sizeof(ScTickDrawItem);
+  static_assert(sizeof(ScTickDrawItem) == kDrawItemBytes && offsetof(ScTickDrawItem, model) == 16, "the device writes the item as five float4");
+  const size_t bytes = frameBlockBytes(maxVisible, maxDraws);
   if (!rb.copyStream) {
     HIP_OK(c, hipStreamCreateWithFlags(&rb.copyStream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
@@ -3164,12 +3166,12 @@ int scTickAcquireFrame(ScTickContext* c, uint32_t framesBack, ScTickFrame* out)
   HIP_OK(c, hipEventSynchronize(rb.copied[f]));               // this frame's copy only: later work keeps running
   const uint32_t* h = rb.hBlock[f];
   std::memset(out, 0, sizeof *out);
-  out->tick = (uint64_t)h[6] | ((uint64_t)h[7] << 32);
-  out->visible = h[0]; out->culled = h[1]; out->renderables_total = h[2];
-  out->draws_emitted = h[3]; out->draws_dropped = h[4]; out->draws_sorted = h[5];
-  out->visible_in_buffer = h[8]; out->draws_in_buffer = h[9];
+  out->tick = (uint64_t)h[kFhTickLo] | ((uint64_t)h[kFhTickHi] << 32);
+  out->visible = h[kFhVisible]; out->culled = h[kFhCulled]; out->renderables_total = h[kFhRenderablesTotal];
+  out->draws_emitted = h[kFhDrawsEmitted]; out->draws_dropped = h[kFhDrawsDropped]; out->draws_sorted = h[kFhDrawsSorted];
+  out->visible_in_buffer = h[kFhVisibleInBuffer]; out->draws_in_buffer = h[kFhDrawsInBuffer];
   out->visible_indices = h + kFrameHeaderWords;
-  out->draws = reinterpret_cast<const ScTickDrawItem*>(h + kFrameHeaderWords + frameVisibleWords(rb.maxVisible));
+  out->draws = reinterpret_cast<const ScTickDrawItem*>(frameItems(h, rb.maxVisible));
   return 1;
 }
 

@@ -173,21 +173,13 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_pass(const PassArgs a)
   }
 }
 
-struct DrawItem80s { uint32_t dense, mesh, material, pad; float model[16]; };
-
 // DrawItem{entity, mesh, material, worldMatrix} (sc_world_partition.cpp:1314-1321) in sorted order
-__global__ __launch_bounds__(kTile) void k_emit_draws_sorted(const DeviceState d, const uint32_t* __restrict__ order, DrawItem80s* __restrict__ items)
+__global__ __launch_bounds__(kTile) void k_emit_draws_sorted(const DeviceState d, const uint32_t* __restrict__ order, float4* __restrict__ items)
 {
   const uint32_t count = d.counters[kCtrDrawsSorted];
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < count; t += gridDim.x * kTile) {
     const uint32_t j = d.visibleIdx[order[t]];
-    const float4 r0 = d.w0[j], r1 = d.w1[j], r2 = d.w2[j];
-    float4* o = reinterpret_cast<float4*>(&items[t]);
-    o[0] = make_float4(__uint_as_float(j), __uint_as_float(d.meshId[j]), __uint_as_float(d.materialId[j]), 0.0f);
-    o[1] = make_float4(r0.x, r1.x, r2.x, 0.0f);
-    o[2] = make_float4(r0.y, r1.y, r2.y, 0.0f);
-    o[3] = make_float4(r0.z, r1.z, r2.z, 0.0f);
-    o[4] = make_float4(r0.w, r1.w, r2.w, 1.0f);
+    writeDrawItem(d, items + 5u * (size_t)t, j, d.w0[j], d.w1[j], d.w2[j]);
   }
 }
 
@@ -211,7 +203,7 @@ void launchSortedDraws(const DeviceState& d, const DrawSortState& st, uint32_t b
     }
     from ^= 1u;
   }
-  hipLaunchKernelGGL(k_emit_draws_sorted, dim3(std::max(keyBlocks, 1u)), dim3(kTile), 0, s, d, st.idx[from], (DrawItem80s*)items);
+  hipLaunchKernelGGL(k_emit_draws_sorted, dim3(std::max(keyBlocks, 1u)), dim3(kTile), 0, s, d, st.idx[from], (float4*)items);
 }
 
 } // namespace sctick

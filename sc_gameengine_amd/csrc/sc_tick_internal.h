@@ -237,7 +237,7 @@ struct TickParams {
   uint32_t borderRecs;      // border messages: records per ring sector of a side, on average (scTickSetBorderCapacity; kBorderRecsPerBin)
   // draw emission folded into the end-of-tick kernel's compaction role (RenderPrepStreamingSystem, sc_world_partition.cpp:1306-1329): the
   // workgroup that places a visible entity in the ordered list knows its position there, i.e. the index of its draw item
-  uint32_t emitMode;        // 0 off, 1 items to emitTarget (DrawItem80[]), 2 the frame read-back block at emitTarget (header, visible head, items)
+  uint32_t emitMode;        // 0 off, 1 items to emitTarget (draw items), 2 the frame read-back block at emitTarget (header, visible head, items)
   uint32_t emitBudget;      // RenderPrepStreaming's draw budget (0 = none)
   uint32_t emitMaxVisible;  // mode 2: entries of the visible list the block holds
   uint32_t emitTickLo, emitTickHi;
@@ -745,11 +745,43 @@ void launchResetParity(const DeviceState& d, uint32_t q, hipStream_t s);
 void launchPatchParents(const DeviceState& d, const uint32_t* pairs, uint32_t count, hipStream_t s);
 void launchGatherRows(const DeviceState& d, const uint32_t* idx, uint32_t count, float* out12, hipStream_t s);
 void launchEmitDraws(const DeviceState& d, uint32_t budget, void* items, hipStream_t s);
-// frame read-back block: header (kFrameHeaderWords), visible indices, draw items
-constexpr uint32_t kFrameHeaderWords = 16;
+// ---- the frame read-back block: the one definition of its layout and of the 80-byte draw item ("Which code writes the frame")
+// [header: kFrameHeaderWords][visible indices: frameVisibleWords(max_visible)][draw items: max_draws of kDrawItemBytes]
+constexpr uint32_t kFrameHeaderWords = 16, kDrawItemBytes = 80;      // (kDrawItemBytes == sizeof(ScTickDrawItem): asserted in sc_tick_api.hip)
+enum : uint32_t { kFhVisible = 0, kFhCulled = 1, kFhRenderablesTotal = 2, kFhDrawsEmitted = 3, kFhDrawsDropped = 4, kFhDrawsSorted = 5,
+                  kFhTickLo = 6, kFhTickHi = 7, kFhVisibleInBuffer = 8, kFhDrawsInBuffer = 9 };      // (words 10 .. 15 are zero)
+// the header's words, by value: a struct a writer indexes, not an array handed out through a pointer ("What the compiler decides on")
+struct FrameHeader { uint32_t w[kFrameHeaderWords]; };
+__host__ __device__ inline FrameHeader frameHeader(uint32_t visible, uint32_t culled, uint32_t total, uint32_t emitted, uint32_t dropped, uint32_t sorted,
+                                                   uint32_t tickLo, uint32_t tickHi, uint32_t visibleInBuffer, uint32_t drawsInBuffer)
+{
+  return FrameHeader{ { visible, culled, total, emitted, dropped, sorted, tickLo, tickHi, visibleInBuffer, drawsInBuffer, 0, 0, 0, 0, 0, 0 } };
+}
+// word k for a thread that writes one of them: selects over registers (a run-time index into the struct would put it into LDS, 16 KB a workgroup)
+__host__ __device__ inline uint32_t frameHeaderWord(const FrameHeader& h, uint32_t k)
+{
+  uint32_t v = 0u;
+#pragma unroll
+  for (uint32_t i = 0; i <= kFhDrawsInBuffer; ++i) v = (k == i) ? h.w[i] : v;
+  return v;
+}
 // words the block keeps for the visible indices: max_visible rounded up to four, so that the draw items behind them stay 16-byte
-// aligned.  The writers take max_visible as the caller gave it -- the clamp of visible_in_buffer -- and find the items through this.
+// aligned.  The writers take max_visible as the caller gave it -- the clamp of visible_in_buffer -- and find the items through frameItems.
 __host__ __device__ inline uint32_t frameVisibleWords(uint32_t maxVisible) { return (maxVisible + 3u) & ~3u; }
+template <typename Word> __host__ __device__ inline Word* frameItems(Word* block, uint32_t maxVisible) { return block + kFrameHeaderWords + frameVisibleWords(maxVisible); }
+inline size_t frameBlockBytes(uint32_t maxVisible, uint32_t maxDraws) { return ((size_t)kFrameHeaderWords + frameVisibleWords(maxVisible)) * 4u + (size_t)maxDraws * kDrawItemBytes; }
+#ifdef __HIPCC__
+// The draw item, written once: DrawItem{entity, mesh, material, worldMatrix} (sc_world_partition.cpp:1314-1321), the model column-major.
+// `o`: the item's five float4; a, b, c: rows 0 .. 2 of entity j's world matrix, loaded by the caller (each source addresses the slab its own way).
+__device__ __forceinline__ void writeDrawItem(const DeviceState& d, float4* o, uint32_t j, float4 a, float4 b, float4 c)
+{
+  o[0] = make_float4(__uint_as_float(j), __uint_as_float(d.meshId[j]), __uint_as_float(d.materialId[j]), 0.0f);
+  o[1] = make_float4(a.x, b.x, c.x, 0.0f);     // column 0
+  o[2] = make_float4(a.y, b.y, c.y, 0.0f);
+  o[3] = make_float4(a.z, b.z, c.z, 0.0f);
+  o[4] = make_float4(a.w, b.w, c.w, 1.0f);     // translation column
+}
+#endif
 void launchEmitDrawsStaged(const DeviceState& d, uint32_t budget, uint32_t* block, uint32_t maxVisible, uint64_t tick, hipStream_t s, hipEvent_t done = nullptr);
 void launchStageFrame(const DeviceState& d, uint32_t* block, uint32_t maxVisible, uint32_t maxDraws, const void* items, uint32_t drawMode /*0 none, 1 plain, 2 sorted*/,
                       uint64_t tick, hipStream_t s, hipEvent_t done = nullptr);

@@ -1359,23 +1359,17 @@ constexpr uint32_t kCompactLdsWords = kCompactWordsMax * 6u;  // per word: vis (
 
 // Draw emission inside the compaction (TickParams::emitMode): the entity placed at position `off` of the ordered visible list is
 // draw item `off` -- DrawItem{entity, mesh, material, worldMatrix}, the first `budget` of them (sc_world_partition.cpp:1306-1329)
-// -- and, with the frame read-back on, entry `off` of the block's copy of the list.  Same items as k_emit_draws /
-// k_emit_draws_staged write from the finished list; no launch of their own, no second pass over the list.
+// -- and, with the frame read-back on, entry `off` of the block's copy of the list.  No launch of its own, no second pass over the list.
 __device__ __forceinline__ void emitVisible(const DeviceState& d, const TickParams& p, uint32_t off, uint32_t j)
 {
   float4* items = reinterpret_cast<float4*>(p.emitTarget);
   if (p.emitMode == 2u) {
     if (off < p.emitMaxVisible) p.emitTarget[kFrameHeaderWords + off] = j;
-    items = reinterpret_cast<float4*>(p.emitTarget + kFrameHeaderWords + frameVisibleWords(p.emitMaxVisible));      // (16-byte aligned; emitMaxVisible itself is the clamp)
+    items = reinterpret_cast<float4*>(frameItems(p.emitTarget, p.emitMaxVisible));      // (16-byte aligned; emitMaxVisible itself is the clamp)
   }
   if (p.emitBudget == 0u || off < p.emitBudget) {
     const float4 a = ldRow(d, 0, j), b = ldRow(d, 1, j), c = ldRow(d, 2, j);
-    float4* o = items + 5u * (size_t)off;
-    o[0] = make_float4(__uint_as_float(j), __uint_as_float(d.meshId[j]), __uint_as_float(d.materialId[j]), 0.0f);
-    o[1] = make_float4(a.x, b.x, c.x, 0.0f);     // column 0
-    o[2] = make_float4(a.y, b.y, c.y, 0.0f);
-    o[3] = make_float4(a.z, b.z, c.z, 0.0f);
-    o[4] = make_float4(a.w, b.w, c.w, 1.0f);     // translation column
+    writeDrawItem(d, items + 5u * (size_t)off, j, a, b, c);
   }
 }
 
@@ -1491,8 +1485,8 @@ __device__ __forceinline__ void compactBody(const DeviceState& d, const TickPara
         d.counters[4] = emitted; d.counters[5] = tv - emitted;
         if (p.emitMode == 2u) {
           const uint32_t nv = tv < p.emitMaxVisible ? tv : p.emitMaxVisible;
-          const uint32_t h[kFrameHeaderWords] = { tv, tc - tv, tc, emitted, tv - emitted, 0u, p.emitTickLo, p.emitTickHi, nv, emitted, 0, 0, 0, 0, 0, 0 };
-          for (uint32_t k = 0; k < kFrameHeaderWords; ++k) p.emitTarget[k] = h[k];
+          const FrameHeader h = frameHeader(tv, tc - tv, tc, emitted, tv - emitted, 0u, p.emitTickLo, p.emitTickHi, nv, emitted);
+          for (uint32_t k = 0; k < kFrameHeaderWords; ++k) p.emitTarget[k] = h.w[k];
         }
       }
     }
@@ -3214,21 +3208,14 @@ __global__ __launch_bounds__(kTile) void k_patch_parents(const DeviceState d, co
 
 // RenderPrepStreamingSystem draw emission (sc_world_partition.cpp:1306-1329): the first `budget`
 // visible entities, in order, become DrawItem{entity, mesh, material, worldMatrix}.
-struct DrawItem80 { uint32_t dense, mesh, material, pad; float model[16]; };
-__global__ __launch_bounds__(kTile) void k_emit_draws(const DeviceState d, uint32_t budget, DrawItem80* __restrict__ items)
+__global__ __launch_bounds__(kTile) void k_emit_draws(const DeviceState d, uint32_t budget, float4* __restrict__ items)
 {
   const uint32_t visible = d.counters[0];
   const uint32_t emitted = (budget > 0 && visible > budget) ? budget : visible;
   if (blockIdx.x == 0 && threadIdx.x == 0) { d.counters[4] = emitted; d.counters[5] = visible - emitted; }
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < emitted; t += gridDim.x * kTile) {
     const uint32_t j = d.visibleIdx[t];
-    const float4 a = ldRow(d, 0, j), b = ldRow(d, 1, j), c = ldRow(d, 2, j);
-    float4* o = reinterpret_cast<float4*>(&items[t]);
-    o[0] = make_float4(__uint_as_float(j), __uint_as_float(d.meshId[j]), __uint_as_float(d.materialId[j]), 0.0f);
-    o[1] = make_float4(a.x, b.x, c.x, 0.0f);     // column 0
-    o[2] = make_float4(a.y, b.y, c.y, 0.0f);
-    o[3] = make_float4(a.z, b.z, c.z, 0.0f);
-    o[4] = make_float4(a.w, b.w, c.w, 1.0f);     // translation column
+    writeDrawItem(d, items + 5u * (size_t)t, j, ldRow(d, 0, j), ldRow(d, 1, j), ldRow(d, 2, j));
   }
 }
 
@@ -3241,13 +3228,13 @@ __global__ __launch_bounds__(kTile) void k_stage_frame(const DeviceState d, uint
   const uint32_t draws = drawMode == 2u ? d.counters[kCtrDrawsSorted] : (drawMode == 1u ? d.counters[4] : 0u);
   const uint32_t nv = visible < maxVisible ? visible : maxVisible, nd = draws < maxDraws ? draws : maxDraws;
   if (blockIdx.x == 0 && threadIdx.x < kFrameHeaderWords) {
-    const uint32_t h[kFrameHeaderWords] = { visible, d.counters[1], d.counters[6], drawMode ? d.counters[4] : 0u, drawMode ? d.counters[5] : 0u,
-                                            drawMode == 2u ? d.counters[kCtrDrawsSorted] : 0u, tickLo, tickHi, nv, nd, 0, 0, 0, 0, 0, 0 };
-    block[threadIdx.x] = h[threadIdx.x];
+    const FrameHeader h = frameHeader(visible, d.counters[1], d.counters[6], drawMode ? d.counters[4] : 0u, drawMode ? d.counters[5] : 0u,
+                                      drawMode == 2u ? d.counters[kCtrDrawsSorted] : 0u, tickLo, tickHi, nv, nd);
+    block[threadIdx.x] = frameHeaderWord(h, threadIdx.x);
   }
   uint32_t* vis = block + kFrameHeaderWords;
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < nv; t += gridDim.x * kTile) vis[t] = d.visibleIdx[t];
-  uint4* out = reinterpret_cast<uint4*>(block + kFrameHeaderWords + frameVisibleWords(maxVisible));      // (16-byte aligned; maxVisible itself is the clamp)
+  uint4* out = reinterpret_cast<uint4*>(frameItems(block, maxVisible));      // (16-byte aligned; maxVisible itself is the clamp)
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < nd * 5u; t += gridDim.x * kTile) out[t] = items[t];
 }
 
@@ -3261,23 +3248,15 @@ __global__ __launch_bounds__(kTile) void k_emit_draws_staged(const DeviceState d
   const uint32_t nv = visible < maxVisible ? visible : maxVisible;
   if (blockIdx.x == 0 && threadIdx.x == 0) { d.counters[4] = emitted; d.counters[5] = visible - emitted; }
   if (blockIdx.x == 0 && threadIdx.x < kFrameHeaderWords) {
-    const uint32_t h[kFrameHeaderWords] = { visible, d.counters[1], d.counters[6], emitted, visible - emitted, 0u, tickLo, tickHi, nv, emitted, 0, 0, 0, 0, 0, 0 };
-    block[threadIdx.x] = h[threadIdx.x];
+    const FrameHeader h = frameHeader(visible, d.counters[1], d.counters[6], emitted, visible - emitted, 0u, tickLo, tickHi, nv, emitted);
+    block[threadIdx.x] = frameHeaderWord(h, threadIdx.x);
   }
   uint32_t* vis = block + kFrameHeaderWords;
-  DrawItem80* items = reinterpret_cast<DrawItem80*>(block + kFrameHeaderWords + frameVisibleWords(maxVisible));
+  float4* items = reinterpret_cast<float4*>(frameItems(block, maxVisible));
   for (uint32_t t = blockIdx.x * kTile + threadIdx.x; t < (emitted > nv ? emitted : nv); t += gridDim.x * kTile) {
     const uint32_t j = d.visibleIdx[t];
     if (t < nv) vis[t] = j;
-    if (t < emitted) {
-      const float4 a = ldRow(d, 0, j), b = ldRow(d, 1, j), c = ldRow(d, 2, j);
-      float4* o = reinterpret_cast<float4*>(&items[t]);
-      o[0] = make_float4(__uint_as_float(j), __uint_as_float(d.meshId[j]), __uint_as_float(d.materialId[j]), 0.0f);
-      o[1] = make_float4(a.x, b.x, c.x, 0.0f);
-      o[2] = make_float4(a.y, b.y, c.y, 0.0f);
-      o[3] = make_float4(a.z, b.z, c.z, 0.0f);
-      o[4] = make_float4(a.w, b.w, c.w, 1.0f);
-    }
+    if (t < emitted) writeDrawItem(d, items + 5u * (size_t)t, j, ldRow(d, 0, j), ldRow(d, 1, j), ldRow(d, 2, j));
   }
 }
 
@@ -3364,40 +3343,39 @@ void launchSnapshotHome(const DeviceState& d, uint32_t sectors, uint32_t n, uint
   else if (d.homeCast) (void)hipMemsetAsync(d.homeCast, 0, (size_t)sectors * sizeof(uint32_t), s);      // no bin is a fast sector until a learn tick orders it (should the pair search ask in between)
   if (n) hipLaunchKernelGGL(k_home_flags, dim3((n + kTile - 1) / kTile), dim3(kTile), 0, s, d, n, binSX, binSZ, vocabMode, vocab, ordered);
 }
-// `done` (may be null): recorded by the dispatch itself -- the event the copy stream waits for, without a marker packet
+// One launch of kTile-wide workgroups whose dispatch carries events (hipExtLaunchKernelGGL): evA / evB take the kernel's own begin / end
+// timestamps, evB alone is its completion signal -- no marker packet on the queue.  With neither it is the plain launch.
+template <typename... Params, typename... Args>
+static void launchWithEvents(void (*kernel)(Params...), uint32_t blocks, hipStream_t s, hipEvent_t evA, hipEvent_t evB, const Args&... args)
+{
+  if (evA || evB) hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(kTile), 0, s, evA, evB, 0, args...);
+  else hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kTile), 0, s, args...);
+}
+// `done` (may be null): recorded by the dispatch itself -- the event the copy stream waits for
 void launchEmitDrawsStaged(const DeviceState& d, uint32_t budget, uint32_t* block, uint32_t maxVisible, uint64_t tick, hipStream_t s, hipEvent_t done)
 {
   const uint32_t work = std::max(maxVisible, budget);
   const uint32_t blocks = std::max(1u, std::min((work + kTile - 1) / kTile, 64u));
-  if (done) hipExtLaunchKernelGGL(k_emit_draws_staged, dim3(blocks), dim3(kTile), 0, s, nullptr, done, 0, d, budget, block, maxVisible, (uint32_t)tick, (uint32_t)(tick >> 32));
-  else hipLaunchKernelGGL(k_emit_draws_staged, dim3(blocks), dim3(kTile), 0, s, d, budget, block, maxVisible, (uint32_t)tick, (uint32_t)(tick >> 32));
+  launchWithEvents(k_emit_draws_staged, blocks, s, nullptr, done, d, budget, block, maxVisible, (uint32_t)tick, (uint32_t)(tick >> 32));
 }
 void launchStageFrame(const DeviceState& d, uint32_t* block, uint32_t maxVisible, uint32_t maxDraws, const void* items, uint32_t drawMode,
                       uint64_t tick, hipStream_t s, hipEvent_t done)
 {
   const uint32_t work = std::max(maxVisible, maxDraws * 5u);
   const uint32_t blocks = std::max(1u, std::min((work + kTile - 1) / kTile, 64u));
-  if (done) hipExtLaunchKernelGGL(k_stage_frame, dim3(blocks), dim3(kTile), 0, s, nullptr, done, 0, d, block, maxVisible, maxDraws, (const uint4*)items, drawMode,
-                                  (uint32_t)tick, (uint32_t)(tick >> 32));
-  else hipLaunchKernelGGL(k_stage_frame, dim3(blocks), dim3(kTile), 0, s, d, block, maxVisible, maxDraws, (const uint4*)items, drawMode,
-                          (uint32_t)tick, (uint32_t)(tick >> 32));
+  launchWithEvents(k_stage_frame, blocks, s, nullptr, done, d, block, maxVisible, maxDraws, (const uint4*)items, drawMode, (uint32_t)tick, (uint32_t)(tick >> 32));
 }
-// evA / evB (both or neither): events that take the kernel's own begin / end timestamps (hipExtLaunchKernelGGL), so the
-// duration bench.py reports is the dispatch's, like the kernel trace's -- not the gap-inclusive span between two
-// hipEventRecord calls on the stream
+// evA / evB (both or neither): the duration bench.py reports is the dispatch's, like the kernel trace's -- not the gap-inclusive span
+// between two hipEventRecord calls on the stream
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
 static void launchHome(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
-  auto kernel = (p.flags & kFlagTailOwnsDirty) ? k_xform_cull_tail<kCull, kAabb, kChain, kHome> : k_xform_cull<kCull, kAabb, kChain, kHome>;
-  if (evA) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
-  else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, d, p);
+  launchWithEvents((p.flags & kFlagTailOwnsDirty) ? k_xform_cull_tail<kCull, kAabb, kChain, kHome> : k_xform_cull<kCull, kAabb, kChain, kHome>, grid, s, evA, evB, d, p);
 }
 template <bool kCull, uint32_t kChain, uint32_t kHome>
 static void launchHomeColliders(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
-  auto kernel = (p.flags & kFlagTailOwnsDirty) ? k_xform_cull_colliders_tail<kCull, kChain, kHome> : k_xform_cull_colliders<kCull, kChain, kHome>;
-  if (evA) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, evA, evB, 0, d, p);
-  else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTile), 0, s, d, p);
+  launchWithEvents((p.flags & kFlagTailOwnsDirty) ? k_xform_cull_colliders_tail<kCull, kChain, kHome> : k_xform_cull_colliders<kCull, kChain, kHome>, grid, s, evA, evB, d, p);
 }
 template <bool kCull, bool kAabb, uint32_t kChain>
 static void launchOne(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
@@ -3483,9 +3461,7 @@ void compactLaunchShape(uint32_t grid, bool merged, uint32_t wideG, uint32_t sha
 void launchCompact(const DeviceState& d, const TickParams& p, uint32_t grid, uint32_t wideG, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
   const uint32_t g = wideG ? wideG : compactGroup(grid, false);
-  auto kernel = wideG ? k_compact_wide : k_compact;
-  if (evA) hipExtLaunchKernelGGL(kernel, dim3((grid + g - 1) / g), dim3(kTile), 0, s, evA, evB, 0, d, p, g);
-  else hipLaunchKernelGGL(kernel, dim3((grid + g - 1) / g), dim3(kTile), 0, s, d, p, g);
+  launchWithEvents(wideG ? k_compact_wide : k_compact, (grid + g - 1) / g, s, evA, evB, d, p, g);
 }
 // Pair-role geometry (round 4, second form): four pair workgroups for every CU -- the fifth resident workgroup of each CU is left to the
 // compaction role, which shares the launch and comes behind the pair role in index order -- and the run as long as that needs:
@@ -3526,8 +3502,7 @@ bool launchPairs(const DeviceState& d, const TickParams& p, hipStream_t s, hipEv
 {
   if (!(p.binSX * p.binSZ)) return false;
   auto kernel = p.colliders ? (p.lazy == 2u ? k_pairs_colliders<true> : k_pairs_colliders<false>) : (p.lazy == 2u ? k_pairs<true> : k_pairs<false>);
-  if (done) hipExtLaunchKernelGGL(kernel, dim3(pairGridFor(p)), dim3(kTile), 0, s, nullptr, done, 0, d, p);
-  else hipLaunchKernelGGL(kernel, dim3(pairGridFor(p)), dim3(kTile), 0, s, d, p);
+  launchWithEvents(kernel, pairGridFor(p), s, nullptr, done, d, p);
   return true;
 }
 void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t compactGrid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
@@ -3537,8 +3512,7 @@ void launchCompactPairs(const DeviceState& d, const TickParams& p, uint32_t comp
   const uint32_t blocks = (compactGrid + g - 1) / g;
   auto kernel = p.colliders ? (p.emitMode ? k_compact_pairs_colliders<true> : k_compact_pairs_colliders<false>)
                             : (p.emitMode ? k_compact_pairs<true> : k_compact_pairs<false>);      // (draw emission in the compaction role: an instance of its own)
-  if (evA || evB) hipExtLaunchKernelGGL(kernel, dim3(blocks + pairGrid), dim3(kTile), 0, s, evA, evB, 0, d, p, blocks, g);
-  else hipLaunchKernelGGL(kernel, dim3(blocks + pairGrid), dim3(kTile), 0, s, d, p, blocks, g);
+  launchWithEvents(kernel, blocks + pairGrid, s, evA, evB, d, p, blocks, g);
 }
 void launchGatherPairs(const DeviceState& d, const TickParams& p, uint32_t parity, uint2* dst, uint32_t* total, hipStream_t s)
 {
@@ -3549,8 +3523,7 @@ void launchCompactPack(const DeviceState& d, const TickParams& p, uint32_t grid,
   const uint32_t g = compactGroup(grid, false);
   const uint32_t blocks = (grid + g - 1) / g;
   // `done`: recorded by the dispatch itself (its completion signal) -- no marker packet behind the kernel on the tick queue
-  if (done) hipExtLaunchKernelGGL(k_compact_pack, dim3(blocks + 8u), dim3(kTile), 0, s, nullptr, done, 0, d, p, blocks, g);
-  else hipLaunchKernelGGL(k_compact_pack, dim3(blocks + 8u), dim3(kTile), 0, s, d, p, blocks, g);
+  launchWithEvents(k_compact_pack, blocks + 8u, s, nullptr, done, d, p, blocks, g);
 }
 void launchBorderPack(const DeviceState& d, const TickParams& p, hipStream_t s)
 {
@@ -3636,7 +3609,7 @@ void launchGatherRows(const DeviceState& d, const uint32_t* idx, uint32_t count,
 }
 void launchEmitDraws(const DeviceState& d, uint32_t budget, void* items, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_emit_draws, dim3(1024), dim3(kTile), 0, s, d, budget, (DrawItem80*)items);
+  hipLaunchKernelGGL(k_emit_draws, dim3(1024), dim3(kTile), 0, s, d, budget, (float4*)items);
 }
 
 } // namespace sctick
