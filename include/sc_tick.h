@@ -356,6 +356,16 @@ int scTickGetLearnTicks(ScTickContext* ctx, uint32_t* learn_ticks);
  * the table.  Host-side, no read-back, no synchronisation -- but a walk over every entity's host record (O(n), about a millisecond
  * at a million entities): for tests and logs, not for the frame loop. */
 int scTickGetBoundsClassStats(ScTickContext* ctx, uint32_t stats[4]);
+/* Topology classes (diagnostics; no result depends on them).  A run of 64 consecutive dense indices is CLOSED when every entity in it has
+ * at most three ancestors and all of them in the same run; its pattern is what the run's entities are to each other and carry as flags
+ * (parent by position in the run, RenderMesh / Bounds, depth, which rotation axes are trivial).  The library numbers the distinct patterns
+ * of the world (by bit pattern, up to 256) wherever it re-links the hierarchy.  In a world with a hierarchy whose every run is closed and
+ * numbered -- worlds built from prefabs look like this -- a tick with SC_TICK_XFORM and without a binning half runs an instance of the fused
+ * kernel that reads a run's pattern from a small table instead of a link word per entity and per ancestor.  Appending roots and removing
+ * entities without a re-link leave the numbering behind; the general instance runs until the next re-link.  stats[0] patterns, [1] runs that
+ * are closed and numbered, [2] runs that are not, as of the last re-link (a pending one is flushed), [3] 1 = the last scTickRun's fused
+ * kernel was that instance.  Host-side, no read-back.  SC_TICK_TOPO_CLASSES=0 at creation: never that instance (A/B switch). */
+int scTickGetTopologyClassStats(ScTickContext* ctx, uint32_t stats[4]);
 /* The layer VOCABULARY of the tiled world: the OR of the group words and the OR of the mask words of every collider that exists on
  * ANY tile, now or later (until the next call; bits 0..15, or 0xFFFFFFFF = all, as scTickUploadLayers).  With it a pipelined tile
  * (scTickSetPipelined / scTickSetPairsStream) leaves the bins unwritten whose own records can meet nothing the world contains --
@@ -641,6 +651,15 @@ int scTickHostCameraViewProj(const float camera_world[16], float fov_y_degrees, 
 /* 1 when no parent link crosses a boundary between runs of `span` consecutive dense indices (parent[i] / span == i / span for every
  * entity with a parent; negative or out-of-range entries are no links), else 0 -- the rule scTickGetTailStats reports on. */
 int scTickHostSpanClosed(const int32_t* parent, uint32_t count, uint32_t span);
+/* The rule behind scTickGetTopologyClassStats, on its own: for a parent array (SC_TICK_NO_PARENT = none) and one flag byte per entity (bit 0
+ * has RenderMesh, bit 1 has Bounds, bits 2 / 3 / 4 rotation about X / Y / Z trivial; other bits ignored), tile_class[t] of every run t of 64
+ * consecutive indices (ceil(count / 64) entries; the last run is clipped to count) = the number of its pattern from 1, in order of first
+ * appearance, or 0 when the run is not closed -- a parent outside the run, more than three ancestors, a cycle, an entry that names no other
+ * entity of the world -- or when its pattern would be number max_patterns + 1 (max_patterns <= 256).  *pattern_count = the patterns numbered.
+ * pattern_words (may be null; [max_patterns][64]): every pattern's words -- bits 0..23 the parent's position in the run or 0xFFFFFF for
+ * none, bit 24 / 25 RenderMesh / Bounds, bits 26..28 depth, bits 29..31 trivial axes; positions past count carry 7 << 26 | 0xFFFFFF. */
+int scTickHostTopologyClasses(const int32_t* parent, const uint8_t* flags, uint32_t count, uint32_t max_patterns,
+                              uint16_t* tile_class, uint32_t* pattern_count, uint32_t* pattern_words);
 
 /* ---- sector data (.scsector) and residency: the callers either side of the tick ----
  * Host-side reader of the editor/streamer sector format, tools/shared/world_format.cpp:185-338 (ReadSectorFile;

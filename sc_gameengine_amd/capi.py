@@ -215,6 +215,7 @@ SYMBOLS = {
     "scTickGetCompactStats": (C.c_int, [_CTX, U32P]),
     "scTickGetFrameStats": (C.c_int, [_CTX, U32P]),
     "scTickGetBoundsClassStats": (C.c_int, [_CTX, U32P]),
+    "scTickGetTopologyClassStats": (C.c_int, [_CTX, U32P]),
     "scTickSetWorldLayers": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int]),
     "scTickResetHostTimes": (C.c_int, [_CTX]),
     "scTickTileStep": (C.c_int, [_CTX, C.c_uint32]),
@@ -302,6 +303,7 @@ SYMBOLS = {
     "scTickHostMat4PerspectiveRhZo": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, F32P]),
     "scTickHostCameraViewProj": (C.c_int, [F32P, C.c_float, C.c_float, C.c_float, C.c_float, F32P]),
     "scTickHostSpanClosed": (C.c_int, [I32P, C.c_uint32, C.c_uint32]),
+    "scTickHostTopologyClasses": (C.c_int, [I32P, U8P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint16), U32P, U32P]),
 }
 
 _LIB = None

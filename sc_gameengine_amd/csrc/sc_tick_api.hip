@@ -99,6 +99,16 @@ struct ScTickContext
   bool tailEnabled = true;             // SC_TICK_TAIL=0 at creation: the end-of-tick kernel keeps the dirty clear and the producer (A/B switch)
   bool spanClosed = false; uint32_t closureSpan = 0;
   bool lastTickTail = false;           // the last tick's fused kernel owned the dirty words (scTickGetTailStats)
+  // Topology classes (topoTable(), bits 16..29 of the tile words): derived with the link words (flushLinks) from hParent and
+  // hFlags.  topoCurrent: the device's link words are the ones the classes were derived from -- dropped by every path that edits link
+  // words on the device without a re-link (appended roots, the in-place remove), until the next re-link.  hTopo: pattern index + 1 per
+  // wave-tile as the tile words carry it.  A tick is eligible for the classed instance (kFlagTopoClasses, fillParams) when the classes are
+  // current and no tile of the world is unclassed.
+  bool topoEnabled = true;             // SC_TICK_TOPO_CLASSES=0 at creation: never eligible (A/B switch)
+  bool topoCurrent = false;
+  uint32_t topoPatterns = 0, topoClassed = 0, topoUnclassed = 0;
+  std::vector<uint16_t> hTopo;
+  bool lastTickTopo = false;           // the last tick's fused kernel was the classed instance (scTickGetTopologyClassStats)
   // The end-of-tick kernel's wide form (k_compact_wide): SC_TICK_VARIANT bit 4 (16) at creation keeps one workgroup per span (A/B switch);
   // SC_TICK_COMPACT_G at creation fixes the spans per workgroup instead of compactWideGroup's rule (measurements, tests).  compactG: this
   // tick's spans per workgroup, 0 = compactBody's form -- part of a captured graph's key; lastCompact: scTickGetCompactStats.
@@ -407,7 +417,7 @@ void tileWords(const ScTickContext* c, uint32_t t, uint32_t out[2])
       else if (c->hLayers[i] != layers) sameLayers = false;
     }
   }
-  out[0] = (cls & kClassMask) | (any ? 0u : kTileNoBounds) | (sameLayers ? kTileLayersShared : 0u);
+  out[0] = (cls & kClassMask) | (any ? 0u : kTileNoBounds) | (sameLayers ? kTileLayersShared : 0u) | ((uint32_t)c->hTopo[t] << kTopoShift);
   out[1] = sameLayers ? layers : 0u;
 }
 // recompute the listed wave-tiles and bring the device copy up to date with one contiguous copy (the caller synchronises)
@@ -543,12 +553,45 @@ void rebuildLinks(ScTickContext* c, std::vector<uint32_t>& link, std::vector<uin
   deriveSpanClosed(c);
 }
 
+// The topology classes of the world as hParent and hFlags stand (behind rebuildLinks: invalid parents are detached), the pattern table
+// and the tile words' class bits to the device (the caller synchronises).  Tile words are copied only where a class changed.
+bool refreshTopoClasses(ScTickContext* c)
+{
+  const uint32_t tiles = (c->n + 63u) / 64u, all = c->cap / 64u;
+  std::vector<uint16_t> cls(tiles, (uint16_t)0);
+  std::vector<uint32_t> words((size_t)kTopoCap * 64u);
+  uint32_t patterns = 0;
+  c->topoCurrent = false;
+  if (!scTickHostTopologyClasses(c->hParent.data(), c->hFlags.data(), c->n, kTopoCap, cls.data(), &patterns, words.data())) return fail(c, "topology classes");
+  c->topoPatterns = patterns; c->topoClassed = 0;
+  for (uint32_t t = 0; t < tiles; ++t) if (cls[t]) c->topoClassed++;
+  c->topoUnclassed = tiles - c->topoClassed;
+  if (patterns) {
+    std::vector<uint32_t> table((size_t)patterns * 128u);
+    for (uint32_t q = 0; q < patterns; ++q)
+      for (uint32_t lane = 0; lane < 64u; ++lane) topoEntry(&words[64u * (size_t)q], lane, &table[((size_t)q * 64u + lane) * 2u]);
+    if (!h2d(c, const_cast<uint2*>(topoTable(c->d.boundsPalette)), table.data(), table.size() * sizeof(uint32_t))) return false;
+  }
+  uint32_t lo = all, hi = 0u;
+  for (uint32_t t = 0; t < all; ++t) {
+    const uint16_t want = t < tiles ? cls[t] : (uint16_t)0;
+    if (c->hTopo[t] == want) continue;
+    c->hTopo[t] = want;
+    c->hTile[2u * (size_t)t] = (c->hTile[2u * (size_t)t] & ~(kTopoMask << kTopoShift)) | ((uint32_t)want << kTopoShift);
+    lo = std::min(lo, t); hi = std::max(hi, t + 1u);
+  }
+  if (lo < hi && !h2d(c, const_cast<uint32_t*>(c->d.tileClass) + 2u * (size_t)lo, c->hTile.data() + 2u * (size_t)lo, (size_t)(hi - lo) * 8u)) return false;
+  c->topoCurrent = true;
+  return true;
+}
+
 int flushLinks(ScTickContext* c)
 {
   if (!c->linksStale) return 1;
   std::vector<uint32_t> link, unreachBits, detached;
   std::vector<std::vector<uint32_t>> deep;
   rebuildLinks(c, link, unreachBits, detached, deep);
+  if (!refreshTopoClasses(c)) return 0;
   if (c->n) { if (!h2d(c, c->d.link, link.data(), (size_t)c->n * 4u)) return 0; }
   launchRootMask(c->d, c->n, c->stream);
   if (!h2d(c, c->d.unreach, unreachBits.data(), unreachBits.size() * 4u)) return 0;
@@ -632,6 +675,11 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   if (p.span != c->closureSpan) deriveSpanClosed(c);       // (appends / removes moved the entity count to another span; hParent is current: flushLinks ran)
   const bool producerOk = !(flags & SC_TICK_PRODUCE_NEXT) || (c->producerKind == 1u && !c->sensors);
   if (c->tailEnabled && (flags & SC_TICK_XFORM) && !(p.flags & kFlagHasDeep) && c->spanClosed && producerOk) p.flags |= kFlagTailOwnsDirty;
+  // The classed instance of the fused kernel (kFlagTopoClasses): a tick with the transform half and without binning, in a world with a
+  // hierarchy (a flat world has no walk to save), no deep level and no unreachable entity, whose every wave-tile is classed by classes
+  // that are current.  Part of a captured graph's key, like every flag.
+  if (c->topoEnabled && c->topoCurrent && (flags & SC_TICK_XFORM) && !(flags & SC_TICK_BROADPHASE) && c->levelOffsets.size() <= 1 && c->unreachable == 0
+      && c->maxDepth >= 1 && c->maxDepth <= kMaxChain && c->n && c->topoUnclassed == 0) p.flags |= kFlagTopoClasses;
   p.freeze = c->freeze ? 1u : 0u;
   p.frustumValid = c->frustumValid ? 1u : 0u;
   // the bin grid is the tile plus a ring of one sector: boxes that poke over the tile edge stay
@@ -1164,6 +1212,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (const char* s = std::getenv("SC_TICK_SPANS")) { const int v = std::atoi(s); if (v > 0) c->spansWanted = (uint32_t)v; }
   if (const char* s = std::getenv("SC_TICK_COMPACT_G")) { const int v = std::atoi(s); if (v > 0) c->compactForceG = (uint32_t)v; }
   if (const char* s = std::getenv("SC_TICK_TAIL")) c->tailEnabled = std::atoi(s) != 0;      // A/B switch: 0 keeps the dirty clear and the root nudge in the end-of-tick kernel
+  if (const char* s = std::getenv("SC_TICK_TOPO_CLASSES")) c->topoEnabled = std::atoi(s) != 0;      // A/B switch: 0 never takes the classed instance of the fused kernel
 
   bool ok = bind(c);
   if (ok) {
@@ -1181,19 +1230,25 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   DeviceState& d = c->d;
   const size_t N = c->cap;
   // one slab for every 4-byte stream, one for the matrix rows (see Stream in sc_tick_internal.h)
+  // The streams' PITCH, in entries: cap + SC_TICK_STREAM_PAD (at creation; rounded up to a multiple of 64, at most 65536; default 0).  With
+  // the default, neighbouring streams lie a power of two apart wherever the capacity is one; the pad is there to measure whether that
+  // costs anything (part B).  Every kernel addresses stream k at k * capBytes, every copy goes through the
+  // per-stream pointers below, and every stream is used up to cap entries only.
+  size_t P = N;
+  if (const char* s = std::getenv("SC_TICK_STREAM_PAD")) { const int v = std::atoi(s); if (v > 0) P = N + (size_t)std::min((v + 63) / 64 * 64, 65536); }
   float* fslab = nullptr; float4* rslab = nullptr;
-  ok = ok && dalloc(c, fslab, (size_t)kStreamCount * N) && dalloc(c, rslab, 3 * N);
+  ok = ok && dalloc(c, fslab, (size_t)kStreamCount * P) && dalloc(c, rslab, 3 * P);
   if (ok) {
-    auto F = [&](uint32_t k) { return fslab + (size_t)k * N; };
+    auto F = [&](uint32_t k) { return fslab + (size_t)k * P; };
     d.fslab = reinterpret_cast<const char*>(fslab); d.rslab = reinterpret_cast<char*>(rslab);
-    d.capBytes = (uint32_t)(N * 4u); d.capBytes16 = (uint32_t)(N * 16u);
+    d.capBytes = (uint32_t)(P * 4u); d.capBytes16 = (uint32_t)(P * 16u);
     d.px = F(kPX); d.py = F(kPY); d.pz = F(kPZ);
     d.rsx = F(kRSX); d.rcx = F(kRCX); d.rsy = F(kRSY); d.rcy = F(kRCY); d.rsz = F(kRSZ); d.rcz = F(kRCZ);
     d.sx = F(kSX); d.sy = F(kSY); d.sz = F(kSZ);
     d.bminx = F(kBMINX); d.bminy = F(kBMINY); d.bminz = F(kBMINZ); d.bmaxx = F(kBMAXX); d.bmaxy = F(kBMAXY); d.bmaxz = F(kBMAXZ);
     d.link = reinterpret_cast<uint32_t*>(F(kLINK)); d.layers = reinterpret_cast<uint32_t*>(F(kLAYERS));
     d.meshId = reinterpret_cast<uint32_t*>(F(kMESH)); d.materialId = reinterpret_cast<uint32_t*>(F(kMATERIAL));
-    d.w0 = rslab; d.w1 = rslab + N; d.w2 = rslab + 2 * N;
+    d.w0 = rslab; d.w1 = rslab + P; d.w2 = rslab + 2 * P;
   }
   ok = ok && dalloc(c, d.dirty, N / 32) && dalloc(c, d.unreach, N / 32) && dalloc(c, d.rootMask, N / 32)
           && dalloc(c, d.vis, N / 64) && dalloc(c, d.cand, N / 64) && dalloc(c, d.recomp, N / 64)
@@ -1205,12 +1260,15 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
     // bounds classes: both tables at their full size from the start, so that their pointers never change under a captured graph,
     // in ONE allocation, the tile words behind the palette: the fused kernel addresses both from one pointer (a second one held
     // in SGPRs across the tile cost its cull-only instances a wave per SIMD).  Every wave-tile starts out as "nobody has Bounds"
+    // (and the topology classes' pattern table in front of the palette: topoTable())
     float* pal = nullptr;
-    ok = ok && dalloc(c, pal, (size_t)kPaletteCap * 8u + N / 64 * 2);
+    ok = ok && dalloc(c, pal, (size_t)kTopoCap * 128u + (size_t)kPaletteCap * 8u + N / 64 * 2);
+    if (pal) pal += (size_t)kTopoCap * 128u;
     uint32_t* tc = pal ? reinterpret_cast<uint32_t*>(pal) + (size_t)kPaletteCap * 8u : nullptr;
     d.boundsPalette = pal; d.tileClass = tc;
     c->hPalette.assign((size_t)kPaletteCap * 8u, 0u);
     c->hTile.assign(N / 64 * 2, 0u);
+    c->hTopo.assign(N / 64, (uint16_t)0);
     for (size_t t = 0; t < N / 64; ++t) c->hTile[2 * t] = kClassMixed | kTileNoBounds | kTileLayersShared;
     ok = ok && h2d(c, tc, c->hTile.data(), c->hTile.size() * sizeof(uint32_t)) && sync(c);
   }
@@ -1572,7 +1630,8 @@ int scTickAppendEntities(ScTickContext* c, uint32_t count, const float* pos3, co
     c->linksStale = true;
     return flushLinks(c);
   }
-  // roots only and the rest of the hierarchy untouched: write just the new link words
+  // roots only and the rest of the hierarchy untouched: write just the new link words (no re-link: the topology classes are behind)
+  c->topoCurrent = false;
   std::vector<uint32_t> link(count);
   for (uint32_t i = 0; i < count; ++i) link[i] = linkWordOfRoot(c->hFlags[first + i]);
   if (!h2d(c, c->d.link + first, link.data(), (size_t)count * 4u)) { c->linksStale = true; return 0; }
@@ -1660,6 +1719,7 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
 
   std::vector<uint32_t> patch;                       // (entity, new parent) pairs for the device link words
   if (!relink) {
+    c->topoCurrent = false;                          // link words are relocated and patched on the device: the topology classes are behind until the next re-link
     std::vector<int32_t>&par = c->hParent, &fc = c->hFirstChild, &ns = c->hNextSib, &ps = c->hPrevSib;
     // 1. unlink the removed entities from surviving parents (indices as before the call)
     for (uint32_t k = 0; k < count; ++k) {
@@ -2009,6 +2069,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
     c->lastFlags = flags;
     c->lastTickTail = false;
+    c->lastTickTopo = false;
     c->lastTickQuiet = false;
     c->lastCompact[0] = c->lastCompact[1] = 0u;
     c->lastFrame[0] = c->lastFrame[1] = 0u;
@@ -2052,6 +2113,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   c->lastFlags = flags;
   c->lastTickQuiet = quiet;
   c->lastTickTail = (p.flags & kFlagTailOwnsDirty) != 0;
+  c->lastTickTopo = (p.flags & kFlagTopoClasses) != 0;
   c->lastTickLearn = false;
   if ((run & SC_TICK_XFORM) && !(run & SC_TICK_BROADPHASE)) c->boxesTouched = true;      // matrices change, the bins do not follow
   if (quiet) {
@@ -3548,6 +3610,15 @@ int scTickGetBoundsClassStats(ScTickContext* c, uint32_t stats[4])
     if ((w & kClassMask) < kPaletteCap) stats[1]++; else stats[2]++;
   }
   for (uint32_t i = 0; i < c->n; ++i) if ((c->hFlags[i] & 2u) && c->hClass[i] == kClassNone) stats[3]++;
+  return 1;
+}
+
+int scTickGetTopologyClassStats(ScTickContext* c, uint32_t stats[4])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  if (!bind(c) || !flushLinks(c)) return 0;
+  stats[0] = c->topoPatterns; stats[1] = c->topoClassed; stats[2] = c->topoUnclassed;
+  stats[3] = c->lastTickTopo ? 1u : 0u;
   return 1;
 }
 

@@ -2,9 +2,12 @@
 // (src/core/src/sc_math.cpp), exported through the C ABI.  Plain C++, no GPU work.
 // Compiled with -ffp-contract=off: the reference is /fp:precise.
 #include "../../include/sc_tick.h"
+#include "sc_tick_internal.h"
 
 #include <cmath>
 #include <cstring>
+#include <unordered_map>
+#include <string>
 
 namespace {
 
@@ -170,6 +173,56 @@ int scTickHostSpanClosed(const int32_t* parent, uint32_t count, uint32_t span)
     if (q < 0 || (uint32_t)q >= count) continue;
     if ((uint32_t)q / span != i / span) return 0;
   }
+  return 1;
+}
+
+// Topology classes (scTickGetTopologyClassStats): the wave-tiles -- runs of 64 consecutive dense indices, the last one clipped to `count` --
+// whose hierarchy is closed, and the distinct patterns among them.  A tile is closed when every entity in it has at most kMaxChain
+// ancestors and all of them in the same tile: its depths are then known from the tile alone, and nothing in it is in or below a cycle (a
+// walk that is still inside the tile after kMaxChain steps up has either a deeper chain or a cycle above it: both leave the tile open).
+// A parent entry other than SC_TICK_NO_PARENT that names no other entity of the world leaves its tile open as well (the re-link detaches
+// such an entity first; the caller passes the array as it stands afterwards).  The pattern of a closed tile is its 64 link words with the
+// parent field replaced by the parent's lane (kNoParent stays), lanes past `count` carrying the word of an inactive lane; patterns are
+// told apart by bit pattern, in order of first appearance, and a tile whose pattern would be number max_patterns + 1 stays unclassed.
+int scTickHostTopologyClasses(const int32_t* parent, const uint8_t* flags, uint32_t count, uint32_t max_patterns,
+                              uint16_t* tile_class, uint32_t* pattern_count, uint32_t* pattern_words)
+{
+  using namespace sctick;
+  if ((count && (!parent || !flags || !tile_class)) || !pattern_count || max_patterns > kTopoCap) return 0;
+  std::unordered_map<std::string, uint32_t> seen;
+  uint32_t patterns = 0;
+  const uint32_t tiles = (count + 63u) / 64u;
+  for (uint32_t t = 0; t < tiles; ++t) {
+    const uint32_t lo = t * 64u, hi = count < lo + 64u ? count : lo + 64u;
+    uint32_t words[64];
+    bool closed = true;
+    for (uint32_t l = 0; l < 64u && closed; ++l) {
+      const uint32_t i = lo + l;
+      if (i >= hi) { words[l] = kTopoInactive; continue; }
+      uint32_t depth = 0, cur = i;
+      for (;;) {
+        const int32_t q = parent[cur];
+        if (q == SC_TICK_NO_PARENT) break;
+        if (q < 0 || (uint32_t)q >= count || (uint32_t)q == cur || (uint32_t)q < lo || (uint32_t)q >= hi || ++depth > kMaxChain) { closed = false; break; }
+        cur = (uint32_t)q;
+      }
+      if (!closed) break;
+      const uint8_t f = flags[i];
+      const uint32_t rel = parent[i] == SC_TICK_NO_PARENT ? kNoParent : (uint32_t)parent[i] - lo;
+      words[l] = rel | ((f & 1u) ? kHasMesh : 0u) | ((f & 2u) ? kHasBounds : 0u) | (depth << kDepthShift) |
+                 ((f & 4u) ? kRotTrivialX : 0u) | ((f & 8u) ? kRotTrivialY : 0u) | ((f & 16u) ? kRotTrivialZ : 0u);
+    }
+    tile_class[t] = 0;
+    if (!closed) continue;
+    const std::string key(reinterpret_cast<const char*>(words), sizeof words);
+    const auto it = seen.find(key);
+    if (it != seen.end()) { tile_class[t] = (uint16_t)(it->second + 1u); continue; }
+    if (patterns >= max_patterns) continue;
+    if (pattern_words) std::memcpy(pattern_words + 64u * (size_t)patterns, words, sizeof words);
+    seen.emplace(key, patterns);
+    tile_class[t] = (uint16_t)(++patterns);
+  }
+  *pattern_count = patterns;
   return 1;
 }
 

@@ -39,6 +39,29 @@ constexpr uint32_t kClassMask = 0xFFFFu, kClassMixed = 0xFFFFu, kClassNone = 0xF
 constexpr uint32_t kTileNoBounds = 1u << 30;         // host bookkeeping: no entity of the tile has Bounds (the kernel never looks)
 constexpr uint32_t kTileLayersShared = 1u << 31;
 constexpr uint32_t kTile = 256;           // entities per workgroup pass (4 waves of 64)
+// Topology classes (topoTable()): a wave-tile whose parent links all stay inside it and whose chains are at most kMaxChain long
+// is "closed"; its pattern is its 64 link words with the parent field replaced by the parent's lane.  The distinct patterns of a world
+// (by bit pattern, up to kTopoCap: 128 KiB of table, what the caches keep beside the streams) are numbered, and pattern index + 1 sits in
+// bits 16..29 of the tile's word 0 (0: the tile is not classed).  Derived by the host wherever link words are (scTickHostTopologyClasses).
+constexpr uint32_t kTopoCap = 256;
+constexpr uint32_t kTopoShift = 16, kTopoMask = 0x3FFFu;
+constexpr uint32_t kTopoInactive = (7u << 26) | 0x00FFFFFFu;      // the link word of a lane past the entity count: (kUnreachable << kDepthShift) | kNoParent
+// One table entry per lane of a pattern, 8 bytes, everything the fused kernel's walk ends up holding:
+//   x: bits 24..31 as the link word has them (mesh, bounds, depth, rotation-trivial bits), bits 0..5 / 6..11 / 12..17 the lanes of ancestors
+//      1 / 2 / 3 (the lane itself above its depth);  y: the rotation-trivial bits of the lane and of ancestors 1..3, three bits each from bit 0
+// the pattern table, [kTopoCap][64] entries of 8 bytes: the kTopoCap * 128 words in front of the bounds palette
+__host__ __device__ inline const uint2* topoTable(const float* boundsPalette) { return reinterpret_cast<const uint2*>(boundsPalette) - (size_t)kTopoCap * 64u; }
+inline void topoEntry(const uint32_t pattern[64], uint32_t lane, uint32_t out[2])
+{
+  const uint32_t own = pattern[lane];
+  uint32_t x = own & 0xFF000000u, y = own >> 29, cur = own, at = lane;
+  for (uint32_t k = 1; k <= 3u; ++k) {
+    const bool up = (cur & 0x00FFFFFFu) != 0x00FFFFFFu;
+    if (up) { at = cur & 63u; cur = pattern[at]; y |= (cur >> 29) << (3u * k); } else { at = lane; cur = 0x00FFFFFFu; }
+    x |= at << (6u * (k - 1u));
+  }
+  out[0] = x; out[1] = y;
+}
 constexpr uint32_t kMaxSpanWords = 128;   // spans up to 4096 entities keep the fused producer's ballots in LDS
 
 struct Frustum6 { float p[6][4]; };       // (nx, ny, nz, d) x 6, Frustum (sc_world_partition.h:39-43)
@@ -92,7 +115,8 @@ struct DeviceState {
   // Bounds classes: a table of the distinct local boxes (found by bit pattern) and, per wave-tile of 64 consecutive entities,
   // what its entities share -- derived from the streams above by the host for the fused kernel alone, which then fetches a
   // shared box / layer word once per tile through the scalar path instead of once per lane.  The streams stay authoritative.
-  const float* boundsPalette;  // [kPaletteCap][8]: bmin.xyz, bmax.xyz as uploaded, two words of padding
+  const float* boundsPalette;  // [kPaletteCap][8]: bmin.xyz, bmax.xyz as uploaded, two words of padding.  The same allocation holds the topology classes'
+                               // pattern table IN FRONT of it (topoTable(): no new member, the kernels' argument block keeps its layout)
   const uint32_t* tileClass;   // [cap / 64][2], == boundsPalette + kPaletteCap * 8 words (one allocation: the kernel addresses both from boundsPalette).
                                // word 0 = palette index shared by the tile's entities with Bounds (kClassMixed: none shared) | kTileLayersShared when
                                // the layer words of its entities WITH A PROXY -- with Bounds, while no collider was ever uploaded -- are all equal
@@ -283,6 +307,8 @@ constexpr uint32_t kFlagDeferredReset = 1u << 17;   // pipelined tiles: a pair k
 constexpr uint32_t kFlagDenseAabbs = 1u << 5; // == SC_TICK_DENSE_AABBS
 constexpr uint32_t kFlagOverlaps = 1u << 19;    // SC_TICK_OVERLAPS as TickParams::flags carries it: the public flag is bit 16, kFlagHasDeep's position, and only
                                                 // the low 16 public bits are copied into the word (fillParams) -- no kernel looks at this bit, the launch list does
+constexpr uint32_t kFlagTopoClasses = 1u << 20;     // every wave-tile of the world is classed and the classes are current: the fused kernel without binning takes
+                                                    // its classed instance (no link word is read: xformCullClassed)
 constexpr uint32_t kFlagTailOwnsDirty = 1u << 18;   // span-closed world: every workgroup of the fused kernel ends the tick for its own span (dirty clear, and the
                                                     // root nudge with SC_TICK_PRODUCE_NEXT: spanTail); the end-of-tick kernel then touches neither
 

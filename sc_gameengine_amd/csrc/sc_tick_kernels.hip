@@ -758,24 +758,72 @@ __device__ __forceinline__ void walkIssue(const DeviceState& d, TileWalk<kChain>
   w.pendDirty = d.dirty[w.a[lev] >> 5];
 }
 
+// The classed form (kFlagTopoClasses): every wave-tile of the world is closed and carries the number of its pattern
+// in its tile word, so the walk reads no link word and makes no trip per level.  Per tile it asks for three things -- the tile word
+// (wave-uniform, the scalar path as the bounds classes read it: written by the host, never by a kernel), the wave-tile's 64 dirty bits
+// (one 8-byte VECTOR load through a per-lane address that is the same in every lane: the words are written by earlier kernels, and a
+// vector load sees what those wrote without any argument about the scalar cache), and the lane's 8-byte entry of the pattern table
+// (topoEntry) -- and ends up holding what walkResolve's last trip leaves in a TileWalk: lk, a[0], a[1], the own rotation bits and top.
+struct ClassPend { uint32_t tw0; uint2 ent, dm; };
+// the next tile's word and dirty bits: requested, not looked at (where walk trip 1 sits)
+__device__ __forceinline__ void classRequest(const DeviceState& d, ClassPend& np, uint32_t i, uint32_t last)
+{
+  const uint32_t a0 = i <= last ? i : last;
+  const uint32_t t = __builtin_amdgcn_readfirstlane(a0 >> 6);
+  np.tw0 = ((ConstU)d.boundsPalette)[kPaletteCap * 8u + 2u * t];
+  np.dm = *reinterpret_cast<const uint2*>(d.dirty + 2u * (a0 >> 6));
+}
+// the lane's table entry (the tile word is looked at here); an unclassed tile -- one past the entity count -- reads entry 0 and drops it
+__device__ __forceinline__ void classIssue(const DeviceState& d, ClassPend& np, uint32_t lane)
+{
+  const uint32_t pat = (np.tw0 >> kTopoShift) & kTopoMask;
+  const uint32_t at = pat ? (pat <= kTopoCap ? pat - 1u : kTopoCap - 1u) : 0u;
+  np.ent = topoTable(d.boundsPalette)[at * 64u + lane];
+}
+// walkResolve's rule on the entry: top = the highest level <= depth whose ancestor's dirty bit is set
+template <uint32_t kChain>
+__device__ __forceinline__ void classResolve(const ClassPend& np, TileWalk<kChain>& w, uint32_t i, uint32_t last, uint32_t lane)
+{
+  asm volatile("" : : "v"(np.ent.x), "v"(np.dm.x), "v"(np.dm.y));
+  const uint32_t pat = (np.tw0 >> kTopoShift) & kTopoMask;
+  const uint32_t x = (i <= last && pat != 0u) ? np.ent.x : (kTopoInactive & 0xFF000000u);
+  w.a[0] = i <= last ? i : last;
+  w.lk = x; w.rotFlags = x >> 29; w.cur = x;
+  const uint32_t depth = linkDepth(x);
+  const bool walk = depth <= kChain;
+  const unsigned long long dm = ((unsigned long long)np.dm.y << 32) | np.dm.x;
+  int top = (walk && ((dm >> lane) & 1ull)) ? 0 : -1;
+#pragma unroll
+  for (uint32_t lev = 1; lev <= kChain; ++lev) {
+    const uint32_t anc = (x >> (6u * (lev - 1u))) & 63u;
+    top = (walk && lev <= depth && ((dm >> anc) & 1ull)) ? (int)lev : top;
+  }
+  w.top = top;
+  if (kChain >= 1) w.a[kChain >= 1 ? 1 : 0] = (w.a[0] & ~63u) + (x & 63u);
+}
+
 // kBatch: how many levels, from level kChain down, have their locals requested in one round trip with the seed rows; the levels
 // below are requested one by one as in xformCullBody (an instance whose registers do not hold every level: profiles/r18)
-template <bool kCull, uint32_t kChain, bool kTail, uint32_t kBatch = kChain + 1>
+// kClassed: the classed form (above).  Every wave-tile is cooperative by construction: the walk's trips, the ballot that chooses the form
+// and the rebuild arm are not instantiated; products, passes, stores, sphere test and spanTail are the same code in the same order.
+template <bool kCull, uint32_t kChain, bool kTail, uint32_t kBatch = kChain + 1, bool kClassed = false>
 __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const TickParams& p)
 {
   static_assert(kBatch >= 1 && kBatch <= kChain + 1, "levels requested together");
+  static_assert(!kClassed || (SC_WAVE_CHAINS && kChain >= 1), "the classed form is the cooperative form");
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t begin = blockIdx.x * p.span;
   const uint32_t end = (begin + p.span < p.n) ? begin + p.span : p.n;
-  const bool doXform = (p.flags & SC_TICK_XFORM) != 0;
+  const bool doXform = kClassed || (p.flags & SC_TICK_XFORM) != 0;      // (kFlagTopoClasses is only set on a tick with SC_TICK_XFORM and without deep levels)
   const bool wantCand = (p.flags & SC_TICK_CULLED_LIST) != 0;
-  const bool hasDeep = (p.flags & kFlagHasDeep) != 0;
+  const bool hasDeep = !kClassed && (p.flags & kFlagHasDeep) != 0;
   uint32_t tailWave = 0;
   if (kTail && !kCull) tailWave = __builtin_amdgcn_readfirstlane(wave);      // (scalar: see spanTail)
 
   uint32_t visCount = 0, candCount = 0;      // wave-uniform running sums
   TileWalk<kChain> w, nw;
+  ClassPend np; uint32_t tw0 = 0u;           // kClassed: what is in flight for the next tile; this tile's word 0
 
   // one tile: stage X on the walk `w`, and (hasNext) the walk of the tile behind it into `nw`, a trip at each seam of X
   auto tile = [&](uint32_t base, auto hasNext) {
@@ -796,7 +844,8 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
     Aff M;
     // ---- W, trip 1: behind X's requests in the queue and in flight with them; trip 2: under the arithmetic
     auto walkAhead = [&]() {
-      if (kNext) { walkRequest(d, nw, i + kTile, last); walkResolve(nw, 0u, i + kTile, last, doXform); if (kChain >= 1) walkIssue(d, nw, 1u, doXform); }
+      if constexpr (kClassed) { if (kNext) classRequest(d, np, i + kTile, last); }
+      else if (kNext) { walkRequest(d, nw, i + kTile, last); walkResolve(nw, 0u, i + kTile, last, doXform); if (kChain >= 1) walkIssue(d, nw, 1u, doXform); }
     };
 #if SC_WAVE_CHAINS
     // The cooperative form, chosen per wave-tile (uniform): every lane with a dirty ancestor above it has its parent in this wave-tile.
@@ -808,8 +857,8 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
     // What a lane reads in a pass that is not its own is thrown away.  A pass nobody in the wave needs is skipped (uniform), and
     // with it every later one.  The two forms are two arms of one branch, the walk's trips written in both: a value asked for in
     // one form and used in the same form is then live in that arm only.
-    bool coop = false;
-    if (kChain >= 1) coop = ballot64(top >= 1 && (w.a[kChain >= 1 ? 1 : 0] >> 6) != (i >> 6)) == 0ull;
+    bool coop = kClassed;
+    if (!kClassed && kChain >= 1) coop = ballot64(top >= 1 && (w.a[kChain >= 1 ? 1 : 0] >> 6) != (i >> 6)) == 0ull;
     if (coop) {
       LocalRaw own;
       if (recompute ? (top == 0 && !fromRoot) : (kCull && active)) M = loadRows(d, rows);
@@ -851,7 +900,8 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
       }
     }
     // ---- W, trip 3: in flight together with the stores
-    if (kNext && kChain >= 2) { walkResolve(nw, 1u, i + kTile, last, doXform); walkIssue(d, nw, 2u, doXform); }
+    if constexpr (kClassed) { if (kNext) classIssue(d, np, lane); }
+    else if (kNext && kChain >= 2) { walkResolve(nw, 1u, i + kTile, last, doXform); walkIssue(d, nw, 2u, doXform); }
     if (recompute) storeRowsPolicy(d, i, M);             // (write-through: SC_ROW_STORE_POLICY)
 
     if (hasDeep) {
@@ -859,7 +909,7 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
       if (lane == 0 && (base + wave * 64u) < p.n) d.recomp[(base >> 6) + wave] = rm;
     }
     // ---- W, trip 4: under the sphere test
-    if (kNext && kChain >= 3) { walkResolve(nw, 2u, i + kTile, last, doXform); walkIssue(d, nw, 3u, doXform); }
+    if (!kClassed && kNext && kChain >= 3) { walkResolve(nw, 2u, i + kTile, last, doXform); walkIssue(d, nw, 3u, doXform); }
 
     if (kCull) {
       const bool cand = active && (lk & kHasMesh);
@@ -867,7 +917,7 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
       // the wave-tile's class word, read here and not at the head of the tile
       const uint32_t t = __builtin_amdgcn_readfirstlane((base >> 6) + wave);
       ConstU tw = (ConstU)d.boundsPalette + (kPaletteCap * 8u + 2u * t);      // (== d.tileClass: one allocation, one pointer held in SGPRs)
-      const uint32_t cls = tw[0] & kClassMask;
+      const uint32_t cls = (kClassed ? tw0 : tw[0]) & kClassMask;      // (classed: the word the walk read a tile ahead serves topology and bounds)
       BoundsCE b = {0, 0, 0, 0, 0, 0};
       if (cls < kPaletteCap) b = paletteBounds((ConstF)d.boundsPalette + 8u * cls);      // (wave-uniform branch; a lane without Bounds never uses b)
       else if (hb) b = loadBounds(d, i);
@@ -879,7 +929,7 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
         visible = sphereVisibleAt(M, b, (ConstF)fr);
       }
       // deeper entities get their matrix (and their bit) from the level kernels
-      if (doXform && depth > kChain && depth != kUnreachable) visible = false;
+      if (!kClassed && doXform && depth > kChain && depth != kUnreachable) visible = false;
       const unsigned long long vm = ballot64(visible);
       const unsigned long long cm = ballot64(cand);
       if (lane == 0 && (base + wave * 64u) < p.n) {
@@ -890,16 +940,20 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
       candCount += (uint32_t)__popcll(cm);
     }
     // ---- W: the last trip, looked at on every path
-    if (kNext) { walkResolve(nw, kChain, i + kTile, last, doXform); w = nw; }
+    if constexpr (kClassed) { if (kNext) { classResolve(np, w, i + kTile, last, lane); tw0 = np.tw0; } }
+    else if (kNext) { walkResolve(nw, kChain, i + kTile, last, doXform); w = nw; }
   };
 
   if (begin < end) {                                   // (uniform: false for the one workgroup of an empty world)
     // prologue: the first tile's walk, trip by trip
     const uint32_t i0 = begin + threadIdx.x, last = end - 1u;
-    walkRequest(d, w, i0, last);
+    if constexpr (kClassed) { classRequest(d, np, i0, last); classIssue(d, np, lane); classResolve(np, w, i0, last, lane); tw0 = np.tw0; }
+    else {
+      walkRequest(d, w, i0, last);
 #pragma unroll
-    for (uint32_t k = 1; k <= kChain; ++k) { walkResolve(w, k - 1u, i0, last, doXform); walkIssue(d, w, k, doXform); }
-    walkResolve(w, kChain, i0, last, doXform);
+      for (uint32_t k = 1; k <= kChain; ++k) { walkResolve(w, k - 1u, i0, last, doXform); walkIssue(d, w, k, doXform); }
+      walkResolve(w, kChain, i0, last, doXform);
+    }
     uint32_t base = begin;
     for (; base + kTile < end; base += kTile) tile(base, std::true_type{});
     tile(base, std::false_type{});
@@ -946,6 +1000,11 @@ __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_tail(const De
   if constexpr (kAabb) xformCullBody<kCull, kAabb, kChain, kHome, false, true>(d, p);
   else xformCullPipelined<kCull, kChain, true, pipelinedBatch(kCull, kChain)>(d, p);
 }
+// The classed instances (kFlagTopoClasses; without binning only, chains 1..kMaxChain), under names of their own like the tail instances
+template <bool kCull, uint32_t kChain>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_classed(const DeviceState d, const TickParams p) { xformCullPipelined<kCull, kChain, false, 1u, true>(d, p); }
+template <bool kCull, uint32_t kChain>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_classed_tail(const DeviceState d, const TickParams p) { xformCullPipelined<kCull, kChain, true, 1u, true>(d, p); }
 template <bool kCull, uint32_t kChain, uint32_t kHome>
 __global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_colliders_tail(const DeviceState d, const TickParams p) { xformCullBody<kCull, true, kChain, kHome, true, true>(d, p); }
 
@@ -3370,6 +3429,14 @@ void launchStageFrame(const DeviceState& d, uint32_t* block, uint32_t maxVisible
 template <bool kCull, bool kAabb, uint32_t kChain, uint32_t kHome>
 static void launchHome(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA, hipEvent_t evB)
 {
+#if SC_WAVE_CHAINS
+  if constexpr (!kAabb && kChain >= 1u) {
+    if (p.flags & kFlagTopoClasses) {
+      launchWithEvents((p.flags & kFlagTailOwnsDirty) ? k_xform_cull_classed_tail<kCull, kChain> : k_xform_cull_classed<kCull, kChain>, grid, s, evA, evB, d, p);
+      return;
+    }
+  }
+#endif
   launchWithEvents((p.flags & kFlagTailOwnsDirty) ? k_xform_cull_tail<kCull, kAabb, kChain, kHome> : k_xform_cull<kCull, kAabb, kChain, kHome>, grid, s, evA, evB, d, p);
 }
 template <bool kCull, uint32_t kChain, uint32_t kHome>

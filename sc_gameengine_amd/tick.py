@@ -630,6 +630,13 @@ class WorldTick:
         self._ok(self.lib.scTickGetBoundsClassStats(self.ctx, _u(st)), "scTickGetBoundsClassStats")
         return {"palette_entries": int(st[0]), "tiles_shared": int(st[1]), "tiles_mixed": int(st[2]), "entities_no_class": int(st[3])}
 
+    def topology_class_stats(self):
+        """topology classes (host-side): distinct patterns, wave-tiles that are closed and numbered, wave-tiles that are not (as of the last
+        re-link), and whether the last run's fused kernel was the classed instance"""
+        st = np.zeros(4, np.uint32)
+        self._ok(self.lib.scTickGetTopologyClassStats(self.ctx, _u(st)), "scTickGetTopologyClassStats")
+        return {"patterns": int(st[0]), "tiles_classed": int(st[1]), "tiles_unclassed": int(st[2]), "classed_last_tick": bool(st[3])}
+
     def reset_host_times(self):
         self._ok(self.lib.scTickResetHostTimes(self.ctx), "scTickResetHostTimes")
 
