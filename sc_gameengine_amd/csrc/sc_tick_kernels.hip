@@ -38,6 +38,21 @@ namespace sctick {
 #ifndef SC_PAIR_OCC
 #define SC_PAIR_OCC __attribute__((amdgpu_waves_per_eu(5, 5)))
 #endif
+// Cache policy of the root nudge's px stores in the fused kernel's tail instances, under SC_ROW_STORE_POLICY's numbers (0 plain, 2 sc1
+// only): _TILE for the classed tail instances, which store in the tile (xformCullPipelined), _TAIL for spanTail.  Measured (DESIGN.md
+// section 11.27): in the tile sc1 takes 0.2-0.9 us off config 3's step against plain -- the px lines no longer sit dirty in the L2s when
+// the kernel ends; in spanTail (config3dyn's instance) sc1 is not below plain, and plain stays.
+#ifndef SC_PX_STORE_POLICY_TILE
+#define SC_PX_STORE_POLICY_TILE 2
+#endif
+#ifndef SC_PX_STORE_POLICY_TAIL
+#define SC_PX_STORE_POLICY_TAIL 0
+#endif
+// SC_DIAG_CLASSED_TAIL (diagnostic builds only, results are wrong on purpose): 1 = the classed tail instances do not end the tick at all
+// -- no px store, no dirty words.  What the end of the tick costs inside the fused kernel, as an upper bound (profiles/r34).
+#ifndef SC_DIAG_CLASSED_TAIL
+#define SC_DIAG_CLASSED_TAIL 0
+#endif
 
 // ------------------------------------------------------------------------------------------
 // 3x4 affine helpers.  Row r of the world matrix is (M[r,0], M[r,1], M[r,2], M[r,3]); the
@@ -88,6 +103,15 @@ __device__ __forceinline__ void stRowPolicy(const DeviceState& d, uint32_t row, 
 #error "SC_ROW_STORE_POLICY: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1"
 #endif
 #endif
+}
+// The dword companion: px[i] of the root nudge, plain or sc1 (kPolicy: SC_ROW_STORE_POLICY's numbers).  A vector store; what is said
+// above about vmcnt holds, and nothing in the kernel reads a px behind its store.
+template <int kPolicy>
+__device__ __forceinline__ void stPxPolicy(const DeviceState& d, uint32_t i, float v)
+{
+  static_assert(kPolicy == 0 || kPolicy == 2, "px store policy: 0 plain, 2 sc1");
+  if constexpr (kPolicy == 0) d.px[i] = v;
+  else asm volatile("global_store_dword %0, %1, %2 sc1" : : "v"(i * 4u), "v"(v), "s"(d.px) : "memory");
 }
 
 // local = T * (R * S) with R = (Rz * Ry) * Rx  (sc_math.cpp:100-142).
@@ -666,7 +690,7 @@ __device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams&
 #pragma unroll
     for (uint32_t u = 0; u < kBatch; ++u) {
       const uint32_t i = begin + u * kTile + tid;
-      if (i < end && ((rm[u] >> (i & 31u)) & 1u)) d.px[i] = x[u] + p.producerParam;
+      if (i < end && ((rm[u] >> (i & 31u)) & 1u)) stPxPolicy<SC_PX_STORE_POLICY_TAIL>(d, i, x[u] + p.producerParam);
     }
     for (uint32_t base = begin + kBatch * kTile; base < end; base += kBatch * kTile) {      // wider spans
 #pragma unroll
@@ -679,7 +703,7 @@ __device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams&
 #pragma unroll
       for (uint32_t u = 0; u < kBatch; ++u) {
         const uint32_t i = base + u * kTile + tid;
-        if (i < end && ((rm[u] >> (i & 31u)) & 1u)) d.px[i] = x[u] + p.producerParam;
+        if (i < end && ((rm[u] >> (i & 31u)) & 1u)) stPxPolicy<SC_PX_STORE_POLICY_TAIL>(d, i, x[u] + p.producerParam);
       }
     }
   }
@@ -701,7 +725,8 @@ __device__ __forceinline__ void spanTail(const DeviceState& d, const TickParams&
 // written with the conditions of xformCullBody waited for the next tile's link word at the head of the loop for that reason
 // alone.  With every walk trip looked at on every path, the wait at the bottom of the loop clears the
 // count for the next trip round.
-// No hazard: between launch and spanTail nothing in the kernel writes a link word or a dirty word, and the only rows read are
+// No hazard: between launch and spanTail nothing in the kernel writes a link word or a dirty word (the classed tail instances, which
+// write a wave-tile's dirty words in its own tile, argue theirs where they do it: kEndInTile), and the only rows read are
 // a clean seed's or a clean entity's own, which nobody writes this tick.  The trip count stays uniform over the workgroup; the
 // last tile of a span, which has no tile to walk ahead of, is a copy of the stage without the walk (kNext).
 // The price is registers -- the raw locals of every level and the next tile's walk in flight -- which these instances have:
@@ -805,7 +830,8 @@ __device__ __forceinline__ void classResolve(const ClassPend& np, TileWalk<kChai
 // kBatch: how many levels, from level kChain down, have their locals requested in one round trip with the seed rows; the levels
 // below are requested one by one as in xformCullBody (an instance whose registers do not hold every level: profiles/r18)
 // kClassed: the classed form (above).  Every wave-tile is cooperative by construction: the walk's trips, the ballot that chooses the form
-// and the rebuild arm are not instantiated; products, passes, stores, sphere test and spanTail are the same code in the same order.
+// and the rebuild arm are not instantiated; products, passes, stores and sphere test are the same code in the same order.  Its tail instances
+// end the tick in the tile instead of calling spanTail (kEndInTile, below).
 template <bool kCull, uint32_t kChain, bool kTail, uint32_t kBatch = kChain + 1, bool kClassed = false>
 __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const TickParams& p)
 {
@@ -818,8 +844,23 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
   const bool doXform = kClassed || (p.flags & SC_TICK_XFORM) != 0;      // (kFlagTopoClasses is only set on a tick with SC_TICK_XFORM and without deep levels)
   const bool wantCand = (p.flags & SC_TICK_CULLED_LIST) != 0;
   const bool hasDeep = !kClassed && (p.flags & kFlagHasDeep) != 0;
+  // The classed tail instances end the tick for a wave-tile in the tile that walks it, not in spanTail: everything spanTail loads is in
+  // the wave already.  Root: the root mask's rule (k_root_mask: no parent and reachable) is "depth 0" on a table entry; a lane past n
+  // or of an unclassed tile carries kTopoInactive, depth 7.  Unreachable: a classed tick has c->unreachable == 0 (fillParams), every
+  // unreach word is zero and (dirty & unreach) | moved is `moved`, the wave-tile's root bits when producing and 0 otherwise.  px: in the
+  // cooperative form -- the only one instantiated here -- a lane reads its own local and nobody else's, so px[i] is read by lane i
+  // alone and is in own.px when the lane recomputes; a clean root asks for it with the tile's other requests.  Hazards:
+  //  - the wave-tile's dirty bits were read a tile ahead BY THIS WAVE (classRequest) and looked at (classResolve, the asm use) before this
+  //    tile starts, and the look-ahead of tile k + 1 is again this wave's: its own store to them can only come behind its own read;
+  //  - a lane whose look-ahead (or prologue) index is past the span's end is clamped to the span's last entity and may read a dirty word
+  //    that another wave of the workgroup, already a tile further, is rewriting: what it reads is dropped (classResolve: i <= last);
+  //  - nothing else in the kernel reads px or a dirty word; the end-of-tick kernel behind it touches neither under kFlagTailOwnsDirty;
+  //  - a captured graph is keyed on kFlagTailOwnsDirty, kFlagTopoClasses and SC_TICK_PRODUCE_NEXT as before: the same flags choose this.
+  // The stores are spanTail's: the same add, the same 32-bit words (those that begin below `end`), bits past n zero.
+  constexpr bool kEndInTile = kClassed && kTail;
+  const bool produce = kEndInTile && !SC_DIAG_CLASSED_TAIL && (p.flags & SC_TICK_PRODUCE_NEXT) != 0;
   uint32_t tailWave = 0;
-  if (kTail && !kCull) tailWave = __builtin_amdgcn_readfirstlane(wave);      // (scalar: see spanTail)
+  if (kTail && !kCull && !kEndInTile) tailWave = __builtin_amdgcn_readfirstlane(wave);      // (scalar: see spanTail)
 
   uint32_t visCount = 0, candCount = 0;      // wave-uniform running sums
   TileWalk<kChain> w, nw;
@@ -861,13 +902,20 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
     if (!kClassed && kChain >= 1) coop = ballot64(top >= 1 && (w.a[kChain >= 1 ? 1 : 0] >> 6) != (i >> 6)) == 0ull;
     if (coop) {
       LocalRaw own;
+      const bool nudge = produce && depth == 0u;          // (kEndInTile: an active root on a producing tick)
       if (recompute ? (top == 0 && !fromRoot) : (kCull && active)) M = loadRows(d, rows);
       if (recompute) own = requestLocal(d, w.a[0], w.rotFlags << 29);
+      else if (kEndInTile && nudge) own.px = ldF(d, kPX, i);      // a clean root: its px in the same round trip
       walkAhead();
       if (recompute) {
         const Aff L = buildLocal(own);
         if (top == 0 && !fromRoot) M = mulAff(M, L);
         else M = L;
+      }
+      if constexpr (kEndInTile && !SC_DIAG_CLASSED_TAIL) {
+        if (nudge) stPxPolicy<SC_PX_STORE_POLICY_TILE>(d, i, own.px + p.producerParam);
+        const unsigned long long nd = ballot64(nudge);
+        if ((lane & 31u) == 0u && active) d.dirty[i >> 5] = (uint32_t)(nd >> lane);      // (lanes 0 and 32: the wave-tile's two words)
       }
       const int src4 = (int)((top >= 1 ? (w.a[kChain >= 1 ? 1 : 0] & 63u) : lane) << 2);
 #pragma unroll
@@ -968,7 +1016,7 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
       d.blockCand[blockIdx.x] = sCand[0] + sCand[1] + sCand[2] + sCand[3];
     }
   }
-  if (kTail) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+  if constexpr (kTail && !kEndInTile) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 }
 
 // Without SC_WAVE_CHAINS: every level's locals in one round trip, but for the chain-3 instance with culling: four levels and the sphere
