@@ -346,6 +346,17 @@ int scTickGetTailStats(ScTickContext* ctx, uint32_t stats[2]);
  * spans per workgroup of the wide form (clamped to what one word per thread allows) instead of the library's rule.
  * SC_TICK_VARIANT bits that remain: 1 (2) home slots off, 3 (8) quiet ticks off, 4 (16) wide compaction off, 5 (32) lazy records off. */
 int scTickGetCompactStats(ScTickContext* ctx, uint32_t stats[2]);
+/* The carried compaction (diagnostics; no result depends on it).  Where a tick's end-of-tick launch would be the wide compaction alone, behind
+ * the classed tail instance of the fused kernel, launched eagerly (no graph replay), on a context without pairs stream, neighbours or frame
+ * read-back, on a run without SC_TICK_DRAWS / SC_TICK_SORT_DRAWS / SC_TICK_BIND_RUNS and with the launch's profiling slot not timed on that
+ * tick, the launch is DEFERRED: the next scTickRun whose fused launch is that instance carries it as a few workgroups at the head of its own
+ * grid -- one launch per tick instead of two -- and any other next call that depends on it settles it first with the launch the tick would
+ * have made: scTickSynchronize, every read of a list, the counts or a frame, scTickGatherVisibleCounts, the graph / pipelined / stream /
+ * read-back / draw-budget setters, and a tick that cannot carry.  Every tick's lists and counts are what they were, one launch later or at
+ * once when asked; scTickGetCompactStats reports the deferred launch's shape.  stats[0] ticks that deferred, [1] compactions carried,
+ * [2] compactions settled, since creation.  Host-side, no read-back, no synchronisation.  A/B switch, read at creation: SC_TICK_CARRY=0
+ * never defers. */
+int scTickGetCarryStats(ScTickContext* ctx, uint32_t stats[3]);
 /* stats[3] of the above alone: learn ticks so far.  Host-side, no read-back, no synchronisation (what a timed loop may ask). */
 int scTickGetLearnTicks(ScTickContext* ctx, uint32_t* learn_ticks);
 /* Bounds classes (diagnostics; no result depends on them).  The library keeps a table of the distinct local boxes it was given

@@ -213,6 +213,7 @@ SYMBOLS = {
     "scTickGetLearnTicks": (C.c_int, [_CTX, U32P]),
     "scTickGetTailStats": (C.c_int, [_CTX, U32P]),
     "scTickGetCompactStats": (C.c_int, [_CTX, U32P]),
+    "scTickGetCarryStats": (C.c_int, [_CTX, U32P]),
     "scTickGetFrameStats": (C.c_int, [_CTX, U32P]),
     "scTickGetBoundsClassStats": (C.c_int, [_CTX, U32P]),
     "scTickGetTopologyClassStats": (C.c_int, [_CTX, U32P]),

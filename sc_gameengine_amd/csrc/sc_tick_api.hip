@@ -33,6 +33,7 @@ struct CapturedGraph {
   TickParams key{};
   uint64_t epoch = ~0ull;                              // ScTickContext::topoEpoch at capture
   uint32_t compactG = 0;                               // ScTickContext::compactG at capture: which form of the end-of-tick kernel is inside
+  uint32_t visSel = 0;                                 // ScTickContext::visSel at capture: which copy of the visibility words the kernels inside write
   bool rccl = false;                                   // the library's RCCL group is inside (captured in relaxed mode)
 };
 
@@ -114,6 +115,20 @@ struct ScTickContext
   // tick's spans per workgroup, 0 = compactBody's form -- part of a captured graph's key; lastCompact: scTickGetCompactStats.
   bool wideCompact = true; uint32_t compactForceG = 0, compactG = 0;
   uint32_t lastCompact[2] = { 0u, 0u };
+  // The carried compaction.  A tick whose end-of-tick launch would be k_compact_wide on its own may DEFER it
+  // (deferCompact's rule): `pending` then holds that launch's arguments, and the next tick's fused launch carries it at the head of
+  // its grid (k_xform_cull_classed_tail_carry) or -- where that tick cannot -- settle() launches it first.  Whoever reads a list or
+  // the counts, or changes how ticks are launched, settles first.  vis / cand / blockVis / blockCand exist twice (visAlt: the second
+  // copy): a carrying tick writes the copy its rider does not read, visSel names the copy the last tick wrote and stateFor hands it
+  // to everyone.  carryEnabled: SC_TICK_CARRY=0 at creation never defers (A/B switch).  carryStats: scTickGetCarryStats.
+  struct PendingCompact { bool on = false; DeviceState d{}; TickParams p{}; uint32_t grid = 0, wideG = 0; };
+  PendingCompact pending;
+  bool carryEnabled = true;
+  bool tickCarry = false, tickDefer = false;           // this tick's fused launch carries `pending` / this tick defers its own (scTickRun decides, enqueueStages acts)
+  uint32_t visSel = 0;
+  uint64_t* visAlt[2] = { nullptr, nullptr };          // vis, cand
+  uint32_t* blockAlt[2] = { nullptr, nullptr };        // blockVis, blockCand
+  uint32_t carryStats[3] = { 0u, 0u, 0u };             // ticks deferred, compactions carried, compactions settled
   uint32_t lastFrame[2] = { 0u, 0u };  // who wrote the last tick's draw items / staged its read-back block (scTickGetFrameStats; framePathFor)
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
   uint32_t lastFlags = 0;
@@ -348,6 +363,8 @@ bool sync(ScTickContext* c)
 DeviceState stateFor(const ScTickContext* c, uint32_t q)
 {
   DeviceState s = c->d;
+  // the visibility words and span counts the last tick wrote (the next one writes): the other copy may still feed a carried compaction
+  if (c->visSel) { s.vis = c->visAlt[0]; s.cand = c->visAlt[1]; s.blockVis = c->blockAlt[0]; s.blockCand = c->blockAlt[1]; }
   if (c->pairsStream && q >= 1u && q < kMaxParity) {
     const ScTickContext::AltSet& a = c->alt[q - 1u];
     s.binCount = a.binCount; s.binLayers = a.binLayers; s.bins = a.bins; s.bigList = a.bigList;
@@ -355,6 +372,16 @@ DeviceState stateFor(const ScTickContext* c, uint32_t q)
     for (int k = 0; k < 8; ++k) { s.borderSend[k] = a.borderSend[k]; s.borderRecv[k] = a.borderRecv[k]; }
   }
   return s;
+}
+
+// A deferred compaction that nothing will carry: its own launch, now, on the tick stream -- plain k_compact_wide with the arguments the
+// deferring tick would have given it, which is the launch order of a tick that never deferred.  Never dropped: carried or settled.
+void settle(ScTickContext* c)
+{
+  if (!c->pending.on) return;
+  launchCompact(c->pending.d, c->pending.p, c->pending.grid, c->pending.wideG, c->stream);
+  c->pending.on = false;
+  c->carryStats[2]++;
 }
 
 // results of the pair half (pairs, ray hits, broadphase counters) are read on the tick stream: let it finish first
@@ -961,11 +988,20 @@ void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path,
   }
   if (flags & (SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE)) {
     // the dominant kernel is timed by its own begin / end timestamps (the figure the roofline uses)
+    // (a carrying tick's launch has the pending compaction at the head of its grid: the timestamps then include that role)
+    const bool carry = !inCapture && c->tickCarry && c->pending.on;
+    auto fused = [&](hipEvent_t evA, hipEvent_t evB) {
+      if (!carry) { launchXformCull(ds, p, grid, c->stream, evA, evB); return; }
+      const ScTickContext::PendingCompact& pc = c->pending;
+      launchXformCullCarry(ds, p, grid, pc.d, pc.p, pc.grid, pc.wideG, c->stream, evA, evB);
+      c->pending.on = false;
+      c->carryStats[1]++;
+    };
     if (timed(c, SC_TICK_K_XFORM_CULL, timing)) {
       const EventPair ev = takeEvents(c);
-      launchXformCull(ds, p, grid, c->stream, ev.a, ev.b);
+      fused(ev.a, ev.b);
       c->times[SC_TICK_K_XFORM_CULL].push_back(ev);
-    } else launchXformCull(ds, p, grid, c->stream);
+    } else fused(nullptr, nullptr);
     if (p.homeMode == kHomeLearn) {
       // the slots handed out by the fused kernel are the remembered ones (the level kernels' and the neighbours' records reserve
       // behind them on every tick); the other copies of the bins start their next tick from the same counts
@@ -1026,6 +1062,11 @@ void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path,
       const bool ride = c->pairsStream && !inCapture && !s.on;
       launchCompactPack(ds, p, grid, c->stream, ride ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
       c->packedRides = ride;
+    } else if (path.needCompact && !inCapture && c->tickDefer) {
+      // deferred: the launch's arguments are kept, the next tick's fused launch carries it or settle() launches it
+      ScTickContext::PendingCompact& pc = c->pending;
+      pc.on = true; pc.d = ds; pc.p = p; pc.grid = grid; pc.wideG = c->compactG;
+      c->carryStats[0]++;
     } else if (path.needCompact) {
       // a quiet tick's end-of-tick kernel: timed in the slot of a broadphase tick's end-of-tick kernel, SC_TICK_K_PAIRS, and like it by the
       // dispatch's own begin / end timestamps (whoever reads that slot sees what the tick's second launch cost, whichever it was)
@@ -1074,7 +1115,7 @@ void dropCaptures(ScTickContext* c) { dropGraphs(c->graph); dropGraphs(c->pairGr
 template <typename Body>
 int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickParams& key, bool rccl, const char* what, Body body)
 {
-  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl || g.compactG != c->compactG) {
+  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl || g.compactG != c->compactG || g.visSel != c->visSel) {
     dropGraphs(&g, 1);
     HIP_OK(c, hipStreamBeginCapture(s, rccl ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
     const int ok = body();
@@ -1083,7 +1124,7 @@ int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickPar
     if (ce != hipSuccess) return fail(c, what, ce);
     if (!g.graph) return fail(c, (std::string(what) + " returned no graph (the capture was invalidated)").c_str());
     HIP_OK(c, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl; g.compactG = c->compactG;
+    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl; g.compactG = c->compactG; g.visSel = c->visSel;
   }
   HIP_OK(c, hipGraphLaunch(g.exec, s));
   return 1;
@@ -1213,6 +1254,7 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
   if (const char* s = std::getenv("SC_TICK_COMPACT_G")) { const int v = std::atoi(s); if (v > 0) c->compactForceG = (uint32_t)v; }
   if (const char* s = std::getenv("SC_TICK_TAIL")) c->tailEnabled = std::atoi(s) != 0;      // A/B switch: 0 keeps the dirty clear and the root nudge in the end-of-tick kernel
   if (const char* s = std::getenv("SC_TICK_TOPO_CLASSES")) c->topoEnabled = std::atoi(s) != 0;      // A/B switch: 0 never takes the classed instance of the fused kernel
+  if (const char* s = std::getenv("SC_TICK_CARRY")) c->carryEnabled = std::atoi(s) != 0;            // A/B switch: 0 never defers a compaction (every tick launches its own)
 
   bool ok = bind(c);
   if (ok) {
@@ -1255,6 +1297,8 @@ ScTickContext* scTickCreateContext(const ScTickContextDesc* desc)
           && dalloc(c, d.blockVis, N / kTile) && dalloc(c, d.blockCand, N / kTile)
           && dalloc(c, d.visibleIdx, N) && dalloc(c, d.culledIdx, N) && dalloc(c, d.counters, kCounterWords)
           && dalloc(c, d.aabbMin, N) && dalloc(c, d.aabbMax, N);
+  // the second copy of what a carried compaction reads while the carrying tick writes (131 KB + 16 KB at 1M entities)
+  ok = ok && dalloc(c, c->visAlt[0], N / 64) && dalloc(c, c->visAlt[1], N / 64) && dalloc(c, c->blockAlt[0], N / kTile) && dalloc(c, c->blockAlt[1], N / kTile);
   { float* f = nullptr; ok = ok && dalloc(c, f, 32); d.frustum = f; }
   {
     // bounds classes: both tables at their full size from the start, so that their pointers never change under a captured graph,
@@ -1340,6 +1384,7 @@ void scTickDestroyContext(ScTickContext* c)
 {
   if (!c) return;
   hipSetDevice(c->device);
+  c->pending.on = false;                               // (a pending compaction has no reader left: dropped)
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->pairsStream) hipStreamSynchronize(c->pairsStream);
   c->stream = c->ownStream;
@@ -1887,6 +1932,7 @@ int scTickSetDrawBudget(ScTickContext* c, uint32_t maxDraws)
 {
   if (!c) return 0;
   if (maxDraws == c->desc.max_draws_budget) return 1;
+  if (c->pending.on) { if (!bind(c)) return 0; settle(c); }
   // a captured tick holds the budget by value (the folded emission, the emission and sort launches, the run table's bound): not in the key
   if (c->graphMode) { if (!bind(c) || !sync(c)) return 0; dropGraphs(c->graph); }
   c->desc.max_draws_budget = maxDraws;
@@ -2074,6 +2120,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     c->lastCompact[0] = c->lastCompact[1] = 0u;
     c->lastFrame[0] = c->lastFrame[1] = 0u;
     c->lastDraws = c->dDraws;
+    settle(c);                                         // (a pending compaction writes the counters: ahead of the zeros)
     HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
     if (c->rb.bytes) {
       // every scTickRun ends with a frame: this one is all zeros under the next tick index, written by the host into the pinned block
@@ -2182,6 +2229,19 @@ int scTickRun(ScTickContext* c, uint32_t flags)
   c->lastFrame[0] = path.items; c->lastFrame[1] = path.block;
   const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
   c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
+  // The carried compaction.  A pending one rides at the head of this tick's fused launch where that launch is the carry-capable instance,
+  // launched eagerly; otherwise it is settled first -- its own launch ahead of everything of this tick, which is the order of two ticks
+  // that never deferred.  A carrying tick writes the other copy of the words (visSel, stateFor).  Then this tick's own compaction:
+  // deferred when its launch would be k_compact_wide alone behind that instance, nothing else of the tick or the context needs the
+  // lists on the device or on the host behind it, and the slot that would time the launch is not being timed on this tick.
+  {
+    const bool instance = !c->graphMode && carryInstance(p);
+    c->tickCarry = c->pending.on && instance;
+    if (c->tickCarry) c->visSel ^= 1u; else settle(c);
+    const bool slotTimed = timed(c, quiet ? SC_TICK_K_PAIRS : SC_TICK_K_COMPACT, c->lastTickSampled);
+    c->tickDefer = c->carryEnabled && instance && alone && c->compactG != 0u && !c->pairsStream && !c->neighbourMask && !c->rb.bytes &&
+                   !(p.flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS | SC_TICK_BIND_RUNS)) && !slotTimed;
+  }
   waitParityFree(c, p);
   const bool replay = c->graphMode && !c->lastTickSampled && !c->lastTickLearn;
   if (replay) {
@@ -2374,6 +2434,7 @@ int scTickSetPairsStream(ScTickContext* c, void* stream)
 {
   if (!c) return 0;
   if (!bind(c)) return 0;
+  settle(c);
   if (!sync(c)) return 0;
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   // The two flows clear the per-parity broadphase state differently (in order: a pair kernel clears the OTHER parity for the
@@ -2429,7 +2490,9 @@ int scTickSetPairsStream(ScTickContext* c, void* stream)
 int scTickSetStream(ScTickContext* c, void* stream, int external)
 {
   if (!c) return 0;
-  if (!bind(c) || !sync(c)) return 0;
+  if (!bind(c)) return 0;
+  settle(c);                                           // (on the stream the deferring tick ran on)
+  if (!sync(c)) return 0;
   dropGraphs(c->graph);
   c->stream = external ? static_cast<hipStream_t>(stream) : c->ownStream;
   return 1;
@@ -2439,6 +2502,7 @@ int scTickSynchronize(ScTickContext* c)
 {
   if (!c) return 0;
   if (!bind(c)) return 0;
+  settle(c);
   return sync(c) ? 1 : 0;
 }
 
@@ -2514,6 +2578,7 @@ int scTickGetCounts(ScTickContext* c, ScTickCounts* out)
 {
   if (!c || !out) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !joinPairs(c)) return 0;
+  settle(c);
   uint32_t k[kCounterWords] = {};
   if (!d2h(c, k, c->d.counters, sizeof k) || !sync(c)) return 0;
   std::memset(out, 0, sizeof *out);
@@ -2552,6 +2617,7 @@ static int readIndexList(ScTickContext* c, const uint32_t* dev, uint32_t counter
 {
   if (!c || !count) return c ? fail(c, "null argument") : 0;
   if (!bind(c)) return 0;
+  settle(c);
   uint32_t k[16] = {};
   if (!d2h(c, k, c->d.counters, sizeof k) || !sync(c)) return 0;
   const uint32_t total = k[counterSlot];
@@ -2579,7 +2645,8 @@ int scTickReadVisibilityBits(ScTickContext* c, uint64_t* words, uint32_t wordCap
   if (!bind(c)) return 0;
   const uint32_t nWords = (c->n + 63u) / 64u;
   if (wordCap < nWords) return fail(c, "word capacity too small");
-  if (nWords && (!d2h(c, words, c->d.vis, (size_t)nWords * 8u) || !sync(c))) return 0;
+  // (the copy the last tick wrote: stateFor.  A pending compaction only reads it -- nothing to settle)
+  if (nWords && (!d2h(c, words, stateFor(c, 0u).vis, (size_t)nWords * 8u) || !sync(c))) return 0;
   if (c->n & 63u) words[nWords - 1] &= (1ull << (c->n & 63u)) - 1ull;
   return 1;
 }
@@ -2684,6 +2751,7 @@ int scTickReadDraws(ScTickContext* c, ScTickDrawItem* items, uint32_t cap, uint3
   if (!c || !count) return c ? fail(c, "null argument") : 0;
   if (!bind(c)) return 0;
   if (!(c->lastFlags & SC_TICK_DRAWS)) return fail(c, "the last scTickRun did not request SC_TICK_DRAWS");
+  settle(c);
   uint32_t k[16] = {};
   if (!d2h(c, k, c->d.counters, sizeof k) || !sync(c)) return 0;
   const uint32_t have = (c->lastFlags & SC_TICK_SORT_DRAWS) ? k[kCtrDrawsSorted] : k[4];
@@ -3177,6 +3245,7 @@ int scTickSetGraphMode(ScTickContext* c, int enable)
 {
   if (!c) return 0;
   if (!bind(c)) return 0;
+  settle(c);                                           // (a replayed tick carries nothing)
   c->graphMode = enable != 0;
   if (!enable) { sync(c); dropCaptures(c); }
   return 1;
@@ -3188,7 +3257,9 @@ void* scTickGetStream(ScTickContext* c) { return c ? (void*)c->stream : nullptr;
 int scTickSetFrameReadback(ScTickContext* c, uint32_t maxVisible, uint32_t maxDraws)
 {
   if (!c) return 0;
-  if (!bind(c) || !sync(c)) return 0;
+  if (!bind(c)) return 0;
+  settle(c);                                           // (a context with a read-back never defers: its frames read the lists on the device)
+  if (!sync(c)) return 0;
   ScTickContext::FrameReadback& rb = c->rb;
   if (rb.copyStream) HIP_OK(c, hipStreamSynchronize(rb.copyStream));
   for (int k = 0; k < 2; ++k) { dfree(c, rb.dBlock[k]); rb.dBlock[k] = nullptr; if (rb.hBlock[k]) { hipHostFree(rb.hBlock[k]); rb.hBlock[k] = nullptr; } rb.inFlight[k] = false; }
@@ -3641,6 +3712,13 @@ int scTickGetCompactStats(ScTickContext* c, uint32_t stats[2])
   return 1;
 }
 
+int scTickGetCarryStats(ScTickContext* c, uint32_t stats[3])
+{
+  if (!c || !stats) return c ? fail(c, "null argument") : 0;
+  for (int k = 0; k < 3; ++k) stats[k] = c->carryStats[k];
+  return 1;
+}
+
 int scTickGetFrameStats(ScTickContext* c, uint32_t stats[2])
 {
   if (!c || !stats) return c ? fail(c, "null argument") : 0;
@@ -3787,7 +3865,9 @@ int scTickGetCommInfo(ScTickContext* c, ScTickCommInfo* out)
 int scTickGatherVisibleCounts(ScTickContext* c, uint32_t* countsOut, uint32_t capacity, uint64_t* offsetOut, uint64_t* totalOut)
 {
   if (!c || !offsetOut || !totalOut) return c ? fail(c, "null argument") : 0;
-  if (!bind(c) || !sync(c)) return 0;                      // both streams idle: the collective below is the communicator's only operation in flight
+  if (!bind(c)) return 0;
+  settle(c);
+  if (!sync(c)) return 0;                                  // both streams idle: the collective below is the communicator's only operation in flight
   const uint32_t ranks = c->comm ? c->commSize : 1u;
   std::vector<uint32_t> counts(ranks, 0u);
   if (!c->comm) {
@@ -3822,6 +3902,7 @@ int scTickSetPipelined(ScTickContext* c, int enable)
 {
   if (!c) return 0;
   if (!bind(c)) return 0;
+  settle(c);
   if (!enable) return scTickSetPairsStream(c, nullptr);
   if (enable < 0 || enable > (int)kMaxParity) return fail(c, "pipeline depth must be 2..4 (1 = the default, 4; 0 = off)");
   // depth d: the pair half of a tick may take up to d - 2 ticks before it holds anything up (a tick's counters are cleared by

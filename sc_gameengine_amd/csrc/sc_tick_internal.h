@@ -279,6 +279,16 @@ struct TickParams {
   uint32_t fastPairs;       // the pair role takes bins that hold nothing but their ordered reserved records through the fast path (homeCast)
   uint32_t colliders;       // scTickUploadColliders was called (DeviceState::colType exists): the fused and level kernels run their collider instances
 };
+// What the wide compaction touches, and nothing else: the slim argument of the body where it runs on another tick's words than the
+// launch's own (a copy of DeviceState and TickParams for the role cost the fused kernel SGPR spills).  flags: only SC_TICK_CULLED_LIST is read.
+struct CompactView {
+  const uint64_t *vis, *cand;
+  const uint32_t *blockVis, *blockCand;
+  uint32_t *visibleIdx, *culledIdx, *counters;
+  uint32_t n, span, flags;
+};
+// The carried compaction: the pending tick's view, its workgroups (at the head of the fused launch's grid) and the spans each takes
+struct CarryParams { CompactView view; uint32_t groups, group; };
 // neighbour directions: d = (dz+1)*3 + (dx+1), skipping the centre -> 0..7; opposite(d) = 7 - d
 __host__ __device__ inline void borderDir(uint32_t d, int& dx, int& dz) { const uint32_t k = d < 4 ? d : d + 1; dx = (int)(k % 3) - 1; dz = (int)(k / 3) - 1; }
 // side messages span the whole ring side including its two end cells (used when no tile exists past them)
@@ -742,6 +752,10 @@ void launchOccupancy(const DeviceState& d, uint32_t n, const float4* q, uint32_t
 
 // launchers (sc_tick_kernels.hip)
 void launchXformCull(const DeviceState& d, const TickParams& p, uint32_t grid, hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
+// the classed tail culling instance with the compaction of the tick before at the head of its grid (carryInstance(p): such an instance exists for this launch)
+bool carryInstance(const TickParams& p);
+void launchXformCullCarry(const DeviceState& d, const TickParams& p, uint32_t grid, const DeviceState& pd, const TickParams& pp, uint32_t pgrid, uint32_t wideG,
+                          hipStream_t s, hipEvent_t evA = nullptr, hipEvent_t evB = nullptr);
 void launchSnapshotHome(const DeviceState& d, uint32_t sectors, uint32_t n, uint32_t binSX, uint32_t binSZ, uint32_t vocabMode, uint32_t vocab, uint32_t ordered, hipStream_t s);
 void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* levelList, uint32_t count, hipStream_t s);
 // the end-of-tick kernel alone.  wideG: spans per workgroup of the wide form (compactWideGroup; 0: one workgroup per span, compactBody)

@@ -832,14 +832,15 @@ __device__ __forceinline__ void classResolve(const ClassPend& np, TileWalk<kChai
 // kClassed: the classed form (above).  Every wave-tile is cooperative by construction: the walk's trips, the ballot that chooses the form
 // and the rebuild arm are not instantiated; products, passes, stores and sphere test are the same code in the same order.  Its tail instances
 // end the tick in the tile instead of calling spanTail (kEndInTile, below).
+// bid: the workgroup's span -- blockIdx.x, but for the carry instance, whose grid begins with the workgroups of another role.
 template <bool kCull, uint32_t kChain, bool kTail, uint32_t kBatch = kChain + 1, bool kClassed = false>
-__device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const TickParams& p)
+__device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const TickParams& p, const uint32_t bid = blockIdx.x)
 {
   static_assert(kBatch >= 1 && kBatch <= kChain + 1, "levels requested together");
   static_assert(!kClassed || (SC_WAVE_CHAINS && kChain >= 1), "the classed form is the cooperative form");
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
-  const uint32_t begin = blockIdx.x * p.span;
+  const uint32_t begin = bid * p.span;
   const uint32_t end = (begin + p.span < p.n) ? begin + p.span : p.n;
   const bool doXform = kClassed || (p.flags & SC_TICK_XFORM) != 0;      // (kFlagTopoClasses is only set on a tick with SC_TICK_XFORM and without deep levels)
   const bool wantCand = (p.flags & SC_TICK_CULLED_LIST) != 0;
@@ -1012,8 +1013,8 @@ __device__ __forceinline__ void xformCullPipelined(const DeviceState& d, const T
     if (lane == 0) { sVis[wave] = visCount; sCand[wave] = candCount; }
     __syncthreads();
     if (threadIdx.x == 0) {
-      d.blockVis[blockIdx.x] = sVis[0] + sVis[1] + sVis[2] + sVis[3];
-      d.blockCand[blockIdx.x] = sCand[0] + sCand[1] + sCand[2] + sCand[3];
+      d.blockVis[bid] = sVis[0] + sVis[1] + sVis[2] + sVis[3];
+      d.blockCand[bid] = sCand[0] + sCand[1] + sCand[2] + sCand[3];
     }
   }
   if constexpr (kTail && !kEndInTile) spanTail(d, p, begin, end, kCull ? (wave << 6) + lane : (tailWave << 6) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
@@ -1707,15 +1708,22 @@ __global__ __launch_bounds__(kTile) void k_compact(const DeviceState d, const Ti
 // and loops over the set bits only -- the word and its offsets come out of the owning lane's registers (readlane: the index is uniform),
 // lane b stores word * 64 + b at offset + popcount(mask below b).  An empty word costs nothing; a full one is one coalesced 256-byte
 // store.  LDS: blockSum4's scratch and one dword per thread.
-__global__ __launch_bounds__(kTile) void k_compact_wide(const DeviceState d, const TickParams p, uint32_t group)
+//
+// The body is a device function over a VIEW of what it touches (CompactView: the four inputs, the two lists, the counters, n, span and
+// flags), so that it also runs as a role at the head of the NEXT tick's fused launch, on the words the tick before left (the carried
+// compaction: k_xform_cull_classed_tail_carry below).  kPrefixBatch: span counts a thread has in flight at
+// once -- 8 where the launch is the compaction's own and its latency is the step's; 4 for the carried role, whose registers have to
+// fit the fused kernel's eight waves per SIMD and whose latency lies under the tile loops of the workgroups behind it.
+template <uint32_t kPrefixBatch>
+__device__ __forceinline__ void compactWideBody(const CompactView& v, uint32_t group, uint32_t bid, uint32_t nblocks)
 {
   constexpr uint32_t kWaves = kTile / 64u;
   static_assert(kWaves == 4u, "the round-robin deal below is written for four waves");
   __shared__ __attribute__((aligned(16))) uint32_t scratch[kCompactScratch];
   __shared__ uint32_t wordCount[kWaves][64];
+  const CompactView& d = v; const CompactView& p = v;      // (the body reads as it did with DeviceState and TickParams)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
-  const uint32_t bid = blockIdx.x, nblocks = gridDim.x;
   const uint32_t width = p.span * group;
   const uint32_t begin = bid * width;
   const uint32_t end = (begin + width < p.n) ? begin + width : p.n;
@@ -1731,7 +1739,6 @@ __global__ __launch_bounds__(kTile) void k_compact_wide(const DeviceState d, con
     rawVis = d.vis[visAt];
     if (doCulled) rawCand = d.cand[visAt];
   }
-  constexpr uint32_t kPrefixBatch = 8;
   const bool lastBlock = bid == nblocks - 1u;
   const uint32_t pre = bid * group;
   const uint32_t lim = lastBlock ? (p.n + p.span - 1u) / p.span : pre;
@@ -1798,6 +1805,26 @@ __global__ __launch_bounds__(kTile) void k_compact_wide(const DeviceState d, con
       if ((cm >> lane) & 1ull) d.culledIdx[oc + __builtin_amdgcn_mbcnt_hi(cHi, __builtin_amdgcn_mbcnt_lo(cLo, 0u))] = i;
     }
   }
+}
+__host__ __device__ __forceinline__ CompactView compactViewOf(const DeviceState& d, const TickParams& p)
+{
+  return CompactView{ d.vis, d.cand, d.blockVis, d.blockCand, d.visibleIdx, d.culledIdx, d.counters, p.n, p.span, p.flags };
+}
+__global__ __launch_bounds__(kTile) void k_compact_wide(const DeviceState d, const TickParams p, uint32_t group)
+{
+  compactWideBody<8u>(compactViewOf(d, p), group, blockIdx.x, gridDim.x);
+}
+
+// The carried compaction (DESIGN.md sections 5 and 11.28).  The classed tail instance with culling, and in front of its workgroups
+// cp.groups workgroups that compact the words of the tick BEFORE: those words, and the span counts, were finished by the previous launch
+// on the stream, the lists and counters[0, 1, 6] are read by nothing on the device, and this launch's own tiles write the OTHER copy of
+// vis / cand / blockVis / blockCand -- so no workgroup of the launch waits for another.  The role goes first in the grid: it is
+// dispatched first and gone long before the tile loops end.  CarryParams is a third argument: DeviceState and TickParams keep their layout.
+template <uint32_t kChain>
+__global__ __launch_bounds__(kTile) SC_XFORM_OCC void k_xform_cull_classed_tail_carry(const DeviceState d, const TickParams p, const CarryParams cp)
+{
+  if (blockIdx.x < cp.groups) { compactWideBody<4u>(cp.view, cp.group, blockIdx.x, cp.groups); return; }      // (uniform per workgroup)
+  xformCullPipelined<true, kChain, true, 1u, true>(d, p, blockIdx.x - cp.groups);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3528,6 +3555,33 @@ void launchXformCull(const DeviceState& d, const TickParams& p, uint32_t grid, h
     case 2: launchXformCullChain<2>(d, p, grid, s, evA, evB); break;
     default: launchXformCullChain<3>(d, p, grid, s, evA, evB); break;
   }
+}
+// The carry instance exists for the launches carryInstance() names; the caller asks first.
+bool carryInstance(const TickParams& p)
+{
+#if SC_WAVE_CHAINS
+  constexpr uint32_t need = kFlagTopoClasses | kFlagTailOwnsDirty | SC_TICK_CULL;
+  return (p.flags & need) == need && !(p.flags & SC_TICK_BROADPHASE) && p.chain >= 1u;
+#else
+  (void)p; return false;
+#endif
+}
+// pd / pp / pgrid / wideG: state, parameters, spans and spans per workgroup of the tick whose compaction rides in front (launchCompact's arguments)
+void launchXformCullCarry(const DeviceState& d, const TickParams& p, uint32_t grid, const DeviceState& pd, const TickParams& pp, uint32_t pgrid, uint32_t wideG,
+                          hipStream_t s, hipEvent_t evA, hipEvent_t evB)
+{
+#if SC_WAVE_CHAINS
+  CarryParams cp;
+  cp.view = compactViewOf(pd, pp);
+  cp.view.flags = pp.flags & SC_TICK_CULLED_LIST;
+  cp.group = wideG; cp.groups = (pgrid + wideG - 1u) / wideG;
+  const uint32_t blocks = cp.groups + grid;
+  switch (p.chain) {
+    case 1: launchWithEvents(k_xform_cull_classed_tail_carry<1>, blocks, s, evA, evB, d, p, cp); break;
+    case 2: launchWithEvents(k_xform_cull_classed_tail_carry<2>, blocks, s, evA, evB, d, p, cp); break;
+    default: launchWithEvents(k_xform_cull_classed_tail_carry<3>, blocks, s, evA, evB, d, p, cp); break;
+  }
+#endif
 }
 void launchDeepLevel(const DeviceState& d, const TickParams& p, const uint32_t* list, uint32_t count, hipStream_t s)
 {

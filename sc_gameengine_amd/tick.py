@@ -610,6 +610,13 @@ class WorldTick:
         self._ok(self.lib.scTickGetCompactStats(self.ctx, _u(st)), "scTickGetCompactStats")
         return {"workgroups": int(st[0]), "spans_per_workgroup": int(st[1])}
 
+    def carry_stats(self):
+        """the carried compaction since creation: ticks that deferred their compaction, compactions carried at the head of the next tick's
+        fused launch, compactions settled by a launch of their own (host-side: no read-back; scTickGetCarryStats)"""
+        st = np.zeros(3, np.uint32)
+        self._ok(self.lib.scTickGetCarryStats(self.ctx, _u(st)), "scTickGetCarryStats")
+        return {"deferred": int(st[0]), "carried": int(st[1]), "settled": int(st[2])}
+
     def frame_stats(self):
         """which code wrote the last tick's frame: (who wrote the draw items, who staged the read-back block) as capi.FRAME_ITEMS_* /
         capi.FRAME_BLOCK_* (host-side: no read-back, no synchronisation; scTickGetFrameStats)"""

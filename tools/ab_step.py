@@ -27,6 +27,8 @@ ap.add_argument("libs", nargs="+")
 ap.add_argument("--workload", default="config3")
 ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--burst", type=int, default=400)
+ap.add_argument("--fused-only", action="store_true", help="the profiled burst times only the fused kernel's slot (set_profiling_kernels): its ticks then defer and carry "
+                                                       "their compaction like the timed burst's, and k_xform_cull_us is the carry instance's duration, role included")
 ap.add_argument("--separate-producer", action="store_true", help="the frame producer as a launch of its own (what the end-of-tick kernel costs without it)")
 args = ap.parse_args()
 
@@ -82,6 +84,8 @@ for rnd in range(args.rounds):
             t.run(flags)
         t.sync()
         res[path]["step_us"].append((time.perf_counter() - t0) / args.burst * 1e6)
+        if args.fused_only:
+            t.set_profiling_kernels([capi.K_XFORM_CULL])
         t.set_profiling(1)
         for _ in range(40):
             t.run(flags)
