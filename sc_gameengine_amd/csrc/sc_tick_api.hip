@@ -26,16 +26,61 @@ thread_local std::string gCreateError;
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; };
 
-// a captured graph of one tick parity and what it was captured for (stale when any of that differs)
-struct CapturedGraph {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  TickParams key{};
-  uint64_t epoch = ~0ull;                              // ScTickContext::topoEpoch at capture
-  uint32_t compactG = 0;                               // ScTickContext::compactG at capture: which form of the end-of-tick kernel is inside
-  uint32_t visSel = 0;                                 // ScTickContext::visSel at capture: which copy of the visibility words the kernels inside write
-  bool rccl = false;                                   // the library's RCCL group is inside (captured in relaxed mode)
+// Which code writes the frame -- the draw items and the read-back block -- on a tick with these TickParams::flags: the one rule behind
+// enqueueStages' launches and scTickGetFrameStats' report; planTick asks once per tick (framePathFor).
+//   stagedEmit   the read-back is on and a plain draw list's budget fits the block: the items go straight into the block
+//   foldEmit     the combined end-of-tick launch runs (compaction and pair search): its compaction role writes the items
+//   stagedByEot  both: that role writes the whole block, header included
+struct FramePath {
+  bool needCompact, pairsNow, stagedEmit, foldEmit, stagedByEot;
+  uint32_t items, block;               // SC_TICK_FRAME_ITEMS_* / SC_TICK_FRAME_BLOCK_*
 };
+
+// The record the readers see, in three groups, each with its own rule (ScTickContext::last, lastBinned, lastWith; recordRun).
+// (1) The last ACCEPTED scTickRun: assigned whole from its plan, never in parts and never by a run that was refused.
+struct RunRecord {
+  uint32_t flags = 0;                                  // as requested (a quiet tick's SC_TICK_BROADPHASE included: scTickReadPairs answers)
+  bool quiet = false, tail = false, topo = false;      // scTickGetBinStats bit 3 / scTickGetTailStats / scTickGetTopologyClassStats
+  uint32_t compact[2] = { 0u, 0u };                    // the end-of-tick launch's shape (scTickGetCompactStats)
+  uint32_t frame[2] = { 0u, 0u };                      // FramePath::items, block (scTickGetFrameStats)
+  void* draws = nullptr;                               // where SC_TICK_DRAWS left its items: the frame read-back block, or null = the draw buffer (scTickReadDraws)
+};
+// (2) The most recent tick that BINNED with home slots -- a quiet or transform-only tick leaves it (scTickGetBinStats)
+struct BinOutcome { bool lazy = false, stay = false, sweepOnly = false; };
+// (3) The last accepted run THAT CARRIED THE FEATURE'S FLAG: what it was sized for or ran as (each reader checks RunRecord::flags first)
+struct LastWith {
+  bool sweepsExact = false;                            // SC_TICK_SWEEPS ran in EXACT mode (scTickGetSweepShapeInfo)
+  bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
+  uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
+  uint32_t bindTouchWords = 0; bool bindEmpty = false; // SC_TICK_BIND_RUNS: the bitmap's size; the run of an empty context (the report reads as zeros)
+};
+
+// Everything decided about one scTickRun.  planTick is its only writer; commitPlan, enqueueStages, graphKey and the record go by it and by
+// nothing else of the tick.  A NEW PER-TICK DECISION IS A FIELD HERE, decided in planTick -- never a context field.
+struct TickPlan {
+  RunRecord rec;                       // what the readers are told once the run is accepted
+  uint32_t run = 0;                    // the flags as run: a quiet tick runs without SC_TICK_BROADPHASE
+  TickParams p{}; uint32_t grid = 0;
+  FramePath path{};
+  uint32_t compactG = 0;               // spans per workgroup of the end-of-tick kernel's wide form, 0 = compactBody's form
+  uint32_t visSel = 0;                 // the copy of the visibility words this tick writes = ScTickContext::visSel once commitPlan has run (a carrying tick: not the copy its rider reads)
+  bool sampled = false, carry = false, defer = false, replay = false, wholeStep = false;
+  bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
+  uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
+  BinOutcome bins;
+};
+
+// What a capture was captured for: stale when any of it differs (graphKey; DESIGN, "What invalidates a capture")
+struct GraphKey {
+  TickParams p{};
+  uint64_t epoch = ~0ull;              // ScTickContext::topoEpoch
+  uint32_t compactG = 0, visSel = 0;   // TickPlan's: which form of the end-of-tick kernel is inside, which copy of the visibility words it writes
+  bool rccl = false;                   // the library's RCCL group is inside (captured in relaxed mode)
+  bool operator==(const GraphKey& o) const
+  { return epoch == o.epoch && compactG == o.compactG && visSel == o.visSel && rccl == o.rccl && std::memcmp(&p, &o.p, sizeof p) == 0; }
+};
+// a captured graph of one tick parity
+struct CapturedGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; };
 
 // a local box as uploaded, by bit pattern (-0 is not +0, a NaN is its bits): the key of the bounds palette
 struct BoxKey {
@@ -99,7 +144,6 @@ struct ScTickContext
   // in-place remove path for the entities it relocates or re-parents.  A tick on which nothing changed scans nothing.
   bool tailEnabled = true;             // SC_TICK_TAIL=0 at creation: the end-of-tick kernel keeps the dirty clear and the producer (A/B switch)
   bool spanClosed = false; uint32_t closureSpan = 0;
-  bool lastTickTail = false;           // the last tick's fused kernel owned the dirty words (scTickGetTailStats)
   // Topology classes (topoTable(), bits 16..29 of the tile words): derived with the link words (flushLinks) from hParent and
   // hFlags.  topoCurrent: the device's link words are the ones the classes were derived from -- dropped by every path that edits link
   // words on the device without a re-link (appended roots, the in-place remove), until the next re-link.  hTopo: pattern index + 1 per
@@ -109,12 +153,10 @@ struct ScTickContext
   bool topoCurrent = false;
   uint32_t topoPatterns = 0, topoClassed = 0, topoUnclassed = 0;
   std::vector<uint16_t> hTopo;
-  bool lastTickTopo = false;           // the last tick's fused kernel was the classed instance (scTickGetTopologyClassStats)
   // The end-of-tick kernel's wide form (k_compact_wide): SC_TICK_VARIANT bit 4 (16) at creation keeps one workgroup per span (A/B switch);
-  // SC_TICK_COMPACT_G at creation fixes the spans per workgroup instead of compactWideGroup's rule (measurements, tests).  compactG: this
-  // tick's spans per workgroup, 0 = compactBody's form -- part of a captured graph's key; lastCompact: scTickGetCompactStats.
-  bool wideCompact = true; uint32_t compactForceG = 0, compactG = 0;
-  uint32_t lastCompact[2] = { 0u, 0u };
+  // SC_TICK_COMPACT_G at creation fixes the spans per workgroup instead of compactWideGroup's rule (measurements, tests).  The tick's
+  // own choice is TickPlan::compactG.
+  bool wideCompact = true; uint32_t compactForceG = 0;
   // The carried compaction.  A tick whose end-of-tick launch would be k_compact_wide on its own may DEFER it
   // (deferCompact's rule): `pending` then holds that launch's arguments, and the next tick's fused launch carries it at the head of
   // its grid (k_xform_cull_classed_tail_carry) or -- where that tick cannot -- settle() launches it first.  Whoever reads a list or
@@ -124,19 +166,16 @@ struct ScTickContext
   struct PendingCompact { bool on = false; DeviceState d{}; TickParams p{}; uint32_t grid = 0, wideG = 0; };
   PendingCompact pending;
   bool carryEnabled = true;
-  bool tickCarry = false, tickDefer = false;           // this tick's fused launch carries `pending` / this tick defers its own (scTickRun decides, enqueueStages acts)
   uint32_t visSel = 0;
   uint64_t* visAlt[2] = { nullptr, nullptr };          // vis, cand
   uint32_t* blockAlt[2] = { nullptr, nullptr };        // blockVis, blockCand
   uint32_t carryStats[3] = { 0u, 0u, 0u };             // ticks deferred, compactions carried, compactions settled
-  uint32_t lastFrame[2] = { 0u, 0u };  // who wrote the last tick's draw items / staged its read-back block (scTickGetFrameStats; framePathFor)
   uint32_t cus = 0;           // compute units (hipDeviceProp_t::multiProcessorCount)
-  uint32_t lastFlags = 0;
+  RunRecord last; BinOutcome lastBinned; LastWith lastWith;      // the record the readers see: recordRun writes it, once a run is accepted
 
   // scratch device buffers for indexed read-back
   uint32_t* dIdx = nullptr; float* dRows = nullptr; uint32_t scratchCap = 0;
   void* dDraws = nullptr;
-  void* lastDraws = nullptr;           // where the last SC_TICK_DRAWS wrote its items (dDraws, or the frame read-back block)
   RayQueryState rays{};                // scTickSetRayQueries: device copies of the batch + the hit buffer
   uint32_t rayCap = 0;
   SweepQueryState sweeps{};            // scTickSetSweepQueries: the same for the capsule sweeps
@@ -153,14 +192,11 @@ struct ScTickContext
   // its report (== ScTickSweepShapeInfo), allocated by the first call that sets EXACT, zeroed on the stream before every launch
   uint32_t sweepShapes = SC_TICK_SWEEP_SHAPES_AABB;
   uint32_t* sweepInfo = nullptr;
-  bool lastSweepsExact = false;        // the last run with SC_TICK_SWEEPS ran them in EXACT mode (scTickGetSweepShapeInfo)
   // scTickSetOverlapQueries: the volumes, the count and id rows and the report's running words; overlapCap: volumes the per-volume arrays
-  // hold, overlapIdCap: id slots.  overlapShapes selects the kernel instance at launch time, like the modes above.  lastOverlap*: what the
-  // last run with SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
+  // hold, overlapIdCap: id slots.  overlapShapes selects the kernel instance at launch time, like the modes above.
   OverlapQueryState overlaps{};
   uint32_t overlapCap = 0; size_t overlapIdCap = 0;
   uint32_t overlapShapes = SC_TICK_OVERLAP_SHAPES_AABB;
-  uint32_t lastOverlapCount = 0, lastOverlapMaxHits = 0, lastOverlapShapes = 0;
   std::vector<uint2> hAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
@@ -173,18 +209,14 @@ struct ScTickContext
   // scTickSetPairShapes: the touching list, its running counts and its report.  All null until the call: nothing is launched.
   PairShapeState pairShapes{};
   // scTickSetPairContacts: one record per entry of the touching list, the kind counts and their report.  All null until the call: nothing
-  // is launched.  lastPairContacts: the last run with SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts).
+  // is launched.
   PairContactState pairContacts{};
-  bool lastPairContacts = false;
   // scTickSetPairManifolds: the same a level up -- five float4 per entry of the touching list, the counts and their report
   PairManifoldState pairManifolds{};
-  bool lastPairManifolds = false;
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
-  // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched); what the
-  // last flagged run was sized for, and whether it was the run of an empty context (nothing launched: the report reads as zeros)
+  // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched)
   BindRunState bind{};
-  uint32_t bindLastTouchWords = 0; bool bindLastEmpty = false;
 
   // profiling
   bool profiling = false;
@@ -204,23 +236,19 @@ struct ScTickContext
   // pipelined tile + graph replay: the pair half (exchange, merge, queries, pair search, snapshot) is a graph of its own,
   // replayed on the pairs stream; the two graphs of a step are ordered by events recorded between them, outside any capture
   CapturedGraph pairGraph[kMaxParity];
-  bool lastTickSampled = false;                        // the last scTickRun was sampled for profiling (ran eagerly; its pair half is timed too)
-  bool lastTickLearn = false;                          // the last scTickRun was a learn tick of the home slots (ran eagerly)
   // home slots of the bins (binEntityWave): remembered at a learn tick, used until the world's shape changes or they age
   bool homeEnabled = true, homeValid = false, homeCountsLive = false;
   bool lazyEnabled = true;                             // lazy records (DeviceState::lazyCtl)
   bool fastPairs = true;                               // ordered home slots: bins without visitors take the pair role's fast path (DeviceState::homeCast)
-  bool lastTickLazy = false, lastTickStay = false, lastTickSweepOnly = false; uint32_t learnTicks = 0;  // scTickGetBinStats
+  uint32_t learnTicks = 0;                             // scTickGetBinStats, scTickGetLearnTicks
   // Quiet ticks (quietTick()): a broadphase tick of a world that cannot pair, whose bins nothing else reads either, runs the device work
   // of the same call without SC_TICK_BROADPHASE; its pair set is empty by construction and reported so by the host
   bool quietEnabled = true;                            // SC_TICK_VARIANT bit 3 switches them off (A/B)
-  bool lastTickQuiet = false;                          // scTickGetBinStats bit 3; scTickGetCounts / scTickReadPairs answer from the host
   bool worldLayersKnown = false; uint32_t worldLayers = 0;   // scTickSetWorldLayers: group bits | mask bits << 16 of every collider of the tiled world
   bool boxesTouched = false;                           // bounds or world matrices were uploaded since the last broadphase tick (TickParams::cleanStay)
   uint64_t homeEpoch = ~0ull; uint32_t homeAge = 0, homePeriod = 64;
   uint32_t homeXform = 0;                              // SC_TICK_XFORM of the learn tick: entities deeper than the fused kernel's chain are binned by the level
                                                        // kernels on transforming ticks and by the fused kernel otherwise -- slots learned one way are not valid the other
-  bool packedRides = false;                            // this tick's `packed` event was attached to the compaction + pack dispatch
 
   // broadphase
   uint32_t sectors = 0, maxPairs = 0;
@@ -236,7 +264,7 @@ struct ScTickContext
   void* laneAllocs[6] = {};                                   // device copies of the lane graph (scTickSetLaneGraph)
   uint2* dTierPatch = nullptr;                                // tier selection: the few modes the caps changed
   bool pairsPending = false;
-  TickParams pendingParams{};
+  TickPlan pendingTick;                                // ... of this tick: its pair half goes by ITS plan (TickParams, sampling, learn), whatever ran in between
   hipStream_t ownStream = nullptr;
   // pipelined tiles (scTickSetPairsStream): merge + queries + pair search of tick t run on a second stream under the fused
   // kernel of tick t+1; everything the two halves share is double-buffered by tick parity (set 0 lives in `d`)
@@ -660,7 +688,7 @@ EventPair takeEvents(ScTickContext* c)
 }
 
 // The profiling sampling rule.  A tick is sampled when profiling is on and its index is a multiple of the period; its pair half
-// goes by the tick's decision (lastTickSampled).  Kernel k is timed on a launch when timing is allowed there -- the tick or its
+// goes by the tick's decision (TickPlan::sampled, kept with the pending tick).  Kernel k is timed on a launch when timing is allowed there -- the tick or its
 // pair half is sampled and runs eagerly: never inside a stream capture -- and k is in the mask.
 bool tickSampled(const ScTickContext* c) { return c->profiling && (c->tickIndex % c->profPeriod) == 0; }
 bool timed(const ScTickContext* c, uint32_t k, bool allowed) { return allowed && c->profiling && ((c->profMask >> k) & 1u); }
@@ -755,12 +783,12 @@ AnchoredRayState anchoredFor(const ScTickContext* c, uint32_t q)
 const char* pendingShapeReader(const ScTickContext* c)
 {
   if (!c->pairsPending) return nullptr;
-  if (c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingParams.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)))
+  if (c->rayShapes == SC_TICK_RAY_SHAPES_EXACT && (c->pendingTick.p.flags & (SC_TICK_RAYS | SC_TICK_ANCHORED_RAYS)))
     return "casts rays in SC_TICK_RAY_SHAPES_EXACT mode";
-  if (c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && (c->pendingParams.flags & SC_TICK_SWEEPS))
+  if (c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && (c->pendingTick.p.flags & SC_TICK_SWEEPS))
     return "sweeps capsules in SC_TICK_SWEEP_SHAPES_EXACT mode";
-  if (c->pendingParams.flags & SC_TICK_PAIR_SHAPES) return "lists the touching pairs (SC_TICK_PAIR_SHAPES)";
-  if (c->pendingParams.flags & SC_TICK_TOUCH_EVENTS) return "reports touch events (SC_TICK_TOUCH_EVENTS)";
+  if (c->pendingTick.p.flags & SC_TICK_PAIR_SHAPES) return "lists the touching pairs (SC_TICK_PAIR_SHAPES)";
+  if (c->pendingTick.p.flags & SC_TICK_TOUCH_EVENTS) return "reports touch events (SC_TICK_TOUCH_EVENTS)";
   return nullptr;
 }
 #define REFUSE_WHILE_SHAPES_PENDING(c, what) \
@@ -781,17 +809,19 @@ bool resyncPairEvents(ScTickContext* c)
   }
   // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
   // the rename -- runPendingPairs forgets it again behind that half
-  if (c->pairsPending && (c->pendingParams.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS))) c->pairEventsResyncAgain = true;
+  if (c->pairsPending && (c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS))) c->pairEventsResyncAgain = true;
   return true;
 }
 
-// the narrow phase of a tick: ONE launch of the pair-shape kernel whatever mix of SC_TICK_PAIR_SHAPES and SC_TICK_TOUCH_EVENTS the tick
-// carries (each pair is decided once), then the list's report and / or the touch state's sweep and finish.  Neither flag: nothing.
-void launchNarrowPhase(ScTickContext* c, const DeviceState& ds, const TickParams& p, hipStream_t s)
+// What closes every pair half, behind the pair search on its stream, now that the pair set is complete.  The narrow phase -- which of its
+// pairs touch: ONE launch of the pair-shape kernel whatever mix of SC_TICK_PAIR_SHAPES and SC_TICK_TOUCH_EVENTS the tick carries (each
+// pair is decided once), then the list's report and / or the touch state's sweep and finish -- then the pair events: what begun, what ended.
+void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickParams& p, hipStream_t s)
 {
-  if (!(p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))) return;
-  launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                   &c->pairContacts, &c->pairManifolds, s);
+  if (p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))
+    launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
+                     &c->pairContacts, &c->pairManifolds, s);
+  if (p.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, s);
 }
 
 // pipelined tiles: a tick refills the bins and counters of its parity, which the pair half of pipeDepth ticks ago read, and
@@ -817,11 +847,11 @@ void waitParityFree(ScTickContext* c, const TickParams& p)
 }
 
 // pipelined tiles: whatever is queued on the pairs stream from here on (the exchange) is ordered behind this tick's pack
-void publishPacked(ScTickContext* c, const TickParams& p)
+// (rode: the event was attached to the compaction + pack dispatch already -- enqueueStages' answer)
+void publishPacked(ScTickContext* c, const TickParams& p, bool rode)
 {
   if (!c->pairsStream || !(p.flags & SC_TICK_BROADPHASE) || !(p.flags & SC_TICK_SPLIT_PAIRS)) return;
-  if (!c->packedRides) hipEventRecord(c->packed[p.parity], c->stream);
-  c->packedRides = false;
+  if (!rode) hipEventRecord(c->packed[p.parity], c->stream);
   hipStreamWaitEvent(c->pairsStream, c->packed[p.parity], 0);
 }
 
@@ -895,15 +925,7 @@ hipError_t publishFrame(ScTickContext* c, bool bindsStaged)
   return hipEventRecord(rb.copied[f], rb.copyStream);
 }
 
-// Which code writes the frame -- the draw items and the read-back block -- on a tick with these TickParams::flags: the one rule behind
-// enqueueStages' launches and scTickGetFrameStats' report; scTickRun asks once per tick.
-//   stagedEmit   the read-back is on and a plain draw list's budget fits the block: the items go straight into the block
-//   foldEmit     the combined end-of-tick launch runs (compaction and pair search): its compaction role writes the items
-//   stagedByEot  both: that role writes the whole block, header included
-struct FramePath {
-  bool needCompact, pairsNow, stagedEmit, foldEmit, stagedByEot;
-  uint32_t items, block;               // SC_TICK_FRAME_ITEMS_* / SC_TICK_FRAME_BLOCK_*
-};
+// the frame path (FramePath) of a tick with these TickParams::flags
 FramePath framePathFor(const ScTickContext* c, uint32_t flags)
 {
   FramePath f;
@@ -944,7 +966,6 @@ hipEvent_t fillFoldEmit(ScTickContext* c, const FramePath& path, TickParams& pe)
 void enqueueFrame(ScTickContext* c, const DeviceState& ds, uint32_t flags, const FramePath& path)
 {
   const uint32_t budget = c->desc.max_draws_budget;
-  c->lastDraws = c->dDraws;
   if ((flags & SC_TICK_DRAWS) && !path.stagedEmit && !path.foldEmit) {
     const uint32_t bound = (budget && budget < c->n) ? budget : c->n;
     if (flags & SC_TICK_SORT_DRAWS) {
@@ -958,8 +979,7 @@ void enqueueFrame(ScTickContext* c, const DeviceState& ds, uint32_t flags, const
   if (!path.stagedByEot) waitFrameBlock(c);             // (the end-of-tick kernel's launch waited already)
   bool binds = false;
   if (path.stagedEmit) {                                // (stagedByEot: the end-of-tick kernel wrote the block)
-    if (!path.stagedByEot) launchEmitDrawsStaged(ds, budget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);
-    c->lastDraws = frameItems(rb.dBlock[f], rb.maxVisible);      // what scTickReadDraws returns for this tick
+    if (!path.stagedByEot) launchEmitDrawsStaged(ds, budget, rb.dBlock[f], rb.maxVisible, rb.frames, c->stream, rb.staged[f]);      // (RunRecord::draws: the items lie in the block)
   } else {
     // (a flagged run is a sorted one, so it comes through here: its bind block is staged ahead of the frame's, whose `staged` covers both)
     binds = rb.bindBytes && (flags & SC_TICK_BIND_RUNS);
@@ -975,12 +995,16 @@ void enqueueFrame(ScTickContext* c, const DeviceState& ds, uint32_t flags, const
 }
 
 // the tick's launches on c->stream, nothing else: safe inside a stream capture (the callers put waitParityFree before
-// and publishPacked behind it).  Launches are timed only on an eager, sampled tick (scTickRun sets lastTickSampled first, and asks for `path`).
-void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path, uint32_t grid, bool inCapture)
+// and publishPacked behind it).  Every per-tick decision comes from the plan; launches are timed only on an eager, sampled tick.
+// Returns whether the `packed` event rode on the compaction + pack dispatch (publishPacked).
+bool enqueueStages(ScTickContext* c, const TickPlan& plan, bool inCapture)
 {
-  const uint32_t flags = p.flags;
+  const TickParams& p = plan.p;
+  const FramePath& path = plan.path;
+  const uint32_t flags = p.flags, grid = plan.grid;
   const DeviceState ds = stateFor(c, p.parity);
-  const bool timing = !inCapture && c->lastTickSampled;
+  const bool timing = !inCapture && plan.sampled;
+  bool rode = false;
   if (c->producerKind && !(flags & SC_TICK_PRODUCE_NEXT)) {
     Scoped s(c, SC_TICK_K_NUDGE, timing);
     if (c->producerKind == 1) launchNudgeRootsX(ds, c->n, c->producerParam, c->stream);
@@ -988,10 +1012,10 @@ void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path,
   }
   if (flags & (SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE)) {
     // the dominant kernel is timed by its own begin / end timestamps (the figure the roofline uses)
-    // (a carrying tick's launch has the pending compaction at the head of its grid: the timestamps then include that role)
-    const bool carry = !inCapture && c->tickCarry && c->pending.on;
+    // (a carrying tick's launch has the pending compaction at the head of its grid: the timestamps then include that role;
+    //  planTick: a carrying or deferring tick is never a captured one)
     auto fused = [&](hipEvent_t evA, hipEvent_t evB) {
-      if (!carry) { launchXformCull(ds, p, grid, c->stream, evA, evB); return; }
+      if (!plan.carry) { launchXformCull(ds, p, grid, c->stream, evA, evB); return; }
       const ScTickContext::PendingCompact& pc = c->pending;
       launchXformCullCarry(ds, p, grid, pc.d, pc.p, pc.grid, pc.wideG, c->stream, evA, evB);
       c->pending.on = false;
@@ -1052,31 +1076,29 @@ void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path,
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
-    launchNarrowPhase(c, ds, p, c->stream);                                                  // the pair set is complete: which of its pairs touch
-    if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);      // ... what begun, what ended
+    closePairHalf(c, ds, p, c->stream);
   } else {
     const bool packToo = path.needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
       Scoped s(c, SC_TICK_K_COMPACT, timing);
       // pipelined tile, eager: the `packed` event rides on the dispatch (publishPacked then only makes the pairs stream wait)
-      const bool ride = c->pairsStream && !inCapture && !s.on;
-      launchCompactPack(ds, p, grid, c->stream, ride ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
-      c->packedRides = ride;
-    } else if (path.needCompact && !inCapture && c->tickDefer) {
+      rode = c->pairsStream && !inCapture && !s.on;
+      launchCompactPack(ds, p, grid, c->stream, rode ? c->packed[p.parity] : nullptr);      // compaction and pack share a launch
+    } else if (path.needCompact && plan.defer) {
       // deferred: the launch's arguments are kept, the next tick's fused launch carries it or settle() launches it
       ScTickContext::PendingCompact& pc = c->pending;
-      pc.on = true; pc.d = ds; pc.p = p; pc.grid = grid; pc.wideG = c->compactG;
+      pc.on = true; pc.d = ds; pc.p = p; pc.grid = grid; pc.wideG = plan.compactG;
       c->carryStats[0]++;
     } else if (path.needCompact) {
       // a quiet tick's end-of-tick kernel: timed in the slot of a broadphase tick's end-of-tick kernel, SC_TICK_K_PAIRS, and like it by the
       // dispatch's own begin / end timestamps (whoever reads that slot sees what the tick's second launch cost, whichever it was)
-      if (c->lastTickQuiet && timed(c, SC_TICK_K_PAIRS, timing)) {
+      if (plan.rec.quiet && timed(c, SC_TICK_K_PAIRS, timing)) {
         const EventPair ev = takeEvents(c);
-        launchCompact(ds, p, grid, c->compactG, c->stream, ev.a, ev.b);
+        launchCompact(ds, p, grid, plan.compactG, c->stream, ev.a, ev.b);
         c->times[SC_TICK_K_PAIRS].push_back(ev);
       } else {
-        Scoped s(c, SC_TICK_K_COMPACT, timing && !c->lastTickQuiet);
-        launchCompact(ds, p, grid, c->compactG, c->stream);
+        Scoped s(c, SC_TICK_K_COMPACT, timing && !plan.rec.quiet);
+        launchCompact(ds, p, grid, plan.compactG, c->stream);
       }
     }
     if (flags & SC_TICK_BROADPHASE) {
@@ -1088,12 +1110,12 @@ void enqueueStages(ScTickContext* c, const TickParams& p, const FramePath& path,
       }
       else {
         { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
-        launchNarrowPhase(c, ds, p, c->stream);
-        if (flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, c->stream);
+        closePairHalf(c, ds, p, c->stream);
       }
     }
   }
   enqueueFrame(c, ds, flags, path);
+  return rode;
 }
 
 // drop captured graphs: every one of the array (the tick's: the quiet tick's too)
@@ -1108,23 +1130,30 @@ template <uint32_t N> void dropGraphs(CapturedGraph (&g)[N]) { dropGraphs(g, N);
 // ... every capture of the context: the tick's graphs and the pair half's (a pipelined tile's)
 void dropCaptures(ScTickContext* c) { dropGraphs(c->graph); dropGraphs(c->pairGraph); }
 
-// Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for other TickParams, another
-// topology epoch, another form of the end-of-tick kernel (compactG), or with / without the library's RCCL group inside (rccl: the
-// group touches the communicator's own resources during capture, so the capture is relaxed).  body() enqueues the work on s; it returns 0 on an error whose text it has set.
-// what: the graph's name in the error texts.
-template <typename Body>
-int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const TickParams& key, bool rccl, const char* what, Body body)
+// The key of a capture of this plan's tick, or of its pair half, as the context stands (rccl: the library's RCCL group goes inside)
+GraphKey graphKey(const ScTickContext* c, const TickPlan& plan, bool rccl)
 {
-  if (!g.exec || g.epoch != c->topoEpoch || std::memcmp(&key, &g.key, sizeof key) != 0 || g.rccl != rccl || g.compactG != c->compactG || g.visSel != c->visSel) {
+  GraphKey k;
+  k.p = plan.p; k.epoch = c->topoEpoch; k.compactG = plan.compactG; k.visSel = plan.visSel; k.rccl = rccl;
+  return k;
+}
+
+// Graph replay: launch g's graph on s, capturing it first when there is none or it was captured for another key (the RCCL group
+// touches the communicator's own resources during capture, so a capture with it inside is relaxed).  body() enqueues the work on s; it
+// returns 0 on an error whose text it has set.  what: the graph's name in the error texts.
+template <typename Body>
+int replayGraph(ScTickContext* c, hipStream_t s, CapturedGraph& g, const GraphKey& key, const char* what, Body body)
+{
+  if (!g.exec || !(g.key == key)) {
     dropGraphs(&g, 1);
-    HIP_OK(c, hipStreamBeginCapture(s, rccl ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
+    HIP_OK(c, hipStreamBeginCapture(s, key.rccl ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
     const int ok = body();
     const hipError_t ce = hipStreamEndCapture(s, &g.graph);
     if (!ok) { if (g.graph) { hipGraphDestroy(g.graph); g.graph = nullptr; } return 0; }
     if (ce != hipSuccess) return fail(c, what, ce);
     if (!g.graph) return fail(c, (std::string(what) + " returned no graph (the capture was invalidated)").c_str());
     HIP_OK(c, hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    g.key = key; g.epoch = c->topoEpoch; g.rccl = rccl; g.compactG = c->compactG; g.visSel = c->visSel;
+    g.key = key;
   }
   HIP_OK(c, hipGraphLaunch(g.exec, s));
   return 1;
@@ -1144,7 +1173,7 @@ void rowsToMat4(const float* r12, float* m16)
 bool lastRunResult(ScTickContext* c, uint32_t flag, const char* notRequested, bool enabledThen, const char* notEnabled, const char* pending,
                    bool onNow, const char* switchedOff)
 {
-  if (!(c->lastFlags & flag)) return fail(c, notRequested);
+  if (!(c->last.flags & flag)) return fail(c, notRequested);
   if (!enabledThen) return fail(c, notEnabled);
   if (c->pairsPending) return fail(c, pending);
   if (!onNow) return fail(c, switchedOff);
@@ -2023,9 +2052,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);
-  // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
-  launchNarrowPhase(c, ds, pp, ps);                                                     // behind the pair search, on its stream
-  if (pp.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, pp, c->pairEvents, ps);
+  closePairHalf(c, ds, pp, ps);      // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
   return rode;
 }
 
@@ -2070,16 +2097,14 @@ static bool quietTick(ScTickContext* c, uint32_t flags)
   return !worldCanPair(c);
 }
 
-int scTickRun(ScTickContext* c, uint32_t flags)
+// An empty context without a broadphase has nothing to launch (emptyTick)
+static bool nothingToRun(const ScTickContext* c, uint32_t flags) { return c->n == 0 && !(flags & SC_TICK_BROADPHASE); }
+
+// Every reason scTickRun refuses a call for, in one order; writes nothing but the error text.  (A run with nothing to launch is asked
+// no more than the checks ahead of that line.)
+static bool tickAccepted(ScTickContext* c, uint32_t flags)
 {
-  if (!c) return 0;
-  if (!bind(c)) return 0;
-  if (!flushLinks(c)) return 0;
-  if (flags & SC_TICK_XFORM) REFUSE_WHILE_SHAPES_PENDING(c, "scTickRun with SC_TICK_XFORM");
   if ((flags & SC_TICK_BROADPHASE) && c->desc.tile_sectors_x == 0) return fail(c, "broadphase requested but the context has no tile rectangle");
-  // An empty context without a broadphase has nothing to launch: the per-tick counts read as zero.  With the broadphase
-  // the stages still run (every kernel copes with n == 0): an emptied tile of a multi-GPU world must rewrite its border
-  // messages (header-only) and take part in the exchange, the merge and the pair search of the boxes its neighbours send.
   if (flags & SC_TICK_PAIR_EVENTS) {
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's pair set)");
     if (!c->pairEvents.ctl) return fail(c, "SC_TICK_PAIR_EVENTS needs scTickSetPairEvents first");
@@ -2100,8 +2125,6 @@ int scTickRun(ScTickContext* c, uint32_t flags)
       return fail(c, "SC_TICK_BIND_RUNS needs SC_TICK_DRAWS | SC_TICK_SORT_DRAWS in the same run (the runs are those of the sorted list; scTickSetDrawSortTable)");
     if (!c->sort.pipeline) return fail(c, "SC_TICK_SORT_DRAWS needs scTickSetDrawSortTable first");
     if (!c->bind.info) return fail(c, "SC_TICK_BIND_RUNS needs scTickSetBindRuns first");
-    c->bindLastTouchWords = c->bind.touchWords;
-    c->bindLastEmpty = c->n == 0 && !(flags & SC_TICK_BROADPHASE);
   }
   if (flags & SC_TICK_OVERLAPS) {
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_OVERLAPS needs SC_TICK_BROADPHASE in the same run (the queries read this tick's bins)");
@@ -2109,32 +2132,9 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     if (c->neighbourMask) return fail(c, "SC_TICK_OVERLAPS cannot run on a context with neighbours (scTickSetTile): overlap queries do not cover tiles");
     if (c->pairsStream) return fail(c, "SC_TICK_OVERLAPS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): overlap queries do not cover tiles");
     if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_OVERLAPS cannot run with SC_TICK_SPLIT_PAIRS: overlap queries do not cover tiles");
-    c->lastOverlapCount = c->overlaps.count; c->lastOverlapMaxHits = c->overlaps.maxHits; c->lastOverlapShapes = c->overlapShapes;
   }
   if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");      // (an empty context's run stages a frame too)
-  if (c->n == 0 && !(flags & SC_TICK_BROADPHASE)) {
-    c->lastFlags = flags;
-    c->lastTickTail = false;
-    c->lastTickTopo = false;
-    c->lastTickQuiet = false;
-    c->lastCompact[0] = c->lastCompact[1] = 0u;
-    c->lastFrame[0] = c->lastFrame[1] = 0u;
-    c->lastDraws = c->dDraws;
-    settle(c);                                         // (a pending compaction writes the counters: ahead of the zeros)
-    HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
-    if (c->rb.bytes) {
-      // every scTickRun ends with a frame: this one is all zeros under the next tick index, written by the host into the pinned block
-      // (nothing is launched and nothing copied; the block's copy of two frames ago is waited for on the host -- a rare tick)
-      ScTickContext::FrameReadback& rb = c->rb;
-      const uint32_t f = frameSlot(rb);
-      if (rb.inFlight[f]) HIP_OK(c, hipEventSynchronize(rb.copied[f]));
-      const FrameHeader h = frameHeader(0u, 0u, 0u, 0u, 0u, 0u, (uint32_t)rb.frames, (uint32_t)(rb.frames >> 32), 0u, 0u);
-      std::memcpy(rb.hBlock[f], h.w, sizeof h.w);
-      HIP_OK(c, publishFrame(c, false));
-      c->lastFrame[1] = SC_TICK_FRAME_BLOCK_HOST;
-    }
-    return 1;
-  }
+  if (nothingToRun(c, flags)) return true;
   if (flags & SC_TICK_PRODUCE_NEXT) {
     if (!(flags & SC_TICK_XFORM)) return fail(c, "SC_TICK_PRODUCE_NEXT needs SC_TICK_XFORM (the producer rides on the end-of-tick kernel)");
     if (!c->producerKind) return fail(c, "SC_TICK_PRODUCE_NEXT needs scTickSetFrameProducer first");
@@ -2148,48 +2148,38 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     return fail(c, "SC_TICK_RAY_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its rays are cast when the matrices may be the next tick's");
   if ((flags & SC_TICK_SWEEPS) && c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT && c->pairsStream)
     return fail(c, "SC_TICK_SWEEP_SHAPES_EXACT cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its sweeps are cast when the matrices may be the next tick's");
-  if (flags & SC_TICK_SWEEPS) c->lastSweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
-  if (flags & SC_TICK_PAIR_SHAPES) c->lastPairContacts = c->pairContacts.ctl != nullptr;
-  if (flags & SC_TICK_PAIR_SHAPES) c->lastPairManifolds = c->pairManifolds.ctl != nullptr;
-  // (a quiet tick keeps the flag in lastFlags -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
-  const bool quiet = quietTick(c, flags);
-  const uint32_t run = quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
-  TickParams p; uint32_t grid;
-  fillParams(c, run, p, grid);
-  if (quiet) p.parity = 0u;                            // (no kernel of it reads the word; its graph is one whatever parity the binning ticks have reached)
-  c->lastFlags = flags;
-  c->lastTickQuiet = quiet;
-  c->lastTickTail = (p.flags & kFlagTailOwnsDirty) != 0;
-  c->lastTickTopo = (p.flags & kFlagTopoClasses) != 0;
-  c->lastTickLearn = false;
-  if ((run & SC_TICK_XFORM) && !(run & SC_TICK_BROADPHASE)) c->boxesTouched = true;      // matrices change, the bins do not follow
-  if (quiet) {
-    // the records go stale like on a transform-only tick: the next binning tick rewrites every always-written slot (cleanStay 0).  The bins'
-    // counters and layer summaries stay at homeCount / homeLayers, where the last pair role left them; the slots age on.
-    c->boxesTouched = true;
-    c->homeAge++;
+  if ((flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS) && c->neighbourMask) {
+    // every message of THIS tick parity needs its buffers: a missing one would make the pack skip that neighbour silently
+    const DeviceState ds = stateFor(c, c->parity);
+    for (uint32_t d = 0; d < 8; ++d)
+      if (((c->neighbourMask >> d) & 1u) && (!ds.borderSend[d] || !ds.borderRecv[d]))
+        return fail(c, "border buffers of this tick parity are not bound (scTickBindBorderBuffers / scTickBindBorderBuffersParity / scTickCommInit)");
   }
-  flags = run;
-  if ((flags & SC_TICK_BROADPHASE) && c->homeEnabled) {
+  return true;
+}
+
+// Decide everything about an accepted run of `flags`, leaving the context's persistent state as it is (commitPlan applies it).  What it
+// does touch are memos, not decisions: worldCanPair's answer and the span-closed state (fillParams).
+static TickPlan planTick(ScTickContext* c, uint32_t flags)
+{
+  TickPlan plan;
+  plan.rec.flags = flags;
+  // (a quiet tick keeps the flag in `flags` -- scTickReadPairs answers, with the empty set -- and everything below goes by `run`)
+  plan.rec.quiet = quietTick(c, flags);
+  const uint32_t run = plan.run = plan.rec.quiet ? (flags & ~(uint32_t)SC_TICK_BROADPHASE) : flags;
+  TickParams& p = plan.p;
+  fillParams(c, run, p, plan.grid);
+  if (plan.rec.quiet) p.parity = 0u;                   // (no kernel of it reads the word; its graph is one whatever parity the binning ticks have reached)
+  plan.rec.tail = (p.flags & kFlagTailOwnsDirty) != 0; plan.rec.topo = (p.flags & kFlagTopoClasses) != 0;
+  if ((run & SC_TICK_BROADPHASE) && c->homeEnabled) {
     // home slots: a learn tick when nothing is remembered, the world's shape changed (entities, hierarchy, layers) or the
-    // slots have aged; every bin copy must be idle and empty for it (a rare event: the streams are joined here)
-    const uint32_t xf = (c->levelOffsets.size() > 1) ? (flags & SC_TICK_XFORM) : 0u;       // (only worlds with deep levels care)
-    if (!c->homeValid || c->homeEpoch != c->topoEpoch || c->homeAge >= c->homePeriod || c->homeXform != xf) {
-      c->homeXform = xf;
-      if (c->pairsStream && !sync(c)) return 0;
-      if (c->homeCountsLive) {
-        for (uint32_t q = 0; q < (c->pairsStream ? c->pipeDepth : 1u); ++q) {
-          const DeviceState o = stateFor(c, q);
-          HIP_OK(c, hipMemsetAsync(o.binCount, 0, (size_t)c->sectors * sizeof(uint32_t), c->stream));
-          HIP_OK(c, hipMemsetAsync(o.binLayers, 0, (size_t)c->sectors * sizeof(uint32_t), c->stream));
-        }
-      }
-      p.homeMode = kHomeLearn;
-      c->homeValid = true; c->homeEpoch = c->topoEpoch; c->homeAge = 0; c->lastTickLearn = true; c->learnTicks++;
-    } else { p.homeMode = kHomeUse; c->homeAge++; }
+    // slots have aged
+    plan.binned = true;
+    plan.homeXform = (c->levelOffsets.size() > 1) ? (run & SC_TICK_XFORM) : 0u;       // (only worlds with deep levels care)
+    plan.learn = !c->homeValid || c->homeEpoch != c->topoEpoch || c->homeAge >= c->homePeriod || c->homeXform != plan.homeXform;
+    p.homeMode = plan.learn ? kHomeLearn : kHomeUse;
     p.homeReset = 1u;
     p.sweepOnly = worldCanPair(c) ? 0u : 1u;
-    c->lastTickSweepOnly = p.sweepOnly != 0u;
     if (p.sweepOnly) p.pairRun = pairRunFor(p.binSX * p.binSZ, c->cus, true);
     p.fastPairs = (c->fastPairs && !p.sweepOnly) ? 1u : 0u;
     // lazy records: only while nothing but this tick's own pair search reads the bins, and that search runs before the next
@@ -2199,69 +2189,139 @@ int scTickRun(ScTickContext* c, uint32_t flags)
     // (and only while the pair half is this library's to issue: with a caller-owned exchange -- scTickRun(.. | SPLIT_PAIRS), the host's
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
-    const bool hostBetweenHalves = (flags & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (p.homeMode == kHomeUse && c->lazyEnabled && !(flags & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    const bool hostBetweenHalves = (run & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
+    p.lazy = (!plan.learn && c->lazyEnabled && !(run & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
-    c->lastTickLazy = p.lazy != 0u;
     // records of entities that did not move stay as they are, unless something else changed boxes since the last tick
-    p.cleanStay = (p.homeMode == kHomeUse && c->lazyEnabled && !c->pairsStream && !c->boxesTouched) ? 1u : 0u;
-    c->lastTickStay = p.cleanStay != 0u;
+    p.cleanStay = (!plan.learn && c->lazyEnabled && !c->pairsStream && !c->boxesTouched) ? 1u : 0u;
+    plan.bins.lazy = p.lazy != 0u; plan.bins.stay = p.cleanStay != 0u; plan.bins.sweepOnly = p.sweepOnly != 0u;
+  }
+  // the end-of-tick launch's shape (enqueueStages' rule for who carries the compaction role): the wide form only where the launch is
+  // the compaction's own
+  const FramePath& path = plan.path = framePathFor(c, p.flags);
+  const bool alone = path.needCompact && !(p.flags & SC_TICK_BROADPHASE);
+  plan.compactG = (alone && c->wideCompact) ? compactWideGroup(p, plan.grid, c->compactForceG) : 0u;
+  if (path.needCompact) compactLaunchShape(plan.grid, path.pairsNow, plan.compactG, plan.rec.compact);
+  plan.rec.frame[0] = path.items; plan.rec.frame[1] = path.block;
+  if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
+  plan.sampled = tickSampled(c);                       // (events need eager launches)
+  plan.replay = c->graphMode && !plan.sampled && !plan.learn;
+  plan.wholeStep = plan.replay && c->captureWholeStep;
+  // The carried compaction.  A pending one rides at the head of this tick's fused launch where that launch is the carry-capable instance,
+  // launched eagerly; otherwise commitPlan settles it first -- its own launch ahead of everything of this tick, which is the order of two
+  // ticks that never deferred.  A carrying tick writes the other copy of the words (visSel, stateFor).  Then this tick's own compaction:
+  // deferred when its launch would be k_compact_wide alone behind that instance, nothing else of the tick or the context needs the
+  // lists on the device or on the host behind it, and the slot that would time the launch is not being timed on this tick.
+  const bool instance = !c->graphMode && carryInstance(p);
+  plan.carry = c->pending.on && instance;
+  plan.visSel = c->visSel ^ (plan.carry ? 1u : 0u);
+  const bool slotTimed = timed(c, plan.rec.quiet ? SC_TICK_K_PAIRS : SC_TICK_K_COMPACT, plan.sampled);
+  plan.defer = c->carryEnabled && instance && alone && plan.compactG != 0u && !c->pairsStream && !c->neighbourMask && !c->rb.bytes &&
+               !(p.flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS | SC_TICK_BIND_RUNS)) && !slotTimed;
+  return plan;
+}
+
+// Apply the plan to the context's persistent state, just ahead of the tick's launches: what the bins remember, the frustum's device
+// copy, and the pending compaction's fate (carried: the tick writes the other copy of the visibility words; else settled now).
+static int commitPlan(ScTickContext* c, const TickPlan& plan)
+{
+  // matrices change and the bins do not follow; a quiet tick's records go stale the same way: the next binning tick rewrites every
+  // always-written slot (cleanStay 0).  The bins' counters and layer summaries stay at homeCount / homeLayers, where the last pair
+  // role left them; the slots age on.
+  if (plan.rec.quiet || ((plan.run & SC_TICK_XFORM) && !(plan.run & SC_TICK_BROADPHASE))) c->boxesTouched = true;
+  if (plan.rec.quiet) c->homeAge++;
+  if (plan.binned) {
+    if (plan.learn) {
+      // every bin copy must be idle and empty for a learn tick (a rare event: the streams are joined here)
+      c->homeXform = plan.homeXform;
+      if (c->pairsStream && !sync(c)) return 0;
+      if (c->homeCountsLive) {
+        for (uint32_t q = 0; q < (c->pairsStream ? c->pipeDepth : 1u); ++q) {
+          const DeviceState o = stateFor(c, q);
+          HIP_OK(c, hipMemsetAsync(o.binCount, 0, (size_t)c->sectors * sizeof(uint32_t), c->stream));
+          HIP_OK(c, hipMemsetAsync(o.binLayers, 0, (size_t)c->sectors * sizeof(uint32_t), c->stream));
+        }
+      }
+      c->homeValid = true; c->homeEpoch = c->topoEpoch; c->homeAge = 0; c->learnTicks++;
+    } else c->homeAge++;
     c->boxesTouched = false;
     c->homeCountsLive = true;
   }
-  if ((flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS) && c->neighbourMask) {
-    // every message of THIS tick parity needs its buffers: a missing one would make the pack skip that neighbour silently
-    const DeviceState ds = stateFor(c, c->parity);
-    for (uint32_t d = 0; d < 8; ++d)
-      if (((c->neighbourMask >> d) & 1u) && (!ds.borderSend[d] || !ds.borderRecv[d]))
-        return fail(c, "border buffers of this tick parity are not bound (scTickBindBorderBuffers / scTickBindBorderBuffersParity / scTickCommInit)");
-  }
-  if (c->frustumStale && (flags & SC_TICK_CULL)) { launchSetFrustum(c->d, c->frustum, c->stream); c->frustumStale = false; }   // outside any graph
+  if (c->frustumStale && (plan.run & SC_TICK_CULL)) { launchSetFrustum(c->d, c->frustum, c->stream); c->frustumStale = false; }   // outside any graph
+  if (plan.carry) c->visSel = plan.visSel; else settle(c);
+  return 1;
+}
 
-  // the end-of-tick launch's shape (enqueueStages' rule for who carries the compaction role): the wide form only where the launch is
-  // the compaction's own
-  const FramePath path = framePathFor(c, p.flags);         // once per tick (here, not in enqueueStages: a replayed graph enqueues nothing)
-  const bool alone = path.needCompact && !(p.flags & SC_TICK_BROADPHASE);
-  c->compactG = (alone && c->wideCompact) ? compactWideGroup(p, grid, c->compactForceG) : 0u;
-  c->lastCompact[0] = c->lastCompact[1] = 0u;
-  if (path.needCompact) compactLaunchShape(grid, path.pairsNow, c->compactG, c->lastCompact);
-  c->lastFrame[0] = path.items; c->lastFrame[1] = path.block;
-  const uint32_t q = (flags & SC_TICK_BROADPHASE) ? c->parity : 0u;
-  c->lastTickSampled = tickSampled(c);                 // (events need eager launches)
-  // The carried compaction.  A pending one rides at the head of this tick's fused launch where that launch is the carry-capable instance,
-  // launched eagerly; otherwise it is settled first -- its own launch ahead of everything of this tick, which is the order of two ticks
-  // that never deferred.  A carrying tick writes the other copy of the words (visSel, stateFor).  Then this tick's own compaction:
-  // deferred when its launch would be k_compact_wide alone behind that instance, nothing else of the tick or the context needs the
-  // lists on the device or on the host behind it, and the slot that would time the launch is not being timed on this tick.
-  {
-    const bool instance = !c->graphMode && carryInstance(p);
-    c->tickCarry = c->pending.on && instance;
-    if (c->tickCarry) c->visSel ^= 1u; else settle(c);
-    const bool slotTimed = timed(c, quiet ? SC_TICK_K_PAIRS : SC_TICK_K_COMPACT, c->lastTickSampled);
-    c->tickDefer = c->carryEnabled && instance && alone && c->compactG != 0u && !c->pairsStream && !c->neighbourMask && !c->rb.bytes &&
-                   !(p.flags & (SC_TICK_DRAWS | SC_TICK_SORT_DRAWS | SC_TICK_BIND_RUNS)) && !slotTimed;
+// The record of an accepted run (ScTickContext::last, lastBinned, lastWith), written in this one place, behind the run's launches (a run
+// that a HIP error ends in commitPlan, a capture or a replay leaves the record of the run before it).  `last` whole; `lastBinned` by a
+// tick that binned; of `lastWith` what belongs to a flag in `with` -- the run's flags (an empty context's run launches nothing: of the
+// features only the bind runs answer for it, with zeros).
+static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* binned, uint32_t with)
+{
+  c->last = rec;
+  if (binned) c->lastBinned = *binned;
+  LastWith& w = c->lastWith;
+  if (with & SC_TICK_BIND_RUNS) { w.bindTouchWords = c->bind.touchWords; w.bindEmpty = nothingToRun(c, rec.flags); }
+  if (with & SC_TICK_OVERLAPS) { w.overlapCount = c->overlaps.count; w.overlapMaxHits = c->overlaps.maxHits; w.overlapShapes = c->overlapShapes; }
+  if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
+  if (with & SC_TICK_PAIR_SHAPES) { w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; }
+}
+
+// The run of an empty context without a broadphase: nothing to launch, the per-tick counts read as zero.  (With the broadphase the
+// stages still run -- every kernel copes with n == 0: an emptied tile of a multi-GPU world must rewrite its border messages, header-only,
+// and take part in the exchange, the merge and the pair search of the boxes its neighbours send.)
+static int emptyTick(ScTickContext* c, uint32_t flags)
+{
+  RunRecord rec;                                     // (value-initialised but for its flags and, below, the frame's block)
+  rec.flags = flags;
+  settle(c);                                         // (a pending compaction writes the counters: ahead of the zeros)
+  HIP_OK(c, hipMemsetAsync(c->d.counters, 0, 8 * sizeof(uint32_t), c->stream));
+  if (c->rb.bytes) {
+    // every scTickRun ends with a frame: this one is all zeros under the next tick index, written by the host into the pinned block
+    // (nothing is launched and nothing copied; the block's copy of two frames ago is waited for on the host -- a rare tick)
+    ScTickContext::FrameReadback& rb = c->rb;
+    const uint32_t f = frameSlot(rb);
+    if (rb.inFlight[f]) HIP_OK(c, hipEventSynchronize(rb.copied[f]));
+    const FrameHeader h = frameHeader(0u, 0u, 0u, 0u, 0u, 0u, (uint32_t)rb.frames, (uint32_t)(rb.frames >> 32), 0u, 0u);
+    std::memcpy(rb.hBlock[f], h.w, sizeof h.w);
+    HIP_OK(c, publishFrame(c, false));
+    rec.frame[1] = SC_TICK_FRAME_BLOCK_HOST;
   }
+  recordRun(c, rec, nullptr, flags & SC_TICK_BIND_RUNS);
+  return 1;
+}
+
+// One tick, in five steps: refuse, plan, commit, launch or replay, record.
+int scTickRun(ScTickContext* c, uint32_t flags)
+{
+  if (!c) return 0;
+  if (!bind(c)) return 0;
+  if (!flushLinks(c)) return 0;
+  if (flags & SC_TICK_XFORM) REFUSE_WHILE_SHAPES_PENDING(c, "scTickRun with SC_TICK_XFORM");
+  if (!tickAccepted(c, flags)) return 0;
+  if (nothingToRun(c, flags)) return emptyTick(c, flags);
+  const TickPlan plan = planTick(c, flags);
+  if (!commitPlan(c, plan)) return 0;
+  const TickParams& p = plan.p;
   waitParityFree(c, p);
-  const bool replay = c->graphMode && !c->lastTickSampled && !c->lastTickLearn;
-  if (replay) {
+  bool rode = false;
+  if (plan.replay) {
     // whole-step capture (scTickTileStep on a tile with neighbours): the RCCL group and the pair half join the graph, so a
     // step of an in-order tile is ONE hipGraphLaunch
-    const bool whole = c->captureWholeStep;
-    if (!replayGraph(c, c->stream, c->graph[quiet ? kMaxParity : q], p, whole, "hipStreamEndCapture", [&] {
-          enqueueStages(c, p, path, grid, true);
-          if (!whole) return 1;
+    const uint32_t q = plan.rec.quiet ? kMaxParity : (plan.run & SC_TICK_BROADPHASE) ? p.parity : 0u;
+    if (!replayGraph(c, c->stream, c->graph[q], graphKey(c, plan, plan.wholeStep), "hipStreamEndCapture", [&] {
+          enqueueStages(c, plan, true);
+          if (!plan.wholeStep) return 1;
           if (!exchangeBorders(c, p.parity, c->stream, true)) return 0;
           enqueuePairHalf(c, p, c->stream);
           return 1;
         })) return 0;
-  } else {
-    enqueueStages(c, p, path, grid, false);
-  }
-  publishPacked(c, p);
-  if (flags & SC_TICK_BROADPHASE) {
-    const bool pairHalfDone = replay && c->captureWholeStep;
-    if ((flags & SC_TICK_SPLIT_PAIRS) && !pairHalfDone) { c->pairsPending = true; c->pendingParams = p; }
+  } else rode = enqueueStages(c, plan, false);
+  publishPacked(c, p, rode);
+  recordRun(c, plan.rec, plan.binned ? &plan.bins : nullptr, flags);
+  if (plan.run & SC_TICK_BROADPHASE) {
+    if ((plan.run & SC_TICK_SPLIT_PAIRS) && !plan.wholeStep) { c->pairsPending = true; c->pendingTick = plan; }
     else { c->lastParity = c->parity; c->parity ^= 1u; }           // (in-order flows alternate between two copies)
   }
   c->tickIndex++;
@@ -2275,12 +2335,13 @@ int scTickRun(ScTickContext* c, uint32_t flags)
 // when the RCCL group is inside: it touches the communicator's resources during capture).
 static int runPendingPairs(ScTickContext* c, bool withExchange)
 {
-  const uint32_t q = c->pendingParams.parity;
+  const TickPlan& tick = c->pendingTick;               // (the tick's own decisions: tickIndex and the record have moved on)
+  const TickParams& pp = tick.p;
+  const uint32_t q = pp.parity;
   hipStream_t ps = c->pairsStream ? c->pairsStream : c->stream;
   if (c->pairsStream) {
-    const TickParams& pp = c->pendingParams;
-    if (c->graphMode && !c->lastTickSampled && !c->lastTickLearn) {
-      if (!replayGraph(c, ps, c->pairGraph[q], pp, withExchange, "hipStreamEndCapture (pair half)", [&] {
+    if (c->graphMode && !tick.sampled && !tick.learn) {
+      if (!replayGraph(c, ps, c->pairGraph[q], graphKey(c, tick, withExchange), "hipStreamEndCapture (pair half)", [&] {
             if (withExchange && !exchangeBorders(c, q, ps, true)) return 0;
             enqueuePairHalf(c, pp, ps);
             return 1;
@@ -2288,7 +2349,7 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
       HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
     } else {
       // a sampled tick times its pair chain too (exchange + merge + queries + pair search, on the pairs stream): SC_TICK_K_PAIRS
-      EventPair ev; const bool on = timed(c, SC_TICK_K_PAIRS, c->lastTickSampled);
+      EventPair ev; const bool on = timed(c, SC_TICK_K_PAIRS, tick.sampled);
       if (on) { ev = takeEvents(c); hipEventRecord(ev.a, ps); }
       if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
       if (!enqueuePairHalf(c, pp, ps, c->pairsDone[q])) HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
@@ -2297,8 +2358,8 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
     c->pairsInFlight[q] = true;
   } else {
     if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
-    Scoped s(c, SC_TICK_K_PAIRS, c->lastTickSampled);      // (the tick's sampling decision: tickIndex has moved on)
-    enqueuePairHalf(c, c->pendingParams, ps);
+    Scoped s(c, SC_TICK_K_PAIRS, tick.sampled);
+    enqueuePairHalf(c, pp, ps);
   }
   if (c->pairEventsResyncAgain) {                     // (in-order flows only: the pair half ran on the tick stream)
     c->pairEventsResyncAgain = false;
@@ -2588,7 +2649,7 @@ int scTickGetCounts(ScTickContext* c, ScTickCounts* out)
   out->renderables_total = k[6];
   out->visible = k[0];
   out->culled = k[1];
-  if (c->sectors && (c->lastFlags & SC_TICK_BROADPHASE) && !c->pairsPending && !c->lastTickQuiet) {      // (a quiet tick: 0 pairs by construction)
+  if (c->sectors && (c->last.flags & SC_TICK_BROADPHASE) && !c->pairsPending && !c->last.quiet) {      // (a quiet tick: 0 pairs by construction)
     TickParams pp{}; pp.maxPairs = c->maxPairs;
     launchGatherPairs(c->d, pp, resultSlot, c->dPairsOut, c->dPairTotal, c->stream);
     uint32_t tot[2] = {};
@@ -2597,7 +2658,7 @@ int scTickGetCounts(ScTickContext* c, ScTickCounts* out)
     out->pairs_truncated = tot[1];
   }
   out->bin_overflow = bp[kCtrSpill];                 // length of the sector overflow list (own boxes + border records that landed in a full bin)
-  out->big_boxes = (c->lastFlags & SC_TICK_SPLIT_PAIRS) ? bp[kCtrBigLocal] : bp[kCtrBig];
+  out->big_boxes = (c->last.flags & SC_TICK_SPLIT_PAIRS) ? bp[kCtrBigLocal] : bp[kCtrBig];
   out->border_lost = bp[kCtrBorderLost];
   if (c->sectors) {
     uint32_t lc[1u + 2u * kMaxParity] = {};
@@ -2606,7 +2667,7 @@ int scTickGetCounts(ScTickContext* c, ScTickCounts* out)
   }
   out->draws_emitted = k[4];
   out->draws_dropped = k[5];
-  out->draws_sorted = (c->lastFlags & SC_TICK_SORT_DRAWS) ? k[kCtrDrawsSorted] : 0u;
+  out->draws_sorted = (c->last.flags & SC_TICK_SORT_DRAWS) ? k[kCtrDrawsSorted] : 0u;
   out->max_depth = c->maxDepth;
   out->unreachable = c->unreachable;
   out->relinks = c->relinks;
@@ -2635,7 +2696,7 @@ int scTickReadVisible(ScTickContext* c, uint32_t* out, uint32_t cap, uint32_t* c
 int scTickReadCulled(ScTickContext* c, uint32_t* out, uint32_t cap, uint32_t* count)
 {
   if (!c) return 0;
-  if (!(c->lastFlags & SC_TICK_CULLED_LIST)) return fail(c, "the last scTickRun did not request SC_TICK_CULLED_LIST");
+  if (!(c->last.flags & SC_TICK_CULLED_LIST)) return fail(c, "the last scTickRun did not request SC_TICK_CULLED_LIST");
   return readIndexList(c, c->d.culledIdx, 1, out, cap, count);
 }
 
@@ -2709,7 +2770,7 @@ int scTickReadWorldAabbs(ScTickContext* c, uint32_t first, uint32_t count, float
 {
   if (!c || !min3 || !max3) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
-  if ((c->lastFlags & (SC_TICK_BROADPHASE | SC_TICK_DENSE_AABBS)) != (SC_TICK_BROADPHASE | SC_TICK_DENSE_AABBS))
+  if ((c->last.flags & (SC_TICK_BROADPHASE | SC_TICK_DENSE_AABBS)) != (SC_TICK_BROADPHASE | SC_TICK_DENSE_AABBS))
     return fail(c, "the last scTickRun did not request SC_TICK_BROADPHASE | SC_TICK_DENSE_AABBS");
   if (!count) return 1;
   std::vector<float4> a(count), b(count);
@@ -2727,7 +2788,7 @@ int scTickReadPairs(ScTickContext* c, uint32_t* pairs2, uint32_t cap, uint32_t* 
   if (!bind(c)) return 0;
   if (!lastRunResult(c, SC_TICK_BROADPHASE, "the last scTickRun did not request SC_TICK_BROADPHASE", true, nullptr,
                      "scTickRunPairs has not been called for the last tick", true, nullptr)) return 0;
-  if (c->lastTickQuiet) { *count = 0; return 1; }      // no two colliders of that tick's world could meet: the empty set, whatever the bins' copies hold
+  if (c->last.quiet) { *count = 0; return 1; }      // no two colliders of that tick's world could meet: the empty set, whatever the bins' copies hold
   // the pair list is kept in per-shard segments on the device; gather them into one list first
   TickParams pp{}; pp.maxPairs = c->maxPairs;
   const uint32_t slot = c->lastParity;
@@ -2750,14 +2811,14 @@ int scTickReadDraws(ScTickContext* c, ScTickDrawItem* items, uint32_t cap, uint3
 {
   if (!c || !count) return c ? fail(c, "null argument") : 0;
   if (!bind(c)) return 0;
-  if (!(c->lastFlags & SC_TICK_DRAWS)) return fail(c, "the last scTickRun did not request SC_TICK_DRAWS");
+  if (!(c->last.flags & SC_TICK_DRAWS)) return fail(c, "the last scTickRun did not request SC_TICK_DRAWS");
   settle(c);
   uint32_t k[16] = {};
   if (!d2h(c, k, c->d.counters, sizeof k) || !sync(c)) return 0;
-  const uint32_t have = (c->lastFlags & SC_TICK_SORT_DRAWS) ? k[kCtrDrawsSorted] : k[4];
+  const uint32_t have = (c->last.flags & SC_TICK_SORT_DRAWS) ? k[kCtrDrawsSorted] : k[4];
   *count = have;
   const uint32_t take = std::min(have, cap);
-  if (take && items) { if (!d2h(c, items, c->lastDraws ? c->lastDraws : c->dDraws, (size_t)take * sizeof(ScTickDrawItem)) || !sync(c)) return 0; }
+  if (take && items) { if (!d2h(c, items, c->last.draws ? c->last.draws : c->dDraws, (size_t)take * sizeof(ScTickDrawItem)) || !sync(c)) return 0; }
   return 1;
 }
 
@@ -2895,12 +2956,12 @@ int scTickReadOverlapHits(ScTickContext* c, uint32_t* counts, uint32_t* ids, uin
 {
   if (!c) return 0;
   // the set is as the run left it while count and max_hits are what that run answered (a same-size call only rewrites volumes)
-  const bool stands = c->overlaps.count == c->lastOverlapCount && c->overlaps.maxHits == c->lastOverlapMaxHits;
+  const bool stands = c->overlaps.count == c->lastWith.overlapCount && c->overlaps.maxHits == c->lastWith.overlapMaxHits;
   if (!bind(c) || !lastRunResult(c, SC_TICK_OVERLAPS, "the last scTickRun did not request SC_TICK_OVERLAPS", true, nullptr,
                                  "overlap hits are ready after scTickRunPairs", stands, "the overlap set was re-sized since the last run with SC_TICK_OVERLAPS: its results are gone")) return 0;
   const OverlapQueryState& o = c->overlaps;
   // the report's sums are formed here, from the per-volume words the waves wrote: no wave adds to a shared word
-  const bool exact = c->lastOverlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT;
+  const bool exact = c->lastWith.overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT;
   std::vector<uint32_t> perVolume(o.count);
   std::vector<uint2> tally(exact ? o.count : 0u);
   if (!d2h(c, perVolume.data(), o.counts, (size_t)o.count * sizeof(uint32_t))) return 0;
@@ -2915,7 +2976,7 @@ int scTickReadOverlapHits(ScTickContext* c, uint32_t* counts, uint32_t* ids, uin
     for (const uint2& t : tally) { refined += t.x; kept += t.y; }
     info->queries = o.count; info->max_hits = o.maxHits; info->hits = (uint32_t)std::min<uint64_t>(hits, 0xFFFFFFFFull);
     info->truncated_queries = truncated; info->refined = (uint32_t)std::min<uint64_t>(refined, 0xFFFFFFFFull);
-    info->kept_as_boxes = (uint32_t)std::min<uint64_t>(kept, 0xFFFFFFFFull); info->shapes = c->lastOverlapShapes; info->pad = 0u;
+    info->kept_as_boxes = (uint32_t)std::min<uint64_t>(kept, 0xFFFFFFFFull); info->shapes = c->lastWith.overlapShapes; info->pad = 0u;
   }
   return 1;
 }
@@ -3032,7 +3093,7 @@ int scTickReadPairContacts(ScTickContext* c, ScTickPairContact* out, uint32_t ca
   if (!c || !info) return c ? fail(c, "null argument") : 0;
   const PairContactState& k = c->pairContacts;
   if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastPairContacts, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)",
+                                 c->lastWith.pairContacts, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)",
                                  "pair contacts are ready after scTickRunPairs", k.ctl != nullptr, "pair contacts were switched off since the last scTickRun")) return 0;
   return readReportAndRecords(c, info, k.info, &ScTickPairContactInfo::written, k.maxTouching, k.rec, sizeof(ScTickPairContact), out, capacity) ? 1 : 0;
 }
@@ -3065,7 +3126,7 @@ int scTickReadPairManifolds(ScTickContext* c, ScTickPairManifold* out, uint32_t 
   if (!c || !info) return c ? fail(c, "null argument") : 0;
   const PairManifoldState& f = c->pairManifolds;
   if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastPairManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)",
+                                 c->lastWith.pairManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)",
                                  "pair manifolds are ready after scTickRunPairs", f.ctl != nullptr, "pair manifolds were switched off since the last scTickRun")) return 0;
   return readReportAndRecords(c, info, f.info, &ScTickPairManifoldInfo::written, f.maxTouching, f.rec, sizeof(ScTickPairManifold), out, capacity) ? 1 : 0;
 }
@@ -3127,7 +3188,7 @@ int scTickGetSweepShapeInfo(ScTickContext* c, ScTickSweepShapeInfo* info)
   static_assert(sizeof(ScTickSweepShapeInfo) == kSweepInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !lastRunResult(c, SC_TICK_SWEEPS, "the last scTickRun did not request SC_TICK_SWEEPS",
-                                 c->lastSweepsExact && c->sweepInfo, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined",
+                                 c->lastWith.sweepsExact && c->sweepInfo, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined",
                                  "the sweep shape report is ready after scTickRunPairs", true, nullptr)) return 0;
   if (!d2h(c, info, c->sweepInfo, sizeof *info) || !sync(c)) return 0;
   return 1;
@@ -3327,9 +3388,9 @@ int scTickSetBindRuns(ScTickContext* c, uint32_t maxRuns)
 
 static bool bindRunsReadable(ScTickContext* c)
 {
-  if (!(c->lastFlags & SC_TICK_BIND_RUNS)) return fail(c, "the last scTickRun did not request SC_TICK_BIND_RUNS");
+  if (!(c->last.flags & SC_TICK_BIND_RUNS)) return fail(c, "the last scTickRun did not request SC_TICK_BIND_RUNS");
   if (!c->bind.info) return fail(c, "bind runs were switched off since the last scTickRun");
-  if (c->bind.touchWords != c->bindLastTouchWords) return fail(c, "the draw sort table was resized since the last scTickRun");
+  if (c->bind.touchWords != c->lastWith.bindTouchWords) return fail(c, "the draw sort table was resized since the last scTickRun");
   return true;
 }
 
@@ -3337,7 +3398,7 @@ int scTickReadBindRuns(ScTickContext* c, ScTickBindRun* runs, uint32_t cap, ScTi
 {
   if (!c || !info) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !bindRunsReadable(c)) return 0;
-  if (c->bindLastEmpty) { std::memset(info, 0, sizeof *info); info->touch_words = c->bindLastTouchWords; return 1; }
+  if (c->lastWith.bindEmpty) { std::memset(info, 0, sizeof *info); info->touch_words = c->lastWith.bindTouchWords; return 1; }
   if (!d2h(c, info, c->bind.info, sizeof *info) || !sync(c)) return 0;
   const uint32_t take = std::min(std::min(info->runs, c->bind.maxRuns), runs ? cap : 0u);
   if (take && (!d2h(c, runs, c->bind.runs, (size_t)take * sizeof(ScTickBindRun)) || !sync(c))) return 0;
@@ -3348,10 +3409,10 @@ int scTickReadMaterialTouches(ScTickContext* c, uint32_t* words, uint32_t wordCa
 {
   if (!c || !wordCount) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !bindRunsReadable(c)) return 0;
-  *wordCount = c->bindLastTouchWords;
-  const uint32_t take = std::min(c->bindLastTouchWords, words ? wordCap : 0u);
+  *wordCount = c->lastWith.bindTouchWords;
+  const uint32_t take = std::min(c->lastWith.bindTouchWords, words ? wordCap : 0u);
   if (!take) return 1;
-  if (c->bindLastEmpty) { std::memset(words, 0, (size_t)take * 4u); return 1; }
+  if (c->lastWith.bindEmpty) { std::memset(words, 0, (size_t)take * 4u); return 1; }
   if (!d2h(c, words, c->bind.touch, (size_t)take * 4u) || !sync(c)) return 0;
   return 1;
 }
@@ -3689,7 +3750,7 @@ int scTickGetTopologyClassStats(ScTickContext* c, uint32_t stats[4])
   if (!c || !stats) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !flushLinks(c)) return 0;
   stats[0] = c->topoPatterns; stats[1] = c->topoClassed; stats[2] = c->topoUnclassed;
-  stats[3] = c->lastTickTopo ? 1u : 0u;
+  stats[3] = c->last.topo ? 1u : 0u;
   return 1;
 }
 
@@ -3700,7 +3761,7 @@ int scTickGetTailStats(ScTickContext* c, uint32_t stats[2])
   uint32_t span, grid;
   computeSpan(c, span, grid);
   if (span != c->closureSpan) deriveSpanClosed(c);
-  stats[0] = c->lastTickTail ? 1u : 0u;
+  stats[0] = c->last.tail ? 1u : 0u;
   stats[1] = c->spanClosed ? 1u : 0u;
   return 1;
 }
@@ -3708,7 +3769,7 @@ int scTickGetTailStats(ScTickContext* c, uint32_t stats[2])
 int scTickGetCompactStats(ScTickContext* c, uint32_t stats[2])
 {
   if (!c || !stats) return c ? fail(c, "null argument") : 0;
-  stats[0] = c->lastCompact[0]; stats[1] = c->lastCompact[1];
+  stats[0] = c->last.compact[0]; stats[1] = c->last.compact[1];
   return 1;
 }
 
@@ -3722,7 +3783,7 @@ int scTickGetCarryStats(ScTickContext* c, uint32_t stats[3])
 int scTickGetFrameStats(ScTickContext* c, uint32_t stats[2])
 {
   if (!c || !stats) return c ? fail(c, "null argument") : 0;
-  stats[0] = c->lastFrame[0]; stats[1] = c->lastFrame[1];
+  stats[0] = c->last.frame[0]; stats[1] = c->last.frame[1];
   return 1;
 }
 
@@ -3732,7 +3793,7 @@ int scTickGetBinStats(ScTickContext* c, uint32_t stats[4])
   stats[0] = stats[1] = stats[2] = stats[3] = 0u;
   if (!bind(c)) return 0;
   if (!c->d.homeA || !c->n) return 1;
-  stats[2] = (c->lastTickLazy ? 1u : 0u) | (c->lastTickStay ? 2u : 0u) | (c->lastTickSweepOnly ? 4u : 0u) | (c->lastTickQuiet ? 8u : 0u); stats[3] = c->learnTicks;
+  stats[2] = (c->lastBinned.lazy ? 1u : 0u) | (c->lastBinned.stay ? 2u : 0u) | (c->lastBinned.sweepOnly ? 4u : 0u) | (c->last.quiet ? 8u : 0u); stats[3] = c->learnTicks;
   if (!c->homeValid) return 1;
   if (!sync(c)) return 0;
   std::vector<uint32_t> a(c->n), b(c->n);
@@ -3961,7 +4022,7 @@ int scTickExchangeBorders(ScTickContext* c)
   if (!c->pairsPending) return fail(c, "scTickExchangeBorders without a preceding scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_SPLIT_PAIRS)");
   if (!c->neighbourMask) return 1;
   if (!c->comm) return fail(c, "no communicator: scTickCommInit first");
-  return exchangeBorders(c, c->pendingParams.parity, c->pairsStream ? c->pairsStream : c->stream, false);
+  return exchangeBorders(c, c->pendingTick.p.parity, c->pairsStream ? c->pairsStream : c->stream, false);
 }
 
 int scTickTileStep(ScTickContext* c, uint32_t flags)

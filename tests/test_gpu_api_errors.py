@@ -95,6 +95,83 @@ def test_split_pairs_protocol_is_enforced():
     t.close()
 
 
+def sphere_volumes(w, k):
+    """k unit spheres over the first entities of the world, in overlap_queries' argument order"""
+    m = np.tile(np.eye(4, dtype=np.float32).ravel(), (k, 1))
+    m[:, 12:15] = w.pos[:k]
+    return (np.full(k, capi.COLLIDER_SPHERE, np.uint8), m, np.zeros((k, 3), np.float32), np.ones(k, np.float32), np.zeros(k, np.float32),
+            np.full(k, 0xFFFF, np.uint32))
+
+
+@pytest.mark.parametrize("refused,text", [
+    (capi.BROADPHASE | capi.OVERLAPS | capi.PRODUCE_NEXT, "PRODUCE_NEXT needs SC_TICK_XFORM"),
+    (capi.XFORM | capi.BROADPHASE | capi.OVERLAPS | capi.DRAWS | capi.SORT_DRAWS, "needs scTickSetDrawSortTable first"),
+])
+def test_a_refused_run_leaves_the_overlap_readers_as_they_were(refused, text):
+    """A run refused behind the SC_TICK_OVERLAPS checks must not pass for the run that answered the re-sized set: the reader still
+    refuses, as it did before the refused call."""
+    w = sw.generate(4, 4, 15)                                  # 240 entities on a 4 x 4-sector tile
+    t = WorldTick.from_world(w, broadphase=True)
+    t.overlap_queries(*sphere_volumes(w, 4))
+    t.run(capi.XFORM | capi.BROADPHASE | capi.OVERLAPS)
+    assert t.overlap_info()["queries"] == 4
+    t.overlap_queries(*sphere_volumes(w, 8))
+    with pytest.raises(capi.ScTickError, match="re-sized since the last run"):
+        t.overlap_info()
+    assert t.lib.scTickRun(t.ctx, refused) == 0 and text in err(t)
+    with pytest.raises(capi.ScTickError, match="re-sized since the last run"):
+        t.overlap_info()
+    with pytest.raises(capi.ScTickError, match="re-sized since the last run"):
+        t.overlap_hits()
+    t.run(capi.XFORM | capi.BROADPHASE | capi.OVERLAPS)      # an accepted run answers the new set
+    assert t.overlap_info()["queries"] == 8
+    t.close()
+
+
+def test_a_refused_run_leaves_the_bind_run_readers_as_they_were():
+    """... and so for SC_TICK_BIND_RUNS behind a draw sort table of another material count (another touch bitmap)."""
+    flagged = capi.XFORM | capi.CULL | capi.DRAWS | capi.SORT_DRAWS | capi.BIND_RUNS
+    w = sw.generate(4, 4, 15)
+    w.material = (np.arange(w.n) % 97).astype(np.uint32)
+    pipeline = (np.arange(97) % 2).astype(np.uint8)
+    t = WorldTick.from_world(w, broadphase=False)
+    t.set_view_proj(camera_view_proj(w.camera))
+    t.set_draw_sort_table(pipeline, 4)
+    t.set_bind_runs(64)
+    t.run(flagged)
+    assert t.bind_runs()[1]["touch_words"] == 4 and len(t.material_touches()) == 97
+    t.set_draw_sort_table(np.concatenate((pipeline, np.zeros(1000, np.uint8))), 4)
+    for read in (t.bind_runs, t.material_touches):
+        with pytest.raises(capi.ScTickError, match="the draw sort table was resized since the last scTickRun"):
+            read()
+    assert t.lib.scTickRun(t.ctx, (flagged & ~capi.XFORM) | capi.PRODUCE_NEXT) == 0 and "PRODUCE_NEXT needs SC_TICK_XFORM" in err(t)
+    for read in (t.bind_runs, t.material_touches):
+        with pytest.raises(capi.ScTickError, match="the draw sort table was resized since the last scTickRun"):
+            read()
+    t.run(flagged)
+    assert t.bind_runs()[1]["touch_words"] == (1097 + 31) // 32
+    t.close()
+
+
+@pytest.mark.parametrize("first_sampled", [True, False])
+def test_a_pending_pair_half_is_timed_by_its_own_ticks_sampling_decision(first_sampled):
+    """Caller-owned split flow with a transform-only tick between the halves: the pair half of tick t is timed when tick t was sampled,
+    whatever the tick in between was."""
+    w = sw.generate(4, 4, 15)
+    t = WorldTick.from_world(w, broadphase=True)
+    t.set_profiling_kernels(None)
+    t.set_profiling(2)                                         # ticks 0, 2, ... are sampled
+    if not first_sampled:
+        t.run(capi.XFORM)                                      # tick 0: the split tick is tick 1, the one between the halves tick 2
+    t.run(capi.XFORM | capi.BROADPHASE | capi.SPLIT_PAIRS)
+    t.run(capi.XFORM)
+    t.run_pairs()
+    t.sync()
+    assert len(t.kernel_times_ms(capi.K_PAIRS)) == (1 if first_sampled else 0)
+    t.set_profiling(0)
+    t.close()
+
+
 def test_profiling_samples_only_the_kernels_asked_for_and_learn_ticks_is_a_host_counter():
     """scTickSetProfiling(n) times every n-th tick's launches by events; scTickSetProfilingKernels narrows that to some kernels (what a
     run that is itself being timed uses: a timed launch costs its queue a few microseconds); scTickGetLearnTicks is scTickGetBinStats'
