@@ -65,6 +65,7 @@ enum {
   SC_TICK_PAIR_SHAPES = 1u << 14,  /* with BROADPHASE: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes) */
   SC_TICK_TOUCH_EVENTS = 1u << 15, /* with BROADPHASE: report which pairs begun and which ended TOUCHING since the last run with this flag (scTickSetTouchEvents) */
   SC_TICK_OVERLAPS    = 0x00010000u, /* bit 16.  With BROADPHASE: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes */
+  SC_TICK_TRIGGERS    = 0x00020000u, /* bit 17.  With BROADPHASE: answer the trigger volumes set by scTickSetTriggerVolumes and report who entered / left since the last run with this flag */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -1430,6 +1431,90 @@ int scTickSetOverlapQueries(ScTickContext* ctx, uint32_t count, const uint8_t* t
  * gives the sizes.  Each of counts, ids and info may be NULL.  Synchronises; the report's sums are formed by this call from the per-volume
  * words the device wrote (saturating at 2^32 - 1). */
 int scTickReadOverlapHits(ScTickContext* ctx, uint32_t* counts, uint32_t* ids, uint32_t query_capacity, ScTickOverlapInfo* info);
+
+/* ---- trigger volumes: anchored overlap volumes with enter / exit events ----
+ * A trigger zone rides on an entity -- a vehicle's proximity zone, a pedestrian's personal space, a pickup, the reference's
+ * Collider::isTrigger bodies (CF_NO_CONTACT_RESPONSE: sc_physics.h:27, sc_physics.cpp:346-347, :438-439) -- and its consumer wants "who
+ * came in, who left", not the member list.  A trigger volume is to an overlap query what an entity-anchored ray is to a ray: given in
+ * its anchor's LOCAL frame, resolved on the device against this tick's world matrix, answered as the overlap query of the resolved volume
+ * would be, and reported as the DIFFERENCE against the last run that carried SC_TICK_TRIGGERS.  A set of its own with a flag of its own;
+ * a context that never calls scTickSetTriggerVolumes allocates and launches nothing for it.
+ * This build's OWN SPEC.  All arithmetic is fp32, unfused, left to right.
+ *   resolve     W = the anchor's world matrix rows as this run's transform stage leaves them (without SC_TICK_XFORM: as they stand), L =
+ *               the volume's local affine matrix (local_mat16, column-major; its last row is not read).  For r, k in 0..2:
+ *                 M[r,k] = (W[r,0]*L[0,k] + W[r,1]*L[1,k]) + W[r,2]*L[2,k]
+ *                 M[r,3] = ((W[r,0]*L[0,3] + W[r,1]*L[1,3]) + W[r,2]*L[2,3]) + W[r,3]
+ *               anchor == SC_TICK_ANCHOR_NONE: M = L untouched (a world-space zone).  A volume has NO MEMBERS this tick when its anchor
+ *               is >= the entity count at run time (SC_TICK_ANCHOR_DEAD always is) or one of the twelve entries of M is not finite;
+ *               scTickReadTriggerMatrices then reports all twelve as the quiet NaN 0x7FC00000.
+ *   members     exactly what scTickSetOverlapQueries answers for a volume with matrix M, the same type, values and mask: the volume box,
+ *               the candidates, the filter, the closed-interval pair rule, the low-corner rule ("every entity once"), and in
+ *               SC_TICK_OVERLAP_SHAPES_EXACT mode the touching pairs' routines with the entity as member A ("overlap queries" above).  An
+ *               unanchored trigger volume's member set equals the overlap query's answer for the same volume, in both modes.
+ *               skip_self[v] != 0 (NULL: all 1): the id (rank << 24 | anchor) never answers; without an anchor it has no effect.
+ *   events      an event is a pair (volume index, id), id = rank << 24 | dense index.  The context remembers, per volume, the member row of
+ *               the last run that carried SC_TICK_TRIGGERS.  A flagged run reports entered = members now that were not remembered and
+ *               exited = remembered members that are not members now, then remembers its own rows.  Unflagged runs leave the memory
+ *               alone.  The order inside both lists and inside a row is unspecified.
+ *   RESYNC      per volume (info.resync_volumes): nothing was remembered for it -- entered is its whole row, exited nothing.  Every volume
+ *               on the first flagged run after a set call that re-sizes, scTickRemoveEntities, a shrinking scTickSetEntityCount and
+ *               scTickSetTile with another rank (ids are renamed); one volume after its own overflow tick.  Appends, and topology, layer and
+ *               collider uploads, force no resync.
+ *   OVERFLOW    per volume (info.overflow_volumes): its true count exceeds max_members.  Its row holds max_members distinct members of the
+ *               true set, as a truncated overlap row does; it contributes NO events, its memory is dropped (it resyncs on the next flagged
+ *               tick on which it fits), and it is counted here and not under resync_volumes.  The other volumes are untouched.
+ *   TRUNCATED   more than max_events entries enter, or leave, over all volumes: info.entered / info.exited carry the true totals, each
+ *               list holds max_events valid, distinct entries, events_truncated = 1.  The memory is complete all the same: the host
+ *               recovers the tick from scTickReadTriggerMembers.  Nothing is lost silently.
+ * The row cap.  While a wave forms the two differences it holds the volume's new row and its remembered row in LDS: 2 rows x
+ * SC_TICK_TRIGGER_MAX_MEMBERS x 4 bytes = 8 KB per wave, 32 KB for the four waves of a workgroup, five workgroups in a CU's 160 KB.
+ * scTickSetTriggerVolumes: anchor, type, radius, half_height, mask [count]; local_mat16 [count][16]; half_extents3 [count][3]; skip_self
+ * [count] or NULL.  Every array but skip_self is required whatever the types.  The set stays until it is replaced; count 0 clears it and
+ * frees it.  The call fails -- and leaves the previous set in place -- on a non-finite entry among the twelve read from local_mat16, a
+ * non-finite half extent, radius or half_height, a type other than BOX, SPHERE, CAPSULE, max_members == 0 with count > 0, max_members
+ * above SC_TICK_TRIGGER_MAX_MEMBERS, a count * max_members beyond 2^30 - 1 id slots, an unknown mode (SC_TICK_OVERLAP_SHAPES_*), a required
+ * array NULL, and while scTickRunPairs is pending.  A call with THE SAME count, max_members, max_events and mode as the current set only
+ * rewrites anchors, locals and values, behind whatever is queued: it KEEPS THE REMEMBERED ROWS, costs no learn tick and leaves a captured
+ * graph valid -- a world-space zone moved by hand this way yields ordinary events.  Anything else re-sizes the set (the query batches'
+ * grow rule, as scTickSetOverlapQueries), forgets every row, costs a learn tick and a fresh capture.
+ * Residency: scTickRemoveEntities renames the anchors of relocated entities (moved_from -> moved_to) and turns the anchors of removed ones
+ * into SC_TICK_ANCHOR_DEAD, as for the anchored rays; skip_self follows because it is derived from the anchor.
+ * A run with SC_TICK_TRIGGERS fails, with a last-error text, where one with SC_TICK_OVERLAPS does: without SC_TICK_BROADPHASE, without a
+ * set, together with SC_TICK_SPLIT_PAIRS, on a context with neighbours and on a pipelined context -- tiles are not covered.  The flag
+ * makes the tick fill every bin (no quiet tick, no lazy records), like the other bin readers. */
+#define SC_TICK_TRIGGER_MAX_MEMBERS 1024u   /* max_members at most: 2 rows x 1 024 ids x 4 bytes = 8 KB of LDS per wave */
+typedef struct ScTickTriggerInfo
+{
+  uint32_t volumes;            /* volumes of the set the run answered */
+  uint32_t max_members;        /* id slots per volume */
+  uint32_t members;            /* sum of the true counts */
+  uint32_t entered;            /* true total of entries */
+  uint32_t exited;             /* true total of exits */
+  uint32_t resync_volumes;     /* volumes nothing was remembered for (and that did not overflow) */
+  uint32_t overflow_volumes;   /* volumes whose count exceeds max_members */
+  uint32_t events_truncated;   /* 1: entered or exited exceeds max_events */
+} ScTickTriggerInfo;
+#ifdef __cplusplus
+static_assert(sizeof(ScTickTriggerInfo) == 32, "ScTickTriggerInfo is 32 bytes");
+#else
+_Static_assert(sizeof(ScTickTriggerInfo) == 32, "ScTickTriggerInfo is 32 bytes");
+#endif
+int scTickSetTriggerVolumes(ScTickContext* ctx, uint32_t count, const uint32_t* anchor, const uint8_t* type, const float* local_mat16,
+                            const float* half_extents3, const float* radius, const float* half_height, const uint32_t* mask,
+                            const uint8_t* skip_self, uint32_t max_members, uint32_t max_events, uint32_t shapes);
+/* The reads below answer for the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_TRIGGERS); they fail when the last run lacked the flag
+ * or the set was re-sized since.  They synchronise; the report's sums are formed by the call from the per-volume words the device wrote
+ * (saturating at 2^32 - 1).  Every output pointer may be NULL.
+ * events: entered2 [entered_cap][2], exited2 [exited_cap][2] as (volume, id); min(info.entered, max_events, entered_cap) pairs are written
+ * (likewise exited). */
+int scTickReadTriggerEvents(ScTickContext* ctx, uint32_t* entered2, uint32_t entered_cap, uint32_t* exited2, uint32_t exited_cap, ScTickTriggerInfo* info);
+/* members: counts [volume_capacity] (true counts), ids [volume_capacity][max_members] (row v: the first min(counts[v], max_members) slots),
+ * for the first min(volumes, volume_capacity) volumes */
+int scTickReadTriggerMembers(ScTickContext* ctx, uint32_t* counts, uint32_t* ids, uint32_t volume_capacity, ScTickTriggerInfo* info);
+/* the resolved world matrices of the last flagged run: mat16 [count][16], column-major with the last row (0, 0, 0, 1) */
+int scTickReadTriggerMatrices(ScTickContext* ctx, uint32_t first, uint32_t count, float* mat16);
+/* the anchors as they stand now (renamed or SC_TICK_ANCHOR_DEAD after scTickRemoveEntities); host-side, needs no run */
+int scTickReadTriggerVolumes(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

@@ -18,6 +18,7 @@ BIND_RUNS = 1 << 13           # SC_TICK_BIND_RUNS: with DRAWS | SORT_DRAWS, the 
 PAIR_SHAPES = 1 << 14         # SC_TICK_PAIR_SHAPES: also list the pairs of this tick whose collider shapes overlap (scTickSetPairShapes)
 TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended TOUCHING since the last run with this flag (scTickSetTouchEvents)
 OVERLAPS = 1 << 16            # SC_TICK_OVERLAPS: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes
+TRIGGERS = 1 << 17            # SC_TICK_TRIGGERS: answer the trigger volumes (scTickSetTriggerVolumes) and report who entered / left since the last run with it
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*: what a capsule sweep's candidates are (scTickSetSweepShapes)
@@ -28,6 +29,7 @@ CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 # SC_TICK_MANIFOLD_*: ScTickPairManifold::kind (scTickSetPairManifolds)
 MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
 MANIFOLD_REDUCED = 1 << 8
+TRIGGER_MAX_MEMBERS = 1024    # SC_TICK_TRIGGER_MAX_MEMBERS: id slots per trigger volume at most
 SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
 K_XFORM_CULL, K_COMPACT, K_PAIRS, K_NUDGE, K_COUNT = 0, 1, 2, 3, 4
@@ -92,6 +94,11 @@ class SweepShapeInfo(C.Structure):
 
 class OverlapInfo(C.Structure):                          # ScTickOverlapInfo: 32 bytes
     _fields_ = [(n, C.c_uint32) for n in ("queries", "max_hits", "hits", "truncated_queries", "refined", "kept_as_boxes", "shapes", "pad")]
+
+
+class TriggerInfo(C.Structure):                          # ScTickTriggerInfo: 32 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("volumes", "max_members", "members", "entered", "exited", "resync_volumes", "overflow_volumes",
+                                          "events_truncated")]
 
 
 class PairShapeInfo(C.Structure):
@@ -286,6 +293,11 @@ SYMBOLS = {
     "scTickReadPairManifolds": (C.c_int, [_CTX, C.POINTER(PairManifold), C.c_uint32, C.POINTER(PairManifoldInfo)]),
     "scTickSetOverlapQueries": (C.c_int, [_CTX, C.c_uint32, U8P, F32P, F32P, F32P, F32P, U32P, U32P, C.c_uint32, C.c_uint32]),
     "scTickReadOverlapHits": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(OverlapInfo)]),
+    "scTickSetTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, U32P, U8P, F32P, F32P, F32P, F32P, U32P, U8P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "scTickReadTriggerEvents": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(TriggerInfo)]),
+    "scTickReadTriggerMembers": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(TriggerInfo)]),
+    "scTickReadTriggerMatrices": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P]),
+    "scTickReadTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

@@ -52,6 +52,7 @@ struct LastWith {
   bool sweepsExact = false;                            // SC_TICK_SWEEPS ran in EXACT mode (scTickGetSweepShapeInfo)
   bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
+  uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
   uint32_t bindTouchWords = 0; bool bindEmpty = false; // SC_TICK_BIND_RUNS: the bitmap's size; the run of an empty context (the report reads as zeros)
 };
 
@@ -65,6 +66,7 @@ struct TickPlan {
   uint32_t compactG = 0;               // spans per workgroup of the end-of-tick kernel's wide form, 0 = compactBody's form
   uint32_t visSel = 0;                 // the copy of the visibility words this tick writes = ScTickContext::visSel once commitPlan has run (a carrying tick: not the copy its rider reads)
   bool sampled = false, carry = false, defer = false, replay = false, wholeStep = false;
+  bool triggers = false;               // the trigger volumes are answered by this tick (k_trigger_volumes, at the overlap queries' launch site)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -198,6 +200,13 @@ struct ScTickContext
   uint32_t overlapCap = 0; size_t overlapIdCap = 0;
   uint32_t overlapShapes = SC_TICK_OVERLAP_SHAPES_AABB;
   std::vector<uint2> hAnchor;
+  // scTickSetTriggerVolumes: the volumes, one id row per volume (the member row IS the remembered row), the per-volume words, the two
+  // event lists and the two slot counters; triggerCap: volumes the per-volume arrays hold, triggerIdCap: id slots, triggerEventCap:
+  // events per list.  hTriggerAnchor mirrors (anchor, skip_self) for scTickRemoveEntities and scTickReadTriggerVolumes.
+  TriggerState triggers{};
+  uint32_t triggerCap = 0, triggerEventCap = 0; size_t triggerIdCap = 0;
+  uint32_t triggerShapes = SC_TICK_OVERLAP_SHAPES_AABB;
+  std::vector<uint2> hTriggerAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
   PairEventState pairEvents{};
@@ -722,6 +731,7 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   computeSpan(c, p.span, grid);
   p.flags = flags & 0xFFFFu;        // SC_TICK_DENSE_AABBS == kFlagDenseAabbs
   if (c->levelOffsets.size() > 1 && (flags & SC_TICK_XFORM)) p.flags |= kFlagHasDeep;
+  if (flags & SC_TICK_TRIGGERS) p.flags |= kFlagTriggers;      // (likewise: bit 17 is kFlagDeferredReset's position)
   if (flags & SC_TICK_OVERLAPS) p.flags |= kFlagOverlaps;      // (the public bit is one of the internal ones' positions: it travels as a bit of its own)
   // The fused kernel's workgroups end the tick for their own spans (spanTail) when the world is span-closed, no level kernel reads `dirty`
   // behind the fused kernel, and the tick's producer is none or the root nudge.  The movers' producer stays in the end-of-tick kernel
@@ -796,9 +806,19 @@ const char* pendingShapeReader(const ScTickContext* c)
          return fail(c, (std::string(what " is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that ") + reads + \
                          ": its pair half reads the matrices and colliders as they stand").c_str()); } while (0)
 
+// Trigger volumes: "nothing remembered" is a per-volume word, reset here by the host -- outside any captured graph -- behind whatever is
+// queued: the next flagged tick is a resync tick for every volume.
+bool resyncTriggers(ScTickContext* c)
+{
+  if (!c->triggers.count) return true;
+  const hipError_t e = hipMemsetAsync(c->triggers.remembered, 0xFF, (size_t)c->triggers.count * sizeof(uint32_t), c->stream);
+  return e == hipSuccess ? true : fail(c, "hipMemsetAsync (trigger volumes)", e);
+}
+
 // (touch events remember pairs by the same ids: they are forgotten in the same places, by the same call)
 bool resyncPairEvents(ScTickContext* c)
 {
+  if (!resyncTriggers(c)) return false;               // (trigger volumes remember members by the same ids: forgotten in the same places)
   if (c->pairEventSlab) {
     const hipError_t e = hipMemsetAsync(c->pairEventSlab, 0, c->pairEventSlabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair events)", e);
@@ -1058,6 +1078,8 @@ bool enqueueStages(ScTickContext* c, const TickPlan& plan, bool inCapture)
   if (path.pairsNow && (flags & SC_TICK_SWEEPS)) launchSweepQueries(ds, p, c->sweeps, exactSweepInfo(c), c->stream);
   // (overlap queries: scTickRun refuses them in a split flow, so this is their one launch site -- the pair half never sees the flag)
   if (path.pairsNow && (flags & kFlagOverlaps)) launchOverlapQueries(ds, p, c->overlaps, c->overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
+  // (trigger volumes: refused in a split flow like the overlap queries -- their one launch site; whether they run is the plan's word)
+  if (plan.triggers) launchTriggerVolumes(ds, p, c->triggers, c->triggerShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
@@ -1869,6 +1891,17 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
     }
     if (changed && !h2d(c, const_cast<uint2*>(c->anchored.anchor), c->hAnchor.data(), (size_t)c->anchored.count * sizeof(uint2))) return 0;
   }
+  if (c->triggers.count) {                              // ... and so do the trigger volumes' anchors (their remembered rows went with resyncPairEvents above)
+    bool changed = false;
+    for (uint32_t k = 0; k < c->triggers.count; ++k) {
+      uint32_t& a = c->hTriggerAnchor[k].x;
+      if (a >= n0) continue;
+      if (removed.count(a)) { a = kAnchorDead; changed = true; continue; }
+      const auto m = newIndexOf.find(a);
+      if (m != newIndexOf.end()) { a = m->second; changed = true; }
+    }
+    if (changed && !h2d(c, const_cast<uint2*>(c->triggers.anchor), c->hTriggerAnchor.data(), (size_t)c->triggers.count * sizeof(uint2))) return 0;
+  }
   {
     // bounds classes: the wave-tiles that took a relocated entity, and those of the shrunk tail
     std::vector<uint32_t> tiles;
@@ -2090,7 +2123,7 @@ static bool worldCanPair(ScTickContext* c)
 static bool quietTick(ScTickContext* c, uint32_t flags)
 {
   constexpr uint32_t kBinReaders = SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_PAIR_EVENTS | SC_TICK_PAIR_SHAPES |
-                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS | SC_TICK_OVERLAPS;
+                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS;
   if (!(flags & SC_TICK_BROADPHASE) || (flags & kBinReaders) || !c->quietEnabled || !c->homeEnabled || !c->lazyEnabled) return false;
   if (!c->n || c->sensors || c->neighbourMask || c->pairsStream || c->pairsPending) return false;
   if (!c->homeValid || c->homeEpoch != c->topoEpoch) return false;      // (a learn tick is due: an append, a remove, a re-link, a layer upload)
@@ -2132,6 +2165,13 @@ static bool tickAccepted(ScTickContext* c, uint32_t flags)
     if (c->neighbourMask) return fail(c, "SC_TICK_OVERLAPS cannot run on a context with neighbours (scTickSetTile): overlap queries do not cover tiles");
     if (c->pairsStream) return fail(c, "SC_TICK_OVERLAPS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): overlap queries do not cover tiles");
     if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_OVERLAPS cannot run with SC_TICK_SPLIT_PAIRS: overlap queries do not cover tiles");
+  }
+  if (flags & SC_TICK_TRIGGERS) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_TRIGGERS needs SC_TICK_BROADPHASE in the same run (the volumes read this tick's bins)");
+    if (!c->triggers.count) return fail(c, "SC_TICK_TRIGGERS needs scTickSetTriggerVolumes first (the set is empty)");
+    if (c->neighbourMask) return fail(c, "SC_TICK_TRIGGERS cannot run on a context with neighbours (scTickSetTile): trigger volumes do not cover tiles");
+    if (c->pairsStream) return fail(c, "SC_TICK_TRIGGERS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): trigger volumes do not cover tiles");
+    if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_TRIGGERS cannot run with SC_TICK_SPLIT_PAIRS: trigger volumes do not cover tiles");
   }
   if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");      // (an empty context's run stages a frame too)
   if (nothingToRun(c, flags)) return true;
@@ -2190,7 +2230,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
     const bool hostBetweenHalves = (run & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (!plan.learn && c->lazyEnabled && !(run & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    p.lazy = (!plan.learn && c->lazyEnabled && !(run & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
     // records of entities that did not move stay as they are, unless something else changed boxes since the last tick
@@ -2204,6 +2244,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   plan.compactG = (alone && c->wideCompact) ? compactWideGroup(p, plan.grid, c->compactForceG) : 0u;
   if (path.needCompact) compactLaunchShape(plan.grid, path.pairsNow, plan.compactG, plan.rec.compact);
   plan.rec.frame[0] = path.items; plan.rec.frame[1] = path.block;
+  plan.triggers = path.pairsNow && (p.flags & kFlagTriggers) != 0u;
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2264,6 +2305,7 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   LastWith& w = c->lastWith;
   if (with & SC_TICK_BIND_RUNS) { w.bindTouchWords = c->bind.touchWords; w.bindEmpty = nothingToRun(c, rec.flags); }
   if (with & SC_TICK_OVERLAPS) { w.overlapCount = c->overlaps.count; w.overlapMaxHits = c->overlaps.maxHits; w.overlapShapes = c->overlapShapes; }
+  if (with & SC_TICK_TRIGGERS) { w.triggerCount = c->triggers.count; w.triggerMaxMembers = c->triggers.maxMembers; w.triggerMaxEvents = c->triggers.maxEvents; }
   if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
   if (with & SC_TICK_PAIR_SHAPES) { w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; }
 }
@@ -2978,6 +3020,172 @@ int scTickReadOverlapHits(ScTickContext* c, uint32_t* counts, uint32_t* ids, uin
     info->truncated_queries = truncated; info->refined = (uint32_t)std::min<uint64_t>(refined, 0xFFFFFFFFull);
     info->kept_as_boxes = (uint32_t)std::min<uint64_t>(kept, 0xFFFFFFFFull); info->shapes = c->lastWith.overlapShapes; info->pad = 0u;
   }
+  return 1;
+}
+
+int scTickSetTriggerVolumes(ScTickContext* c, uint32_t count, const uint32_t* anchor, const uint8_t* type, const float* localMat16, const float* halfExtents3,
+                            const float* radius, const float* halfHeight, const uint32_t* mask, const uint8_t* skipSelf, uint32_t maxMembers,
+                            uint32_t maxEvents, uint32_t shapes)
+{
+  static_assert(sizeof(ScTickTriggerInfo) == 8u * sizeof(uint32_t), "ScTickTriggerInfo is eight words");
+  static_assert(kTriggerRowCap == SC_TICK_TRIGGER_MAX_MEMBERS, "the trigger row caps differ");
+  if (!c) return 0;
+  if (count && (!anchor || !type || !localMat16 || !halfExtents3 || !radius || !halfHeight || !mask)) return fail(c, "null argument");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (shapes != SC_TICK_OVERLAP_SHAPES_AABB && shapes != SC_TICK_OVERLAP_SHAPES_EXACT) return fail(c, "trigger volumes: unknown shape mode (SC_TICK_OVERLAP_SHAPES_*)");
+  if (count && !maxMembers) return fail(c, "trigger volumes: max_members must be at least 1");
+  if (maxMembers > kTriggerRowCap) return fail(c, "trigger volumes: max_members exceeds SC_TICK_TRIGGER_MAX_MEMBERS (a wave's two rows fit its LDS)");
+  if ((uint64_t)count * maxMembers > 0x3FFFFFFFull) return fail(c, "trigger volumes: count * max_members does not fit (at most 2^30 - 1 id slots)");
+  if (maxEvents > (1u << 27)) return fail(c, "trigger volumes: at most 2^27 events per list");
+  // the kernel never sees a value it has no answer for: checked before anything changes, so a refused call leaves the previous set in place
+  std::vector<float4> v((size_t)count * kOverlapVolumeWords);
+  std::vector<uint2> an(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const float* m = localMat16 + 16u * (size_t)i;            // column-major: m[col * 4 + row]
+    const uint8_t t = type[i];
+    if (t != SC_TICK_COLLIDER_BOX && t != SC_TICK_COLLIDER_SPHERE && t != SC_TICK_COLLIDER_CAPSULE)
+      return fail(c, "trigger volumes: a volume's type is SC_TICK_COLLIDER_BOX, _SPHERE or _CAPSULE");
+    const float he[3] = { halfExtents3[3 * (size_t)i], halfExtents3[3 * (size_t)i + 1], halfExtents3[3 * (size_t)i + 2] };
+    const float values[5] = { he[0], he[1], he[2], radius[i], halfHeight[i] };
+    bool finite = true;
+    for (float x : values) finite = finite && std::isfinite(x);
+    for (int col = 0; col < 4; ++col) for (int row = 0; row < 3; ++row) finite = finite && std::isfinite(m[col * 4 + row]);
+    if (!finite) return fail(c, "trigger volumes: local_mat16, half_extents, radius and half_height must be finite");
+    float4* q = &v[(size_t)i * kOverlapVolumeWords];
+    for (int row = 0; row < 3; ++row) q[row] = make_float4(m[row], m[4 + row], m[8 + row], m[12 + row]);
+    const float hh = halfHeight[i] < 0.0f ? 0.0f : halfHeight[i];      // the record as scTickUploadColliders stores it
+    q[3] = t == SC_TICK_COLLIDER_BOX ? make_float4(he[0], he[1], he[2], 0.0f)
+         : t == SC_TICK_COLLIDER_SPHERE ? make_float4(0.0f, 0.0f, 0.0f, radius[i]) : make_float4(0.0f, hh, 0.0f, radius[i]);
+    const uint32_t words[4] = { t, mask[i], 0u, 0u };
+    std::memcpy(&q[4], words, sizeof words);
+    an[i] = make_uint2(anchor[i], skipSelf ? (skipSelf[i] ? 1u : 0u) : 1u);
+  }
+  if (!bind(c)) return 0;
+  TriggerState& t = c->triggers;
+  // The same count, max_members, max_events and mode as the current set: only anchors, locals and values are rewritten, behind whatever is
+  // queued -- the remembered rows stay, no epoch bump, so no learn tick, and a captured graph (which holds the buffers, the sizes and
+  // the kernel instance) stays valid.
+  const uint32_t perVolume = count ? maxMembers : 0u, events = count ? maxEvents : 0u;
+  if (count != t.count || perVolume != t.maxMembers || events != t.maxEvents || shapes != c->triggerShapes) {
+    if (!sync(c)) return 0;
+    const size_t slots = (size_t)count * perVolume;
+    auto empty = [&] {
+      dfree(c, t.ids); dfree(c, t.entered); dfree(c, t.exited); dfree(c, t.ctl);
+      t.ids = nullptr; t.entered = t.exited = nullptr; t.ctl = nullptr;
+      c->triggerIdCap = 0; c->triggerEventCap = 0; t.count = 0; t.maxMembers = 0; t.maxEvents = 0;
+    };
+    if (!count) empty();                                       // count 0 clears the set AND frees it (growBatch below keeps the per-volume arrays' capacity)
+    else {
+      if (slots > c->triggerIdCap) {                           // the id rows: kept within their capacity, allocated anew beyond it
+        dfree(c, t.ids); t.ids = nullptr; c->triggerIdCap = 0;
+        if (!dalloc(c, t.ids, std::max<size_t>(slots, 1024u))) { empty(); return 0; }
+        c->triggerIdCap = std::max<size_t>(slots, 1024u);
+      }
+      if (events > c->triggerEventCap || !t.entered) {
+        dfree(c, t.entered); dfree(c, t.exited); t.entered = t.exited = nullptr; c->triggerEventCap = 0;
+        const size_t room = std::max<size_t>(events, 64u);
+        if (!dalloc(c, t.entered, room) || !dalloc(c, t.exited, room)) { empty(); return 0; }
+        c->triggerEventCap = (uint32_t)room;
+      }
+      if (!t.ctl && !dalloc(c, t.ctl, 2u)) { empty(); return 0; }
+    }
+    if (!growBatch(c, c->triggerCap, t.count, count, batchArray(t.local, false, kOverlapVolumeWords), batchArray(t.anchor), batchArray(t.world, true, 3),
+                   batchArray(t.counts, true), batchArray(t.remembered, true), batchArray(t.stat, true))) { empty(); return 0; }
+    if (!count) {                                              // freed, not kept: a context that clears its set holds nothing for it
+      dfree(c, const_cast<float4*>(t.local)); dfree(c, const_cast<uint2*>(t.anchor)); dfree(c, t.world); dfree(c, t.counts); dfree(c, t.remembered); dfree(c, t.stat);
+      t = TriggerState{}; c->triggerCap = 0;
+    }
+    t.maxMembers = perVolume; t.maxEvents = events;
+    c->triggerShapes = shapes;
+    c->hTriggerAnchor = an;
+    if (!resyncTriggers(c)) return 0;                          // a re-sized set remembers nothing
+  } else c->hTriggerAnchor = an;
+  if (!count) return 1;
+  if (!h2d(c, const_cast<float4*>(t.local), v.data(), v.size() * sizeof(float4)) ||
+      !h2d(c, const_cast<uint2*>(t.anchor), an.data(), an.size() * sizeof(uint2))) return 0;
+  return sync(c) ? 1 : 0;
+}
+
+// the gate of the trigger readers: the last run carried the flag and the set is the size that run answered
+static bool triggerResult(ScTickContext* c)
+{
+  const TriggerState& t = c->triggers;
+  const bool stands = t.count == c->lastWith.triggerCount && t.maxMembers == c->lastWith.triggerMaxMembers && t.maxEvents == c->lastWith.triggerMaxEvents;
+  return bind(c) && lastRunResult(c, SC_TICK_TRIGGERS, "the last scTickRun did not request SC_TICK_TRIGGERS", true, nullptr,
+                                  "trigger results are ready after scTickRunPairs", stands,
+                                  "the trigger set was re-sized since the last run with SC_TICK_TRIGGERS: its results are gone");
+}
+
+// the report: sums of the per-volume words the waves wrote (no wave adds to a shared word per hit)
+static bool triggerInfo(ScTickContext* c, ScTickTriggerInfo* info, std::vector<uint32_t>* countsOut)
+{
+  const TriggerState& t = c->triggers;
+  std::vector<uint32_t> counts(t.count);
+  std::vector<uint4> stat(t.count);
+  if (!d2h(c, counts.data(), t.counts, (size_t)t.count * sizeof(uint32_t)) || !d2h(c, stat.data(), t.stat, (size_t)t.count * sizeof(uint4)) || !sync(c)) return false;
+  if (info) {
+    uint64_t members = 0, entered = 0, exited = 0; uint32_t resync = 0, overflow = 0;
+    for (uint32_t n : counts) members += n;
+    for (const uint4& s : stat) { entered += s.x; exited += s.y; resync += (s.z & kTriggerResync) ? 1u : 0u; overflow += (s.z & kTriggerOverflow) ? 1u : 0u; }
+    info->volumes = t.count; info->max_members = t.maxMembers; info->members = (uint32_t)std::min<uint64_t>(members, 0xFFFFFFFFull);
+    info->entered = (uint32_t)std::min<uint64_t>(entered, 0xFFFFFFFFull); info->exited = (uint32_t)std::min<uint64_t>(exited, 0xFFFFFFFFull);
+    info->resync_volumes = resync; info->overflow_volumes = overflow;
+    info->events_truncated = (entered > t.maxEvents || exited > t.maxEvents) ? 1u : 0u;
+  }
+  if (countsOut) countsOut->swap(counts);
+  return true;
+}
+
+int scTickReadTriggerEvents(ScTickContext* c, uint32_t* entered2, uint32_t enteredCap, uint32_t* exited2, uint32_t exitedCap, ScTickTriggerInfo* info)
+{
+  if (!c) return 0;
+  if (!triggerResult(c)) return 0;
+  const TriggerState& t = c->triggers;
+  ScTickTriggerInfo sums;
+  if (!triggerInfo(c, &sums, nullptr)) return 0;
+  const uint32_t in = entered2 ? std::min(std::min(sums.entered, t.maxEvents), enteredCap) : 0u;
+  const uint32_t out = exited2 ? std::min(std::min(sums.exited, t.maxEvents), exitedCap) : 0u;
+  if (in && !d2h(c, entered2, t.entered, (size_t)in * sizeof(uint2))) return 0;
+  if (out && !d2h(c, exited2, t.exited, (size_t)out * sizeof(uint2))) return 0;
+  if ((in || out) && !sync(c)) return 0;
+  if (info) *info = sums;
+  return 1;
+}
+
+int scTickReadTriggerMembers(ScTickContext* c, uint32_t* counts, uint32_t* ids, uint32_t volumeCapacity, ScTickTriggerInfo* info)
+{
+  if (!c) return 0;
+  if (!triggerResult(c)) return 0;
+  const TriggerState& t = c->triggers;
+  ScTickTriggerInfo sums;
+  std::vector<uint32_t> perVolume;
+  if (!triggerInfo(c, &sums, &perVolume)) return 0;
+  const uint32_t take = std::min(t.count, volumeCapacity);
+  if (take && ids && (!d2h(c, ids, t.ids, (size_t)take * t.maxMembers * sizeof(uint32_t)) || !sync(c))) return 0;
+  if (take && counts) std::memcpy(counts, perVolume.data(), (size_t)take * sizeof(uint32_t));
+  if (info) *info = sums;
+  return 1;
+}
+
+int scTickReadTriggerMatrices(ScTickContext* c, uint32_t first, uint32_t count, float* mat16)
+{
+  if (!c) return 0;
+  if (count && !mat16) return fail(c, "null argument");
+  if (!triggerResult(c)) return 0;
+  if ((uint64_t)first + count > c->triggers.count) return fail(c, "range exceeds the trigger volume count");
+  if (!count) return 1;
+  std::vector<float> rows((size_t)count * 12u);
+  if (!d2h(c, rows.data(), c->triggers.world + 3u * (size_t)first, rows.size() * sizeof(float)) || !sync(c)) return 0;
+  for (uint32_t k = 0; k < count; ++k) rowsToMat4(&rows[12u * (size_t)k], mat16 + 16u * (size_t)k);
+  return 1;
+}
+
+int scTickReadTriggerVolumes(ScTickContext* c, uint32_t first, uint32_t count, uint32_t* anchor)
+{
+  if (!c) return 0;
+  if (count && !anchor) return fail(c, "null argument");
+  if ((uint64_t)first + count > c->triggers.count) return fail(c, "range exceeds the trigger volume count");
+  for (uint32_t k = 0; k < count; ++k) anchor[k] = c->hTriggerAnchor[first + k].x;      // (host mirror: no read-back)
   return 1;
 }
 

@@ -317,6 +317,7 @@ constexpr uint32_t kFlagDeferredReset = 1u << 17;   // pipelined tiles: a pair k
 constexpr uint32_t kFlagDenseAabbs = 1u << 5; // == SC_TICK_DENSE_AABBS
 constexpr uint32_t kFlagOverlaps = 1u << 19;    // SC_TICK_OVERLAPS as TickParams::flags carries it: the public flag is bit 16, kFlagHasDeep's position, and only
                                                 // the low 16 public bits are copied into the word (fillParams) -- no kernel looks at this bit, the launch list does
+constexpr uint32_t kFlagTriggers = 1u << 21;    // SC_TICK_TRIGGERS (public bit 17, kFlagDeferredReset's position) likewise: the launch list looks at it, no kernel does
 constexpr uint32_t kFlagTopoClasses = 1u << 20;     // every wave-tile of the world is classed and the classes are current: the fused kernel without binning takes
                                                     // its classed instance (no link word is read: xformCullClassed)
 constexpr uint32_t kFlagTailOwnsDirty = 1u << 18;   // span-closed world: every workgroup of the fused kernel ends the tick for its own span (dirty clear, and the
@@ -378,6 +379,27 @@ struct OverlapQueryState {
 };
 // exact (SC_TICK_OVERLAP_SHAPES_EXACT): the instance that asks the touching pairs' routines about a refinable candidate -- chosen on the host
 void launchOverlapQueries(const DeviceState& d, const TickParams& p, const OverlapQueryState& q, bool exact, hipStream_t s);
+// ---- trigger volumes (include/sc_tick.h "trigger volumes"): overlap volumes given in an entity's local frame, resolved against this tick's
+// world matrix of that entity by the kernel that answers them, which also forms the difference against the row it remembers.  A kernel
+// argument of their own.  Volume v is kOverlapVolumeWords 16-byte words like an overlap query's -- rows 0..2 of its LOCAL matrix, its
+// collider record, (type, mask, 0, 0) -- plus its (anchor, skip_self) word.  ONE id row per volume in device memory: it is the member row
+// the readers see and the remembered row the next flagged tick diffs against; remembered[v] says how many of its slots are remembered.
+constexpr uint32_t kTriggerRowCap = 1024;        // == SC_TICK_TRIGGER_MAX_MEMBERS: two rows of 4 KB per wave in LDS while diffing
+constexpr uint32_t kTriggerNone = 0xFFFFFFFFu;   // remembered[v]: nothing is remembered for the volume (the next flagged tick resyncs it)
+constexpr uint32_t kTriggerResync = 1u, kTriggerOverflow = 2u;      // stat[v].z bits
+struct TriggerState {
+  const float4* local;      // [count][kOverlapVolumeWords]
+  const uint2* anchor;      // [count] (dense index | kAnchorNone | kAnchorDead, skip_self)
+  float4* world;            // [count][3] the resolved rows of the last flagged run (NaN rows: a volume without members by the resolve)
+  uint32_t* counts;         // [count] the true number of members per volume
+  uint32_t* ids;            // [count][maxMembers] the member row = the remembered row
+  uint32_t* remembered;     // [count] slots of the row that are remembered, or kTriggerNone.  Reset by the HOST, outside any captured graph
+  uint4* stat;              // [count] (entered, exited, kTrigger* bits, 0) per volume: the report's sums are the reader's
+  uint32_t* ctl;            // [2] event slots reserved this tick (entered, exited): one atomic per list per wave that has events
+  uint2* entered; uint2* exited;     // [maxEvents] each: (volume, id)
+  uint32_t count, maxMembers, maxEvents;
+};
+void launchTriggerVolumes(const DeviceState& d, const TickParams& p, const TriggerState& t, bool exact, hipStream_t s);
 // ---- entity-anchored rays (include/sc_tick.h "entity-anchored rays"): given in an entity's local frame, resolved against this tick's
 // world matrix of that entity by the kernel that casts them.  A kernel argument of their own, like the sweeps'. ----
 constexpr uint32_t kAnchorNone = 0xFFFFFFFFu;    // == SC_TICK_ANCHOR_NONE: origin and direction are world space

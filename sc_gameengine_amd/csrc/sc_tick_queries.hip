@@ -755,6 +755,230 @@ __global__ __launch_bounds__(kTile) void k_overlap_queries(const DeviceState d, 
   }
 }
 
+// ---- trigger volumes (own spec, include/sc_tick.h "trigger volumes") -----------------------------------------------------------
+// An overlap volume in an entity's local frame, and the tick-to-tick difference of its answer: what the anchored rays are to the rays.
+// One wave per volume.  The volume index is made scalar, so the local matrix, the anchor word and the twelve words of the anchor's matrix
+// rows come through the scalar path, as in k_anchored_rays.  The wave
+//   1. resolves M = W * L (fp32, unfused, left to right; kAnchorNone: M = L untouched) and notes the rows for the reader; an anchor beyond
+//      the entity count or a non-finite entry among the twelve: no members this tick, the rows noted as quiet NaNs;
+//   2. walks sectors, big list and overflow list by k_overlap_queries' rules -- A SECOND COPY OF THAT LOOP, kept apart so that the
+//      overlap kernels' instruction streams stay what they were -- collecting its row in LDS;
+//   3. fetches the row it remembers (the volume's row in device memory, TriggerState::remembered slots of it) into LDS beside it;
+//   4. forms entered = new \ old and exited = old \ new by chunked compares: a lane holds one id of one row and reads the other row
+//      four ids per 16-byte LDS read, every lane the same address (a broadcast, no bank conflict); an id that is an event gets bit 31
+//      (no id has it: ranks are below 128) so that nothing is compared twice;
+//   5. reserves its slots of the two event lists with ONE atomic per list, and only when it has events (no per-hit
+//      additions to a shared word; a steady world adds nothing at all), and writes (volume, id) pairs into the slots below maxEvents;
+//   6. overwrites its row in device memory -- the member row the readers see IS the remembered row -- and its per-volume words: the true
+//      count, the slots remembered (kTriggerNone after an overflow), (entered, exited, resync / overflow bits).
+// No pointer is swapped and no state lives outside the volume's own words, so one captured graph replays every tick.
+template <bool kExact>
+__global__ __launch_bounds__(kTile) void k_trigger_volumes(const DeviceState d, const TickParams p, const TriggerState t)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t triggerRows[];      // [kTile / 64][2][stride]
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
+  if (r >= t.count) return;
+  const uint32_t stride = (t.maxMembers + 3u) & ~3u;                          // rows start on 16 bytes and are read four ids at a time
+  uint32_t* rowNew = triggerRows + (size_t)(threadIdx.x >> 6) * 2u * stride;
+  uint32_t* rowOld = rowNew + stride;
+
+  // 1. resolve
+  const float4* vol = t.local + (size_t)kOverlapVolumeWords * r;
+  const float4 l0 = vol[0], l1 = vol[1], l2 = vol[2], word = vol[4];
+  const uint2 an = t.anchor[r];
+  float4 r0 = l0, r1 = l1, r2 = l2;
+  bool alive = true;
+  uint32_t skipId = 0xFFFFFFFFu;
+  if (an.x != kAnchorNone) {
+    alive = an.x < p.n;
+    if (alive) {
+      const float4 w[3] = { d.w0[an.x], d.w1[an.x], d.w2[an.x] };
+      float4 m[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        m[k].x = (w[k].x * l0.x + w[k].y * l1.x) + w[k].z * l2.x;
+        m[k].y = (w[k].x * l0.y + w[k].y * l1.y) + w[k].z * l2.y;
+        m[k].z = (w[k].x * l0.z + w[k].y * l1.z) + w[k].z * l2.z;
+        m[k].w = ((w[k].x * l0.w + w[k].y * l1.w) + w[k].z * l2.w) + w[k].w;
+      }
+      r0 = m[0]; r1 = m[1]; r2 = m[2];
+      if (an.y) skipId = p.rankBits | an.x;                                   // the carrier never answers
+    }
+  }
+  alive = alive && isfinite(r0.x) && isfinite(r0.y) && isfinite(r0.z) && isfinite(r0.w) && isfinite(r1.x) && isfinite(r1.y) && isfinite(r1.z) &&
+          isfinite(r1.w) && isfinite(r2.x) && isfinite(r2.y) && isfinite(r2.z) && isfinite(r2.w);
+  if (!alive) { const float q = __uint_as_float(0x7FC00000u); r0 = r1 = r2 = make_float4(q, q, q, q); }
+  if (lane == 0) { float4* out = t.world + 3u * (size_t)r; out[0] = r0; out[1] = r1; out[2] = r2; }
+
+  Member mv;
+  mv.s = vol[3]; mv.type = __float_as_uint(word.x);
+  mv.c[0][0] = r0.x; mv.c[0][1] = r1.x; mv.c[0][2] = r2.x;
+  mv.c[1][0] = r0.y; mv.c[1][1] = r1.y; mv.c[1][2] = r2.y;
+  mv.c[2][0] = r0.z; mv.c[2][1] = r1.z; mv.c[2][2] = r2.z;
+  mv.T[0] = r0.w; mv.T[1] = r1.w; mv.T[2] = r2.w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) mv.n[k] = dot3(mv.c[k], mv.c[k]);
+  mv.ok = mv.n[0] > 0.0f && mv.n[1] > 0.0f && mv.n[2] > 0.0f && isfinite(mv.n[0]) && isfinite(mv.n[1]) && isfinite(mv.n[2]);
+  const uint32_t mask = __float_as_uint(word.y);
+  float vmn[3], vmx[3];
+  memberAabb(mv, vmn, vmx);
+
+  // 2. the walk (k_overlap_queries' loop; a volume without members has a NaN box: no sector, and the lists are not looked at either)
+  const float fx0 = floorf(vmn[0] * p.invSector) - p.binOx, fx1 = floorf(vmx[0] * p.invSector) - p.binOx;
+  const float fz0 = floorf(vmn[2] * p.invSector) - p.binOz, fz1 = floorf(vmx[2] * p.invSector) - p.binOz;
+  const float gridX = (float)p.binSX - 1.0f, gridZ = (float)p.binSZ - 1.0f;
+  uint32_t gx0 = 0u, gz0 = 0u, width = 0u, nSec = 0u;
+  if (p.binSX && fx1 >= 0.0f && fz1 >= 0.0f && fx0 <= gridX && fz0 <= gridZ) {
+    gx0 = (uint32_t)(fx0 < 0.0f ? 0.0f : fx0); gz0 = (uint32_t)(fz0 < 0.0f ? 0.0f : fz0);
+    const uint32_t gx1 = (uint32_t)(fx1 > gridX ? gridX : fx1), gz1 = (uint32_t)(fz1 > gridZ ? gridZ : fz1);
+    width = gx1 - gx0 + 1u;
+    nSec = width * (gz1 - gz0 + 1u);
+  }
+  const uint32_t ctr = kCtrPar + 8u * p.parity;
+  const uint32_t nbig = alive ? min(d.counters[ctr + kCtrBig], p.bigCap) : 0u, nspill = alive ? min(d.counters[ctr + kCtrSpill], p.ovfCap) : 0u;
+  const uint32_t bigEnd = nSec + (nbig + 63u) / 64u, spillChunks = (nspill + 63u) / 64u;
+  bool anyOverflow = false;
+  uint32_t total = 0u;                                  // (wave-uniform)
+  uint32_t gx = gx0, gz = gz0;
+  for (uint32_t k = 0; k < bigEnd + (anyOverflow ? spillChunks : 0u); ++k) {
+    float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = lo;
+    bool have = false, bySector = false;
+    uint32_t sx = 0u, sz = 0u;
+    if (k < nSec) {
+      const uint32_t s = gz * p.binSX + gx;
+      uint32_t n = d.binCount[s];
+      if (n > kBinCap) { n = kBinCap; anyOverflow = true; }
+      have = lane < n; bySector = true; sx = gx; sz = gz;
+      if (have) { const float4* rec = d.bins + 2u * ((size_t)s * kBinCap + lane); lo = rec[0]; hi = rec[1]; }
+      if (++gx == gx0 + width) { gx = gx0; ++gz; }
+    } else if (k < bigEnd) {
+      const uint32_t b = (k - nSec) * 64u + lane;
+      have = b < nbig;
+      if (have) { lo = d.bigList[2u * (size_t)b]; hi = d.bigList[2u * (size_t)b + 1u]; }
+    } else {
+      const uint32_t e = (k - bigEnd) * 64u + lane;
+      have = e < nspill; bySector = true;
+      if (have) {
+        lo = d.spill[2u * (size_t)e]; hi = d.spill[2u * (size_t)e + 1u];
+        const uint32_t s = d.spillSector[e];
+        sx = s % p.binSX; sz = s / p.binSX;
+      }
+    }
+    const uint32_t lay = __float_as_uint(lo.w);
+    const uint32_t id = __float_as_uint(hi.w) & ~kPrimary;
+    bool hit = have && ((lay & 0xFFFFu) & mask) != 0u && (lay >> 16) != 0u && id != skipId &&
+               lo.x <= vmx[0] && vmn[0] <= hi.x && lo.y <= vmx[1] && vmn[1] <= hi.y && lo.z <= vmx[2] && vmn[2] <= hi.z;
+    if (bySector) {
+      const float lx = lo.x > vmn[0] ? lo.x : vmn[0], lz = lo.z > vmn[2] ? lo.z : vmn[2];
+      hit = hit && (floorf(lx * p.invSector) - p.binOx) == (float)sx && (floorf(lz * p.invSector) - p.binOz) == (float)sz;
+    }
+    if constexpr (kExact) {
+      if (hit) {
+        const Member m = fetchMember(d, id, p.n, p.rankBits);
+        if (m.ok && mv.ok) {
+          const bool boxA = m.type == kColliderBox, boxB = mv.type == kColliderBox;
+          bool apart;
+          if (boxA && boxB) apart = boxBoxApart(m, mv);
+          else if (boxA) apart = roundBoxApart(mv, m);
+          else if (boxB) apart = roundBoxApart(m, mv);
+          else apart = roundRoundApart(m, mv);
+          hit = !apart;
+        }
+      }
+    }
+    const unsigned long long hm = ballot64(hit);
+    if (hit) {
+      const uint32_t at = total + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
+      if (at < t.maxMembers) rowNew[at] = id;
+    }
+    total += (uint32_t)__popcll(hm);
+  }
+
+  // 3. the remembered row beside the new one, both padded to whole 16-byte reads with a word no id equals
+  const uint32_t rem = t.remembered[r];
+  const bool overflow = total > t.maxMembers, resync = rem == kTriggerNone;
+  const uint32_t nNew = overflow ? t.maxMembers : total;
+  const uint32_t nOld = (resync || overflow) ? 0u : (rem < t.maxMembers ? rem : t.maxMembers);
+  uint32_t* row = t.ids + (size_t)r * t.maxMembers;
+  for (uint32_t i = lane; i < ((nOld + 3u) & ~3u); i += 64u) rowOld[i] = i < nOld ? row[i] : 0xFFFFFFFFu;
+  if (lane < 3u && nNew + lane < ((nNew + 3u) & ~3u)) rowNew[nNew + lane] = 0xFFFFFFFFu;
+  __builtin_amdgcn_wave_barrier();
+
+  // 4. the two differences (an overflowing volume has no events; a resync tick enters its whole row)
+  uint32_t entered = 0u, exited = 0u;
+  if (!overflow) {
+    for (uint32_t base = 0; base < nNew; base += 64u) {
+      const uint32_t i = base + lane;
+      const bool in = i < nNew;
+      const uint32_t x = in ? rowNew[i] : 0u;
+      bool found = false;
+      for (uint32_t j = 0; j < nOld; j += 4u) {
+        const uint4 o = *reinterpret_cast<const uint4*>(rowOld + j);
+        found = found || o.x == x || o.y == x || o.z == x || o.w == x;
+      }
+      const bool ev = in && !found;
+      if (ev) rowNew[i] = x | kPrimary;
+      entered += (uint32_t)__popcll(ballot64(ev));
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t base = 0; base < nOld; base += 64u) {
+      const uint32_t i = base + lane;
+      const bool in = i < nOld;
+      const uint32_t x = in ? rowOld[i] : 0u;
+      bool found = false;
+      for (uint32_t j = 0; j < nNew; j += 4u) {
+        const uint4 o = *reinterpret_cast<const uint4*>(rowNew + j);
+        found = found || (o.x & ~kPrimary) == x || (o.y & ~kPrimary) == x || (o.z & ~kPrimary) == x || (o.w & ~kPrimary) == x;
+      }
+      const bool ev = in && !found;
+      if (ev) rowOld[i] = x | kPrimary;
+      exited += (uint32_t)__popcll(ballot64(ev));
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    // 5. the event slots: one reservation per list, the marked ids behind it
+    uint32_t baseIn = 0u, baseOut = 0u;
+    if (lane == 0) {
+      if (entered) baseIn = atomicAdd(&t.ctl[0], entered);
+      if (exited) baseOut = atomicAdd(&t.ctl[1], exited);
+    }
+    baseIn = __shfl(baseIn, 0, 64); baseOut = __shfl(baseOut, 0, 64);
+    if (entered) {
+      uint32_t done = 0u;
+      for (uint32_t base = 0; base < nNew; base += 64u) {
+        const uint32_t i = base + lane;
+        const uint32_t x = i < nNew ? rowNew[i] : 0u;
+        const bool ev = (x & kPrimary) != 0u;
+        const unsigned long long em = ballot64(ev);
+        const uint32_t at = baseIn + done + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
+        if (ev && at < t.maxEvents) t.entered[at] = make_uint2(r, x & ~kPrimary);
+        done += (uint32_t)__popcll(em);
+      }
+    }
+    if (exited) {
+      uint32_t done = 0u;
+      for (uint32_t base = 0; base < nOld; base += 64u) {
+        const uint32_t i = base + lane;
+        const uint32_t x = i < nOld ? rowOld[i] : 0u;
+        const bool ev = (x & kPrimary) != 0u;
+        const unsigned long long em = ballot64(ev);
+        const uint32_t at = baseOut + done + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
+        if (ev && at < t.maxEvents) t.exited[at] = make_uint2(r, x & ~kPrimary);
+        done += (uint32_t)__popcll(em);
+      }
+    }
+  }
+
+  // 6. the row in place, and the volume's words
+  for (uint32_t i = lane; i < nNew; i += 64u) row[i] = rowNew[i] & ~kPrimary;
+  if (lane == 0) {
+    t.counts[r] = total;
+    t.remembered[r] = overflow ? kTriggerNone : nNew;
+    t.stat[r] = make_uint4(entered, exited, overflow ? kTriggerOverflow : (resync ? kTriggerResync : 0u), 0u);
+  }
+}
+
 // ---- the traffic AI's obstacle ray (src/engine/traffic/sc_traffic_ai.cpp:300-345) --------------------------------------------
 // Every agent of the OnRails tier casts one ray per step from 1.7 m ahead of its origin (0.6 m up) along its heading --
 // forward = normalize(sin(yaw), 0, cos(yaw)) with the yaw's sin / cos as the entity's rotation streams hold them (host libm) --
@@ -932,6 +1156,18 @@ void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQu
 void launchOverlapQueries(const DeviceState& d, const TickParams& p, const OverlapQueryState& q, bool exact, hipStream_t s)
 {
   launchWavePerQuery(exact ? k_overlap_queries<true> : k_overlap_queries<false>, q.count, s, d, p, q);
+}
+
+// a wave per volume like the queries above, plus the wave's two rows in LDS: 2 * 4 * roundup4(maxMembers) bytes per wave, 32 KB per
+// workgroup at the row cap; the two slot counters start every tick at zero (inside a captured graph too)
+void launchTriggerVolumes(const DeviceState& d, const TickParams& p, const TriggerState& t, bool exact, hipStream_t s)
+{
+  if (!t.count) return;
+  const uint32_t perBlock = kTile / 64u;
+  const uint32_t stride = (std::min(t.maxMembers, kTriggerRowCap) + 3u) & ~3u;
+  hipMemsetAsync(t.ctl, 0, 2u * sizeof(uint32_t), s);
+  hipLaunchKernelGGL(exact ? k_trigger_volumes<true> : k_trigger_volumes<false>, dim3((t.count + perBlock - 1) / perBlock), dim3(kTile),
+                     perBlock * 2u * stride * sizeof(uint32_t), s, d, p, t);
 }
 
 void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool fromSnapshot, bool exact, hipStream_t s)

@@ -372,6 +372,70 @@ class WorldTick:
             self._ok(self.lib.scTickReadOverlapHits(self.ctx, _u(counts), _u(ids), k, None), "scTickReadOverlapHits")
         return counts[:k].copy(), ids[:k, :mh].copy()
 
+    # ---- trigger volumes: anchored overlap volumes with enter / exit events ----
+    def trigger_volumes(self, anchor, type, local_matrices, half_extents, radius, half_height, mask, skip_self=None, max_members=64,
+                        max_events=1024, shapes=capi.OVERLAP_SHAPES_AABB):
+        """Volumes like overlap_queries' in the local frame of the entities `anchor` (dense indices; capi.ANCHOR_NONE: world space),
+        answered by every run with capi.TRIGGERS against that tick's matrices and boxes, and reported as who entered and who left since
+        the last run with the flag (scTickSetTriggerVolumes).  skip_self: per volume, whether the anchor itself never answers (None: all).
+        A call with the same count, max_members, max_events and mode as the current set keeps what is remembered and costs no learn
+        tick and no graph capture."""
+        an = np.ascontiguousarray(anchor, np.uint32).reshape(-1)
+        k = len(an)
+        t = np.ascontiguousarray(type, np.uint8).reshape(-1)
+        m, he = _c32(local_matrices).reshape(-1, 16), _c32(half_extents).reshape(-1, 3)
+        r, hh = _c32(radius).reshape(-1), _c32(half_height).reshape(-1)
+        mk = np.ascontiguousarray(mask, np.uint32).reshape(-1)
+        sk = None if skip_self is None else np.ascontiguousarray(skip_self, np.uint8).reshape(-1)
+        assert len(t) == k and len(m) == k and len(he) == k and len(r) == k and len(hh) == k and len(mk) == k and (sk is None or len(sk) == k)
+        self._ok(self.lib.scTickSetTriggerVolumes(self.ctx, k, _u(an), t.ctypes.data_as(capi.U8P), _f(m), _f(he), _f(r), _f(hh), _u(mk),
+                                                  None if sk is None else sk.ctypes.data_as(capi.U8P), int(max_members), int(max_events),
+                                                  int(shapes)), "scTickSetTriggerVolumes")
+        self._trigger_volumes, self._trigger_events = k, int(max_events)
+
+    def trigger_info(self):
+        """What the last run's trigger volumes found (scTickReadTriggerMembers): a dict with volumes, max_members, members, entered,
+        exited, resync_volumes, overflow_volumes, events_truncated."""
+        info = capi.TriggerInfo()
+        self._ok(self.lib.scTickReadTriggerMembers(self.ctx, None, None, 0, C.byref(info)), "scTickReadTriggerMembers")
+        return {k: int(getattr(info, k)) for k, _ in capi.TriggerInfo._fields_}
+
+    def trigger_members(self):
+        """(counts [k], ids [k, max_members]) of the last run with capi.TRIGGERS: counts[v] is the true number of members of volume v, the
+        first min(counts[v], max_members) slots of ids[v] hold distinct ids (rank << 24 | dense index) of them, in no particular order."""
+        info = self.trigger_info()
+        k, mm = info["volumes"], info["max_members"]
+        counts, ids = np.zeros(max(k, 1), np.uint32), np.zeros((max(k, 1), max(mm, 1)), np.uint32)
+        if k:
+            self._ok(self.lib.scTickReadTriggerMembers(self.ctx, _u(counts), _u(ids), k, None), "scTickReadTriggerMembers")
+        return counts[:k].copy(), ids[:k, :mm].copy()
+
+    def trigger_events(self):
+        """(entered [e, 2], exited [x, 2]) of the last run with capi.TRIGGERS as (volume, id) pairs in no particular order; when
+        trigger_info()["events_truncated"] is set each list holds max_events of the true entries."""
+        cap = max(getattr(self, "_trigger_events", 0), 1)
+        ent, exi = np.zeros((cap, 2), np.uint32), np.zeros((cap, 2), np.uint32)
+        info = capi.TriggerInfo()
+        self._ok(self.lib.scTickReadTriggerEvents(self.ctx, _u(ent), cap, _u(exi), cap, C.byref(info)), "scTickReadTriggerEvents")
+        room = getattr(self, "_trigger_events", 0)
+        return ent[:min(info.entered, room)].copy(), exi[:min(info.exited, room)].copy()
+
+    def trigger_matrices(self):
+        """[k, 16] column-major: the volumes' world matrices as the last run with capi.TRIGGERS resolved them (NaN: no members by the
+        resolve -- a dead anchor or a non-finite entry)."""
+        k = getattr(self, "_trigger_volumes", 0)
+        out = np.zeros((max(k, 1), 16), np.float32)
+        self._ok(self.lib.scTickReadTriggerMatrices(self.ctx, 0, k, _f(out)), "scTickReadTriggerMatrices")
+        return out[:k].copy()
+
+    def trigger_anchors(self):
+        """The anchors as they stand now: renamed by remove_entities where their entity moved, capi.ANCHOR_DEAD where it was removed."""
+        k = getattr(self, "_trigger_volumes", 0)
+        out = np.zeros(max(k, 1), np.uint32)
+        if k:
+            self._ok(self.lib.scTickReadTriggerVolumes(self.ctx, 0, k, _u(out)), "scTickReadTriggerVolumes")
+        return out[:k].copy()
+
     def occupied(self, pos, radius, mask):
         """isOccupiedWorld for a batch of points (sc_traffic_spawner.cpp:93-116); returns a uint8 array."""
         p, r = _c32(pos).reshape(-1, 3), _c32(radius).reshape(-1)
