@@ -66,6 +66,7 @@ enum {
   SC_TICK_TOUCH_EVENTS = 1u << 15, /* with BROADPHASE: report which pairs begun and which ended TOUCHING since the last run with this flag (scTickSetTouchEvents) */
   SC_TICK_OVERLAPS    = 0x00010000u, /* bit 16.  With BROADPHASE: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes */
   SC_TICK_TRIGGERS    = 0x00020000u, /* bit 17.  With BROADPHASE: answer the trigger volumes set by scTickSetTriggerVolumes and report who entered / left since the last run with this flag */
+  SC_TICK_ANCHORED_SWEEPS = 0x00040000u, /* bit 18.  With BROADPHASE: answer the entity-anchored capsule sweeps set by scTickSetAnchoredSweeps against this tick's matrices and boxes */
   SC_TICK_FULL        = SC_TICK_XFORM | SC_TICK_CULL | SC_TICK_BROADPHASE
 };
 
@@ -1515,6 +1516,65 @@ int scTickReadTriggerMembers(ScTickContext* ctx, uint32_t* counts, uint32_t* ids
 int scTickReadTriggerMatrices(ScTickContext* ctx, uint32_t first, uint32_t count, float* mat16);
 /* the anchors as they stand now (renamed or SC_TICK_ANCHOR_DEAD after scTickRemoveEntities); host-side, needs no run */
 int scTickReadTriggerVolumes(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
+
+/* ---- entity-anchored capsule sweeps over the broadphase bins ----
+ * Capsule sweeps that follow an entity on the device: what the anchored rays are to the ray queries and the trigger volumes to the overlap
+ * queries.  The consumer of a capsule sweep is almost always a moving entity -- a pedestrian's or a kinematic body's move test, a ground
+ * probe under a vehicle, the clearance test ahead of an agent (PhysicsWorld::sweepCapsule, sc_physics.h:179, sc_physics.cpp:779-810, takes
+ * start and end in world space) -- and in resident mode that entity's pose of this frame exists only on the device.  An anchored sweep is
+ * given once, in its anchor's LOCAL frame; every run with SC_TICK_ANCHORED_SWEEPS resolves it against that tick's world matrix of the
+ * anchor and answers it against that tick's boxes: no host round trip, no learn tick, no graph re-capture in the frame loop.
+ * This build's OWN SPEC.  All arithmetic is fp32, unfused, left to right.  For sweep k with anchor a, local start ls, local end le, and
+ * R_r = (w_r.x, w_r.y, w_r.z, w_r.w) row r (0..2) of a's world matrix as this run's transform stage leaves it (without SC_TICK_XFORM: as
+ * it stands on the device):
+ *   s_r = ((R_r.x*ls.x + R_r.y*ls.y) + R_r.z*ls.z) + R_r.w                       (the anchored rays' origin formula)
+ *   end_frame SC_TICK_SWEEP_END_LOCAL (0)         le is a point in the anchor's frame:   e_r by the same formula as s_r
+ *   end_frame SC_TICK_SWEEP_END_WORLD_OFFSET (1)  le is a world-space displacement:      e_r = s_r + le_r
+ * (the offset form: a probe "0.4 m straight down whatever the chassis' tilt", a world velocity times dt).
+ *   anchor      SC_TICK_ANCHOR_NONE: s = ls untouched; e = le untouched (frame 0), e_r = ls_r + le_r (frame 1)
+ * The resolved sweep (s, e, radius, half_height, mask, skip_id) is then answered exactly as a sweep of scTickSetSweepQueries, under the
+ * context's sweep mode (scTickSetSweepShapes: AABB or EXACT): same sweeper, same zero-length rule (|e - s|^2 <= 1e-6: an overlap test at
+ * s), same filter, same tests, same tie rule, same ScTickSweepHit.  An unanchored frame-0 sweep equals the plain sweep query's answer bit
+ * for bit, in both modes.
+ *   skip_self   != 0 (NULL: every sweep) on a sweep that has an anchor: skip_id = rank << 24 | a, the anchor's own box never answers;
+ *               otherwise no box is skipped
+ *   radius, half_height   world metres: the anchor's scale does not scale them, and the sweeper stays UPRIGHT in world space whatever the
+ *               anchor's rotation (the reference's sweeper is upright) -- a limit of this spec
+ * ScTickSweepHit::pad carries the sweep's status:
+ *   SC_TICK_ASWEEP_ANSWERED (0)    the record is the answer
+ *   SC_TICK_ASWEEP_NO_ANCHOR (1)   the anchor is >= the entity count at run time (SC_TICK_ANCHOR_DEAD always is)
+ *   SC_TICK_ASWEEP_NOT_FINITE (2)  a component of s or e is not finite, or (d.x*d.x + d.y*d.y) + d.z*d.z of d = e - s is not finite
+ * Statuses 1 and 2 are a miss (SweepHit{}) and scTickReadAnchoredSweepSegments reports the quiet NaN 0x7FC00000 in all six words for
+ * them: a mover that lost its anchor must not read "path clear", which is why the status exists and is not 0.
+ * scTickGetAnchoredSweepShapeInfo reports the three words of ScTickSweepShapeInfo for the last run with this flag in EXACT mode, under
+ * the rules of scTickGetSweepShapeInfo; the report is separate from the plain sweeps': a run with both flags fills both.
+ * Residency: scTickRemoveEntities renames the anchors of relocated entities and turns the anchors of removed ones into
+ * SC_TICK_ANCHOR_DEAD, as for the anchored rays and the trigger volumes.  scTickAppendEntities and scTickSetEntityCount leave them alone.
+ * A run with SC_TICK_ANCHORED_SWEEPS fails, with a last-error text, without SC_TICK_BROADPHASE, without a set, together with
+ * SC_TICK_SPLIT_PAIRS, on a context with neighbours and on a pipelined context -- tiles are not covered.  The flag makes the tick fill
+ * every bin (no quiet tick, no lazy records), like the other bin readers.  A context that never calls scTickSetAnchoredSweeps allocates
+ * and launches nothing for them.
+ * Not covered: rotated sweepers, a capsule scaled by its anchor, tiles, split flows, pipelined contexts, contact points. */
+enum { SC_TICK_SWEEP_END_LOCAL = 0, SC_TICK_SWEEP_END_WORLD_OFFSET = 1 };
+enum { SC_TICK_ASWEEP_ANSWERED = 0, SC_TICK_ASWEEP_NO_ANCHOR = 1, SC_TICK_ASWEEP_NOT_FINITE = 2 };
+/* anchor, radius, half_height, mask: [count]; local_start3 / local_end3: [count][3]; skip_self: uint8 [count] or NULL (all 1); end_frame:
+ * uint8 [count] or NULL (all 0).  The set stays until it is replaced; count 0 clears and frees it.  A call with THE SAME COUNT as the
+ * current set only rewrites the device arrays, behind whatever is queued: no learn tick, and a captured graph stays valid; another count
+ * behaves like scTickSetSweepQueries.  Fails -- and leaves the previous set in place -- when a local start, local end, radius or
+ * half_height is not finite, a radius is negative, an end_frame is neither 0 nor 1, a required array is NULL, or scTickRunPairs is
+ * pending. */
+int scTickSetAnchoredSweeps(ScTickContext* ctx, uint32_t count, const uint32_t* anchor, const float* local_start3, const float* local_end3,
+                            const float* radius, const float* half_height, const uint32_t* mask, const uint8_t* skip_self,
+                            const uint8_t* end_frame);
+/* The reads below answer for the last scTickRun(... | SC_TICK_BROADPHASE | SC_TICK_ANCHORED_SWEEPS); they fail when the last run lacked
+ * the flag or the set was re-sized since.  They synchronise. */
+int scTickReadAnchoredSweepHits(ScTickContext* ctx, ScTickSweepHit* hits, uint32_t capacity, uint32_t* count);
+/* the resolved world-space segments of sweeps first .. first + count - 1: start3 / end3 [count][3] (either may be NULL) */
+int scTickReadAnchoredSweepSegments(ScTickContext* ctx, uint32_t first, uint32_t count, float* start3, float* end3);
+/* of the last run with the flag; fails when that run swept in AABB mode.  Copies the 16 bytes of `info`. */
+int scTickGetAnchoredSweepShapeInfo(ScTickContext* ctx, ScTickSweepShapeInfo* info);
+/* the anchors as they stand now (renamed or SC_TICK_ANCHOR_DEAD after scTickRemoveEntities); host-side, needs no run */
+int scTickReadAnchoredSweeps(ScTickContext* ctx, uint32_t first, uint32_t count, uint32_t* anchor);
 
 /* isOccupiedWorld (src/engine/traffic/sc_traffic_spawner.cpp:93-116), for a batch of at most 256 points: blocked[k] = 1
  * when some entity whose collision group meets mask[k] has dx*dx + dz*dz < radius[k]*radius[k] to point k, measured on

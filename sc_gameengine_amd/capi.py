@@ -19,6 +19,7 @@ PAIR_SHAPES = 1 << 14         # SC_TICK_PAIR_SHAPES: also list the pairs of this
 TOUCH_EVENTS = 1 << 15        # SC_TICK_TOUCH_EVENTS: which pairs begun / ended TOUCHING since the last run with this flag (scTickSetTouchEvents)
 OVERLAPS = 1 << 16            # SC_TICK_OVERLAPS: answer the overlap queries set by scTickSetOverlapQueries against this tick's boxes
 TRIGGERS = 1 << 17            # SC_TICK_TRIGGERS: answer the trigger volumes (scTickSetTriggerVolumes) and report who entered / left since the last run with it
+ANCHORED_SWEEPS = 1 << 18     # SC_TICK_ANCHORED_SWEEPS: answer the entity-anchored capsule sweeps (scTickSetAnchoredSweeps) against this tick's matrices and boxes
 ANCHOR_NONE, ANCHOR_DEAD = 0xFFFFFFFF, 0xFFFFFFFE      # SC_TICK_ANCHOR_*: a world-space ray; a ray whose anchor was removed
 RAY_SHAPES_AABB, RAY_SHAPES_EXACT = 0, 1               # SC_TICK_RAY_SHAPES_*: what a ray's candidates are (scTickSetRayShapes)
 SWEEP_SHAPES_AABB, SWEEP_SHAPES_EXACT = 0, 1           # SC_TICK_SWEEP_SHAPES_*: what a capsule sweep's candidates are (scTickSetSweepShapes)
@@ -29,6 +30,8 @@ CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 # SC_TICK_MANIFOLD_*: ScTickPairManifold::kind (scTickSetPairManifolds)
 MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
 MANIFOLD_REDUCED = 1 << 8
+SWEEP_END_LOCAL, SWEEP_END_WORLD_OFFSET = 0, 1         # SC_TICK_SWEEP_END_*: what an anchored sweep's local_end is (scTickSetAnchoredSweeps)
+ASWEEP_ANSWERED, ASWEEP_NO_ANCHOR, ASWEEP_NOT_FINITE = 0, 1, 2      # SC_TICK_ASWEEP_*: ScTickSweepHit::pad of an anchored sweep
 TRIGGER_MAX_MEMBERS = 1024    # SC_TICK_TRIGGER_MAX_MEMBERS: id slots per trigger volume at most
 SWEEP_SHAPES_TOL, SWEEP_SHAPES_STEPS, SWEEP_SHAPES_SEEN = 1e-3, 12, 256
 FULL = XFORM | CULL | BROADPHASE
@@ -298,6 +301,11 @@ SYMBOLS = {
     "scTickReadTriggerMembers": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(TriggerInfo)]),
     "scTickReadTriggerMatrices": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P]),
     "scTickReadTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
+    "scTickSetAnchoredSweeps": (C.c_int, [_CTX, C.c_uint32, U32P, F32P, F32P, F32P, F32P, U32P, U8P, U8P]),
+    "scTickReadAnchoredSweepHits": (C.c_int, [_CTX, C.POINTER(SweepHit), C.c_uint32, U32P]),
+    "scTickReadAnchoredSweepSegments": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, F32P, F32P]),
+    "scTickGetAnchoredSweepShapeInfo": (C.c_int, [_CTX, C.POINTER(SweepShapeInfo)]),
+    "scTickReadAnchoredSweeps": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, U32P]),
     "scTickQueryOccupied": (C.c_int, [_CTX, C.c_uint32, F32P, F32P, U32P, U8P]),
     "scTickSetProfiling": (C.c_int, [_CTX, C.c_int]),
     "scTickSetProfilingKernels": (C.c_int, [_CTX, C.c_uint32]),

@@ -53,6 +53,7 @@ struct LastWith {
   bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
   uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
+  uint32_t asweepCount = 0; bool asweepsExact = false;  // what SC_TICK_ANCHORED_SWEEPS answered, and in which mode (scTickReadAnchoredSweep*, scTickGetAnchoredSweepShapeInfo)
   uint32_t bindTouchWords = 0; bool bindEmpty = false; // SC_TICK_BIND_RUNS: the bitmap's size; the run of an empty context (the report reads as zeros)
 };
 
@@ -67,6 +68,7 @@ struct TickPlan {
   uint32_t visSel = 0;                 // the copy of the visibility words this tick writes = ScTickContext::visSel once commitPlan has run (a carrying tick: not the copy its rider reads)
   bool sampled = false, carry = false, defer = false, replay = false, wholeStep = false;
   bool triggers = false;               // the trigger volumes are answered by this tick (k_trigger_volumes, at the overlap queries' launch site)
+  bool anchoredSweeps = false;         // the entity-anchored sweeps are answered by this tick (k_anchored_sweeps, next to the trigger volumes' launch)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -207,6 +209,13 @@ struct ScTickContext
   uint32_t triggerCap = 0, triggerEventCap = 0; size_t triggerIdCap = 0;
   uint32_t triggerShapes = SC_TICK_OVERLAP_SHAPES_AABB;
   std::vector<uint2> hTriggerAnchor;
+  // scTickSetAnchoredSweeps: the entity-anchored capsule sweeps, their hits and resolved segments; asweepInfo: the words of their EXACT
+  // report (their own, not sweepInfo), allocated with the first set.  hSweepAnchor mirrors the anchor words for scTickRemoveEntities and
+  // scTickReadAnchoredSweeps.  All null until the call: nothing is launched.
+  AnchoredSweepState asweeps{};
+  uint32_t asweepCap = 0;
+  uint32_t* asweepInfo = nullptr;
+  std::vector<uint4> hSweepAnchor;
   // scTickSetPairEvents: the tables, marks and control words of the pair events (one allocation, pairEventSlab: zero bytes all over =
   // nothing remembered, which is how a rename resyncs), the report and the two lists.  All null until the call: nothing is launched.
   PairEventState pairEvents{};
@@ -731,6 +740,7 @@ void fillParams(ScTickContext* c, uint32_t flags, TickParams& p, uint32_t& grid)
   computeSpan(c, p.span, grid);
   p.flags = flags & 0xFFFFu;        // SC_TICK_DENSE_AABBS == kFlagDenseAabbs
   if (c->levelOffsets.size() > 1 && (flags & SC_TICK_XFORM)) p.flags |= kFlagHasDeep;
+  if (flags & SC_TICK_ANCHORED_SWEEPS) p.flags |= kFlagAnchoredSweeps;      // (likewise: bit 18 is kFlagTailOwnsDirty's position)
   if (flags & SC_TICK_TRIGGERS) p.flags |= kFlagTriggers;      // (likewise: bit 17 is kFlagDeferredReset's position)
   if (flags & SC_TICK_OVERLAPS) p.flags |= kFlagOverlaps;      // (the public bit is one of the internal ones' positions: it travels as a bit of its own)
   // The fused kernel's workgroups end the tick for their own spans (spanTail) when the world is span-closed, no level kernel reads `dirty`
@@ -1080,6 +1090,9 @@ bool enqueueStages(ScTickContext* c, const TickPlan& plan, bool inCapture)
   if (path.pairsNow && (flags & kFlagOverlaps)) launchOverlapQueries(ds, p, c->overlaps, c->overlapShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
   // (trigger volumes: refused in a split flow like the overlap queries -- their one launch site; whether they run is the plan's word)
   if (plan.triggers) launchTriggerVolumes(ds, p, c->triggers, c->triggerShapes == SC_TICK_OVERLAP_SHAPES_EXACT, c->stream);
+  // (entity-anchored sweeps: refused in a split flow too -- their one launch site, by the plan's word; their EXACT report has its own words)
+  if (plan.anchoredSweeps)
+    launchAnchoredSweeps(ds, p, c->asweeps, c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT ? c->asweepInfo : nullptr, c->stream);
   // entity-anchored rays: resolved against the matrices the transform stage just left and cast in one launch; in a split flow they are
   // only resolved here, into this parity's snapshot -- the pair half casts them behind the merge, when a pipelined tile's matrices may
   // already be the next tick's
@@ -1902,6 +1915,17 @@ int scTickRemoveEntities(ScTickContext* c, const uint32_t* idx, uint32_t count, 
     }
     if (changed && !h2d(c, const_cast<uint2*>(c->triggers.anchor), c->hTriggerAnchor.data(), (size_t)c->triggers.count * sizeof(uint2))) return 0;
   }
+  if (c->asweeps.count) {                               // ... and the anchored sweeps' anchors
+    bool changed = false;
+    for (uint32_t k = 0; k < c->asweeps.count; ++k) {
+      uint32_t& a = c->hSweepAnchor[k].x;
+      if (a >= n0) continue;
+      if (removed.count(a)) { a = kAnchorDead; changed = true; continue; }
+      const auto m = newIndexOf.find(a);
+      if (m != newIndexOf.end()) { a = m->second; changed = true; }
+    }
+    if (changed && !h2d(c, const_cast<uint4*>(c->asweeps.anchor), c->hSweepAnchor.data(), (size_t)c->asweeps.count * sizeof(uint4))) return 0;
+  }
   {
     // bounds classes: the wave-tiles that took a relocated entity, and those of the shrunk tail
     std::vector<uint32_t> tiles;
@@ -2123,7 +2147,8 @@ static bool worldCanPair(ScTickContext* c)
 static bool quietTick(ScTickContext* c, uint32_t flags)
 {
   constexpr uint32_t kBinReaders = SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_PAIR_EVENTS | SC_TICK_PAIR_SHAPES |
-                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS;
+                                   SC_TICK_TOUCH_EVENTS | SC_TICK_DENSE_AABBS | SC_TICK_SPLIT_PAIRS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS |
+                                   SC_TICK_ANCHORED_SWEEPS;
   if (!(flags & SC_TICK_BROADPHASE) || (flags & kBinReaders) || !c->quietEnabled || !c->homeEnabled || !c->lazyEnabled) return false;
   if (!c->n || c->sensors || c->neighbourMask || c->pairsStream || c->pairsPending) return false;
   if (!c->homeValid || c->homeEpoch != c->topoEpoch) return false;      // (a learn tick is due: an append, a remove, a re-link, a layer upload)
@@ -2172,6 +2197,13 @@ static bool tickAccepted(ScTickContext* c, uint32_t flags)
     if (c->neighbourMask) return fail(c, "SC_TICK_TRIGGERS cannot run on a context with neighbours (scTickSetTile): trigger volumes do not cover tiles");
     if (c->pairsStream) return fail(c, "SC_TICK_TRIGGERS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): trigger volumes do not cover tiles");
     if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_TRIGGERS cannot run with SC_TICK_SPLIT_PAIRS: trigger volumes do not cover tiles");
+  }
+  if (flags & SC_TICK_ANCHORED_SWEEPS) {
+    if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_ANCHORED_SWEEPS needs SC_TICK_BROADPHASE in the same run (the sweeps read this tick's bins)");
+    if (!c->asweeps.count) return fail(c, "SC_TICK_ANCHORED_SWEEPS needs scTickSetAnchoredSweeps first (the set is empty)");
+    if (c->neighbourMask) return fail(c, "SC_TICK_ANCHORED_SWEEPS cannot run on a context with neighbours (scTickSetTile): anchored sweeps do not cover tiles");
+    if (c->pairsStream) return fail(c, "SC_TICK_ANCHORED_SWEEPS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): anchored sweeps do not cover tiles");
+    if (flags & SC_TICK_SPLIT_PAIRS) return fail(c, "SC_TICK_ANCHORED_SWEEPS cannot run with SC_TICK_SPLIT_PAIRS: anchored sweeps do not cover tiles");
   }
   if (c->rb.bytes && c->graphMode) return fail(c, "graph replay and the frame read-back cannot be combined");      // (an empty context's run stages a frame too)
   if (nothingToRun(c, flags)) return true;
@@ -2230,7 +2262,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
     //  transport, scTickRunPairs -- the host may upload matrices, bounds or layers, append or remove entities, or run a transform-only
     //  tick between the halves, and a rebuild would then read the world of a later moment than tick t's: every record is written)
     const bool hostBetweenHalves = (run & SC_TICK_SPLIT_PAIRS) && !c->pairsStream && !c->ownStep;
-    p.lazy = (!plan.learn && c->lazyEnabled && !(run & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
+    p.lazy = (!plan.learn && c->lazyEnabled && !(run & (SC_TICK_RAYS | SC_TICK_SWEEPS | SC_TICK_ANCHORED_RAYS | SC_TICK_OVERLAPS | SC_TICK_TRIGGERS | SC_TICK_ANCHORED_SWEEPS)) && !c->sensors && !hostBetweenHalves) ? (!c->pairsStream ? 1u : (c->worldLayersKnown ? 2u : 0u)) : 0u;
     p.vocab = c->worldLayers;
     p.vocabKnown = c->worldLayersKnown ? 1u : 0u;
     // records of entities that did not move stay as they are, unless something else changed boxes since the last tick
@@ -2245,6 +2277,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   if (path.needCompact) compactLaunchShape(plan.grid, path.pairsNow, plan.compactG, plan.rec.compact);
   plan.rec.frame[0] = path.items; plan.rec.frame[1] = path.block;
   plan.triggers = path.pairsNow && (p.flags & kFlagTriggers) != 0u;
+  plan.anchoredSweeps = path.pairsNow && (p.flags & kFlagAnchoredSweeps) != 0u;
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2306,6 +2339,7 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   if (with & SC_TICK_BIND_RUNS) { w.bindTouchWords = c->bind.touchWords; w.bindEmpty = nothingToRun(c, rec.flags); }
   if (with & SC_TICK_OVERLAPS) { w.overlapCount = c->overlaps.count; w.overlapMaxHits = c->overlaps.maxHits; w.overlapShapes = c->overlapShapes; }
   if (with & SC_TICK_TRIGGERS) { w.triggerCount = c->triggers.count; w.triggerMaxMembers = c->triggers.maxMembers; w.triggerMaxEvents = c->triggers.maxEvents; }
+  if (with & SC_TICK_ANCHORED_SWEEPS) { w.asweepCount = c->asweeps.count; w.asweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT; }
   if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
   if (with & SC_TICK_PAIR_SHAPES) { w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; }
 }
@@ -3448,6 +3482,101 @@ int scTickReadAnchoredRays(ScTickContext* c, uint32_t first, uint32_t count, uin
   if (count && !anchor) return fail(c, "null argument");
   if ((uint64_t)first + count > c->anchored.count) return fail(c, "range exceeds the anchored ray count");
   for (uint32_t k = 0; k < count; ++k) anchor[k] = c->hAnchor[first + k].x;      // (host mirror: no read-back)
+  return 1;
+}
+
+int scTickSetAnchoredSweeps(ScTickContext* c, uint32_t count, const uint32_t* anchor, const float* localStart3, const float* localEnd3, const float* radius,
+                            const float* halfHeight, const uint32_t* mask, const uint8_t* skipSelf, const uint8_t* endFrame)
+{
+  static_assert(kASweepAnswered == SC_TICK_ASWEEP_ANSWERED && kASweepNoAnchor == SC_TICK_ASWEEP_NO_ANCHOR && kASweepNotFinite == SC_TICK_ASWEEP_NOT_FINITE,
+                "anchored sweep statuses differ");
+  if (!c) return 0;
+  if (count && (!anchor || !localStart3 || !localEnd3 || !radius || !halfHeight || !mask)) return fail(c, "null argument");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  // checked before anything changes, so a refused call leaves the previous set in place
+  std::vector<float4> a(count), b(count); std::vector<uint4> an(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    a[i] = make_float4(localStart3[3 * (size_t)i], localStart3[3 * (size_t)i + 1], localStart3[3 * (size_t)i + 2], radius[i]);
+    b[i] = make_float4(localEnd3[3 * (size_t)i], localEnd3[3 * (size_t)i + 1], localEnd3[3 * (size_t)i + 2], halfHeight[i]);
+    const uint32_t frame = endFrame ? endFrame[i] : (uint32_t)SC_TICK_SWEEP_END_LOCAL;
+    an[i] = make_uint4(anchor[i], skipSelf ? (skipSelf[i] ? 1u : 0u) : 1u, frame, mask[i]);
+    const float v[8] = { a[i].x, a[i].y, a[i].z, a[i].w, b[i].x, b[i].y, b[i].z, b[i].w };
+    for (float x : v) if (!std::isfinite(x)) return fail(c, "anchored sweeps: local_start, local_end, radius and half_height must be finite");
+    if (radius[i] < 0.0f) return fail(c, "anchored sweeps: radius must be >= 0");
+    if (frame != SC_TICK_SWEEP_END_LOCAL && frame != SC_TICK_SWEEP_END_WORLD_OFFSET)
+      return fail(c, "anchored sweeps: end_frame is SC_TICK_SWEEP_END_LOCAL or SC_TICK_SWEEP_END_WORLD_OFFSET");
+  }
+  if (!bind(c)) return 0;
+  AnchoredSweepState& q = c->asweeps;
+  // The same count as the current set: only the device arrays are rewritten, behind whatever is queued on the tick stream -- no epoch
+  // bump, so no learn tick, and a captured graph (which holds the buffers and the count) stays valid.
+  if (count != q.count) {
+    if (!sync(c)) return 0;
+    if (count && !c->asweepInfo && !dalloc(c, c->asweepInfo, kSweepInfoWords)) return 0;
+    if (!growBatch(c, c->asweepCap, q.count, count, batchArray(q.start), batchArray(q.end), batchArray(q.anchor), batchArray(q.hits, true),
+                   batchArray(q.segment, true, 2))) return 0;
+    if (!count) {                                        // freed, not kept: a context that clears its set holds nothing for it
+      dfree(c, const_cast<float4*>(q.start)); dfree(c, const_cast<float4*>(q.end)); dfree(c, const_cast<uint4*>(q.anchor)); dfree(c, q.hits);
+      dfree(c, q.segment); dfree(c, c->asweepInfo);
+      q = AnchoredSweepState{}; c->asweepCap = 0; c->asweepInfo = nullptr;
+    }
+  }
+  c->hSweepAnchor = an;
+  if (!count) return 1;
+  if (!h2d(c, const_cast<float4*>(q.start), a.data(), (size_t)count * sizeof(float4)) ||
+      !h2d(c, const_cast<float4*>(q.end), b.data(), (size_t)count * sizeof(float4)) ||
+      !h2d(c, const_cast<uint4*>(q.anchor), an.data(), (size_t)count * sizeof(uint4))) return 0;
+  return sync(c) ? 1 : 0;
+}
+
+// the gate of the anchored sweeps' readers: the last run carried the flag and the set is the size that run answered
+static bool anchoredSweepResult(ScTickContext* c, bool enabledThen = true, const char* notEnabled = nullptr)
+{
+  return bind(c) && lastRunResult(c, SC_TICK_ANCHORED_SWEEPS, "the last scTickRun did not request SC_TICK_ANCHORED_SWEEPS", enabledThen, notEnabled,
+                                  "anchored sweep results are ready after scTickRunPairs", c->asweeps.count == c->lastWith.asweepCount,
+                                  "the anchored sweep set was re-sized since the last run with SC_TICK_ANCHORED_SWEEPS: its results are gone");
+}
+
+int scTickReadAnchoredSweepHits(ScTickContext* c, ScTickSweepHit* hits, uint32_t cap, uint32_t* count)
+{
+  if (!c || !count) return c ? fail(c, "null argument") : 0;
+  if (!anchoredSweepResult(c)) return 0;
+  *count = c->asweeps.count;
+  const uint32_t take = std::min(c->asweeps.count, cap);
+  if (take && hits) { if (!d2h(c, hits, c->asweeps.hits, (size_t)take * sizeof(SweepHit48)) || !sync(c)) return 0; }
+  return 1;
+}
+
+int scTickReadAnchoredSweepSegments(ScTickContext* c, uint32_t first, uint32_t count, float* start3, float* end3)
+{
+  if (!c) return 0;
+  if (!anchoredSweepResult(c)) return 0;
+  if ((uint64_t)first + count > c->asweeps.count) return fail(c, "range exceeds the anchored sweep count");
+  if (!count || (!start3 && !end3)) return 1;
+  std::vector<float4> seg((size_t)count * 2u);
+  if (!d2h(c, seg.data(), c->asweeps.segment + 2u * (size_t)first, seg.size() * sizeof(float4)) || !sync(c)) return 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    const float4 s = seg[2u * (size_t)k], e = seg[2u * (size_t)k + 1u];
+    if (start3) { start3[3 * (size_t)k] = s.x; start3[3 * (size_t)k + 1] = s.y; start3[3 * (size_t)k + 2] = s.z; }
+    if (end3) { end3[3 * (size_t)k] = e.x; end3[3 * (size_t)k + 1] = e.y; end3[3 * (size_t)k + 2] = e.z; }
+  }
+  return 1;
+}
+
+int scTickGetAnchoredSweepShapeInfo(ScTickContext* c, ScTickSweepShapeInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  if (!anchoredSweepResult(c, c->lastWith.asweepsExact && c->asweepInfo, "the last scTickRun swept in SC_TICK_SWEEP_SHAPES_AABB mode: nothing was refined")) return 0;
+  if (!d2h(c, info, c->asweepInfo, sizeof *info) || !sync(c)) return 0;
+  return 1;
+}
+
+int scTickReadAnchoredSweeps(ScTickContext* c, uint32_t first, uint32_t count, uint32_t* anchor)
+{
+  if (!c) return 0;
+  if (count && !anchor) return fail(c, "null argument");
+  if ((uint64_t)first + count > c->asweeps.count) return fail(c, "range exceeds the anchored sweep count");
+  for (uint32_t k = 0; k < count; ++k) anchor[k] = c->hSweepAnchor[first + k].x;      // (host mirror: no read-back)
   return 1;
 }
 

@@ -318,7 +318,8 @@ constexpr uint32_t kFlagDenseAabbs = 1u << 5; // == SC_TICK_DENSE_AABBS
 constexpr uint32_t kFlagOverlaps = 1u << 19;    // SC_TICK_OVERLAPS as TickParams::flags carries it: the public flag is bit 16, kFlagHasDeep's position, and only
                                                 // the low 16 public bits are copied into the word (fillParams) -- no kernel looks at this bit, the launch list does
 constexpr uint32_t kFlagTriggers = 1u << 21;    // SC_TICK_TRIGGERS (public bit 17, kFlagDeferredReset's position) likewise: the launch list looks at it, no kernel does
-constexpr uint32_t kFlagTopoClasses = 1u << 20;     // every wave-tile of the world is classed and the classes are current: the fused kernel without binning takes
+constexpr uint32_t kFlagAnchoredSweeps = 1u << 22;      // SC_TICK_ANCHORED_SWEEPS (public bit 18, kFlagTailOwnsDirty's position) likewise
+constexpr uint32_t kFlagTopoClasses = 1u << 20;    // every wave-tile of the world is classed and the classes are current: the fused kernel without binning takes
                                                     // its classed instance (no link word is read: xformCullClassed)
 constexpr uint32_t kFlagTailOwnsDirty = 1u << 18;   // span-closed world: every workgroup of the fused kernel ends the tick for its own span (dirty clear, and the
                                                     // root nudge with SC_TICK_PRODUCE_NEXT: spanTail); the end-of-tick kernel then touches neither
@@ -416,6 +417,19 @@ struct AnchoredRayState {
 };
 void launchAnchoredRays(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, bool fromSnapshot, bool exact, hipStream_t s);   // resolve + cast; fromSnapshot (pair half): cast
 void launchAnchoredRaySnapshot(const DeviceState& d, const TickParams& p, const AnchoredRayState& q, hipStream_t s);      // tick half: resolve
+// ---- entity-anchored capsule sweeps (include/sc_tick.h "entity-anchored capsule sweeps"): given in an entity's local frame, resolved
+// against this tick's world matrix of that entity by the kernel that sweeps them.  A kernel argument of their own. ----
+constexpr uint32_t kASweepAnswered = 0, kASweepNoAnchor = 1, kASweepNotFinite = 2;      // == SC_TICK_ASWEEP_*: SweepHit48::pad
+struct AnchoredSweepState {
+  const float4* start;      // local xyz + radius (world metres)
+  const float4* end;        // local xyz -- a point of the anchor's frame, or a world-space displacement (end_frame) -- + half height
+  const uint4* anchor;      // (dense index of the anchor | kAnchorNone | kAnchorDead, skip_self, end_frame, mask)
+  SweepHit48* hits;
+  float4* segment;          // [count][2] the resolved (start, end) of the last flagged run; quiet NaNs where the status is not 0
+  uint32_t count;
+};
+// exactInfo: as for launchSweepQueries, words of their own (== ScTickSweepShapeInfo, scTickGetAnchoredSweepShapeInfo)
+void launchAnchoredSweeps(const DeviceState& d, const TickParams& p, const AnchoredSweepState& q, uint32_t* exactInfo, hipStream_t s);
 // ---- pair begin / end events (sc_tick_pair_events.hip; include/sc_tick.h "pair events"): the difference between this tick's pair set and
 // the set of the last tick that ran with SC_TICK_PAIR_EVENTS, formed on the device behind the pair search.  A kernel argument of its own.
 // Two open-addressing tables of 64-bit keys a << 32 | b (0 = empty: a < b rules it out) are used in turn: the one holding the remembered

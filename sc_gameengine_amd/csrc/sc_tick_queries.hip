@@ -616,6 +616,115 @@ __global__ __launch_bounds__(kTile) void k_sweep_queries(const DeviceState d, co
   }
 }
 
+// ---- entity-anchored capsule sweeps (own spec, include/sc_tick.h "entity-anchored capsule sweeps") ----------------------------
+// A sweep whose consumer is a moving entity -- a pedestrian's move test, a ground probe under a vehicle (PhysicsWorld::sweepCapsule,
+// sc_physics.cpp:779-810, takes world-space points) -- is given in its anchor's local frame and taken through this tick's world matrix
+// of the anchor, fp32, unfused, left to right: the start by resolveAnchoredRay's origin formula,
+//   s_r = ((R_r.x*ls.x + R_r.y*ls.y) + R_r.z*ls.z) + R_r.w
+// the end by the same formula (end_frame 0: a point of the anchor's frame) or e_r = s_r + le_r (end_frame 1: a world-space
+// displacement).  kAnchorNone: s = ls, e = le or ls + le, untouched.  The status: an anchor beyond the entity count (a dead anchor is);
+// a component of s or e, or the squared length of e - s as the sweep kernels form it, that is not finite.
+struct ResolvedSweep { float s[3], e[3]; uint32_t skipId, status; };
+
+__device__ __forceinline__ ResolvedSweep resolveAnchoredSweep(const DeviceState& d, const TickParams& p, const float4& ls, const float4& le, const uint4 an)
+{
+  ResolvedSweep r;
+  const float l[3] = { ls.x, ls.y, ls.z }, m[3] = { le.x, le.y, le.z };
+  r.skipId = 0xFFFFFFFFu; r.status = kASweepAnswered;
+  if (an.x == kAnchorNone) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { r.s[k] = l[k]; r.e[k] = an.z ? l[k] + m[k] : m[k]; }
+  } else {
+    r.s[0] = r.s[1] = r.s[2] = 0.0f; r.e[0] = r.e[1] = r.e[2] = 0.0f;
+    if (an.x >= p.n) { r.status = kASweepNoAnchor; return r; }
+    const float4 row[3] = { d.w0[an.x], d.w1[an.x], d.w2[an.x] };
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      r.s[k] = ((row[k].x * l[0] + row[k].y * l[1]) + row[k].z * l[2]) + row[k].w;
+      r.e[k] = an.z ? r.s[k] + m[k] : ((row[k].x * m[0] + row[k].y * m[1]) + row[k].z * m[2]) + row[k].w;
+    }
+    if (an.y) r.skipId = p.rankBits | an.x;                                    // the anchor's own box never answers
+  }
+  const float dv[3] = { r.e[0] - r.s[0], r.e[1] - r.s[1], r.e[2] - r.s[2] };
+  const float lenSq = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];         // (as k_sweep_queries forms it)
+  if (!(isfinite(r.s[0]) && isfinite(r.s[1]) && isfinite(r.s[2]) && isfinite(r.e[0]) && isfinite(r.e[1]) && isfinite(r.e[2]) && isfinite(lenSq)))
+    r.status = kASweepNotFinite;
+  return r;
+}
+
+// One wave per sweep.  The sweep index is made scalar as in k_anchored_rays, so the sweep's words, its anchor word and the twelve words
+// of the anchor's matrix rows come through the scalar path: one fetch per wave.  Behind the resolve the body IS k_sweep_queries' -- its
+// set-up, its two casts, its hit writer -- written out a second time: that kernel's comment and DESIGN 11.20 say why it is not shared.
+// Lane 0 also notes the status in the record's pad word and the resolved segment (quiet NaNs for a sweep that was not answered).
+// info (kExact): three words of their own, zeroed on the stream before the launch, added to only when non-zero.
+template <bool kExact>
+__global__ __launch_bounds__(kTile) void k_anchored_sweeps(const DeviceState d, const TickParams p, const AnchoredSweepState q, uint32_t* __restrict__ info)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = __builtin_amdgcn_readfirstlane(blockIdx.x * (kTile / 64u) + (threadIdx.x >> 6));
+  if (r >= q.count) return;
+  const float4 a = q.start[r], b = q.end[r];
+  const uint4 an = q.anchor[r];
+  const ResolvedSweep rs = resolveAnchoredSweep(d, p, a, b, an);
+  SweepHit48 out;
+  out.hit = 0u; out.id = 0xFFFFFFFFu; out.distance = 0.0f;
+  out.position[0] = out.position[1] = out.position[2] = 0.0f;
+  out.normal[0] = 0.0f; out.normal[1] = 1.0f; out.normal[2] = 0.0f;           // SweepHit{} (sc_physics.h:116)
+  out.layer = 0u; out.travel = 0.0f; out.pad = rs.status;
+  if (rs.status != kASweepAnswered) {                   // (wave-uniform: every operand came through the scalar path)
+    if (lane == 0) {
+      const float nan = __uint_as_float(0x7FC00000u);
+      q.hits[r] = out;
+      q.segment[2u * (size_t)r] = make_float4(nan, nan, nan, 0.0f);
+      q.segment[2u * (size_t)r + 1u] = make_float4(nan, nan, nan, 0.0f);
+    }
+    return;
+  }
+  const float o[3] = { rs.s[0], rs.s[1], rs.s[2] };
+  const float radius = a.w, hh = (b.w > 0.0f) ? b.w : 0.0f;
+  const float grow[3] = { radius, hh + radius, radius };
+  const float ay = (hh * hh > 0.0f) ? hh : 0.0f;       // (dot(A, A) of A = (0, hh, 0) is hh*hh to the bit)
+  const float dv[3] = { rs.e[0] - rs.s[0], rs.e[1] - rs.s[1], rs.e[2] - rs.s[2] };
+  const float lenSq = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];
+  float far = 0.0f, dir[3] = { 0.0f, 0.0f, 0.0f };
+  if (lenSq > 1e-6f) {
+    far = sqrtf(lenSq);
+    const float inv = 1.0f / far;
+    dir[0] = dv[0] * inv; dir[1] = dv[1] * inv; dir[2] = dv[2] * inv;
+  }
+  WaveRay w; w.valid = true; w.hit = false; w.t = 0.0f; w.id = 0xFFFFFFFFu; w.axis = 3u; w.layer = 0u;
+  float wn[3] = { 0.0f, 1.0f, 0.0f };
+  uint32_t* seenRow = nullptr;
+  if constexpr (kExact) {
+    __shared__ uint32_t seen[kTile / 64u][kSweepSeenCap];
+    seenRow = seen[threadIdx.x >> 6];
+  }
+  SweepTally tally; tally.seen = seenRow; tally.nSeen = 0u; tally.refined = 0u; tally.kept = 0u; tally.exhausted = 0u;
+  if constexpr (kExact) castSegmentWave<true, true>(w, d, p, o, dir, far, an.w, rs.skipId, grow, radius, wn, ay, &tally);
+  else castSegmentWave<true>(w, d, p, o, dir, far, an.w, rs.skipId, grow, radius);
+  if (w.hit) {
+    out.hit = 1u; out.id = w.id; out.layer = w.layer; out.travel = w.t;
+    out.distance = far > 0.0f ? w.t / far : 0.0f;                              // the hit FRACTION (m_closestHitFraction, :801)
+    out.position[0] = o[0] + dir[0] * w.t; out.position[1] = o[1] + dir[1] * w.t; out.position[2] = o[2] + dir[2] * w.t;   // the capsule's centre
+    if constexpr (kExact) { out.normal[0] = wn[0]; out.normal[1] = wn[1]; out.normal[2] = wn[2]; }
+    else if (w.axis < 3u) {                             // the face entered; a sweep that starts in overlap keeps (0,1,0)
+      const float dn = w.axis == 0u ? dir[0] : (w.axis == 1u ? dir[1] : dir[2]);
+      const float sgn = dn > 0.0f ? -1.0f : 1.0f;
+      out.normal[0] = w.axis == 0u ? sgn : 0.0f; out.normal[1] = w.axis == 1u ? sgn : 0.0f; out.normal[2] = w.axis == 2u ? sgn : 0.0f;
+    }
+  }
+  if (lane == 0) {
+    q.hits[r] = out;
+    q.segment[2u * (size_t)r] = make_float4(rs.s[0], rs.s[1], rs.s[2], 0.0f);
+    q.segment[2u * (size_t)r + 1u] = make_float4(rs.e[0], rs.e[1], rs.e[2], 0.0f);
+    if constexpr (kExact) {
+      if (tally.refined) atomicAdd(&info[0], tally.refined);
+      if (tally.kept) atomicAdd(&info[1], tally.kept);
+      if (tally.exhausted) atomicAdd(&info[2], tally.exhausted);
+    }
+  }
+}
+
 // ---- overlap queries (own spec, include/sc_tick.h "overlap queries") ---------------------------------------------------------
 // "Which entities are inside this volume": a collider without an entity -- type, record and world matrix as an entity's would be --
 // tested against the world exactly as the touching pairs test a pair.  The volume's box is the collider box rule (colliderAabb,
@@ -1151,6 +1260,12 @@ void launchSweepQueries(const DeviceState& d, const TickParams& p, const SweepQu
 {
   if (exactInfo) hipMemsetAsync(exactInfo, 0, kSweepInfoWords * sizeof(uint32_t), s);      // (an empty batch reports zeros)
   launchWavePerQuery(exactInfo ? k_sweep_queries<true> : k_sweep_queries<false>, q.count, s, d, p, q, exactInfo);
+}
+
+void launchAnchoredSweeps(const DeviceState& d, const TickParams& p, const AnchoredSweepState& q, uint32_t* exactInfo, hipStream_t s)
+{
+  if (exactInfo) hipMemsetAsync(exactInfo, 0, kSweepInfoWords * sizeof(uint32_t), s);      // (words of their own: a run with both flags fills both reports)
+  launchWavePerQuery(exactInfo ? k_anchored_sweeps<true> : k_anchored_sweeps<false>, q.count, s, d, p, q, exactInfo);
 }
 
 void launchOverlapQueries(const DeviceState& d, const TickParams& p, const OverlapQueryState& q, bool exact, hipStream_t s)

@@ -436,6 +436,57 @@ class WorldTick:
             self._ok(self.lib.scTickReadTriggerVolumes(self.ctx, 0, k, _u(out)), "scTickReadTriggerVolumes")
         return out[:k].copy()
 
+    # ---- entity-anchored capsule sweeps: given in an entity's local frame, resolved on the device every tick ----
+    def anchored_sweeps(self, anchor, local_start, local_end, radius, half_height, mask, skip_self=None, end_frame=None):
+        """Upright-capsule sweeps in the local frame of the entities `anchor` (dense indices; capi.ANCHOR_NONE: world space), answered by
+        every run with capi.ANCHORED_SWEEPS against that tick's matrices and boxes, in the context's sweep mode (scTickSetAnchoredSweeps).
+        end_frame: per sweep capi.SWEEP_END_LOCAL (local_end is a point of the anchor's frame; None: all) or capi.SWEEP_END_WORLD_OFFSET
+        (a world-space displacement from the resolved start).  skip_self: per sweep, whether the anchor's own box never answers (None:
+        all).  A call with as many sweeps as the current set costs no learn tick and no graph capture."""
+        an = np.ascontiguousarray(anchor, np.uint32).reshape(-1)
+        k = len(an)
+        a, b = _c32(local_start).reshape(-1, 3), _c32(local_end).reshape(-1, 3)
+        r, hh = _c32(radius).reshape(-1), _c32(half_height).reshape(-1)
+        mk = np.ascontiguousarray(mask, np.uint32).reshape(-1)
+        sk = None if skip_self is None else np.ascontiguousarray(skip_self, np.uint8).reshape(-1)
+        ef = None if end_frame is None else np.ascontiguousarray(end_frame, np.uint8).reshape(-1)
+        assert len(a) == k and len(b) == k and len(r) == k and len(hh) == k and len(mk) == k and (sk is None or len(sk) == k) and (ef is None or len(ef) == k)
+        self._ok(self.lib.scTickSetAnchoredSweeps(self.ctx, k, _u(an), _f(a), _f(b), _f(r), _f(hh), _u(mk),
+                                                  None if sk is None else sk.ctypes.data_as(capi.U8P),
+                                                  None if ef is None else ef.ctypes.data_as(capi.U8P)), "scTickSetAnchoredSweeps")
+        self._anchored_sweeps = k
+
+    def anchored_sweep_hits(self):
+        """Structured array like sweep_hits() of the last run's anchored sweeps; `pad` is the status (capi.ASWEEP_*)."""
+        n = C.c_uint32()
+        self._ok(self.lib.scTickReadAnchoredSweepHits(self.ctx, None, 0, C.byref(n)), "scTickReadAnchoredSweepHits")
+        buf = (capi.SweepHit * max(n.value, 1))()
+        if n.value:
+            self._ok(self.lib.scTickReadAnchoredSweepHits(self.ctx, buf, n.value, C.byref(n)), "scTickReadAnchoredSweepHits")
+        return np.frombuffer(buf, dtype=SWEEP_HIT_DTYPE, count=n.value).copy()
+
+    def anchored_sweep_segments(self):
+        """(start [k, 3], end [k, 3]): the world-space segments the last run with capi.ANCHORED_SWEEPS resolved (NaN: not answered)."""
+        k = getattr(self, "_anchored_sweeps", 0)
+        a, b = np.zeros((max(k, 1), 3), np.float32), np.zeros((max(k, 1), 3), np.float32)
+        self._ok(self.lib.scTickReadAnchoredSweepSegments(self.ctx, 0, k, _f(a), _f(b)), "scTickReadAnchoredSweepSegments")
+        return a[:k].copy(), b[:k].copy()
+
+    def anchored_sweep_anchors(self):
+        """The anchors as they stand now: renamed by remove_entities where their entity moved, capi.ANCHOR_DEAD where it was removed."""
+        k = getattr(self, "_anchored_sweeps", 0)
+        out = np.zeros(max(k, 1), np.uint32)
+        if k:
+            self._ok(self.lib.scTickReadAnchoredSweeps(self.ctx, 0, k, _u(out)), "scTickReadAnchoredSweeps")
+        return out[:k].copy()
+
+    def anchored_sweep_shape_info(self):
+        """What the last run's anchored sweeps did with their candidates in capi.SWEEP_SHAPES_EXACT mode (scTickGetAnchoredSweepShapeInfo):
+        a dict with refined, kept_as_boxes, exhausted.  Separate from sweep_shape_info()."""
+        info = capi.SweepShapeInfo()
+        self._ok(self.lib.scTickGetAnchoredSweepShapeInfo(self.ctx, C.byref(info)), "scTickGetAnchoredSweepShapeInfo")
+        return {k: int(getattr(info, k)) for k, _ in capi.SweepShapeInfo._fields_ if k != "pad"}
+
     def occupied(self, pos, radius, mask):
         """isOccupiedWorld for a batch of points (sc_traffic_spawner.cpp:93-116); returns a uint8 array."""
         p, r = _c32(pos).reshape(-1, 3), _c32(radius).reshape(-1)
