@@ -1233,6 +1233,67 @@ int scTickGetPairManifolds(ScTickContext* ctx, uint32_t* enabled);
 /* out: [capacity] records, may be NULL with capacity 0 */
 int scTickReadPairManifolds(ScTickContext* ctx, ScTickPairManifold* out, uint32_t capacity, ScTickPairManifoldInfo* info);
 
+/* ---- pair islands: the connected components of the touching pairs ----
+ * What a rigid-body host does next with a tick's touching list is group it: Bullet builds simulation islands, the connected components of
+ * the contact graph in which a static body belongs to no island and joins none (btSimulationIslandManager; PhysicsWorld::isBodyActive,
+ * sc_physics.cpp:593, reports its island state).  Islands are what a solver parallelises over and what sleeping goes by.  While pair
+ * islands are enabled, every run with SC_TICK_PAIR_SHAPES also labels every entity and every entry of the touching list with its island.
+ * No run flag of its own.  This build's OWN SPEC, definition by definition:
+ *   IDS        as scTickReadPairs gives them: rank << 24 | dense index.
+ *   MOVABLE    An entity e of this context is movable when e < count and (group(e) & fixed_groups) == 0, group being the low 16 bits of
+ *              its layer word (scTickUploadLayers).  Every other member id is FIXED: a set group bit, a neighbour tile's rank, an index
+ *              at or above the count.  fixed_groups is the caller's: the reference puts static bodies on layer 2 (sc_physics.cpp:372-379);
+ *              0 makes every own entity movable.
+ *   EDGES      the entries of this tick's touching list as the narrow-phase pass wrote them: the first min(touching, max_touching)
+ *              entries, pairs kept on their AABB answer and pairs named twice included.  An entry is LINKING when both members are
+ *              movable; otherwise it is ANCHORED and joins nothing.
+ *   ISLANDS    An island is a connected component of the movable entities under the linking edges; a movable entity with no linking
+ *              edge is an island of one.  label(e) = the id of the member with the smallest dense index in e's island;
+ *              label(a fixed e below the count) = SC_TICK_ISLAND_NONE.  The labels are a function of the inputs alone: they depend
+ *              neither on scheduling nor on the order inside the list.
+ *   EDGE ISLANDS   edge_island(i), for entry i of the touching list: the label of its first member if that member is movable, else the
+ *              label of its second member if that one is, else SC_TICK_ISLAND_NONE.  It sits beside contact record i and manifold
+ *              record i of the same tick, so a host groups contacts by island without a lookup.
+ *   NO MEMORY  Every flagged run recomputes from its own list.  scTickRemoveEntities, a changed count, a layer upload and a tile change
+ *              need no resync rule.
+ *   TRUNCATED LISTS   With a truncated touching list or pair list the islands are those of what was listed and may be split;
+ *              ScTickPairIslandInfo::list_truncated says so.
+ * LIMITS: a neighbour tile's bodies are fixed, so an island never crosses a tile border.  A pipelined context already refuses the flag.
+ * No sleeping state is kept: the library only groups.
+ *   scTickSetPairIslands(enable, fixed_groups) needs scTickSetPairShapes(max_touching > 0) first and refuses fixed_groups bits above 15
+ *   -- either fails with a last-error text and nothing changes.  DEVICE MEMORY: 8 bytes per entity of the context's capacity (the
+ *   union-find's word and the label), 4 bytes per entry of max_touching, 32 KB of per-workgroup tallies, 8 control words and 8 report
+ *   words; 0 frees them.  It drops
+ *   captured graphs, asks for no learn tick and fails while scTickRunPairs is pending.  scTickSetPairShapes(0) switches islands off too;
+ *   scTickSetPairShapes(another size) re-sizes their buffer and keeps fixed_groups.  A second call with another fixed_groups reaches the
+ *   next run, in graph mode too.
+ * The pass is four more launches between the narrow-phase pass and the list's report, on the pair half's stream, with no host round
+ * trip -- a thread per entity (its own root, or none), a thread per entry (a lock-free union-find: the larger root is hooked under the
+ * smaller with a compare-and-swap), a thread per entity and entry (labels, edge islands, the counts), one workgroup for the report --, the
+ * counts read on the device, so they replay from a captured graph.  In the split flow they run behind scTickRunPairs; between the halves
+ * of such a tick scTickUploadLayers is refused while islands are enabled.  A context that never enables it allocates and launches
+ * exactly what it did before.
+ * scTickReadPairIslands synchronises like scTickReadPairContacts and copies the 32 bytes of `info`, min(count, label_capacity) labels and
+ * min(edges, edge_capacity) edge islands, nothing else.  It fails when the last run did not carry SC_TICK_PAIR_SHAPES, when islands were
+ * not enabled at that run, when they were switched off since, and while scTickRunPairs is pending. */
+#define SC_TICK_ISLAND_NONE 0xFFFFFFFFu    /* the label of a fixed entity, the island of an entry with no movable member */
+typedef struct ScTickPairIslandInfo     /* 32 bytes */
+{
+  uint32_t edges;           /* entries of the touching list looked at: min(touching, max_touching) */
+  uint32_t linking;         /* entries with two movable members */
+  uint32_t anchored;        /* the others; edges == linking + anchored */
+  uint32_t islands;         /* islands of two or more members */
+  uint32_t bodies;          /* members of those islands */
+  uint32_t movable;         /* movable entities below the count */
+  uint32_t list_truncated;  /* ScTickPairShapeInfo::truncated | pairs_truncated of the same run */
+  uint32_t gave_up;         /* 0; non-zero: a lane left a loop at its bound, the labels are not to be trusted */
+} ScTickPairIslandInfo;
+int scTickSetPairIslands(ScTickContext* ctx, uint32_t enable, uint32_t fixed_groups);
+int scTickGetPairIslands(ScTickContext* ctx, uint32_t* enabled, uint32_t* fixed_groups);
+/* labels: [label_capacity], edge_islands: [edge_capacity]; either may be NULL with capacity 0 */
+int scTickReadPairIslands(ScTickContext* ctx, uint32_t* labels, uint32_t label_capacity, uint32_t* edge_islands, uint32_t edge_capacity,
+                          ScTickPairIslandInfo* info);
+
 /* ---- touch events: the tick-to-tick difference of the touching set ----
  * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on
  * every tick, with no memory.  A host that keeps a contact cache or fires trigger enter / exit wants begin / end of TOUCHING: two yawed

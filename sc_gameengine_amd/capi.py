@@ -30,6 +30,7 @@ CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 # SC_TICK_MANIFOLD_*: ScTickPairManifold::kind (scTickSetPairManifolds)
 MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
 MANIFOLD_REDUCED = 1 << 8
+ISLAND_NONE = 0xFFFFFFFF      # SC_TICK_ISLAND_NONE: the label of a fixed entity, the island of an entry with no movable member (scTickSetPairIslands)
 SWEEP_END_LOCAL, SWEEP_END_WORLD_OFFSET = 0, 1         # SC_TICK_SWEEP_END_*: what an anchored sweep's local_end is (scTickSetAnchoredSweeps)
 ASWEEP_ANSWERED, ASWEEP_NO_ANCHOR, ASWEEP_NOT_FINITE = 0, 1, 2      # SC_TICK_ASWEEP_*: ScTickSweepHit::pad of an anchored sweep
 TRIGGER_MAX_MEMBERS = 1024    # SC_TICK_TRIGGER_MAX_MEMBERS: id slots per trigger volume at most
@@ -122,6 +123,10 @@ class PairManifold(C.Structure):                         # ScTickPairManifold: 8
 
 class PairManifoldInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("written", "points", "with_one", "with_two", "with_three", "with_four", "face", "reduced")]
+
+
+class PairIslandInfo(C.Structure):                       # ScTickPairIslandInfo: 32 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("edges", "linking", "anchored", "islands", "bodies", "movable", "list_truncated", "gave_up")]
 
 
 class Frame(C.Structure):
@@ -294,6 +299,9 @@ SYMBOLS = {
     "scTickSetPairManifolds": (C.c_int, [_CTX, C.c_uint32]),
     "scTickGetPairManifolds": (C.c_int, [_CTX, U32P]),
     "scTickReadPairManifolds": (C.c_int, [_CTX, C.POINTER(PairManifold), C.c_uint32, C.POINTER(PairManifoldInfo)]),
+    "scTickSetPairIslands": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "scTickGetPairIslands": (C.c_int, [_CTX, U32P, U32P]),
+    "scTickReadPairIslands": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairIslandInfo)]),
     "scTickSetOverlapQueries": (C.c_int, [_CTX, C.c_uint32, U8P, F32P, F32P, F32P, F32P, U32P, U32P, C.c_uint32, C.c_uint32]),
     "scTickReadOverlapHits": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(OverlapInfo)]),
     "scTickSetTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, U32P, U8P, F32P, F32P, F32P, F32P, U32P, U8P, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -51,6 +51,7 @@ struct BinOutcome { bool lazy = false, stay = false, sweepOnly = false; };
 struct LastWith {
   bool sweepsExact = false;                            // SC_TICK_SWEEPS ran in EXACT mode (scTickGetSweepShapeInfo)
   bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
+  bool pairIslands = false;                            // ... and computed the islands (scTickReadPairIslands)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
   uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
   uint32_t asweepCount = 0; bool asweepsExact = false;  // what SC_TICK_ANCHORED_SWEEPS answered, and in which mode (scTickReadAnchoredSweep*, scTickGetAnchoredSweepShapeInfo)
@@ -69,6 +70,7 @@ struct TickPlan {
   bool sampled = false, carry = false, defer = false, replay = false, wholeStep = false;
   bool triggers = false;               // the trigger volumes are answered by this tick (k_trigger_volumes, at the overlap queries' launch site)
   bool anchoredSweeps = false;         // the entity-anchored sweeps are answered by this tick (k_anchored_sweeps, next to the trigger volumes' launch)
+  bool pairIslands = false;            // the pair islands are computed by this tick's pair half (launchPairIslands, inside the narrow phase's launch order)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -231,6 +233,8 @@ struct ScTickContext
   PairContactState pairContacts{};
   // scTickSetPairManifolds: the same a level up -- five float4 per entry of the touching list, the counts and their report
   PairManifoldState pairManifolds{};
+  // scTickSetPairIslands: the union-find's two words per entity of capacity, an island word per entry of the touching list, the counts and their report
+  PairIslandState pairIslands{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched)
@@ -846,11 +850,12 @@ bool resyncPairEvents(ScTickContext* c)
 // What closes every pair half, behind the pair search on its stream, now that the pair set is complete.  The narrow phase -- which of its
 // pairs touch: ONE launch of the pair-shape kernel whatever mix of SC_TICK_PAIR_SHAPES and SC_TICK_TOUCH_EVENTS the tick carries (each
 // pair is decided once), then the list's report and / or the touch state's sweep and finish -- then the pair events: what begun, what ended.
-void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickParams& p, hipStream_t s)
+void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickPlan& plan, hipStream_t s)
 {
+  const TickParams& p = plan.p;
   if (p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))
     launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                     &c->pairContacts, &c->pairManifolds, s);
+                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, s);
   if (p.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, s);
 }
 
@@ -1111,7 +1116,7 @@ bool enqueueStages(ScTickContext* c, const TickPlan& plan, bool inCapture)
       c->times[SC_TICK_K_PAIRS].push_back(ev);
       if (done) hipEventRecord(done, c->stream);
     } else launchCompactPairs(ds, pe, grid, c->stream, nullptr, done);      // (`staged` rides on the dispatch: its completion signal)
-    closePairHalf(c, ds, p, c->stream);
+    closePairHalf(c, ds, plan, c->stream);
   } else {
     const bool packToo = path.needCompact && (flags & SC_TICK_BROADPHASE) && (flags & SC_TICK_SPLIT_PAIRS);
     if (packToo) {
@@ -1145,7 +1150,7 @@ bool enqueueStages(ScTickContext* c, const TickPlan& plan, bool inCapture)
       }
       else {
         { Scoped s(c, SC_TICK_K_PAIRS, timing); launchPairs(ds, p, c->stream); }
-        closePairHalf(c, ds, p, c->stream);
+        closePairHalf(c, ds, plan, c->stream);
       }
     }
   }
@@ -1262,27 +1267,45 @@ bool sizeNarrowLevel(ScTickContext* c, State& s, Rec* State::*rec, uint32_t ctlW
   return true;
 }
 
-// The chain for a list of maxTouching entries (0: everything off), with contacts and manifolds where wanted: contacts need the list,
-// manifolds the contacts.  `set` is the level the calling setter sets.  A failed allocation leaves all three off (the allocator's text
-// stands): nothing is ever on without what it needs, or sized for another list.
-enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds };
-bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds)
+// The islands' level: an island word per entry, and the union-find's two words per entity of the context's capacity.  The caller's
+// fixed groups stay with the state across a re-size.
+bool sizeIslandLevel(ScTickContext* c, uint32_t entries, uint32_t fixedGroups)
+{
+  PairIslandState& s = c->pairIslands;
+  dfree(c, s.parent); dfree(c, s.labels); dfree(c, s.partial);
+  s.parent = nullptr; s.labels = nullptr; s.partial = nullptr;
+  if (!sizeNarrowLevel(c, s, &PairIslandState::edge, kPiCtlWords, kPiInfoWords, 1u, entries)) return false;
+  if (!entries) return true;
+  if (!dalloc(c, s.parent, c->cap) || !dalloc(c, s.labels, c->cap) || !dalloc(c, s.partial, 4u * kPiMaxBlocks)) return false;
+  s.cap = c->cap; s.fixedGroups = fixedGroups;
+  return true;
+}
+
+// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds and islands where wanted: contacts and
+// islands need the list, manifolds the contacts.  `set` is the level the calling setter sets.  A failed allocation leaves all four off
+// (the allocator's text stands): nothing is ever on without what it needs, or sized for another list.
+enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands };
+bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups)
 {
   const uint32_t contactEntries = contacts ? maxTouching : 0u;
   const uint32_t manifoldEntries = (contacts && manifolds) ? maxTouching : 0u;
+  const uint32_t islandEntries = islands ? maxTouching : 0u;
   // a level is allocated afresh when the setter sets it or the list under it is allocated afresh, freed when it has to be off, and
   // otherwise stays as it is (scTickSetPairContacts(1) leaves the list and the manifolds alone)
   const bool doList = set == kNarrowList;
   const bool doContacts = doList || set == kNarrowContacts || !contactEntries;
   const bool doManifolds = doList || set == kNarrowManifolds || !manifoldEntries;
+  const bool doIslands = doList || set == kNarrowIslands || !islandEntries;
   bool ok = true;
   if (doList) ok = sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, maxTouching);
   if (ok && doContacts) ok = sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, contactEntries);
   if (ok && doManifolds) ok = sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, manifoldEntries);
+  if (ok && doIslands) ok = sizeIslandLevel(c, islandEntries, fixedGroups);
   if (!ok) {      // everything off (0 entries: a level is freed, nothing is allocated)
     sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, 0u);
     sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, 0u);
     sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, 0u);
+    sizeIslandLevel(c, 0u, 0u);
   }
   return ok;
 }
@@ -1649,6 +1672,9 @@ int scTickUploadLayers(ScTickContext* c, uint32_t first, uint32_t count, const u
 {
   if (!c || !group || !mask) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
+  // (the island pass of a pending pair half decides "movable" from the layer words as they stand when it runs)
+  if (c->pairsPending && c->pendingTick.pairIslands)
+    return fail(c, "scTickUploadLayers is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that computes pair islands: its pair half reads the layer words as they stand");
   if (!count) return 1;
   std::vector<uint32_t> packed(count);
   for (uint32_t i = 0; i < count; ++i) {
@@ -2097,8 +2123,9 @@ static int exchangeBorders(ScTickContext* c, uint32_t parity, hipStream_t s, boo
 
 // merge what the neighbours sent, answer the ray queries, search the pairs: the half of a tile's step behind the exchange
 // `done` (may be null) rides on the half's last dispatch; false = it could not (nothing launched): record it on the stream
-static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t ps, hipEvent_t done = nullptr)
+static bool enqueuePairHalf(ScTickContext* c, const TickPlan& tick, hipStream_t ps, hipEvent_t done = nullptr)
 {
+  const TickParams& pp = tick.p;
   const DeviceState ds = stateFor(c, pp.parity);
   launchBorderMerge(ds, pp, ps);
   // (exact shapes: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
@@ -2109,7 +2136,7 @@ static bool enqueuePairHalf(ScTickContext* c, const TickParams& pp, hipStream_t 
   if (raysInPairHalf(c, pp.flags) && ds.aLane) launchAgentFrontRaysFromSnapshot(ds, pp, ps);      // ... and so do the agents' obstacle rays
   // (pair events are refused on a pipelined tile, the only flow that hands a `done` event in: nothing is queued behind a dispatch it rides on)
   const bool rode = launchPairs(ds, pp, ps, done);
-  closePairHalf(c, ds, pp, ps);      // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
+  closePairHalf(c, ds, tick, ps);      // (the touching pairs: an in-order tile's matrices are still this tick's here; a pipelined context was refused by scTickRun)
   return rode;
 }
 
@@ -2278,6 +2305,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   plan.rec.frame[0] = path.items; plan.rec.frame[1] = path.block;
   plan.triggers = path.pairsNow && (p.flags & kFlagTriggers) != 0u;
   plan.anchoredSweeps = path.pairsNow && (p.flags & kFlagAnchoredSweeps) != 0u;
+  plan.pairIslands = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairIslands.ctl != nullptr;      // (whichever half closes the pair search)
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2341,7 +2369,9 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   if (with & SC_TICK_TRIGGERS) { w.triggerCount = c->triggers.count; w.triggerMaxMembers = c->triggers.maxMembers; w.triggerMaxEvents = c->triggers.maxEvents; }
   if (with & SC_TICK_ANCHORED_SWEEPS) { w.asweepCount = c->asweeps.count; w.asweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT; }
   if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
-  if (with & SC_TICK_PAIR_SHAPES) { w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; }
+  if (with & SC_TICK_PAIR_SHAPES) {
+    w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; w.pairIslands = c->pairIslands.ctl != nullptr;
+  }
 }
 
 // The run of an empty context without a broadphase: nothing to launch, the per-tick counts read as zero.  (With the broadphase the
@@ -2390,7 +2420,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
           enqueueStages(c, plan, true);
           if (!plan.wholeStep) return 1;
           if (!exchangeBorders(c, p.parity, c->stream, true)) return 0;
-          enqueuePairHalf(c, p, c->stream);
+          enqueuePairHalf(c, plan, c->stream);
           return 1;
         })) return 0;
   } else rode = enqueueStages(c, plan, false);
@@ -2419,7 +2449,7 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
     if (c->graphMode && !tick.sampled && !tick.learn) {
       if (!replayGraph(c, ps, c->pairGraph[q], graphKey(c, tick, withExchange), "hipStreamEndCapture (pair half)", [&] {
             if (withExchange && !exchangeBorders(c, q, ps, true)) return 0;
-            enqueuePairHalf(c, pp, ps);
+            enqueuePairHalf(c, tick, ps);
             return 1;
           })) return 0;
       HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
@@ -2428,14 +2458,14 @@ static int runPendingPairs(ScTickContext* c, bool withExchange)
       EventPair ev; const bool on = timed(c, SC_TICK_K_PAIRS, tick.sampled);
       if (on) { ev = takeEvents(c); hipEventRecord(ev.a, ps); }
       if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
-      if (!enqueuePairHalf(c, pp, ps, c->pairsDone[q])) HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
+      if (!enqueuePairHalf(c, tick, ps, c->pairsDone[q])) HIP_OK(c, hipEventRecord(c->pairsDone[q], ps));
       if (on) { hipEventRecord(ev.b, ps); c->times[SC_TICK_K_PAIRS].push_back(ev); }
     }
     c->pairsInFlight[q] = true;
   } else {
     if (withExchange && !exchangeBorders(c, q, ps, false)) return 0;
     Scoped s(c, SC_TICK_K_PAIRS, tick.sampled);
-    enqueuePairHalf(c, pp, ps);
+    enqueuePairHalf(c, tick, ps);
   }
   if (c->pairEventsResyncAgain) {                     // (in-order flows only: the pair half ran on the tick stream)
     c->pairEventsResyncAgain = false;
@@ -3302,8 +3332,9 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  // (pair contacts follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
-  return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr) ? 1 : 0;
+  // (pair contacts and pair islands follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
+  return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
+                         c->pairIslands.fixedGroups) ? 1 : 0;
 }
 
 int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
@@ -3319,7 +3350,8 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   // (pair manifolds need the contacts: off with them)
-  return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr) ? 1 : 0;
+  return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
+                         c->pairIslands.fixedGroups) ? 1 : 0;
 }
 
 int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
@@ -3352,7 +3384,8 @@ int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u) ? 1 : 0;
+  return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u, c->pairIslands.ctl != nullptr,
+                         c->pairIslands.fixedGroups) ? 1 : 0;
 }
 
 int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
@@ -3371,6 +3404,41 @@ int scTickReadPairManifolds(ScTickContext* c, ScTickPairManifold* out, uint32_t 
                                  c->lastWith.pairManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)",
                                  "pair manifolds are ready after scTickRunPairs", f.ctl != nullptr, "pair manifolds were switched off since the last scTickRun")) return 0;
   return readReportAndRecords(c, info, f.info, &ScTickPairManifoldInfo::written, f.maxTouching, f.rec, sizeof(ScTickPairManifold), out, capacity) ? 1 : 0;
+}
+
+int scTickSetPairIslands(ScTickContext* c, uint32_t enable, uint32_t fixedGroups)
+{
+  static_assert(sizeof(ScTickPairIslandInfo) == 32u && sizeof(ScTickPairIslandInfo) == kPiInfoWords * sizeof(uint32_t), "the device writes the report word by word");
+  static_assert(kIslandNone == SC_TICK_ISLAND_NONE, "the island of a fixed member differs from the header's");
+  if (!c) return 0;
+  if (enable && !c->pairShapes.ctl) return fail(c, "scTickSetPairIslands needs scTickSetPairShapes(max_touching > 0) first");
+  if (fixedGroups >> 16) return fail(c, "scTickSetPairIslands: fixed_groups bits above 15 are not supported");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old fixed groups; no epoch bump: the bins are not concerned
+  return sizeNarrowPhase(c, kNarrowIslands, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, enable != 0u,
+                         enable ? fixedGroups : 0u) ? 1 : 0;
+}
+
+int scTickGetPairIslands(ScTickContext* c, uint32_t* enabled, uint32_t* fixedGroups)
+{
+  if (!c || !enabled || !fixedGroups) return c ? fail(c, "null argument") : 0;
+  *enabled = c->pairIslands.ctl ? 1u : 0u;
+  *fixedGroups = c->pairIslands.fixedGroups;
+  return 1;
+}
+
+int scTickReadPairIslands(ScTickContext* c, uint32_t* labels, uint32_t labelCapacity, uint32_t* edgeIslands, uint32_t edgeCapacity, ScTickPairIslandInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  const PairIslandState& s = c->pairIslands;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                 c->lastWith.pairIslands, "pair islands were not enabled at the last scTickRun (scTickSetPairIslands)",
+                                 "pair islands are ready after scTickRunPairs", s.ctl != nullptr, "pair islands were switched off since the last scTickRun")) return 0;
+  // the report and the edge islands like every record reader; then the labels of the entities there are now
+  if (!readReportAndRecords(c, info, s.info, &ScTickPairIslandInfo::edges, s.maxTouching, s.edge, sizeof(uint32_t), edgeIslands, edgeCapacity)) return 0;
+  const uint32_t m = std::min(std::min(c->n, s.cap), labels ? labelCapacity : 0u);
+  return (!m || (d2h(c, labels, s.labels, (size_t)m * sizeof(uint32_t)) && sync(c))) ? 1 : 0;
 }
 
 int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info)

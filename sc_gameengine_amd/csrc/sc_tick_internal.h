@@ -528,6 +528,24 @@ constexpr uint32_t kPmInfoWords = 8;
 constexpr uint32_t kManifoldNone = 0, kManifoldSingle = 1, kManifoldSegment = 2, kManifoldFace = 3, kManifoldReduced = 1u << 8;      // == SC_TICK_MANIFOLD_*
 constexpr float kManifoldSkin = 2.5e-4f, kManifoldFlat = 1e-3f;      // == SC_TICK_MANIFOLD_SKIN, SC_TICK_MANIFOLD_FLAT
 constexpr uint32_t kManifoldWave = 64;          // threads per workgroup of k_pair_manifolds: one wave, its clip polygons in LDS
+// ---- pair islands (sc_tick_pair_islands.hip; include/sc_tick.h "pair islands"): the connected components of the movable entities under
+// the linking entries of the touching list, by a lock-free union-find between the narrow-phase pass and the list's report.  All null
+// until scTickSetPairIslands: nothing is launched.
+struct PairIslandState {
+  uint32_t* edge;                 // [maxTouching]: the island of list entry i
+  uint32_t* ctl;                  // word kPiGaveUp alone
+  uint32_t* info;                 // what the last tick with islands reports (== ScTickPairIslandInfo)
+  uint32_t maxTouching;           // the touching list's
+  uint32_t* partial;              // [kPiMaxBlocks][4]: the tallies kPiLinking .. kPiMovable of every workgroup, rewritten by every launch, summed by the report
+  uint32_t* parent;               // [cap] the union-find: a dense index <= the entity's own, or kIslandNone for a fixed entity
+  uint32_t* labels;               // [cap] what scTickReadPairIslands returns; between init and flatten: != 0 = a hook landed on this root
+  uint32_t cap;                   // the context's padded capacity
+  uint32_t fixedGroups;           // the caller's: a group bit in it makes an entity fixed
+};
+constexpr uint32_t kPiLinking = 0, kPiIslands = 1, kPiBodies = 2, kPiMovable = 3, kPiGaveUp = 4, kPiCtlWords = 8;
+constexpr uint32_t kPiMaxBlocks = 2048;         // workgroups per launch of the pass at most (grid-stride beyond)
+constexpr uint32_t kPiInfoWords = 8;
+constexpr uint32_t kIslandNone = 0xFFFFFFFFu;   // == SC_TICK_ISLAND_NONE
 // The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
 // (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
 // fp32, unfused, left to right, as the header states it operation by operation.
@@ -761,8 +779,11 @@ __device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
 // (SC_TICK_TOUCH_EVENTS) may each be null, or not enabled (no ctl): then that half is not written.
 // `contacts` (scTickSetPairContacts; null or not enabled: nothing more is launched) adds k_pair_contacts between the pass and the list's report.
 // `manifolds` (scTickSetPairManifolds; the same) adds k_pair_manifolds behind the contacts' report.
+// `islands` (scTickSetPairIslands; null: this tick computes none) adds the island pass behind all of them, still ahead of the list's report.
 void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, hipStream_t s);
+                      const PairManifoldState* manifolds, const PairIslandState* islands, hipStream_t s);
+// the island pass and its report (sc_tick_pair_islands.hip), launched by launchPairShapes between the narrow-phase pass and the list's report
+void launchPairIslands(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairIslandState& islands, hipStream_t s);
 // k_pair_manifolds and its report (sc_tick_pair_manifolds.hip), launched by launchPairShapes between the contacts' report and the list's
 void launchPairManifolds(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairManifoldState& manifolds, hipStream_t s);
 // ---- bind runs of the sorted draw list and the material touch set (sc_tick_bindruns.hip; include/sc_tick.h "bind runs") ----

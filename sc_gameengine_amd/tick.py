@@ -997,6 +997,35 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairManifoldInfo._fields_}
         return rec[:min(out["written"], cap)].copy(), out
 
+    # ---- pair islands: the connected components of the movable entities under the touching list ----
+    def pair_islands(self, on, fixed_groups=2):
+        """Compute, on every run with capi.PAIR_SHAPES, the islands of the touching list (scTickSetPairIslands): entities whose group has a
+        bit of fixed_groups are fixed and join nothing (the reference's static bodies are on layer 2).  Needs set_pair_shapes(max_touching
+        > 0) first.  Drops captured graphs, costs no learn tick."""
+        self._ok(self.lib.scTickSetPairIslands(self.ctx, 1 if on else 0, int(fixed_groups)), "scTickSetPairIslands")
+
+    def pair_islands_enabled(self):
+        on, fixed = C.c_uint32(), C.c_uint32()
+        self._ok(self.lib.scTickGetPairIslands(self.ctx, C.byref(on), C.byref(fixed)), "scTickGetPairIslands")
+        return bool(on.value)
+
+    def pair_islands_fixed_groups(self):
+        """The fixed_groups the islands go by (0 while they are off)."""
+        on, fixed = C.c_uint32(), C.c_uint32()
+        self._ok(self.lib.scTickGetPairIslands(self.ctx, C.byref(on), C.byref(fixed)), "scTickGetPairIslands")
+        return int(fixed.value)
+
+    def read_pair_islands(self):
+        """(labels[count], edge_islands[n], info) of the last run with capi.PAIR_SHAPES while islands were enabled: labels[e] is the id of
+        the member with the smallest dense index in e's island (capi.ISLAND_NONE for a fixed entity), edge_islands[i] the island of entry
+        i of read_pair_shapes()'s list; info is a dict (edges, linking, anchored, islands, bodies, movable, list_truncated, gave_up)."""
+        cap = getattr(self, "_max_touching", 0)
+        labels, edges = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        info = capi.PairIslandInfo()
+        self._ok(self.lib.scTickReadPairIslands(self.ctx, _u(labels), self.n, _u(edges), cap, C.byref(info)), "scTickReadPairIslands")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairIslandInfo._fields_}
+        return labels[:self.n].copy(), edges[:min(out["edges"], cap)].copy(), out
+
     # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
     def set_touch_events(self, max_tracked, max_events):
         """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report
