@@ -1294,6 +1294,80 @@ int scTickGetPairIslands(ScTickContext* ctx, uint32_t* enabled, uint32_t* fixed_
 int scTickReadPairIslands(ScTickContext* ctx, uint32_t* labels, uint32_t label_capacity, uint32_t* edge_islands, uint32_t edge_capacity,
                           ScTickPairIslandInfo* info);
 
+/* ---- pair persistence: this run's contact points matched to the last run's ----
+ * Every flagged run writes its manifolds from nothing; a rigid-body host needs to know which of this tick's contact points is the same
+ * point as last tick's -- for warm starting, accumulated impulses and contact age (Bullet's btPersistentManifold behind
+ * sc_physics.cpp:218-225).  While pair persistence is enabled, every run with SC_TICK_PAIR_SHAPES also matches each entry of its touching
+ * list to the entry of the same pair in the last such run, each manifold point of the entry to a point of that earlier manifold, carries
+ * a per-point age and a 16-byte caller payload across the match, and remembers this run for the next one.  No run flag of its own.  This
+ * build's OWN SPEC, operation by operation; all arithmetic fp32, unfused, left to right; dot as the touching pairs define it.
+ *   LOCAL POINT   Entry i with listed pair (a, b) and manifold record i of this run.  For each slot s < count: c_k and n_k are the columns
+ *              of a's world matrix this tick and their squared norms as the touching pairs form them; u_k = c_k / sqrt(n_k) per component
+ *              (the box frame's u, whatever a's collider type); r = point[s] - T_a; x_s,k = dot(r, u_k).  A record with count == 0
+ *              (SC_TICK_MANIFOLD_NONE) has no local points.  The record's stored fp32 point is the input.
+ *   REMEMBERED RUN   the last run with SC_TICK_PAIR_SHAPES while persistence was enabled, unless a resync (below) came since.  Its
+ *              entries are the first min(touching, max_touching) of its list; the remembered entry of a pair is the smallest entry index
+ *              of that run that names the pair.
+ *   PAIR MATCH   prev_entry is that index, or SC_TICK_PERSIST_NONE when the pair is not remembered or nothing is.  A pair that this
+ *              run's list names twice matches the same remembered entry from both entries.
+ *   POINT MATCH   greedy, in slot order, one to one.  m2 = match_dist * match_dist, one fp32 product formed once per run.  For
+ *              s = 0 .. count-1, over the remembered entry's slots t = 0 .. count_old-1 that no earlier s took, y_t its local points:
+ *              e_k = x_s,k - y_t,k; d = (e_0*e_0 + e_1*e_1) + e_2*e_2; t is a candidate when d <= m2.  The first candidate is the best; a
+ *              later one replaces it only when its d is strictly smaller.  With a best t: prev_slot[s] = t, age[s] = min(age_old[t] + 1,
+ *              255), payload[s] = payload_old[t] bit for bit, and t is taken.  Otherwise prev_slot[s] = 0xFF, age[s] = 0 and payload[s] is
+ *              four +0.  A NaN d matches nothing.  Slots at or above count are 0xFF, 0 and +0.
+ *   RESYNC     on the first flagged run after enabling, after scTickRemoveEntities, after a shrinking scTickSetEntityCount, after
+ *              scTickSetTile to another rank, and after scTickSetPairShapes with another size: nothing is remembered, every prev_entry is
+ *              NONE and info.resync = 1.  A rename between the halves of a split tick is forgotten again behind the pair half, as for
+ *              pair events.  Runs without SC_TICK_PAIR_SHAPES leave the memory alone.  A same-value second call of the setter keeps the
+ *              memory; a call with another match_dist keeps it too and reaches the next run, in graph mode as well.
+ *   TRUNCATED LISTS   Entries beyond max_touching are neither answered nor remembered.  info.list_truncated is
+ *              ScTickPairShapeInfo::truncated | pairs_truncated of the run.  The tables are sized by max_touching: they cannot overflow.
+ * LIMITS: matching is in a's frame only, with no drift test of a remembered point against b and no feature ids; a neighbour tile's shapes
+ * give NONE and so no points; a pipelined context already refuses the flag.
+ *   scTickSetPairPersistence(enable, match_dist) needs pair manifolds enabled, and match_dist finite and > 0 -- otherwise it fails with a
+ *   last-error text and nothing changes.  DEVICE MEMORY, per entry of max_touching: the 16-byte record, and on each of two sides 48
+ *   bytes of local points, 16 bytes of ages and count and 64 bytes of payload rows (272 bytes); per side a table of slots = the power
+ *   of two >= max(2 * max_touching, 64), 12 bytes a slot; 16 KB of per-workgroup tallies, 16 control words and 16 report words; 0 frees
+ *   them.  It drops captured graphs, asks for no learn tick and fails while scTickRunPairs is pending.  scTickSetPairManifolds(0),
+ *   scTickSetPairContacts(0) and scTickSetPairShapes(0) switch persistence off too.
+ * The pass is three more launches behind the manifolds', ahead of the list's report, on the pair half's stream, with no host round trip
+ * -- a thread per entry (enter, look up, match, write), a thread per slot (the remembered side's table cleared: the next run's empty
+ * "current"), one workgroup for the report, which turns the sides over --, the counts, the side and the validity read on the device, so
+ * both parities of the tick replay from captured graphs.  A context that never enables it allocates and launches exactly what it did before.
+ *   scTickWritePairPayloads overwrites rows [first, first + count) of the last flagged run's payload rows -- the rows the next flagged
+ *   run carries from --, ordered behind that run on its stream.  It fails when the last run did not carry SC_TICK_PAIR_SHAPES with
+ *   persistence on, when first + count exceeds that run's `written`, and while scTickRunPairs is pending.  scTickReadPairPayloads
+ *   returns min(written, capacity) of those rows as they stand: what the run carried, then what was written.
+ * The reads synchronise and fail like scTickReadPairManifolds. */
+#define SC_TICK_PERSIST_NONE 0xFFFFFFFFu   /* prev_entry of a pair that is not remembered */
+typedef struct ScTickPairPersist        /* 16 bytes, record i beside manifold record i */
+{
+  uint32_t prev_entry;                  /* entry of the remembered run's list, or SC_TICK_PERSIST_NONE */
+  uint8_t  prev_slot[4];                /* slot of that entry's manifold, or 0xFF */
+  uint8_t  age[4];                      /* flagged runs this point has been matched for, saturating at 255 */
+  uint32_t reserved;                    /* 0 */
+} ScTickPairPersist;
+typedef struct ScTickPairPersistInfo    /* 32 bytes */
+{
+  uint32_t written;         /* min(touching, max_touching) */
+  uint32_t kept_pairs;      /* entries with a prev_entry */
+  uint32_t new_pairs;       /* the others; written == kept_pairs + new_pairs */
+  uint32_t kept_points;     /* slots below count with a prev_slot */
+  uint32_t new_points;      /* slots below count without */
+  uint32_t resync;          /* 1: nothing was remembered */
+  uint32_t list_truncated;  /* ScTickPairShapeInfo::truncated | pairs_truncated of the same run */
+  uint32_t gave_up;         /* 0; non-zero: a probe loop reached its bound (it cannot at load one half), the records are not to be trusted */
+} ScTickPairPersistInfo;
+int scTickSetPairPersistence(ScTickContext* ctx, uint32_t enable, float match_dist);
+int scTickGetPairPersistence(ScTickContext* ctx, uint32_t* enabled, float* match_dist);
+/* out: [capacity] records, may be NULL with capacity 0 */
+int scTickReadPairPersistence(ScTickContext* ctx, ScTickPairPersist* out, uint32_t capacity, ScTickPairPersistInfo* info);
+/* rows: [count][4][4] floats -- four payload rows of four words per entry */
+int scTickWritePairPayloads(ScTickContext* ctx, const float* rows, uint32_t first, uint32_t count);
+/* rows: [capacity][4][4] floats, may be NULL with capacity 0 */
+int scTickReadPairPayloads(ScTickContext* ctx, float* rows, uint32_t capacity);
+
 /* ---- touch events: the tick-to-tick difference of the touching set ----
  * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on
  * every tick, with no memory.  A host that keeps a contact cache or fires trigger enter / exit wants begin / end of TOUCHING: two yawed

@@ -30,6 +30,7 @@ CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 # SC_TICK_MANIFOLD_*: ScTickPairManifold::kind (scTickSetPairManifolds)
 MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
 MANIFOLD_REDUCED = 1 << 8
+PERSIST_NONE = 0xFFFFFFFF     # SC_TICK_PERSIST_NONE: ScTickPairPersist::prev_entry of a pair that is not remembered (scTickSetPairPersistence)
 ISLAND_NONE = 0xFFFFFFFF      # SC_TICK_ISLAND_NONE: the label of a fixed entity, the island of an entry with no movable member (scTickSetPairIslands)
 SWEEP_END_LOCAL, SWEEP_END_WORLD_OFFSET = 0, 1         # SC_TICK_SWEEP_END_*: what an anchored sweep's local_end is (scTickSetAnchoredSweeps)
 ASWEEP_ANSWERED, ASWEEP_NO_ANCHOR, ASWEEP_NOT_FINITE = 0, 1, 2      # SC_TICK_ASWEEP_*: ScTickSweepHit::pad of an anchored sweep
@@ -127,6 +128,14 @@ class PairManifoldInfo(C.Structure):
 
 class PairIslandInfo(C.Structure):                       # ScTickPairIslandInfo: 32 bytes
     _fields_ = [(n, C.c_uint32) for n in ("edges", "linking", "anchored", "islands", "bodies", "movable", "list_truncated", "gave_up")]
+
+
+class PairPersist(C.Structure):                          # ScTickPairPersist: 16 bytes
+    _fields_ = [("prev_entry", C.c_uint32), ("prev_slot", C.c_uint8 * 4), ("age", C.c_uint8 * 4), ("reserved", C.c_uint32)]
+
+
+class PairPersistInfo(C.Structure):                      # ScTickPairPersistInfo: 32 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("written", "kept_pairs", "new_pairs", "kept_points", "new_points", "resync", "list_truncated", "gave_up")]
 
 
 class Frame(C.Structure):
@@ -302,6 +311,11 @@ SYMBOLS = {
     "scTickSetPairIslands": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "scTickGetPairIslands": (C.c_int, [_CTX, U32P, U32P]),
     "scTickReadPairIslands": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairIslandInfo)]),
+    "scTickSetPairPersistence": (C.c_int, [_CTX, C.c_uint32, C.c_float]),
+    "scTickGetPairPersistence": (C.c_int, [_CTX, U32P, F32P]),
+    "scTickReadPairPersistence": (C.c_int, [_CTX, C.POINTER(PairPersist), C.c_uint32, C.POINTER(PairPersistInfo)]),
+    "scTickWritePairPayloads": (C.c_int, [_CTX, F32P, C.c_uint32, C.c_uint32]),
+    "scTickReadPairPayloads": (C.c_int, [_CTX, F32P, C.c_uint32]),
     "scTickSetOverlapQueries": (C.c_int, [_CTX, C.c_uint32, U8P, F32P, F32P, F32P, F32P, U32P, U32P, C.c_uint32, C.c_uint32]),
     "scTickReadOverlapHits": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(OverlapInfo)]),
     "scTickSetTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, U32P, U8P, F32P, F32P, F32P, F32P, U32P, U8P, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -52,6 +52,7 @@ struct LastWith {
   bool sweepsExact = false;                            // SC_TICK_SWEEPS ran in EXACT mode (scTickGetSweepShapeInfo)
   bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
   bool pairIslands = false;                            // ... and computed the islands (scTickReadPairIslands)
+  bool pairPersist = false;                            // ... and matched the contact points to the run before (scTickReadPairPersistence, the payload calls)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
   uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
   uint32_t asweepCount = 0; bool asweepsExact = false;  // what SC_TICK_ANCHORED_SWEEPS answered, and in which mode (scTickReadAnchoredSweep*, scTickGetAnchoredSweepShapeInfo)
@@ -71,6 +72,7 @@ struct TickPlan {
   bool triggers = false;               // the trigger volumes are answered by this tick (k_trigger_volumes, at the overlap queries' launch site)
   bool anchoredSweeps = false;         // the entity-anchored sweeps are answered by this tick (k_anchored_sweeps, next to the trigger volumes' launch)
   bool pairIslands = false;            // the pair islands are computed by this tick's pair half (launchPairIslands, inside the narrow phase's launch order)
+  bool pairPersist = false;            // the contact points are matched to the last flagged run's by this tick's pair half (launchPairPersist, the same)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -235,6 +237,8 @@ struct ScTickContext
   PairManifoldState pairManifolds{};
   // scTickSetPairIslands: the union-find's two words per entity of capacity, an island word per entry of the touching list, the counts and their report
   PairIslandState pairIslands{};
+  // scTickSetPairPersistence: two sides of table, local points, ages and payload rows per entry of the touching list, the records and their report
+  PairPersistState pairPersist{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched)
@@ -841,9 +845,13 @@ bool resyncPairEvents(ScTickContext* c)
     const hipError_t e = hipMemsetAsync(c->touchEventSlab, 0, c->touchEventSlabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (touch events)", e);
   }
+  if (c->pairPersist.ctl) {                           // (pair persistence remembers entries by the same ids: both tables empty, nothing valid)
+    const hipError_t e = hipMemsetAsync(c->pairPersist.ctl, 0, c->pairPersist.slabBytes, c->stream);
+    if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair persistence)", e);
+  }
   // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
   // the rename -- runPendingPairs forgets it again behind that half
-  if (c->pairsPending && (c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS))) c->pairEventsResyncAgain = true;
+  if (c->pairsPending && ((c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS)) || c->pendingTick.pairPersist)) c->pairEventsResyncAgain = true;
   return true;
 }
 
@@ -855,7 +863,7 @@ void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickPlan& plan
   const TickParams& p = plan.p;
   if (p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))
     launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, s);
+                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, plan.pairPersist ? &c->pairPersist : nullptr, s);
   if (p.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, s);
 }
 
@@ -1281,12 +1289,44 @@ bool sizeIslandLevel(ScTickContext* c, uint32_t entries, uint32_t fixedGroups)
   return true;
 }
 
-// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds and islands where wanted: contacts and
-// islands need the list, manifolds the contacts.  `set` is the level the calling setter sets.  A failed allocation leaves all four off
-// (the allocator's text stands): nothing is ever on without what it needs, or sized for another list.
-enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands };
-bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups)
+// The persistence level: a record per entry, two sides of local points (with ages and counts) and payload rows per entry, and one slab of
+// control words and both sides' tables, which a resync zeroes as a whole.  The caller's match distance stays with the state across a re-size.
+bool sizePersistLevel(ScTickContext* c, uint32_t entries)
 {
+  PairPersistState& s = c->pairPersist;
+  const float matchDist = s.matchDist;
+  dfree(c, s.rec); dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.partial);
+  for (int k = 0; k < 2; ++k) { dfree(c, s.local[k]); dfree(c, s.payload[k]); }
+  s = PairPersistState{};
+  if (!entries) return true;
+  uint64_t slots = 64u;
+  while (slots < 2ull * entries) slots <<= 1;
+  if (slots > (1ull << 31)) return fail(c, "pair persistence: max_touching is too large for its tables");
+  // [control words][key 0][key 1][value 0][value 1]: the keys 8-byte aligned behind 64 bytes of control words
+  const size_t words = (size_t)kPpCtlWords + 2u * 2u * (size_t)slots + 2u * (size_t)slots;
+  bool ok = dalloc(c, s.ctl, words) && dalloc(c, s.info, kPpInfoWords) && dalloc(c, s.rec, entries) && dalloc(c, s.partial, 4u * kPpMaxBlocks);
+  for (int k = 0; k < 2 && ok; ++k) ok = dalloc(c, s.local[k], 4u * (size_t)entries) && dalloc(c, s.payload[k], 4u * (size_t)entries);
+  if (!ok) {
+    dfree(c, s.rec); dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.partial);
+    for (int k = 0; k < 2; ++k) { dfree(c, s.local[k]); dfree(c, s.payload[k]); }
+    s = PairPersistState{};
+    return false;
+  }
+  s.key[0] = reinterpret_cast<unsigned long long*>(s.ctl + kPpCtlWords); s.key[1] = s.key[0] + slots;
+  s.val[0] = reinterpret_cast<uint32_t*>(s.key[1] + slots); s.val[1] = s.val[0] + slots;
+  s.slots = (uint32_t)slots; s.slabBytes = words * sizeof(uint32_t);
+  s.maxTouching = entries; s.matchDist = matchDist;
+  return true;
+}
+
+// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds, islands and persistence where wanted:
+// contacts and islands need the list, manifolds the contacts, persistence the manifolds.  `set` is the level the calling setter sets.  A
+// failed allocation leaves all five off (the allocator's text stands): nothing is ever on without what it needs, or sized for another list.
+enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands, kNarrowPersist };
+bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups, bool persist)
+{
+  // (persistence holds a memory: it is allocated afresh -- a resync -- only when its size changes, and so survives a same-size scTickSetPairShapes)
+  const uint32_t persistEntries = (contacts && manifolds && persist) ? maxTouching : 0u;
   const uint32_t contactEntries = contacts ? maxTouching : 0u;
   const uint32_t manifoldEntries = (contacts && manifolds) ? maxTouching : 0u;
   const uint32_t islandEntries = islands ? maxTouching : 0u;
@@ -1301,11 +1341,13 @@ bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bo
   if (ok && doContacts) ok = sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, contactEntries);
   if (ok && doManifolds) ok = sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, manifoldEntries);
   if (ok && doIslands) ok = sizeIslandLevel(c, islandEntries, fixedGroups);
+  if (ok && persistEntries != c->pairPersist.maxTouching) ok = sizePersistLevel(c, persistEntries);
   if (!ok) {      // everything off (0 entries: a level is freed, nothing is allocated)
     sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, 0u);
     sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, 0u);
     sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, 0u);
     sizeIslandLevel(c, 0u, 0u);
+    sizePersistLevel(c, 0u);
   }
   return ok;
 }
@@ -2306,6 +2348,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   plan.triggers = path.pairsNow && (p.flags & kFlagTriggers) != 0u;
   plan.anchoredSweeps = path.pairsNow && (p.flags & kFlagAnchoredSweeps) != 0u;
   plan.pairIslands = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairIslands.ctl != nullptr;      // (whichever half closes the pair search)
+  plan.pairPersist = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairPersist.ctl != nullptr;
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2371,6 +2414,7 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
   if (with & SC_TICK_PAIR_SHAPES) {
     w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; w.pairIslands = c->pairIslands.ctl != nullptr;
+    w.pairPersist = c->pairPersist.ctl != nullptr;
   }
 }
 
@@ -3334,7 +3378,7 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   // (pair contacts and pair islands follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
   return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
@@ -3351,7 +3395,7 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   // (pair manifolds need the contacts: off with them)
   return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
@@ -3385,7 +3429,7 @@ int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
@@ -3417,7 +3461,7 @@ int scTickSetPairIslands(ScTickContext* c, uint32_t enable, uint32_t fixedGroups
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old fixed groups; no epoch bump: the bins are not concerned
   return sizeNarrowPhase(c, kNarrowIslands, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, enable != 0u,
-                         enable ? fixedGroups : 0u) ? 1 : 0;
+                         enable ? fixedGroups : 0u, c->pairPersist.ctl != nullptr) ? 1 : 0;
 }
 
 int scTickGetPairIslands(ScTickContext* c, uint32_t* enabled, uint32_t* fixedGroups)
@@ -3439,6 +3483,82 @@ int scTickReadPairIslands(ScTickContext* c, uint32_t* labels, uint32_t labelCapa
   if (!readReportAndRecords(c, info, s.info, &ScTickPairIslandInfo::edges, s.maxTouching, s.edge, sizeof(uint32_t), edgeIslands, edgeCapacity)) return 0;
   const uint32_t m = std::min(std::min(c->n, s.cap), labels ? labelCapacity : 0u);
   return (!m || (d2h(c, labels, s.labels, (size_t)m * sizeof(uint32_t)) && sync(c))) ? 1 : 0;
+}
+
+int scTickSetPairPersistence(ScTickContext* c, uint32_t enable, float matchDist)
+{
+  static_assert(sizeof(ScTickPairPersist) == 16u && sizeof(ScTickPairPersist) == sizeof(uint4), "the device writes the record with one 16-byte store");
+  static_assert(sizeof(ScTickPairPersistInfo) == 32u && sizeof(ScTickPairPersistInfo) <= kPpInfoSide * sizeof(uint32_t), "the device writes the report word by word");
+  static_assert(kPersistNone == SC_TICK_PERSIST_NONE, "the entry of an unmatched pair differs from the header's");
+  if (!c) return 0;
+  if (enable && !c->pairManifolds.ctl) return fail(c, "scTickSetPairPersistence needs scTickSetPairManifolds(1) first");
+  if (enable && !(std::isfinite(matchDist) && matchDist > 0.0f)) return fail(c, "scTickSetPairPersistence: match_dist must be finite and > 0");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old match distance; no epoch bump: the bins are not concerned
+  if (enable && c->pairPersist.ctl) { c->pairPersist.matchDist = matchDist; return 1; }      // (already on: what is remembered stays)
+  if (!sizeNarrowPhase(c, kNarrowPersist, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
+                       c->pairIslands.fixedGroups, enable != 0u)) return 0;
+  c->pairPersist.matchDist = enable ? matchDist : 0.0f;
+  return 1;
+}
+
+int scTickGetPairPersistence(ScTickContext* c, uint32_t* enabled, float* matchDist)
+{
+  if (!c || !enabled || !matchDist) return c ? fail(c, "null argument") : 0;
+  *enabled = c->pairPersist.ctl ? 1u : 0u;
+  *matchDist = c->pairPersist.ctl ? c->pairPersist.matchDist : 0.0f;
+  return 1;
+}
+
+namespace {
+// the gate of the persistence readers and of the payload write: the last run matched, its pair half is through, the buffers are still there
+bool pairPersistResult(ScTickContext* c)
+{
+  return bind(c) && lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                  c->lastWith.pairPersist, "pair persistence was not enabled at the last scTickRun (scTickSetPairPersistence)",
+                                  "pair persistence is ready after scTickRunPairs", c->pairPersist.ctl != nullptr,
+                                  "pair persistence was switched off since the last scTickRun");
+}
+// that run's `written` and the side it filled, as the finish kernel left them
+bool pairPersistFilled(ScTickContext* c, uint32_t& written, uint32_t& side)
+{
+  uint32_t w[kPpInfoWords];
+  if (!d2h(c, w, c->pairPersist.info, sizeof w) || !sync(c)) return false;
+  written = std::min(w[0], c->pairPersist.maxTouching); side = w[kPpInfoSide] & 1u;
+  return true;
+}
+} // namespace
+
+int scTickReadPairPersistence(ScTickContext* c, ScTickPairPersist* out, uint32_t capacity, ScTickPairPersistInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  const PairPersistState& s = c->pairPersist;
+  if (!pairPersistResult(c)) return 0;
+  return readReportAndRecords(c, info, s.info, &ScTickPairPersistInfo::written, s.maxTouching, s.rec, sizeof(ScTickPairPersist), out, capacity) ? 1 : 0;
+}
+
+int scTickWritePairPayloads(ScTickContext* c, const float* rows, uint32_t first, uint32_t count)
+{
+  if (!c || (!rows && count)) return c ? fail(c, "null argument") : 0;
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!pairPersistResult(c)) return 0;
+  uint32_t written = 0, side = 0;
+  if (!pairPersistFilled(c, written, side)) return 0;
+  if ((uint64_t)first + count > written) return fail(c, "scTickWritePairPayloads: the range exceeds the records the last run wrote");
+  if (!count) return 1;
+  // (the rows the next flagged run carries from: behind the run on its stream)
+  return (h2d(c, c->pairPersist.payload[side] + 4u * (size_t)first, rows, (size_t)count * 4u * sizeof(float4)) && sync(c)) ? 1 : 0;
+}
+
+int scTickReadPairPayloads(ScTickContext* c, float* rows, uint32_t capacity)
+{
+  if (!c) return 0;
+  if (!pairPersistResult(c)) return 0;
+  uint32_t written = 0, side = 0;
+  if (!pairPersistFilled(c, written, side)) return 0;
+  const uint32_t m = std::min(written, rows ? capacity : 0u);
+  return (!m || (d2h(c, rows, c->pairPersist.payload[side], (size_t)m * 4u * sizeof(float4)) && sync(c))) ? 1 : 0;
 }
 
 int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info)

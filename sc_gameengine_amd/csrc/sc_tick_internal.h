@@ -546,6 +546,31 @@ constexpr uint32_t kPiLinking = 0, kPiIslands = 1, kPiBodies = 2, kPiMovable = 3
 constexpr uint32_t kPiMaxBlocks = 2048;         // workgroups per launch of the pass at most (grid-stride beyond)
 constexpr uint32_t kPiInfoWords = 8;
 constexpr uint32_t kIslandNone = 0xFFFFFFFFu;   // == SC_TICK_ISLAND_NONE
+// ---- pair persistence (sc_tick_pair_persist.hip; include/sc_tick.h "pair persistence"): every entry of the touching list matched to the
+// entry of the same pair in the last flagged run, its manifold points matched to that entry's points in `a`'s frame, an age and a
+// 16-byte payload per point carried across the match.  Two sides, used in turn like the pair events' tables: the one the last flagged run
+// filled ("remembered") is probed and -- by the sweep -- emptied, the other ("current") is filled.  All null until
+// scTickSetPairPersistence: nothing is launched.
+struct PairPersistState {
+  uint4* rec;                     // [maxTouching]: record i of list entry i (== ScTickPairPersist)
+  uint32_t* ctl;                  // kPp* words below, and behind them in the same allocation (`slabBytes` in all) the tables of both sides:
+                                  // zero bytes all over = nothing remembered
+  uint32_t* info;                 // [kPpInfoWords]: what the last flagged run reports (== ScTickPairPersistInfo), then the side it filled
+  uint32_t maxTouching;           // the touching list's
+  unsigned long long* key[2];     // [slots] each: a << 32 | b of a listed pair, 0 = empty
+  uint32_t* val[2];               // [slots] each: ~(the smallest entry index that names the slot's pair), kept by an atomic maximum; 0 = none
+  float4* local[2];               // [4 * maxTouching] each: entry i's four local points (twelve floats), then (ages, count, 0, 0)
+  float4* payload[2];             // [4 * maxTouching] each: entry i's four payload rows
+  uint32_t* partial;              // [kPpMaxBlocks][4]: every workgroup's tallies, rewritten by every launch, summed by the finish
+  uint32_t slots;                 // power of two >= 2 * maxTouching (and >= 64)
+  float matchDist;                // the caller's
+  size_t slabBytes;
+};
+constexpr uint32_t kPpCur = 0, kPpValid = 1, kPpGaveUp = 2, kPpCtlWords = 16;
+constexpr uint32_t kPpKeptPairs = 0, kPpKeptPoints = 1, kPpNewPoints = 2;      // a workgroup's tallies (the fourth word is not used)
+constexpr uint32_t kPpMaxBlocks = 1024;         // workgroups of k_pair_persist_match at most (grid-stride beyond)
+constexpr uint32_t kPpInfoWords = 16, kPpInfoSide = 8;
+constexpr uint32_t kPersistNone = 0xFFFFFFFFu;  // == SC_TICK_PERSIST_NONE
 // The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
 // (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
 // fp32, unfused, left to right, as the header states it operation by operation.
@@ -780,8 +805,12 @@ __device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
 // `contacts` (scTickSetPairContacts; null or not enabled: nothing more is launched) adds k_pair_contacts between the pass and the list's report.
 // `manifolds` (scTickSetPairManifolds; the same) adds k_pair_manifolds behind the contacts' report.
 // `islands` (scTickSetPairIslands; null: this tick computes none) adds the island pass behind all of them, still ahead of the list's report.
+// `persist` (scTickSetPairPersistence; null: this tick matches nothing) adds the persistence pass behind the manifolds', ahead of the list's report.
 void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, const PairIslandState* islands, hipStream_t s);
+                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, hipStream_t s);
+// the persistence pass, its sweep and its report (sc_tick_pair_persist.hip), launched by launchPairShapes behind launchPairManifolds
+void launchPairPersist(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairManifoldState& manifolds, const PairPersistState& persist,
+                       hipStream_t s);
 // the island pass and its report (sc_tick_pair_islands.hip), launched by launchPairShapes between the narrow-phase pass and the list's report
 void launchPairIslands(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairIslandState& islands, hipStream_t s);
 // k_pair_manifolds and its report (sc_tick_pair_manifolds.hip), launched by launchPairShapes between the contacts' report and the list's

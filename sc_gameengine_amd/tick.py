@@ -1026,6 +1026,55 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairIslandInfo._fields_}
         return labels[:self.n].copy(), edges[:min(out["edges"], cap)].copy(), out
 
+    # ---- pair persistence: this run's manifold points matched to the last flagged run's, with an age and a payload per point ----
+    PERSIST_DTYPE = np.dtype([("prev_entry", np.uint32), ("prev_slot", np.uint8, 4), ("age", np.uint8, 4), ("reserved", np.uint32)])
+
+    def pair_persistence(self, on, match_dist=0.02):
+        """Match, on every run with capi.PAIR_SHAPES, every entry of the touching list and every point of its manifold to the last such
+        run's (scTickSetPairPersistence): points match within match_dist metres in the first member's frame (the default is Bullet's
+        contact breaking threshold).  Needs set_pair_manifolds(True) first.  Drops captured graphs, costs no learn tick; a second call
+        while it is on keeps what is remembered."""
+        self._ok(self.lib.scTickSetPairPersistence(self.ctx, 1 if on else 0, float(match_dist)), "scTickSetPairPersistence")
+
+    def _pair_persistence(self):
+        on, dist = C.c_uint32(), C.c_float()
+        self._ok(self.lib.scTickGetPairPersistence(self.ctx, C.byref(on), C.byref(dist)), "scTickGetPairPersistence")
+        return bool(on.value), float(dist.value)
+
+    def pair_persistence_enabled(self):
+        return self._pair_persistence()[0]
+
+    def pair_persistence_match_dist(self):
+        """The match_dist the matching goes by (0 while it is off)."""
+        return self._pair_persistence()[1]
+
+    def write_pair_payloads(self, rows, first=0):
+        """Overwrite the payload rows [first, first + len(rows)) of the last flagged run -- float32 [n][4][4], four words for each of an
+        entry's four slots -- which the next flagged run carries to the points it matches (scTickWritePairPayloads): where a solver
+        leaves its accumulated impulses."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 4, 4)
+        self._ok(self.lib.scTickWritePairPayloads(self.ctx, _f(rows), int(first), len(rows)), "scTickWritePairPayloads")
+
+    def read_pair_payloads(self):
+        """rows[n][4][4] of the last flagged run as they stand: what the run carried, then what write_pair_payloads wrote."""
+        cap = getattr(self, "_max_touching", 0)
+        info = capi.PairPersistInfo()
+        self._ok(self.lib.scTickReadPairPersistence(self.ctx, None, 0, C.byref(info)), "scTickReadPairPersistence")
+        rows = np.zeros((max(cap, 1), 4, 4), np.float32)
+        self._ok(self.lib.scTickReadPairPayloads(self.ctx, _f(rows), cap), "scTickReadPairPayloads")
+        return rows[:min(int(info.written), cap)].copy()
+
+    def read_pair_persistence(self):
+        """(records[n], info) of the last run with capi.PAIR_SHAPES while persistence was enabled: a structured array (prev_entry,
+        prev_slot[4], age[4], reserved), record i for entry i of read_pair_shapes()'s list and record i of read_pair_manifolds(); info is a
+        dict (written, kept_pairs, new_pairs, kept_points, new_points, resync, list_truncated, gave_up)."""
+        cap = getattr(self, "_max_touching", 0)
+        rec = np.zeros(max(cap, 1), self.PERSIST_DTYPE)
+        info = capi.PairPersistInfo()
+        self._ok(self.lib.scTickReadPairPersistence(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairPersist)), cap, C.byref(info)), "scTickReadPairPersistence")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairPersistInfo._fields_}
+        return rec[:min(out["written"], cap)].copy(), out
+
     # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
     def set_touch_events(self, max_tracked, max_events):
         """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report
