@@ -1259,7 +1259,7 @@ int scTickReadPairManifolds(ScTickContext* ctx, ScTickPairManifold* out, uint32_
  *   TRUNCATED LISTS   With a truncated touching list or pair list the islands are those of what was listed and may be split;
  *              ScTickPairIslandInfo::list_truncated says so.
  * LIMITS: a neighbour tile's bodies are fixed, so an island never crosses a tile border.  A pipelined context already refuses the flag.
- * No sleeping state is kept: the library only groups.
+ * The islands keep no sleeping state: they only group (the rest state is pair sleep's, below, opt-in).
  *   scTickSetPairIslands(enable, fixed_groups) needs scTickSetPairShapes(max_touching > 0) first and refuses fixed_groups bits above 15
  *   -- either fails with a last-error text and nothing changes.  DEVICE MEMORY: 8 bytes per entity of the context's capacity (the
  *   union-find's word and the label), 4 bytes per entry of max_touching, 32 KB of per-workgroup tallies, 8 control words and 8 report
@@ -1367,6 +1367,79 @@ int scTickReadPairPersistence(ScTickContext* ctx, ScTickPairPersist* out, uint32
 int scTickWritePairPayloads(ScTickContext* ctx, const float* rows, uint32_t first, uint32_t count);
 /* rows: [capacity][4][4] floats, may be NULL with capacity 0 */
 int scTickReadPairPayloads(ScTickContext* ctx, float* rows, uint32_t capacity);
+
+/* ---- pair sleep: islands at rest fall asleep and wake ----
+ * The islands are what sleeping goes by; the one step of Bullet's island pipeline a rigid-body host still ran on the CPU every tick is which
+ * islands are at rest, which bodies just fell asleep and which were just woken (PhysicsWorld::isBodyActive / activateBody,
+ * sc_physics.h:167-168; the traffic AI asks every frame, sc_traffic_ai.cpp:382-383).  The library has no velocities; it has what Bullet's
+ * thresholds stand in for: every tick's world matrices, resident, next to the island labels.  While pair sleep is enabled, every run with
+ * SC_TICK_PAIR_SHAPES (pair islands being on) also does the following, on the world rows w_0, w_1, w_2 of the run (three float4 per
+ * entity, .w the translation) as its narrow phase reads them.  No run flag of its own.  This build's OWN SPEC:
+ *   STILL      Every own entity below the count keeps an ANCHOR POSE of three rows a_0..a_2 (48 bytes).  still(e) holds when
+ *              |w_r.w - a_r.w| <= lin_tol for the three rows and |w_r.{x,y,z} - a_r.{x,y,z}| <= ang_tol for the nine other elements: plain
+ *              fp32 -- subtract, absolute value, compare.  A NaN anywhere (a row or the anchor) makes the entity not still.  When not
+ *              still, the anchor becomes the current pose: a creep of 0.4 * tol per run trips on the third run and starts over.
+ *   REST       rest(e) = still ? min(rest_old + 1, 255) : 0 -- 8 bits, saturating like persistence's age; rest_runs is in 1 .. 255.
+ *              Tracked for movable and fixed entities alike (movable and fixed as the pair islands define them).
+ *   AWAKE ISLANDS   An island of this run (by this run's labels) is awake when a member has rest < rest_runs, or when an anchored entry
+ *              of the listed touching list -- one member movable, the other not -- names one of its members together with an own
+ *              fixed entity below the count that has rest == 0 in this run (a kinematic platform under a stack).
+ *   ASLEEP     asleep(e) = e is movable and its island is not awake.  An island of one sleeps by itself.
+ *   STATE      per entity: rest | SC_TICK_SLEEP_ASLEEP | SC_TICK_SLEEP_STILL | SC_TICK_SLEEP_MOVABLE (bits 8, 9, 10).
+ *   EVENTS     fell_asleep: the ids (rank << 24 | index) asleep now and not at the last flagged run; woke: the reverse.  The order
+ *              inside a list is unspecified.  Each list holds at most max_events ids; the true counts are in info, with an overflow bit
+ *              per list in info.flags; which ids a short list holds is unspecified.
+ *   WAKE       scTickWakeEntities sets rest = 0 and marks the anchor unset (NaN rows) for the named own entities: the next flagged run
+ *              sees them not still, and `woke` reports their islands.  An id of another rank or at or above the count fails the call and
+ *              nothing changes.  It is a write to device state outside any captured graph: a captured graph replays across it.
+ *   RESYNC     on the first flagged run after enabling, after scTickRemoveEntities, after a shrinking scTickSetEntityCount, after
+ *              scTickSetTile to another rank, after scTickSetPairShapes with another size and after a set call with another max_events:
+ *              nothing is remembered, every anchor becomes the current pose, every rest is 0, there are no events and info.flags has
+ *              SC_TICK_SLEEP_INFO_RESYNC.  A rename between the halves of a split tick is forgotten again behind the pair half, as for pair
+ *              events.  A same-parameter set call keeps the memory; a changed tolerance or rest_runs keeps it too, reaches the next run
+ *              and drops captured graphs (a capture holds them as kernel arguments).  Runs without SC_TICK_PAIR_SHAPES leave the memory
+ *              alone.  An entity that a growing count newly covers starts from the zeroed state: rest 0, an anchor of all zeros.
+ * LIMITS: no velocities and no forces -- a host that pushes a sleeping body calls scTickWakeEntities; the tolerances are absolute on
+ * matrix elements (a scaled body's rotation elements scale with it); a member of another rank, or one at or above the count, counts as
+ * still -- it is the other tile's to report, and an island never crosses a tile border; the awake entries are counted, not compacted into
+ * a work list; the epoch is a 32-bit word (2^32 flagged runs); a pipelined context already refuses the flag.
+ *   scTickSetPairSleep(enable, lin_tol, ang_tol, rest_runs, max_events) needs pair islands enabled, the tolerances finite and >= 0,
+ *   rest_runs in 1 .. 255 and max_events > 0 -- otherwise it fails with a last-error text and nothing changes.  DEVICE MEMORY: per entity
+ *   of the context's capacity 48 bytes of anchor, 4 of state and 4 of an `awake` word (indexed by island root), 4 * max_events bytes per
+ *   event list, 32 KB of per-workgroup tallies, 16 control words and 8 report words; 0 frees them.  It asks for no learn tick and fails
+ *   while scTickRunPairs is pending, as does scTickWakeEntities.  scTickSetPairIslands(0) and scTickSetPairShapes(0) switch sleep off too.
+ * The pass is four more launches behind the islands', ahead of the list's report, on the pair half's stream, with no host round trip: a
+ * thread per entity (rows against anchor; a movable entity with rest < rest_runs stores the run's epoch into the awake word of its
+ * island), a thread per entry (the anchored-entry rule), a thread per entity and entry (asleep, state word, events by ballot with one
+ * slot reservation per list and wave that has events), one workgroup for the report, which moves the epoch on.  Every writer of an awake
+ * word writes the same value: no read-modify-write, no clearing pass.  Counts, epoch and validity are read on the device, so both
+ * parities of the tick replay from captured graphs.  A context that never enables it allocates and launches exactly what it did before.
+ *   scTickReadPairSleep returns the report, min(entity count, state_capacity) state words, and of each list min(true count, max_events,
+ *   its capacity) ids; each array may be NULL with capacity 0.  It synchronises and fails like scTickReadPairIslands. */
+#define SC_TICK_SLEEP_ASLEEP  (1u << 8)
+#define SC_TICK_SLEEP_STILL   (1u << 9)
+#define SC_TICK_SLEEP_MOVABLE (1u << 10)
+#define SC_TICK_SLEEP_INFO_RESYNC         1u
+#define SC_TICK_SLEEP_INFO_FELL_OVERFLOW  2u
+#define SC_TICK_SLEEP_INFO_WOKE_OVERFLOW  4u
+#define SC_TICK_SLEEP_INFO_LIST_TRUNCATED 8u    /* ScTickPairIslandInfo::list_truncated of the same run */
+typedef struct ScTickPairSleepInfo      /* 32 bytes */
+{
+  uint32_t flags;           /* SC_TICK_SLEEP_INFO_* */
+  uint32_t asleep;          /* entities asleep */
+  uint32_t islands_asleep;  /* island roots asleep, singles included */
+  uint32_t fell_asleep;     /* true count of the run's fell_asleep events */
+  uint32_t woke;            /* true count of the run's woke events */
+  uint32_t awake_entries;   /* entries of the listed touching list whose edge island is awake */
+  uint32_t epoch;           /* flagged runs since the last resync, that run being 1 */
+  uint32_t pad;             /* 0 */
+} ScTickPairSleepInfo;
+int scTickSetPairSleep(ScTickContext* ctx, uint32_t enable, float lin_tol, float ang_tol, uint32_t rest_runs, uint32_t max_events);
+int scTickGetPairSleep(ScTickContext* ctx, uint32_t* enabled, float* lin_tol, float* ang_tol, uint32_t* rest_runs, uint32_t* max_events);
+/* ids: [n] rank << 24 | index of own entities below the count */
+int scTickWakeEntities(ScTickContext* ctx, const uint32_t* ids, uint32_t n);
+int scTickReadPairSleep(ScTickContext* ctx, uint32_t* states, uint32_t state_capacity, uint32_t* fell_asleep, uint32_t fell_capacity,
+                        uint32_t* woke, uint32_t woke_capacity, ScTickPairSleepInfo* info);
 
 /* ---- touch events: the tick-to-tick difference of the touching set ----
  * Pair events report begin / end for the AABB pair set; the touching pairs decide which pairs really overlap but return the whole list on

@@ -31,6 +31,8 @@ CONTACT_DEEP, CONTACT_DEGENERATE = 1 << 8, 1 << 9
 MANIFOLD_NONE, MANIFOLD_SINGLE, MANIFOLD_SEGMENT, MANIFOLD_FACE = 0, 1, 2, 3
 MANIFOLD_REDUCED = 1 << 8
 PERSIST_NONE = 0xFFFFFFFF     # SC_TICK_PERSIST_NONE: ScTickPairPersist::prev_entry of a pair that is not remembered (scTickSetPairPersistence)
+SLEEP_ASLEEP, SLEEP_STILL, SLEEP_MOVABLE = 1 << 8, 1 << 9, 1 << 10      # SC_TICK_SLEEP_*: bits of a state word above its rest count (scTickSetPairSleep)
+SLEEP_INFO_RESYNC, SLEEP_INFO_FELL_OVERFLOW, SLEEP_INFO_WOKE_OVERFLOW, SLEEP_INFO_LIST_TRUNCATED = 1, 2, 4, 8      # SC_TICK_SLEEP_INFO_*: ScTickPairSleepInfo::flags
 ISLAND_NONE = 0xFFFFFFFF      # SC_TICK_ISLAND_NONE: the label of a fixed entity, the island of an entry with no movable member (scTickSetPairIslands)
 SWEEP_END_LOCAL, SWEEP_END_WORLD_OFFSET = 0, 1         # SC_TICK_SWEEP_END_*: what an anchored sweep's local_end is (scTickSetAnchoredSweeps)
 ASWEEP_ANSWERED, ASWEEP_NO_ANCHOR, ASWEEP_NOT_FINITE = 0, 1, 2      # SC_TICK_ASWEEP_*: ScTickSweepHit::pad of an anchored sweep
@@ -136,6 +138,10 @@ class PairPersist(C.Structure):                          # ScTickPairPersist: 16
 
 class PairPersistInfo(C.Structure):                      # ScTickPairPersistInfo: 32 bytes
     _fields_ = [(n, C.c_uint32) for n in ("written", "kept_pairs", "new_pairs", "kept_points", "new_points", "resync", "list_truncated", "gave_up")]
+
+
+class PairSleepInfo(C.Structure):                        # ScTickPairSleepInfo: 32 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("flags", "asleep", "islands_asleep", "fell_asleep", "woke", "awake_entries", "epoch", "pad")]
 
 
 class Frame(C.Structure):
@@ -316,6 +322,10 @@ SYMBOLS = {
     "scTickReadPairPersistence": (C.c_int, [_CTX, C.POINTER(PairPersist), C.c_uint32, C.POINTER(PairPersistInfo)]),
     "scTickWritePairPayloads": (C.c_int, [_CTX, F32P, C.c_uint32, C.c_uint32]),
     "scTickReadPairPayloads": (C.c_int, [_CTX, F32P, C.c_uint32]),
+    "scTickSetPairSleep": (C.c_int, [_CTX, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
+    "scTickGetPairSleep": (C.c_int, [_CTX, U32P, F32P, F32P, U32P, U32P]),
+    "scTickWakeEntities": (C.c_int, [_CTX, U32P, C.c_uint32]),
+    "scTickReadPairSleep": (C.c_int, [_CTX, U32P, C.c_uint32, U32P, C.c_uint32, U32P, C.c_uint32, C.POINTER(PairSleepInfo)]),
     "scTickSetOverlapQueries": (C.c_int, [_CTX, C.c_uint32, U8P, F32P, F32P, F32P, F32P, U32P, U32P, C.c_uint32, C.c_uint32]),
     "scTickReadOverlapHits": (C.c_int, [_CTX, U32P, U32P, C.c_uint32, C.POINTER(OverlapInfo)]),
     "scTickSetTriggerVolumes": (C.c_int, [_CTX, C.c_uint32, U32P, U8P, F32P, F32P, F32P, F32P, U32P, U8P, C.c_uint32, C.c_uint32, C.c_uint32]),

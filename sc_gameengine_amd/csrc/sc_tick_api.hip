@@ -53,6 +53,7 @@ struct LastWith {
   bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
   bool pairIslands = false;                            // ... and computed the islands (scTickReadPairIslands)
   bool pairPersist = false;                            // ... and matched the contact points to the run before (scTickReadPairPersistence, the payload calls)
+  bool pairSleep = false;                              // ... and kept the rest state (scTickReadPairSleep)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
   uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
   uint32_t asweepCount = 0; bool asweepsExact = false;  // what SC_TICK_ANCHORED_SWEEPS answered, and in which mode (scTickReadAnchoredSweep*, scTickGetAnchoredSweepShapeInfo)
@@ -73,6 +74,7 @@ struct TickPlan {
   bool anchoredSweeps = false;         // the entity-anchored sweeps are answered by this tick (k_anchored_sweeps, next to the trigger volumes' launch)
   bool pairIslands = false;            // the pair islands are computed by this tick's pair half (launchPairIslands, inside the narrow phase's launch order)
   bool pairPersist = false;            // the contact points are matched to the last flagged run's by this tick's pair half (launchPairPersist, the same)
+  bool pairSleep = false;              // the rest state is kept by this tick's pair half (launchPairSleep, behind the islands)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -239,6 +241,8 @@ struct ScTickContext
   PairIslandState pairIslands{};
   // scTickSetPairPersistence: two sides of table, local points, ages and payload rows per entry of the touching list, the records and their report
   PairPersistState pairPersist{};
+  // scTickSetPairSleep: an anchor pose, a state word and an awake word per entity of capacity, two event lists and their report
+  PairSleepState pairSleep{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched)
@@ -849,9 +853,14 @@ bool resyncPairEvents(ScTickContext* c)
     const hipError_t e = hipMemsetAsync(c->pairPersist.ctl, 0, c->pairPersist.slabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair persistence)", e);
   }
+  if (c->pairSleep.ctl) {                             // (pair sleep keeps anchors and rest counts by dense index: nothing remembered, the epoch from 1)
+    const hipError_t e = hipMemsetAsync(c->pairSleep.ctl, 0, c->pairSleep.slabBytes, c->stream);
+    if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair sleep)", e);
+  }
   // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
   // the rename -- runPendingPairs forgets it again behind that half
-  if (c->pairsPending && ((c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS)) || c->pendingTick.pairPersist)) c->pairEventsResyncAgain = true;
+  if (c->pairsPending && ((c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS)) || c->pendingTick.pairPersist || c->pendingTick.pairSleep))
+    c->pairEventsResyncAgain = true;
   return true;
 }
 
@@ -863,7 +872,8 @@ void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickPlan& plan
   const TickParams& p = plan.p;
   if (p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))
     launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, plan.pairPersist ? &c->pairPersist : nullptr, s);
+                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, plan.pairPersist ? &c->pairPersist : nullptr,
+                     plan.pairSleep ? &c->pairSleep : nullptr, s);
   if (p.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, s);
 }
 
@@ -1319,12 +1329,42 @@ bool sizePersistLevel(ScTickContext* c, uint32_t entries)
   return true;
 }
 
-// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds, islands and persistence where wanted:
-// contacts and islands need the list, manifolds the contacts, persistence the manifolds.  `set` is the level the calling setter sets.  A
-// failed allocation leaves all five off (the allocator's text stands): nothing is ever on without what it needs, or sized for another list.
-enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands, kNarrowPersist };
-bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups, bool persist)
+// The sleep level: one slab -- control words, a state word and an awake word per entity of the context's capacity, three anchor rows per
+// entity --, which a resync zeroes as a whole; the two event lists, the report and the resolve's tallies.  The caller's tolerances and
+// rest_runs stay with the state across a re-size.
+bool sizeSleepLevel(ScTickContext* c, uint32_t entries, uint32_t maxEvents)
 {
+  PairSleepState& s = c->pairSleep;
+  const float linTol = s.linTol, angTol = s.angTol;
+  const uint32_t restRuns = s.restRuns;
+  dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.fell); dfree(c, s.woke); dfree(c, s.partial);
+  s = PairSleepState{};
+  if (!entries || !maxEvents) return true;
+  // [control words][state][awake][anchor]: the anchor rows 16-byte aligned behind 64 bytes of control words and 2 * cap words (cap is a multiple of the tile)
+  const size_t words = (size_t)kPzCtlWords + 2u * (size_t)c->cap + 12u * (size_t)c->cap;
+  if (!dalloc(c, s.ctl, words) || !dalloc(c, s.info, kPzInfoWords) || !dalloc(c, s.fell, maxEvents) || !dalloc(c, s.woke, maxEvents) ||
+      !dalloc(c, s.partial, 4u * kPzMaxBlocks)) {
+    dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.fell); dfree(c, s.woke); dfree(c, s.partial);
+    s = PairSleepState{};
+    return false;
+  }
+  s.state = s.ctl + kPzCtlWords; s.awake = s.state + c->cap; s.anchor = reinterpret_cast<float4*>(s.awake + c->cap);
+  s.slabBytes = words * sizeof(uint32_t);
+  s.cap = c->cap; s.maxTouching = entries; s.maxEvents = maxEvents;
+  s.linTol = linTol; s.angTol = angTol; s.restRuns = restRuns;
+  return true;
+}
+
+// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds, islands, persistence and sleep where wanted:
+// contacts and islands need the list, manifolds the contacts, persistence the manifolds, sleep the islands (sleepEvents: its max_events,
+// 0 = off).  `set` is the level the calling setter sets.  A failed allocation leaves all six off (the allocator's text stands): nothing
+// is ever on without what it needs, or sized for another list.
+enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands, kNarrowPersist, kNarrowSleep };
+bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups, bool persist,
+                     uint32_t sleepEvents)
+{
+  // (sleep holds a memory like persistence: allocated afresh -- a resync -- only when the list's size or max_events changes)
+  const uint32_t sleepEntries = (islands && sleepEvents) ? maxTouching : 0u;
   // (persistence holds a memory: it is allocated afresh -- a resync -- only when its size changes, and so survives a same-size scTickSetPairShapes)
   const uint32_t persistEntries = (contacts && manifolds && persist) ? maxTouching : 0u;
   const uint32_t contactEntries = contacts ? maxTouching : 0u;
@@ -1342,12 +1382,14 @@ bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bo
   if (ok && doManifolds) ok = sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, manifoldEntries);
   if (ok && doIslands) ok = sizeIslandLevel(c, islandEntries, fixedGroups);
   if (ok && persistEntries != c->pairPersist.maxTouching) ok = sizePersistLevel(c, persistEntries);
+  if (ok && (sleepEntries != c->pairSleep.maxTouching || (sleepEntries && sleepEvents != c->pairSleep.maxEvents))) ok = sizeSleepLevel(c, sleepEntries, sleepEvents);
   if (!ok) {      // everything off (0 entries: a level is freed, nothing is allocated)
     sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, 0u);
     sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, 0u);
     sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, 0u);
     sizeIslandLevel(c, 0u, 0u);
     sizePersistLevel(c, 0u);
+    sizeSleepLevel(c, 0u, 0u);
   }
   return ok;
 }
@@ -2349,6 +2391,7 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   plan.anchoredSweeps = path.pairsNow && (p.flags & kFlagAnchoredSweeps) != 0u;
   plan.pairIslands = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairIslands.ctl != nullptr;      // (whichever half closes the pair search)
   plan.pairPersist = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairPersist.ctl != nullptr;
+  plan.pairSleep = plan.pairIslands && c->pairSleep.ctl != nullptr;
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2415,6 +2458,7 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   if (with & SC_TICK_PAIR_SHAPES) {
     w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; w.pairIslands = c->pairIslands.ctl != nullptr;
     w.pairPersist = c->pairPersist.ctl != nullptr;
+    w.pairSleep = c->pairIslands.ctl != nullptr && c->pairSleep.ctl != nullptr;
   }
 }
 
@@ -3378,7 +3422,7 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   // (pair contacts and pair islands follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
   return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
 }
 
 int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
@@ -3395,7 +3439,7 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   // (pair manifolds need the contacts: off with them)
   return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
 }
 
 int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
@@ -3429,7 +3473,7 @@ int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
   return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr) ? 1 : 0;
+                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
 }
 
 int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
@@ -3461,7 +3505,7 @@ int scTickSetPairIslands(ScTickContext* c, uint32_t enable, uint32_t fixedGroups
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old fixed groups; no epoch bump: the bins are not concerned
   return sizeNarrowPhase(c, kNarrowIslands, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, enable != 0u,
-                         enable ? fixedGroups : 0u, c->pairPersist.ctl != nullptr) ? 1 : 0;
+                         enable ? fixedGroups : 0u, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
 }
 
 int scTickGetPairIslands(ScTickContext* c, uint32_t* enabled, uint32_t* fixedGroups)
@@ -3485,6 +3529,86 @@ int scTickReadPairIslands(ScTickContext* c, uint32_t* labels, uint32_t labelCapa
   return (!m || (d2h(c, labels, s.labels, (size_t)m * sizeof(uint32_t)) && sync(c))) ? 1 : 0;
 }
 
+int scTickSetPairSleep(ScTickContext* c, uint32_t enable, float linTol, float angTol, uint32_t restRuns, uint32_t maxEvents)
+{
+  static_assert(sizeof(ScTickPairSleepInfo) == 32u && sizeof(ScTickPairSleepInfo) == kPzInfoWords * sizeof(uint32_t), "the device writes the report word by word");
+  static_assert(kSleepAsleep == SC_TICK_SLEEP_ASLEEP && kSleepStill == SC_TICK_SLEEP_STILL && kSleepMovable == SC_TICK_SLEEP_MOVABLE, "the state bits differ from the header's");
+  static_assert(kSleepResync == SC_TICK_SLEEP_INFO_RESYNC && kSleepFellOverflow == SC_TICK_SLEEP_INFO_FELL_OVERFLOW && kSleepWokeOverflow == SC_TICK_SLEEP_INFO_WOKE_OVERFLOW &&
+                kSleepListTruncated == SC_TICK_SLEEP_INFO_LIST_TRUNCATED, "the report's flags differ from the header's");
+  if (!c) return 0;
+  if (enable && !c->pairIslands.ctl) return fail(c, "scTickSetPairSleep needs scTickSetPairIslands(1) first");
+  if (enable && !(std::isfinite(linTol) && linTol >= 0.0f && std::isfinite(angTol) && angTol >= 0.0f))
+    return fail(c, "scTickSetPairSleep: lin_tol and ang_tol must be finite and >= 0");
+  if (enable && (restRuns < 1u || restRuns > 255u)) return fail(c, "scTickSetPairSleep: rest_runs must be in 1 .. 255");
+  if (enable && !maxEvents) return fail(c, "scTickSetPairSleep: max_events must be > 0");
+  if (enable && maxEvents > (1u << 24)) return fail(c, "scTickSetPairSleep: at most 2^24 events a list");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  if (!bind(c) || !sync(c)) return 0;
+  PairSleepState& z = c->pairSleep;
+  if (enable && z.ctl && z.maxEvents == maxEvents) {        // (already on: what is remembered stays)
+    // a captured tick holds the tolerances and rest_runs as kernel arguments
+    if (z.linTol != linTol || z.angTol != angTol || z.restRuns != restRuns) dropCaptures(c);
+    z.linTol = linTol; z.angTol = angTol; z.restRuns = restRuns;
+    return 1;
+  }
+  dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
+  if (!sizeNarrowPhase(c, kNarrowSleep, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
+                       c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, enable ? maxEvents : 0u)) return 0;
+  if (enable) { z.linTol = linTol; z.angTol = angTol; z.restRuns = restRuns; }
+  return 1;
+}
+
+int scTickGetPairSleep(ScTickContext* c, uint32_t* enabled, float* linTol, float* angTol, uint32_t* restRuns, uint32_t* maxEvents)
+{
+  if (!c || !enabled || !linTol || !angTol || !restRuns || !maxEvents) return c ? fail(c, "null argument") : 0;
+  const PairSleepState& z = c->pairSleep;
+  *enabled = z.ctl ? 1u : 0u;
+  *linTol = z.ctl ? z.linTol : 0.0f; *angTol = z.ctl ? z.angTol : 0.0f;
+  *restRuns = z.ctl ? z.restRuns : 0u; *maxEvents = z.ctl ? z.maxEvents : 0u;
+  return 1;
+}
+
+int scTickWakeEntities(ScTickContext* c, const uint32_t* ids, uint32_t n)
+{
+  if (!c || (!ids && n)) return c ? fail(c, "null argument") : 0;
+  if (!c->pairSleep.ctl) return fail(c, "scTickWakeEntities needs scTickSetPairSleep(1) first");
+  if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
+  const uint32_t count = std::min(c->n, c->pairSleep.cap);
+  std::vector<uint32_t> dense(n);
+  for (uint32_t i = 0; i < n; ++i) {                        // (every id is checked before anything is written)
+    if ((ids[i] >> 24) != c->rank) return fail(c, "scTickWakeEntities: an id of another rank");
+    dense[i] = ids[i] & 0x00FFFFFFu;
+    if (dense[i] >= count) return fail(c, "scTickWakeEntities: an id at or above the entity count");
+  }
+  if (!n) return 1;
+  if (!bind(c) || !sync(c)) return 0;                       // behind every run issued so far, outside any captured graph
+  uint32_t* dIds = nullptr;
+  if (!dalloc(c, dIds, n, false)) return 0;
+  const bool ok = h2d(c, dIds, dense.data(), (size_t)n * sizeof(uint32_t));
+  if (ok) launchPairSleepWake(c->pairSleep, dIds, n, c->stream);
+  const bool done = ok && sync(c);
+  dfree(c, dIds);
+  return done ? 1 : 0;
+}
+
+int scTickReadPairSleep(ScTickContext* c, uint32_t* states, uint32_t stateCapacity, uint32_t* fellAsleep, uint32_t fellCapacity, uint32_t* woke, uint32_t wokeCapacity,
+                        ScTickPairSleepInfo* info)
+{
+  if (!c || !info) return c ? fail(c, "null argument") : 0;
+  const PairSleepState& z = c->pairSleep;
+  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                 c->lastWith.pairSleep, "pair sleep was not enabled at the last scTickRun (scTickSetPairSleep)",
+                                 "pair sleep is ready after scTickRunPairs", z.ctl != nullptr, "pair sleep was switched off since the last scTickRun")) return 0;
+  if (!d2h(c, info, z.info, sizeof *info) || !sync(c)) return 0;
+  const uint32_t ns = std::min(std::min(c->n, z.cap), states ? stateCapacity : 0u);
+  const uint32_t nf = std::min(std::min(info->fell_asleep, z.maxEvents), fellAsleep ? fellCapacity : 0u);
+  const uint32_t nw = std::min(std::min(info->woke, z.maxEvents), woke ? wokeCapacity : 0u);
+  if (ns && !d2h(c, states, z.state, (size_t)ns * sizeof(uint32_t))) return 0;
+  if (nf && !d2h(c, fellAsleep, z.fell, (size_t)nf * sizeof(uint32_t))) return 0;
+  if (nw && !d2h(c, woke, z.woke, (size_t)nw * sizeof(uint32_t))) return 0;
+  return ((ns | nf | nw) == 0u || sync(c)) ? 1 : 0;
+}
+
 int scTickSetPairPersistence(ScTickContext* c, uint32_t enable, float matchDist)
 {
   static_assert(sizeof(ScTickPairPersist) == 16u && sizeof(ScTickPairPersist) == sizeof(uint4), "the device writes the record with one 16-byte store");
@@ -3498,7 +3622,7 @@ int scTickSetPairPersistence(ScTickContext* c, uint32_t enable, float matchDist)
   dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old match distance; no epoch bump: the bins are not concerned
   if (enable && c->pairPersist.ctl) { c->pairPersist.matchDist = matchDist; return 1; }      // (already on: what is remembered stays)
   if (!sizeNarrowPhase(c, kNarrowPersist, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                       c->pairIslands.fixedGroups, enable != 0u)) return 0;
+                       c->pairIslands.fixedGroups, enable != 0u, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u)) return 0;
   c->pairPersist.matchDist = enable ? matchDist : 0.0f;
   return 1;
 }

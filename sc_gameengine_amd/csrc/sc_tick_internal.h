@@ -571,6 +571,32 @@ constexpr uint32_t kPpKeptPairs = 0, kPpKeptPoints = 1, kPpNewPoints = 2;      /
 constexpr uint32_t kPpMaxBlocks = 1024;         // workgroups of k_pair_persist_match at most (grid-stride beyond)
 constexpr uint32_t kPpInfoWords = 16, kPpInfoSide = 8;
 constexpr uint32_t kPersistNone = 0xFFFFFFFFu;  // == SC_TICK_PERSIST_NONE
+// ---- pair sleep (sc_tick_pair_sleep.hip; include/sc_tick.h "pair sleep"): which islands are at rest, which bodies fell asleep, which were
+// woken.  Per entity of capacity an anchor pose (three float4), a state word and an `awake` word (indexed by the island's root); two event
+// lists.  One slab: zero bytes all over = nothing remembered, the next flagged run is a resync.  All null until scTickSetPairSleep:
+// nothing is launched.
+struct PairSleepState {
+  uint32_t* ctl;                  // kPz* words below, and behind them in the same allocation (`slabBytes` in all) state, awake and anchor
+  uint32_t* info;                 // [kPzInfoWords]: what the last flagged run reports (== ScTickPairSleepInfo)
+  uint32_t maxTouching;           // the touching list's (a re-sized list is a resync)
+  uint32_t* state;                // [cap]: rest | ASLEEP << 8 | STILL << 9 | MOVABLE << 10 as of the last flagged run
+  uint32_t* awake;                // [cap]: word r == the run's epoch = the island with root r is awake in this run
+  float4* anchor;                 // [3 * cap]: rows 0..2 of entity e at 3 * e; a NaN row = unset
+  uint32_t* fell;                 // [maxEvents] ids that fell asleep in the last flagged run
+  uint32_t* woke;                 // [maxEvents] ids that woke
+  uint32_t* partial;              // [kPzMaxBlocks][4]: every workgroup's tallies of the resolve, rewritten by every launch, summed by the finish
+  uint32_t cap;                   // the context's padded capacity
+  uint32_t maxEvents;
+  uint32_t restRuns;              // 1 .. 255
+  float linTol, angTol;
+  size_t slabBytes;
+};
+constexpr uint32_t kPzEpoch = 0, kPzValid = 1, kPzFell = 2, kPzWoke = 3, kPzCtlWords = 16;
+constexpr uint32_t kPzAsleep = 0, kPzIslandsAsleep = 1, kPzAwakeEntries = 2;      // a workgroup's tallies (the fourth word is not used)
+constexpr uint32_t kPzMaxBlocks = 2048;         // workgroups per launch of the pass at most (grid-stride beyond)
+constexpr uint32_t kPzInfoWords = 8;
+constexpr uint32_t kSleepAsleep = 1u << 8, kSleepStill = 1u << 9, kSleepMovable = 1u << 10;      // == SC_TICK_SLEEP_ASLEEP / _STILL / _MOVABLE
+constexpr uint32_t kSleepResync = 1u, kSleepFellOverflow = 2u, kSleepWokeOverflow = 4u, kSleepListTruncated = 8u;      // == SC_TICK_SLEEP_INFO_*
 // The shapes as the touching pairs take them (include/sc_tick.h "touching pairs"), shared with the exact shapes for capsule sweeps
 // (sc_tick_queries.hip): a member through its matrix, the round and the box frame built from it, and the two distance cores.  All of it
 // fp32, unfused, left to right, as the header states it operation by operation.
@@ -806,8 +832,15 @@ __device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
 // `manifolds` (scTickSetPairManifolds; the same) adds k_pair_manifolds behind the contacts' report.
 // `islands` (scTickSetPairIslands; null: this tick computes none) adds the island pass behind all of them, still ahead of the list's report.
 // `persist` (scTickSetPairPersistence; null: this tick matches nothing) adds the persistence pass behind the manifolds', ahead of the list's report.
+// `sleep` (scTickSetPairSleep; null: this tick keeps no rest state) adds the sleep pass behind the islands', ahead of the list's report.
 void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, hipStream_t s);
+                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, const PairSleepState* sleep,
+                      hipStream_t s);
+// the sleep pass and its report (sc_tick_pair_sleep.hip), launched by launchPairShapes behind launchPairIslands; launchPairSleepWake is
+// scTickWakeEntities' one launch over `n` dense indices on the device
+void launchPairSleep(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairIslandState& islands, const PairSleepState& sleep,
+                     hipStream_t s);
+void launchPairSleepWake(const PairSleepState& sleep, const uint32_t* ids, uint32_t n, hipStream_t s);
 // the persistence pass, its sweep and its report (sc_tick_pair_persist.hip), launched by launchPairShapes behind launchPairManifolds
 void launchPairPersist(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairManifoldState& manifolds, const PairPersistState& persist,
                        hipStream_t s);

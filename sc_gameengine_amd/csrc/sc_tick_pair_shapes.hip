@@ -229,7 +229,8 @@ __global__ __launch_bounds__(64) void k_pair_contacts_finish(const PairShapeStat
 // One narrow-phase launch per tick, whatever mix of SC_TICK_PAIR_SHAPES (list) and SC_TICK_TOUCH_EVENTS (touch) the run carries: each
 // pair is decided once.  Behind it the list's report and / or the touch state's sweep and finish (k_pair_events_sweep / _finish, unchanged).
 void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, hipStream_t s)
+                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, const PairSleepState* sleep,
+                      hipStream_t s)
 {
   if (list && !list->ctl) list = nullptr;
   if (touch && !touch->ctl) touch = nullptr;
@@ -250,6 +251,7 @@ void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShape
   if (list && manifolds && manifolds->ctl) launchPairManifolds(d, p, e, *manifolds, s);      // behind the contacts' report, before the list's
   if (list && manifolds && manifolds->ctl && persist && persist->ctl) launchPairPersist(d, p, e, *manifolds, *persist, s);      // behind the manifolds' records
   if (list && islands && islands->ctl) launchPairIslands(d, p, e, *islands, s);      // needs the list, not the contacts; before the list's report
+  if (list && islands && islands->ctl && sleep && sleep->ctl) launchPairSleep(d, p, e, *islands, *sleep, s);      // labels and edge islands are final
   if (list) hipLaunchKernelGGL(k_pair_shapes_finish, dim3(1), dim3(64), 0, s, e);
   if (touch) launchPairEventsTail(t, s);
 }

@@ -1075,6 +1075,43 @@ class WorldTick:
         out = {k: int(getattr(info, k)) for k, _ in capi.PairPersistInfo._fields_}
         return rec[:min(out["written"], cap)].copy(), out
 
+    # ---- pair sleep: which islands are at rest, who fell asleep, who woke ----
+    def pair_sleep(self, on, lin_tol=0.005, ang_tol=0.005, rest_runs=120, max_events=4096):
+        """Keep, on every run with capi.PAIR_SHAPES, a rest state per entity (scTickSetPairSleep): an entity is still while its world rows
+        stay within lin_tol (translation) / ang_tol (the nine other elements) of an anchor pose, an island falls asleep once every member
+        has been still for rest_runs runs (1 .. 255; the default is Bullet's 2 s at 60 Hz), and each run reports at most max_events ids
+        per event list.  Needs pair_islands(True) first.  A second call with the same max_events keeps what is remembered."""
+        self._ok(self.lib.scTickSetPairSleep(self.ctx, 1 if on else 0, float(lin_tol), float(ang_tol), int(rest_runs), int(max_events)), "scTickSetPairSleep")
+
+    def pair_sleep_params(self):
+        """(enabled, lin_tol, ang_tol, rest_runs, max_events) as the context holds them (zeros while off)"""
+        on, rr, me = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        lt, at = C.c_float(), C.c_float()
+        self._ok(self.lib.scTickGetPairSleep(self.ctx, C.byref(on), C.byref(lt), C.byref(at), C.byref(rr), C.byref(me)), "scTickGetPairSleep")
+        return bool(on.value), float(lt.value), float(at.value), int(rr.value), int(me.value)
+
+    @property
+    def pair_sleep_enabled(self):
+        return self.pair_sleep_params()[0]
+
+    def wake_entities(self, ids):
+        """The host's activateBody (scTickWakeEntities): rest = 0 and no anchor for the ids (rank << 24 | index) of own entities, so the
+        next flagged run reports their islands in `woke`.  Outside any captured graph: graph mode replays across it."""
+        i = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._ok(self.lib.scTickWakeEntities(self.ctx, _u(i), len(i)), "scTickWakeEntities")
+
+    def read_pair_sleep(self):
+        """(states[n], fell_asleep, woke, info) of the last run with capi.PAIR_SHAPES while pair sleep was enabled: the state word per
+        entity (rest | capi.SLEEP_ASLEEP | SLEEP_STILL | SLEEP_MOVABLE), the two event lists as ids -- each cut at max_events, the true
+        counts in info -- and info as a dict (flags, asleep, islands_asleep, fell_asleep, woke, awake_entries, epoch, pad)."""
+        cap = self.pair_sleep_params()[4]
+        states = np.zeros(max(self.n, 1), np.uint32)
+        fell, woke = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        info = capi.PairSleepInfo()
+        self._ok(self.lib.scTickReadPairSleep(self.ctx, _u(states), self.n, _u(fell), cap, _u(woke), cap, C.byref(info)), "scTickReadPairSleep")
+        out = {k: int(getattr(info, k)) for k, _ in capi.PairSleepInfo._fields_}
+        return states[:self.n].copy(), fell[:min(out["fell_asleep"], cap)].copy(), woke[:min(out["woke"], cap)].copy(), out
+
     # ---- touch events: which pairs begun / ended TOUCHING since the last run with capi.TOUCH_EVENTS ----
     def set_touch_events(self, max_tracked, max_events):
         """Remember the touching set -- the pairs of the tick's list that the collider shapes do not prove apart -- on the device and report
