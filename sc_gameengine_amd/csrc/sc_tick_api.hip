@@ -50,10 +50,7 @@ struct BinOutcome { bool lazy = false, stay = false, sweepOnly = false; };
 // (3) The last accepted run THAT CARRIED THE FEATURE'S FLAG: what it was sized for or ran as (each reader checks RunRecord::flags first)
 struct LastWith {
   bool sweepsExact = false;                            // SC_TICK_SWEEPS ran in EXACT mode (scTickGetSweepShapeInfo)
-  bool pairContacts = false, pairManifolds = false;    // SC_TICK_PAIR_SHAPES wrote them (scTickReadPairContacts / scTickReadPairManifolds)
-  bool pairIslands = false;                            // ... and computed the islands (scTickReadPairIslands)
-  bool pairPersist = false;                            // ... and matched the contact points to the run before (scTickReadPairPersistence, the payload calls)
-  bool pairSleep = false;                              // ... and kept the rest state (scTickReadPairSleep)
+  uint32_t narrow = 0;                                 // the NarrowStage set SC_TICK_PAIR_SHAPES ran with: TickPlan::narrow of that run (narrowResult)
   uint32_t overlapCount = 0, overlapMaxHits = 0, overlapShapes = 0;      // what SC_TICK_OVERLAPS answered (scTickReadOverlapHits)
   uint32_t triggerCount = 0, triggerMaxMembers = 0, triggerMaxEvents = 0;     // what SC_TICK_TRIGGERS answered (scTickReadTrigger*)
   uint32_t asweepCount = 0; bool asweepsExact = false;  // what SC_TICK_ANCHORED_SWEEPS answered, and in which mode (scTickReadAnchoredSweep*, scTickGetAnchoredSweepShapeInfo)
@@ -72,9 +69,7 @@ struct TickPlan {
   bool sampled = false, carry = false, defer = false, replay = false, wholeStep = false;
   bool triggers = false;               // the trigger volumes are answered by this tick (k_trigger_volumes, at the overlap queries' launch site)
   bool anchoredSweeps = false;         // the entity-anchored sweeps are answered by this tick (k_anchored_sweeps, next to the trigger volumes' launch)
-  bool pairIslands = false;            // the pair islands are computed by this tick's pair half (launchPairIslands, inside the narrow phase's launch order)
-  bool pairPersist = false;            // the contact points are matched to the last flagged run's by this tick's pair half (launchPairPersist, the same)
-  bool pairSleep = false;              // the rest state is kept by this tick's pair half (launchPairSleep, behind the islands)
+  uint32_t narrow = 0;                 // the NarrowStage set this tick's pair half executes (launchPairShapes goes by it, the record copies it)
   bool binned = false, learn = false;  // the home slots' side of a binning tick: it ran at all / as a learn tick ...
   uint32_t homeXform = 0;              // ... learnt with or without SC_TICK_XFORM (ScTickContext::homeXform)
   BinOutcome bins;
@@ -227,22 +222,11 @@ struct ScTickContext
   PairEventState pairEvents{};
   void* pairEventSlab = nullptr; size_t pairEventSlabBytes = 0;
   bool pairEventsResyncAgain = false;      // ids were renamed between the halves of a split tick: forget again what its pair half remembers
-  // scTickSetTouchEvents: the same state a second time, for the touching set (filled by the narrow-phase kernel).  All null until the call.
-  PairEventState touchEvents{};
+  // The narrow phase: the touch events' state (scTickSetTouchEvents: the pair events' state a second time, filled by the narrow-phase
+  // kernel; touchEventSlab is its one allocation) and the six stages of the touching pairs, which sizeNarrowPhase alone sizes.  All null
+  // until the setters' calls: nothing is launched.
+  NarrowPhase narrow{};
   void* touchEventSlab = nullptr; size_t touchEventSlabBytes = 0;
-  // scTickSetPairShapes: the touching list, its running counts and its report.  All null until the call: nothing is launched.
-  PairShapeState pairShapes{};
-  // scTickSetPairContacts: one record per entry of the touching list, the kind counts and their report.  All null until the call: nothing
-  // is launched.
-  PairContactState pairContacts{};
-  // scTickSetPairManifolds: the same a level up -- five float4 per entry of the touching list, the counts and their report
-  PairManifoldState pairManifolds{};
-  // scTickSetPairIslands: the union-find's two words per entity of capacity, an island word per entry of the touching list, the counts and their report
-  PairIslandState pairIslands{};
-  // scTickSetPairPersistence: two sides of table, local points, ages and payload rows per entry of the touching list, the records and their report
-  PairPersistState pairPersist{};
-  // scTickSetPairSleep: an anchor pose, a state word and an awake word per entity of capacity, two event lists and their report
-  PairSleepState pairSleep{};
   DrawSortState sort{};                // renderer draw order (scTickSetDrawSortTable); key/idx buffers allocated on first use
   uint8_t* dPipeline = nullptr; uint32_t pipelineCap = 0;
   // scTickSetBindRuns: run table, report and touch bitmap of the sorted list (all null until the call: nothing is launched)
@@ -849,17 +833,17 @@ bool resyncPairEvents(ScTickContext* c)
     const hipError_t e = hipMemsetAsync(c->touchEventSlab, 0, c->touchEventSlabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (touch events)", e);
   }
-  if (c->pairPersist.ctl) {                           // (pair persistence remembers entries by the same ids: both tables empty, nothing valid)
-    const hipError_t e = hipMemsetAsync(c->pairPersist.ctl, 0, c->pairPersist.slabBytes, c->stream);
+  if (c->narrow.persist.ctl) {                           // (pair persistence remembers entries by the same ids: both tables empty, nothing valid)
+    const hipError_t e = hipMemsetAsync(c->narrow.persist.ctl, 0, c->narrow.persist.slabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair persistence)", e);
   }
-  if (c->pairSleep.ctl) {                             // (pair sleep keeps anchors and rest counts by dense index: nothing remembered, the epoch from 1)
-    const hipError_t e = hipMemsetAsync(c->pairSleep.ctl, 0, c->pairSleep.slabBytes, c->stream);
+  if (c->narrow.sleep.ctl) {                             // (pair sleep keeps anchors and rest counts by dense index: nothing remembered, the epoch from 1)
+    const hipError_t e = hipMemsetAsync(c->narrow.sleep.ctl, 0, c->narrow.sleep.slabBytes, c->stream);
     if (e != hipSuccess) return fail(c, "hipMemsetAsync (pair sleep)", e);
   }
   // caller-owned split flow: the pair half of the tick already issued is still to come and will remember ITS set, in the ids from before
   // the rename -- runPendingPairs forgets it again behind that half
-  if (c->pairsPending && ((c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS)) || c->pendingTick.pairPersist || c->pendingTick.pairSleep))
+  if (c->pairsPending && ((c->pendingTick.p.flags & (SC_TICK_PAIR_EVENTS | SC_TICK_TOUCH_EVENTS)) || (c->pendingTick.narrow & (kStagePersist | kStageSleep))))
     c->pairEventsResyncAgain = true;
   return true;
 }
@@ -870,10 +854,7 @@ bool resyncPairEvents(ScTickContext* c)
 void closePairHalf(ScTickContext* c, const DeviceState& ds, const TickPlan& plan, hipStream_t s)
 {
   const TickParams& p = plan.p;
-  if (p.flags & (SC_TICK_PAIR_SHAPES | SC_TICK_TOUCH_EVENTS))
-    launchPairShapes(ds, p, (p.flags & SC_TICK_PAIR_SHAPES) ? &c->pairShapes : nullptr, (p.flags & SC_TICK_TOUCH_EVENTS) ? &c->touchEvents : nullptr,
-                     &c->pairContacts, &c->pairManifolds, plan.pairIslands ? &c->pairIslands : nullptr, plan.pairPersist ? &c->pairPersist : nullptr,
-                     plan.pairSleep ? &c->pairSleep : nullptr, s);
+  if (plan.narrow) launchPairShapes(ds, p, c->narrow, plan.narrow, s);
   if (p.flags & SC_TICK_PAIR_EVENTS) launchPairEvents(ds, p, c->pairEvents, s);
 }
 
@@ -1238,6 +1219,34 @@ bool lastRunResult(ScTickContext* c, uint32_t flag, const char* notRequested, bo
   return joinPairs(c);
 }
 
+// The stages of the touching pairs that are enabled now, as a NarrowStage set: a stage is on while its control words exist
+uint32_t narrowOn(const ScTickContext* c)
+{
+  const NarrowPhase& np = c->narrow;
+  return (np.list.ctl ? kStageList : 0u) | (np.contacts.ctl ? kStageContacts : 0u) | (np.manifolds.ctl ? kStageManifolds : 0u) |
+         (np.islands.ctl ? kStageIslands : 0u) | (np.persist.ctl ? kStagePersist : 0u) | (np.sleep.ctl ? kStageSleep : 0u);
+}
+
+// The gate of the touching pairs' readers, one row per stage: its bit -- in LastWith::narrow "it ran then", in narrowOn "it is on now" --
+// and its texts (the list always ran with its flag: no such text)
+struct NarrowReader { uint32_t stage; const char *notEnabled, *pending, *switchedOff; };
+const NarrowReader kNarrowReaders[] = {
+  { kStageList, nullptr, "touching pairs are ready after scTickRunPairs", "touching pairs were switched off since the last scTickRun" },
+  { kStageContacts, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)", "pair contacts are ready after scTickRunPairs", "pair contacts were switched off since the last scTickRun" },
+  { kStageManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)", "pair manifolds are ready after scTickRunPairs", "pair manifolds were switched off since the last scTickRun" },
+  { kStageIslands, "pair islands were not enabled at the last scTickRun (scTickSetPairIslands)", "pair islands are ready after scTickRunPairs", "pair islands were switched off since the last scTickRun" },
+  { kStagePersist, "pair persistence was not enabled at the last scTickRun (scTickSetPairPersistence)", "pair persistence is ready after scTickRunPairs", "pair persistence was switched off since the last scTickRun" },
+  { kStageSleep, "pair sleep was not enabled at the last scTickRun (scTickSetPairSleep)", "pair sleep is ready after scTickRunPairs", "pair sleep was switched off since the last scTickRun" },
+};
+bool narrowResult(ScTickContext* c, uint32_t stage)
+{
+  for (const NarrowReader& r : kNarrowReaders)
+    if (r.stage == stage)
+      return bind(c) && lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
+                                      !r.notEnabled || (c->lastWith.narrow & stage) != 0u, r.notEnabled, r.pending, (narrowOn(c) & stage) != 0u, r.switchedOff);
+  return false;
+}
+
 // ... and what most of them do next: the report, then the first min(the report's count, what the device keeps, the caller's room) records
 template <typename Info>
 bool readReportAndRecords(ScTickContext* c, Info* info, const uint32_t* devInfo, uint32_t Info::*count, uint32_t kept, const void* devRec,
@@ -1272,42 +1281,70 @@ bool growBatch(ScTickContext* c, uint32_t& cap, uint32_t& held, uint32_t count, 
   return true;
 }
 
-// The narrow-phase buffers are a chain -- the touching list, a contact record per entry of it, a manifold record per entry -- and this is
-// the one place that sizes them.  One level: its control words, its report and recsPer records per entry; 0 entries: freed, all null.
+// ---- the narrow phase's buffers.  What the caller wants of them is ONE record: every setter's arguments as the context holds them.
+// narrowWanted reads the current record off the context; a setter changes its own fields and hands the record to sizeNarrowPhase, the
+// one place that sizes the six stages and the one that writes the caller's parameters into their states.
+struct NarrowWant {
+  uint32_t maxTouching = 0;            // the list's entries; 0: everything off
+  bool contacts = false, manifolds = false, islands = false, persist = false;
+  uint32_t fixedGroups = 0;            // islands
+  float matchDist = 0.0f;              // persistence
+  uint32_t sleepEvents = 0;            // sleep: its max_events; 0: off
+  float linTol = 0.0f, angTol = 0.0f; uint32_t restRuns = 0;
+};
+NarrowWant narrowWanted(const ScTickContext* c)
+{
+  const NarrowPhase& np = c->narrow;
+  const uint32_t on = narrowOn(c);
+  NarrowWant w;                        // (a stage that is off holds zeros)
+  w.maxTouching = np.list.maxTouching;
+  w.contacts = (on & kStageContacts) != 0u; w.manifolds = (on & kStageManifolds) != 0u; w.islands = (on & kStageIslands) != 0u; w.persist = (on & kStagePersist) != 0u;
+  w.fixedGroups = np.islands.fixedGroups; w.matchDist = np.persist.matchDist;
+  w.sleepEvents = np.sleep.maxEvents; w.linTol = np.sleep.linTol; w.angTol = np.sleep.angTol; w.restRuns = np.sleep.restRuns;
+  return w;
+}
+
+// One level freed, all null: what a level that goes off, one that is allocated afresh and a failed allocation all go through
+template <typename State, typename... P> void freeLevel(ScTickContext* c, State& s, P*... allocations) { (dfree(c, allocations), ...); s = State{}; }
+template <typename State, typename Rec> void freeNarrowLevel(ScTickContext* c, State& s, Rec* State::*rec) { freeLevel(c, s, s.*rec, s.ctl, s.info); }
+void freeIslandLevel(ScTickContext* c) { PairIslandState& s = c->narrow.islands; freeLevel(c, s, s.edge, s.ctl, s.info, s.parent, s.labels, s.partial); }
+void freePersistLevel(ScTickContext* c)
+{
+  PairPersistState& s = c->narrow.persist;
+  freeLevel(c, s, s.rec, s.ctl, s.info, s.partial, s.local[0], s.local[1], s.payload[0], s.payload[1]);
+}
+void freeSleepLevel(ScTickContext* c) { PairSleepState& s = c->narrow.sleep; freeLevel(c, s, s.ctl, s.info, s.fell, s.woke, s.partial); }
+
+// One level allocated afresh for `entries` entries of the list (0: freed, nothing allocated); a failure leaves what it allocated in the
+// state, and sizeNarrowPhase frees every level.  The list, the contacts and the manifolds: control words, a report, recsPer records per entry.
 template <typename State, typename Rec>
 bool sizeNarrowLevel(ScTickContext* c, State& s, Rec* State::*rec, uint32_t ctlWords, uint32_t infoWords, uint32_t recsPer, uint32_t entries)
 {
-  dfree(c, s.*rec); dfree(c, s.ctl); dfree(c, s.info);
-  s = State{};
+  freeNarrowLevel(c, s, rec);
   if (!entries) return true;
   if (!dalloc(c, s.ctl, ctlWords) || !dalloc(c, s.info, infoWords) || !dalloc(c, s.*rec, (size_t)recsPer * entries, false)) return false;
   s.maxTouching = entries;
   return true;
 }
 
-// The islands' level: an island word per entry, and the union-find's two words per entity of the context's capacity.  The caller's
-// fixed groups stay with the state across a re-size.
-bool sizeIslandLevel(ScTickContext* c, uint32_t entries, uint32_t fixedGroups)
+// The islands: an island word per entry, and the union-find's two words per entity of the context's capacity
+bool sizeIslandLevel(ScTickContext* c, uint32_t entries)
 {
-  PairIslandState& s = c->pairIslands;
-  dfree(c, s.parent); dfree(c, s.labels); dfree(c, s.partial);
-  s.parent = nullptr; s.labels = nullptr; s.partial = nullptr;
-  if (!sizeNarrowLevel(c, s, &PairIslandState::edge, kPiCtlWords, kPiInfoWords, 1u, entries)) return false;
+  PairIslandState& s = c->narrow.islands;
+  freeIslandLevel(c);
   if (!entries) return true;
-  if (!dalloc(c, s.parent, c->cap) || !dalloc(c, s.labels, c->cap) || !dalloc(c, s.partial, 4u * kPiMaxBlocks)) return false;
-  s.cap = c->cap; s.fixedGroups = fixedGroups;
+  if (!dalloc(c, s.ctl, kPiCtlWords) || !dalloc(c, s.info, kPiInfoWords) || !dalloc(c, s.edge, entries, false) || !dalloc(c, s.parent, c->cap) ||
+      !dalloc(c, s.labels, c->cap) || !dalloc(c, s.partial, 4u * kPiMaxBlocks)) return false;
+  s.maxTouching = entries; s.cap = c->cap;
   return true;
 }
 
-// The persistence level: a record per entry, two sides of local points (with ages and counts) and payload rows per entry, and one slab of
-// control words and both sides' tables, which a resync zeroes as a whole.  The caller's match distance stays with the state across a re-size.
+// Persistence: a record per entry, two sides of local points (with ages and counts) and payload rows per entry, and one slab of control
+// words and both sides' tables, which a resync zeroes as a whole
 bool sizePersistLevel(ScTickContext* c, uint32_t entries)
 {
-  PairPersistState& s = c->pairPersist;
-  const float matchDist = s.matchDist;
-  dfree(c, s.rec); dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.partial);
-  for (int k = 0; k < 2; ++k) { dfree(c, s.local[k]); dfree(c, s.payload[k]); }
-  s = PairPersistState{};
+  PairPersistState& s = c->narrow.persist;
+  freePersistLevel(c);
   if (!entries) return true;
   uint64_t slots = 64u;
   while (slots < 2ull * entries) slots <<= 1;
@@ -1316,82 +1353,64 @@ bool sizePersistLevel(ScTickContext* c, uint32_t entries)
   const size_t words = (size_t)kPpCtlWords + 2u * 2u * (size_t)slots + 2u * (size_t)slots;
   bool ok = dalloc(c, s.ctl, words) && dalloc(c, s.info, kPpInfoWords) && dalloc(c, s.rec, entries) && dalloc(c, s.partial, 4u * kPpMaxBlocks);
   for (int k = 0; k < 2 && ok; ++k) ok = dalloc(c, s.local[k], 4u * (size_t)entries) && dalloc(c, s.payload[k], 4u * (size_t)entries);
-  if (!ok) {
-    dfree(c, s.rec); dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.partial);
-    for (int k = 0; k < 2; ++k) { dfree(c, s.local[k]); dfree(c, s.payload[k]); }
-    s = PairPersistState{};
-    return false;
-  }
+  if (!ok) return false;
   s.key[0] = reinterpret_cast<unsigned long long*>(s.ctl + kPpCtlWords); s.key[1] = s.key[0] + slots;
   s.val[0] = reinterpret_cast<uint32_t*>(s.key[1] + slots); s.val[1] = s.val[0] + slots;
   s.slots = (uint32_t)slots; s.slabBytes = words * sizeof(uint32_t);
-  s.maxTouching = entries; s.matchDist = matchDist;
+  s.maxTouching = entries;
   return true;
 }
 
-// The sleep level: one slab -- control words, a state word and an awake word per entity of the context's capacity, three anchor rows per
-// entity --, which a resync zeroes as a whole; the two event lists, the report and the resolve's tallies.  The caller's tolerances and
-// rest_runs stay with the state across a re-size.
+// Sleep: one slab -- control words, a state word and an awake word per entity of the context's capacity, three anchor rows per entity --,
+// which a resync zeroes as a whole; the two event lists, the report and the resolve's tallies
 bool sizeSleepLevel(ScTickContext* c, uint32_t entries, uint32_t maxEvents)
 {
-  PairSleepState& s = c->pairSleep;
-  const float linTol = s.linTol, angTol = s.angTol;
-  const uint32_t restRuns = s.restRuns;
-  dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.fell); dfree(c, s.woke); dfree(c, s.partial);
-  s = PairSleepState{};
-  if (!entries || !maxEvents) return true;
+  PairSleepState& s = c->narrow.sleep;
+  freeSleepLevel(c);
+  if (!entries) return true;
   // [control words][state][awake][anchor]: the anchor rows 16-byte aligned behind 64 bytes of control words and 2 * cap words (cap is a multiple of the tile)
   const size_t words = (size_t)kPzCtlWords + 2u * (size_t)c->cap + 12u * (size_t)c->cap;
   if (!dalloc(c, s.ctl, words) || !dalloc(c, s.info, kPzInfoWords) || !dalloc(c, s.fell, maxEvents) || !dalloc(c, s.woke, maxEvents) ||
-      !dalloc(c, s.partial, 4u * kPzMaxBlocks)) {
-    dfree(c, s.ctl); dfree(c, s.info); dfree(c, s.fell); dfree(c, s.woke); dfree(c, s.partial);
-    s = PairSleepState{};
-    return false;
-  }
+      !dalloc(c, s.partial, 4u * kPzMaxBlocks)) return false;
   s.state = s.ctl + kPzCtlWords; s.awake = s.state + c->cap; s.anchor = reinterpret_cast<float4*>(s.awake + c->cap);
   s.slabBytes = words * sizeof(uint32_t);
   s.cap = c->cap; s.maxTouching = entries; s.maxEvents = maxEvents;
-  s.linTol = linTol; s.angTol = angTol; s.restRuns = restRuns;
   return true;
 }
 
-// The chain for a list of maxTouching entries (0: everything off), with contacts, manifolds, islands, persistence and sleep where wanted:
-// contacts and islands need the list, manifolds the contacts, persistence the manifolds, sleep the islands (sleepEvents: its max_events,
-// 0 = off).  `set` is the level the calling setter sets.  A failed allocation leaves all six off (the allocator's text stands): nothing
-// is ever on without what it needs, or sized for another list.
+// Make the context match `want`; `level` is the stage the calling setter sets.  Dependencies are settled here, once: nothing without the
+// list, no manifolds without contacts, no persistence without manifolds, no sleep without islands.  The list, contacts, manifolds and
+// islands are allocated afresh when the setter sets them or the list is allocated afresh, freed when they have to be off, and otherwise
+// left alone.  Persistence and sleep hold a memory: allocated afresh -- a resync -- only when the list's size (sleep: or max_events)
+// differs from theirs.  Then the caller's parameters are written from the record, zero where a stage is off.  A failed allocation leaves
+// all six off (the allocator's text stands): nothing is ever on without what it needs, or sized for another list.
 enum NarrowLevel { kNarrowList, kNarrowContacts, kNarrowManifolds, kNarrowIslands, kNarrowPersist, kNarrowSleep };
-bool sizeNarrowPhase(ScTickContext* c, NarrowLevel set, uint32_t maxTouching, bool contacts, bool manifolds, bool islands, uint32_t fixedGroups, bool persist,
-                     uint32_t sleepEvents)
+bool sizeNarrowPhase(ScTickContext* c, NarrowLevel level, const NarrowWant& want)
 {
-  // (sleep holds a memory like persistence: allocated afresh -- a resync -- only when the list's size or max_events changes)
-  const uint32_t sleepEntries = (islands && sleepEvents) ? maxTouching : 0u;
-  // (persistence holds a memory: it is allocated afresh -- a resync -- only when its size changes, and so survives a same-size scTickSetPairShapes)
-  const uint32_t persistEntries = (contacts && manifolds && persist) ? maxTouching : 0u;
-  const uint32_t contactEntries = contacts ? maxTouching : 0u;
-  const uint32_t manifoldEntries = (contacts && manifolds) ? maxTouching : 0u;
-  const uint32_t islandEntries = islands ? maxTouching : 0u;
-  // a level is allocated afresh when the setter sets it or the list under it is allocated afresh, freed when it has to be off, and
-  // otherwise stays as it is (scTickSetPairContacts(1) leaves the list and the manifolds alone)
-  const bool doList = set == kNarrowList;
-  const bool doContacts = doList || set == kNarrowContacts || !contactEntries;
-  const bool doManifolds = doList || set == kNarrowManifolds || !manifoldEntries;
-  const bool doIslands = doList || set == kNarrowIslands || !islandEntries;
+  NarrowPhase& np = c->narrow;
+  NarrowWant w = want;
+  w.contacts = w.contacts && w.maxTouching; w.islands = w.islands && w.maxTouching;
+  w.manifolds = w.manifolds && w.contacts; w.persist = w.persist && w.manifolds;
+  if (!w.islands) w.sleepEvents = 0u;
+  const uint32_t m = w.maxTouching, persistEntries = w.persist ? m : 0u, sleepEntries = w.sleepEvents ? m : 0u;
+  const bool list = level == kNarrowList;
   bool ok = true;
-  if (doList) ok = sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, maxTouching);
-  if (ok && doContacts) ok = sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, contactEntries);
-  if (ok && doManifolds) ok = sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, manifoldEntries);
-  if (ok && doIslands) ok = sizeIslandLevel(c, islandEntries, fixedGroups);
-  if (ok && persistEntries != c->pairPersist.maxTouching) ok = sizePersistLevel(c, persistEntries);
-  if (ok && (sleepEntries != c->pairSleep.maxTouching || (sleepEntries && sleepEvents != c->pairSleep.maxEvents))) ok = sizeSleepLevel(c, sleepEntries, sleepEvents);
-  if (!ok) {      // everything off (0 entries: a level is freed, nothing is allocated)
-    sizeNarrowLevel(c, c->pairShapes, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, 0u);
-    sizeNarrowLevel(c, c->pairContacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, 0u);
-    sizeNarrowLevel(c, c->pairManifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, 0u);
-    sizeIslandLevel(c, 0u, 0u);
-    sizePersistLevel(c, 0u);
-    sizeSleepLevel(c, 0u, 0u);
+  if (list) ok = sizeNarrowLevel(c, np.list, &PairShapeState::list, kPsCtlWords, kPsInfoWords, 1u, m);
+  if (ok && (list || level == kNarrowContacts || !w.contacts)) ok = sizeNarrowLevel(c, np.contacts, &PairContactState::rec, kPcCtlWords, kPcInfoWords, 2u, w.contacts ? m : 0u);
+  if (ok && (list || level == kNarrowManifolds || !w.manifolds)) ok = sizeNarrowLevel(c, np.manifolds, &PairManifoldState::rec, kPmCtlWords, kPmInfoWords, 5u, w.manifolds ? m : 0u);
+  if (ok && (list || level == kNarrowIslands || !w.islands)) ok = sizeIslandLevel(c, w.islands ? m : 0u);
+  if (ok && persistEntries != np.persist.maxTouching) ok = sizePersistLevel(c, persistEntries);
+  if (ok && (sleepEntries != np.sleep.maxTouching || w.sleepEvents != np.sleep.maxEvents)) ok = sizeSleepLevel(c, sleepEntries, w.sleepEvents);
+  if (!ok) {
+    freeNarrowLevel(c, np.list, &PairShapeState::list); freeNarrowLevel(c, np.contacts, &PairContactState::rec); freeNarrowLevel(c, np.manifolds, &PairManifoldState::rec);
+    freeIslandLevel(c); freePersistLevel(c); freeSleepLevel(c);
+    return false;
   }
-  return ok;
+  np.islands.fixedGroups = w.islands ? w.fixedGroups : 0u;
+  np.persist.matchDist = w.persist ? w.matchDist : 0.0f;
+  const bool sleep = w.sleepEvents != 0u;
+  np.sleep.linTol = sleep ? w.linTol : 0.0f; np.sleep.angTol = sleep ? w.angTol : 0.0f; np.sleep.restRuns = sleep ? w.restRuns : 0u;
+  return true;
 }
 
 } // namespace
@@ -1757,7 +1776,7 @@ int scTickUploadLayers(ScTickContext* c, uint32_t first, uint32_t count, const u
   if (!c || !group || !mask) return c ? fail(c, "null argument") : 0;
   if (!bind(c) || !rangeOk(c, first, count)) return 0;
   // (the island pass of a pending pair half decides "movable" from the layer words as they stand when it runs)
-  if (c->pairsPending && c->pendingTick.pairIslands)
+  if (c->pairsPending && (c->pendingTick.narrow & kStageIslands))
     return fail(c, "scTickUploadLayers is refused between scTickRun(.. | SC_TICK_SPLIT_PAIRS) and scTickRunPairs of a tick that computes pair islands: its pair half reads the layer words as they stand");
   if (!count) return 1;
   std::vector<uint32_t> packed(count);
@@ -2281,12 +2300,12 @@ static bool tickAccepted(ScTickContext* c, uint32_t flags)
   }
   if (flags & SC_TICK_PAIR_SHAPES) {
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_PAIR_SHAPES needs SC_TICK_BROADPHASE in the same run (the touching pairs are those of this tick's pair list)");
-    if (!c->pairShapes.ctl) return fail(c, "SC_TICK_PAIR_SHAPES needs scTickSetPairShapes first");
+    if (!c->narrow.list.ctl) return fail(c, "SC_TICK_PAIR_SHAPES needs scTickSetPairShapes first");
     if (c->pairsStream) return fail(c, "SC_TICK_PAIR_SHAPES cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its pair half runs when the matrices may be the next tick's");
   }
   if (flags & SC_TICK_TOUCH_EVENTS) {
     if (!(flags & SC_TICK_BROADPHASE)) return fail(c, "SC_TICK_TOUCH_EVENTS needs SC_TICK_BROADPHASE in the same run (the events are the difference of this tick's touching set)");
-    if (!c->touchEvents.ctl) return fail(c, "SC_TICK_TOUCH_EVENTS needs scTickSetTouchEvents first");
+    if (!c->narrow.touch.ctl) return fail(c, "SC_TICK_TOUCH_EVENTS needs scTickSetTouchEvents first");
     if (c->pairsStream) return fail(c, "SC_TICK_TOUCH_EVENTS cannot run on a pipelined context (scTickSetPipelined / scTickSetPairsStream): its tick parities overlap in time, and its pair half runs when the matrices may be the next tick's");
   }
   if (flags & SC_TICK_BIND_RUNS) {
@@ -2389,9 +2408,17 @@ static TickPlan planTick(ScTickContext* c, uint32_t flags)
   plan.rec.frame[0] = path.items; plan.rec.frame[1] = path.block;
   plan.triggers = path.pairsNow && (p.flags & kFlagTriggers) != 0u;
   plan.anchoredSweeps = path.pairsNow && (p.flags & kFlagAnchoredSweeps) != 0u;
-  plan.pairIslands = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairIslands.ctl != nullptr;      // (whichever half closes the pair search)
-  plan.pairPersist = (p.flags & SC_TICK_PAIR_SHAPES) != 0u && c->pairPersist.ctl != nullptr;
-  plan.pairSleep = plan.pairIslands && c->pairSleep.ctl != nullptr;
+  // the narrow phase's stages (whichever half closes the pair search): the two flags' states are there (tickAccepted); a stage behind the
+  // list runs when it is enabled and what it needs runs
+  if (p.flags & SC_TICK_TOUCH_EVENTS) plan.narrow |= kStageTouch;
+  if (p.flags & SC_TICK_PAIR_SHAPES) {
+    const uint32_t on = narrowOn(c);
+    uint32_t st = kStageList | (on & (kStageContacts | kStageIslands));
+    if (st & kStageContacts) st |= on & kStageManifolds;
+    if (st & kStageManifolds) st |= on & kStagePersist;
+    if (st & kStageIslands) st |= on & kStageSleep;
+    plan.narrow |= st;
+  }
   if (path.stagedEmit) plan.rec.draws = frameItems(c->rb.dBlock[frameSlot(c->rb)], c->rb.maxVisible);
   plan.sampled = tickSampled(c);                       // (events need eager launches)
   plan.replay = c->graphMode && !plan.sampled && !plan.learn;
@@ -2445,7 +2472,7 @@ static int commitPlan(ScTickContext* c, const TickPlan& plan)
 // that a HIP error ends in commitPlan, a capture or a replay leaves the record of the run before it).  `last` whole; `lastBinned` by a
 // tick that binned; of `lastWith` what belongs to a flag in `with` -- the run's flags (an empty context's run launches nothing: of the
 // features only the bind runs answer for it, with zeros).
-static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* binned, uint32_t with)
+static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* binned, uint32_t with, uint32_t narrow)
 {
   c->last = rec;
   if (binned) c->lastBinned = *binned;
@@ -2455,11 +2482,7 @@ static void recordRun(ScTickContext* c, const RunRecord& rec, const BinOutcome* 
   if (with & SC_TICK_TRIGGERS) { w.triggerCount = c->triggers.count; w.triggerMaxMembers = c->triggers.maxMembers; w.triggerMaxEvents = c->triggers.maxEvents; }
   if (with & SC_TICK_ANCHORED_SWEEPS) { w.asweepCount = c->asweeps.count; w.asweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT; }
   if (with & SC_TICK_SWEEPS) w.sweepsExact = c->sweepShapes == SC_TICK_SWEEP_SHAPES_EXACT;
-  if (with & SC_TICK_PAIR_SHAPES) {
-    w.pairContacts = c->pairContacts.ctl != nullptr; w.pairManifolds = c->pairManifolds.ctl != nullptr; w.pairIslands = c->pairIslands.ctl != nullptr;
-    w.pairPersist = c->pairPersist.ctl != nullptr;
-    w.pairSleep = c->pairIslands.ctl != nullptr && c->pairSleep.ctl != nullptr;
-  }
+  if (with & SC_TICK_PAIR_SHAPES) w.narrow = narrow;
 }
 
 // The run of an empty context without a broadphase: nothing to launch, the per-tick counts read as zero.  (With the broadphase the
@@ -2482,7 +2505,7 @@ static int emptyTick(ScTickContext* c, uint32_t flags)
     HIP_OK(c, publishFrame(c, false));
     rec.frame[1] = SC_TICK_FRAME_BLOCK_HOST;
   }
-  recordRun(c, rec, nullptr, flags & SC_TICK_BIND_RUNS);
+  recordRun(c, rec, nullptr, flags & SC_TICK_BIND_RUNS, 0u);
   return 1;
 }
 
@@ -2513,7 +2536,7 @@ int scTickRun(ScTickContext* c, uint32_t flags)
         })) return 0;
   } else rode = enqueueStages(c, plan, false);
   publishPacked(c, p, rode);
-  recordRun(c, plan.rec, plan.binned ? &plan.bins : nullptr, flags);
+  recordRun(c, plan.rec, plan.binned ? &plan.bins : nullptr, flags, plan.narrow);
   if (plan.run & SC_TICK_BROADPHASE) {
     if ((plan.run & SC_TICK_SPLIT_PAIRS) && !plan.wholeStep) { c->pairsPending = true; c->pendingTick = plan; }
     else { c->lastParity = c->parity; c->parity ^= 1u; }           // (in-order flows alternate between two copies)
@@ -3400,7 +3423,7 @@ int scTickReadPairEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, 
 int scTickSetTouchEvents(ScTickContext* c, uint32_t maxTracked, uint32_t maxEvents)
 {
   if (!c) return 0;
-  return setEventState(c, c->touchEvents, c->touchEventSlab, c->touchEventSlabBytes, "touch events", maxTracked, maxEvents);
+  return setEventState(c, c->narrow.touch, c->touchEventSlab, c->touchEventSlabBytes, "touch events", maxTracked, maxEvents);
 }
 
 int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap, uint32_t* ended2, uint32_t endedCap, ScTickTouchEventInfo* info)
@@ -3408,7 +3431,7 @@ int scTickReadTouchEvents(ScTickContext* c, uint32_t* begun2, uint32_t begunCap,
   static_assert(sizeof(ScTickTouchEventInfo) == sizeof(ScTickPairEventInfo) && offsetof(ScTickTouchEventInfo, events_truncated) == offsetof(ScTickPairEventInfo, events_truncated),
                 "the two reports are the same six words");
   if (!c) return 0;
-  return readEventState(c, c->touchEvents, SC_TICK_TOUCH_EVENTS, "the last scTickRun did not request SC_TICK_TOUCH_EVENTS", "touch events are ready after scTickRunPairs",
+  return readEventState(c, c->narrow.touch, SC_TICK_TOUCH_EVENTS, "the last scTickRun did not request SC_TICK_TOUCH_EVENTS", "touch events are ready after scTickRunPairs",
                         "touch events were switched off since the last scTickRun", begun2, begunCap, ended2, endedCap, reinterpret_cast<ScTickPairEventInfo*>(info));
 }
 
@@ -3420,9 +3443,10 @@ int scTickSetPairShapes(ScTickContext* c, uint32_t maxTouching)
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  // (pair contacts and pair islands follow the list: off with it, re-sized with it -- and pair manifolds follow the contacts)
-  return sizeNarrowPhase(c, kNarrowList, maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
+  // (every other stage follows the list: off with it, re-sized with it)
+  NarrowWant w = narrowWanted(c);
+  w.maxTouching = maxTouching;
+  return sizeNarrowPhase(c, kNarrowList, w) ? 1 : 0;
 }
 
 int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
@@ -3433,19 +3457,19 @@ int scTickSetPairContacts(ScTickContext* c, uint32_t enable)
                 kContactBoxFaceA == SC_TICK_CONTACT_BOX_FACE_A && kContactBoxFaceB == SC_TICK_CONTACT_BOX_FACE_B && kContactBoxEdge == SC_TICK_CONTACT_BOX_EDGE &&
                 kContactDeep == SC_TICK_CONTACT_DEEP && kContactDegenerate == SC_TICK_CONTACT_DEGENERATE, "the contact kinds differ from the header's");
   if (!c) return 0;
-  if (enable && !c->pairShapes.ctl) return fail(c, "scTickSetPairContacts needs scTickSetPairShapes(max_touching > 0) first");
+  NarrowWant w = narrowWanted(c);
+  if (enable && !w.maxTouching) return fail(c, "scTickSetPairContacts needs scTickSetPairShapes(max_touching > 0) first");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  // (pair manifolds need the contacts: off with them)
-  return sizeNarrowPhase(c, kNarrowContacts, c->pairShapes.maxTouching, enable != 0u, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
+  w.contacts = enable != 0u;      // (pair manifolds need the contacts: off with them)
+  return sizeNarrowPhase(c, kNarrowContacts, w) ? 1 : 0;
 }
 
 int scTickGetPairContacts(ScTickContext* c, uint32_t* enabled)
 {
   if (!c || !enabled) return c ? fail(c, "null argument") : 0;
-  *enabled = c->pairContacts.ctl ? 1u : 0u;
+  *enabled = c->narrow.contacts.ctl ? 1u : 0u;
   return 1;
 }
 
@@ -3453,10 +3477,8 @@ int scTickReadPairContacts(ScTickContext* c, ScTickPairContact* out, uint32_t ca
 {
   static_assert(sizeof(ScTickPairContactInfo) == kPcInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairContactState& k = c->pairContacts;
-  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastWith.pairContacts, "pair contacts were not enabled at the last scTickRun (scTickSetPairContacts)",
-                                 "pair contacts are ready after scTickRunPairs", k.ctl != nullptr, "pair contacts were switched off since the last scTickRun")) return 0;
+  const PairContactState& k = c->narrow.contacts;
+  if (!narrowResult(c, kStageContacts)) return 0;
   return readReportAndRecords(c, info, k.info, &ScTickPairContactInfo::written, k.maxTouching, k.rec, sizeof(ScTickPairContact), out, capacity) ? 1 : 0;
 }
 
@@ -3468,18 +3490,19 @@ int scTickSetPairManifolds(ScTickContext* c, uint32_t enable)
                 kManifoldFace == SC_TICK_MANIFOLD_FACE && kManifoldReduced == SC_TICK_MANIFOLD_REDUCED, "the manifold kinds differ from the header's");
   static_assert(kManifoldSkin == SC_TICK_MANIFOLD_SKIN && kManifoldFlat == SC_TICK_MANIFOLD_FLAT, "the manifold tolerances differ from the header's");
   if (!c) return 0;
-  if (enable && !c->pairContacts.ctl) return fail(c, "scTickSetPairManifolds needs scTickSetPairContacts(1) first");
+  NarrowWant w = narrowWanted(c);
+  if (enable && !w.contacts) return fail(c, "scTickSetPairManifolds needs scTickSetPairContacts(1) first");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  return sizeNarrowPhase(c, kNarrowManifolds, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, enable != 0u, c->pairIslands.ctl != nullptr,
-                         c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
+  w.manifolds = enable != 0u;
+  return sizeNarrowPhase(c, kNarrowManifolds, w) ? 1 : 0;
 }
 
 int scTickGetPairManifolds(ScTickContext* c, uint32_t* enabled)
 {
   if (!c || !enabled) return c ? fail(c, "null argument") : 0;
-  *enabled = c->pairManifolds.ctl ? 1u : 0u;
+  *enabled = c->narrow.manifolds.ctl ? 1u : 0u;
   return 1;
 }
 
@@ -3487,10 +3510,8 @@ int scTickReadPairManifolds(ScTickContext* c, ScTickPairManifold* out, uint32_t 
 {
   static_assert(sizeof(ScTickPairManifoldInfo) == kPmInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairManifoldState& f = c->pairManifolds;
-  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastWith.pairManifolds, "pair manifolds were not enabled at the last scTickRun (scTickSetPairManifolds)",
-                                 "pair manifolds are ready after scTickRunPairs", f.ctl != nullptr, "pair manifolds were switched off since the last scTickRun")) return 0;
+  const PairManifoldState& f = c->narrow.manifolds;
+  if (!narrowResult(c, kStageManifolds)) return 0;
   return readReportAndRecords(c, info, f.info, &ScTickPairManifoldInfo::written, f.maxTouching, f.rec, sizeof(ScTickPairManifold), out, capacity) ? 1 : 0;
 }
 
@@ -3499,30 +3520,29 @@ int scTickSetPairIslands(ScTickContext* c, uint32_t enable, uint32_t fixedGroups
   static_assert(sizeof(ScTickPairIslandInfo) == 32u && sizeof(ScTickPairIslandInfo) == kPiInfoWords * sizeof(uint32_t), "the device writes the report word by word");
   static_assert(kIslandNone == SC_TICK_ISLAND_NONE, "the island of a fixed member differs from the header's");
   if (!c) return 0;
-  if (enable && !c->pairShapes.ctl) return fail(c, "scTickSetPairIslands needs scTickSetPairShapes(max_touching > 0) first");
+  NarrowWant w = narrowWanted(c);
+  if (enable && !w.maxTouching) return fail(c, "scTickSetPairIslands needs scTickSetPairShapes(max_touching > 0) first");
   if (fixedGroups >> 16) return fail(c, "scTickSetPairIslands: fixed_groups bits above 15 are not supported");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old fixed groups; no epoch bump: the bins are not concerned
-  return sizeNarrowPhase(c, kNarrowIslands, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, enable != 0u,
-                         enable ? fixedGroups : 0u, c->pairPersist.ctl != nullptr, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u) ? 1 : 0;
+  w.islands = enable != 0u; w.fixedGroups = fixedGroups;
+  return sizeNarrowPhase(c, kNarrowIslands, w) ? 1 : 0;
 }
 
 int scTickGetPairIslands(ScTickContext* c, uint32_t* enabled, uint32_t* fixedGroups)
 {
   if (!c || !enabled || !fixedGroups) return c ? fail(c, "null argument") : 0;
-  *enabled = c->pairIslands.ctl ? 1u : 0u;
-  *fixedGroups = c->pairIslands.fixedGroups;
+  *enabled = c->narrow.islands.ctl ? 1u : 0u;
+  *fixedGroups = c->narrow.islands.fixedGroups;
   return 1;
 }
 
 int scTickReadPairIslands(ScTickContext* c, uint32_t* labels, uint32_t labelCapacity, uint32_t* edgeIslands, uint32_t edgeCapacity, ScTickPairIslandInfo* info)
 {
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairIslandState& s = c->pairIslands;
-  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastWith.pairIslands, "pair islands were not enabled at the last scTickRun (scTickSetPairIslands)",
-                                 "pair islands are ready after scTickRunPairs", s.ctl != nullptr, "pair islands were switched off since the last scTickRun")) return 0;
+  const PairIslandState& s = c->narrow.islands;
+  if (!narrowResult(c, kStageIslands)) return 0;
   // the report and the edge islands like every record reader; then the labels of the entities there are now
   if (!readReportAndRecords(c, info, s.info, &ScTickPairIslandInfo::edges, s.maxTouching, s.edge, sizeof(uint32_t), edgeIslands, edgeCapacity)) return 0;
   const uint32_t m = std::min(std::min(c->n, s.cap), labels ? labelCapacity : 0u);
@@ -3536,7 +3556,8 @@ int scTickSetPairSleep(ScTickContext* c, uint32_t enable, float linTol, float an
   static_assert(kSleepResync == SC_TICK_SLEEP_INFO_RESYNC && kSleepFellOverflow == SC_TICK_SLEEP_INFO_FELL_OVERFLOW && kSleepWokeOverflow == SC_TICK_SLEEP_INFO_WOKE_OVERFLOW &&
                 kSleepListTruncated == SC_TICK_SLEEP_INFO_LIST_TRUNCATED, "the report's flags differ from the header's");
   if (!c) return 0;
-  if (enable && !c->pairIslands.ctl) return fail(c, "scTickSetPairSleep needs scTickSetPairIslands(1) first");
+  NarrowWant w = narrowWanted(c);
+  if (enable && !w.islands) return fail(c, "scTickSetPairSleep needs scTickSetPairIslands(1) first");
   if (enable && !(std::isfinite(linTol) && linTol >= 0.0f && std::isfinite(angTol) && angTol >= 0.0f))
     return fail(c, "scTickSetPairSleep: lin_tol and ang_tol must be finite and >= 0");
   if (enable && (restRuns < 1u || restRuns > 255u)) return fail(c, "scTickSetPairSleep: rest_runs must be in 1 .. 255");
@@ -3544,36 +3565,27 @@ int scTickSetPairSleep(ScTickContext* c, uint32_t enable, float linTol, float an
   if (enable && maxEvents > (1u << 24)) return fail(c, "scTickSetPairSleep: at most 2^24 events a list");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
-  PairSleepState& z = c->pairSleep;
-  if (enable && z.ctl && z.maxEvents == maxEvents) {        // (already on: what is remembered stays)
-    // a captured tick holds the tolerances and rest_runs as kernel arguments
-    if (z.linTol != linTol || z.angTol != angTol || z.restRuns != restRuns) dropCaptures(c);
-    z.linTol = linTol; z.angTol = angTol; z.restRuns = restRuns;
-    return 1;
-  }
-  dropCaptures(c);       // a captured tick holds the old buffers (or none); no epoch bump: the bins are not concerned
-  if (!sizeNarrowPhase(c, kNarrowSleep, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                       c->pairIslands.fixedGroups, c->pairPersist.ctl != nullptr, enable ? maxEvents : 0u)) return 0;
-  if (enable) { z.linTol = linTol; z.angTol = angTol; z.restRuns = restRuns; }
-  return 1;
+  // a captured tick holds the buffers (or none), and the tolerances and rest_runs as kernel arguments; no epoch bump: the bins are not
+  // concerned.  (Already on with this max_events: what is remembered stays, and so do the captures where nothing changes)
+  if (!(enable && w.sleepEvents == maxEvents && w.linTol == linTol && w.angTol == angTol && w.restRuns == restRuns)) dropCaptures(c);
+  w.sleepEvents = enable ? maxEvents : 0u; w.linTol = linTol; w.angTol = angTol; w.restRuns = restRuns;
+  return sizeNarrowPhase(c, kNarrowSleep, w) ? 1 : 0;
 }
 
 int scTickGetPairSleep(ScTickContext* c, uint32_t* enabled, float* linTol, float* angTol, uint32_t* restRuns, uint32_t* maxEvents)
 {
   if (!c || !enabled || !linTol || !angTol || !restRuns || !maxEvents) return c ? fail(c, "null argument") : 0;
-  const PairSleepState& z = c->pairSleep;
-  *enabled = z.ctl ? 1u : 0u;
-  *linTol = z.ctl ? z.linTol : 0.0f; *angTol = z.ctl ? z.angTol : 0.0f;
-  *restRuns = z.ctl ? z.restRuns : 0u; *maxEvents = z.ctl ? z.maxEvents : 0u;
+  const PairSleepState& z = c->narrow.sleep;      // (all zero while off)
+  *enabled = z.ctl ? 1u : 0u; *linTol = z.linTol; *angTol = z.angTol; *restRuns = z.restRuns; *maxEvents = z.maxEvents;
   return 1;
 }
 
 int scTickWakeEntities(ScTickContext* c, const uint32_t* ids, uint32_t n)
 {
   if (!c || (!ids && n)) return c ? fail(c, "null argument") : 0;
-  if (!c->pairSleep.ctl) return fail(c, "scTickWakeEntities needs scTickSetPairSleep(1) first");
+  if (!c->narrow.sleep.ctl) return fail(c, "scTickWakeEntities needs scTickSetPairSleep(1) first");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
-  const uint32_t count = std::min(c->n, c->pairSleep.cap);
+  const uint32_t count = std::min(c->n, c->narrow.sleep.cap);
   std::vector<uint32_t> dense(n);
   for (uint32_t i = 0; i < n; ++i) {                        // (every id is checked before anything is written)
     if ((ids[i] >> 24) != c->rank) return fail(c, "scTickWakeEntities: an id of another rank");
@@ -3585,7 +3597,7 @@ int scTickWakeEntities(ScTickContext* c, const uint32_t* ids, uint32_t n)
   uint32_t* dIds = nullptr;
   if (!dalloc(c, dIds, n, false)) return 0;
   const bool ok = h2d(c, dIds, dense.data(), (size_t)n * sizeof(uint32_t));
-  if (ok) launchPairSleepWake(c->pairSleep, dIds, n, c->stream);
+  if (ok) launchPairSleepWake(c->narrow.sleep, dIds, n, c->stream);
   const bool done = ok && sync(c);
   dfree(c, dIds);
   return done ? 1 : 0;
@@ -3595,10 +3607,8 @@ int scTickReadPairSleep(ScTickContext* c, uint32_t* states, uint32_t stateCapaci
                         ScTickPairSleepInfo* info)
 {
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairSleepState& z = c->pairSleep;
-  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                 c->lastWith.pairSleep, "pair sleep was not enabled at the last scTickRun (scTickSetPairSleep)",
-                                 "pair sleep is ready after scTickRunPairs", z.ctl != nullptr, "pair sleep was switched off since the last scTickRun")) return 0;
+  const PairSleepState& z = c->narrow.sleep;
+  if (!narrowResult(c, kStageSleep)) return 0;
   if (!d2h(c, info, z.info, sizeof *info) || !sync(c)) return 0;
   const uint32_t ns = std::min(std::min(c->n, z.cap), states ? stateCapacity : 0u);
   const uint32_t nf = std::min(std::min(info->fell_asleep, z.maxEvents), fellAsleep ? fellCapacity : 0u);
@@ -3615,41 +3625,33 @@ int scTickSetPairPersistence(ScTickContext* c, uint32_t enable, float matchDist)
   static_assert(sizeof(ScTickPairPersistInfo) == 32u && sizeof(ScTickPairPersistInfo) <= kPpInfoSide * sizeof(uint32_t), "the device writes the report word by word");
   static_assert(kPersistNone == SC_TICK_PERSIST_NONE, "the entry of an unmatched pair differs from the header's");
   if (!c) return 0;
-  if (enable && !c->pairManifolds.ctl) return fail(c, "scTickSetPairPersistence needs scTickSetPairManifolds(1) first");
+  NarrowWant w = narrowWanted(c);
+  if (enable && !w.manifolds) return fail(c, "scTickSetPairPersistence needs scTickSetPairManifolds(1) first");
   if (enable && !(std::isfinite(matchDist) && matchDist > 0.0f)) return fail(c, "scTickSetPairPersistence: match_dist must be finite and > 0");
   if (c->pairsPending) return fail(c, "scTickRunPairs is pending");
   if (!bind(c) || !sync(c)) return 0;
   dropCaptures(c);       // a captured tick holds the old buffers (or none) and the old match distance; no epoch bump: the bins are not concerned
-  if (enable && c->pairPersist.ctl) { c->pairPersist.matchDist = matchDist; return 1; }      // (already on: what is remembered stays)
-  if (!sizeNarrowPhase(c, kNarrowPersist, c->pairShapes.maxTouching, c->pairContacts.ctl != nullptr, c->pairManifolds.ctl != nullptr, c->pairIslands.ctl != nullptr,
-                       c->pairIslands.fixedGroups, enable != 0u, c->pairSleep.ctl ? c->pairSleep.maxEvents : 0u)) return 0;
-  c->pairPersist.matchDist = enable ? matchDist : 0.0f;
-  return 1;
+  w.persist = enable != 0u; w.matchDist = matchDist;      // (already on: its size stays, and with it what is remembered)
+  return sizeNarrowPhase(c, kNarrowPersist, w) ? 1 : 0;
 }
 
 int scTickGetPairPersistence(ScTickContext* c, uint32_t* enabled, float* matchDist)
 {
   if (!c || !enabled || !matchDist) return c ? fail(c, "null argument") : 0;
-  *enabled = c->pairPersist.ctl ? 1u : 0u;
-  *matchDist = c->pairPersist.ctl ? c->pairPersist.matchDist : 0.0f;
+  *enabled = c->narrow.persist.ctl ? 1u : 0u;
+  *matchDist = c->narrow.persist.ctl ? c->narrow.persist.matchDist : 0.0f;
   return 1;
 }
 
 namespace {
 // the gate of the persistence readers and of the payload write: the last run matched, its pair half is through, the buffers are still there
-bool pairPersistResult(ScTickContext* c)
-{
-  return bind(c) && lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES",
-                                  c->lastWith.pairPersist, "pair persistence was not enabled at the last scTickRun (scTickSetPairPersistence)",
-                                  "pair persistence is ready after scTickRunPairs", c->pairPersist.ctl != nullptr,
-                                  "pair persistence was switched off since the last scTickRun");
-}
+bool pairPersistResult(ScTickContext* c) { return narrowResult(c, kStagePersist); }
 // that run's `written` and the side it filled, as the finish kernel left them
 bool pairPersistFilled(ScTickContext* c, uint32_t& written, uint32_t& side)
 {
   uint32_t w[kPpInfoWords];
-  if (!d2h(c, w, c->pairPersist.info, sizeof w) || !sync(c)) return false;
-  written = std::min(w[0], c->pairPersist.maxTouching); side = w[kPpInfoSide] & 1u;
+  if (!d2h(c, w, c->narrow.persist.info, sizeof w) || !sync(c)) return false;
+  written = std::min(w[0], c->narrow.persist.maxTouching); side = w[kPpInfoSide] & 1u;
   return true;
 }
 } // namespace
@@ -3657,7 +3659,7 @@ bool pairPersistFilled(ScTickContext* c, uint32_t& written, uint32_t& side)
 int scTickReadPairPersistence(ScTickContext* c, ScTickPairPersist* out, uint32_t capacity, ScTickPairPersistInfo* info)
 {
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairPersistState& s = c->pairPersist;
+  const PairPersistState& s = c->narrow.persist;
   if (!pairPersistResult(c)) return 0;
   return readReportAndRecords(c, info, s.info, &ScTickPairPersistInfo::written, s.maxTouching, s.rec, sizeof(ScTickPairPersist), out, capacity) ? 1 : 0;
 }
@@ -3672,7 +3674,7 @@ int scTickWritePairPayloads(ScTickContext* c, const float* rows, uint32_t first,
   if ((uint64_t)first + count > written) return fail(c, "scTickWritePairPayloads: the range exceeds the records the last run wrote");
   if (!count) return 1;
   // (the rows the next flagged run carries from: behind the run on its stream)
-  return (h2d(c, c->pairPersist.payload[side] + 4u * (size_t)first, rows, (size_t)count * 4u * sizeof(float4)) && sync(c)) ? 1 : 0;
+  return (h2d(c, c->narrow.persist.payload[side] + 4u * (size_t)first, rows, (size_t)count * 4u * sizeof(float4)) && sync(c)) ? 1 : 0;
 }
 
 int scTickReadPairPayloads(ScTickContext* c, float* rows, uint32_t capacity)
@@ -3682,7 +3684,7 @@ int scTickReadPairPayloads(ScTickContext* c, float* rows, uint32_t capacity)
   uint32_t written = 0, side = 0;
   if (!pairPersistFilled(c, written, side)) return 0;
   const uint32_t m = std::min(written, rows ? capacity : 0u);
-  return (!m || (d2h(c, rows, c->pairPersist.payload[side], (size_t)m * 4u * sizeof(float4)) && sync(c))) ? 1 : 0;
+  return (!m || (d2h(c, rows, c->narrow.persist.payload[side], (size_t)m * 4u * sizeof(float4)) && sync(c))) ? 1 : 0;
 }
 
 int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, ScTickPairShapeInfo* info)
@@ -3690,9 +3692,8 @@ int scTickReadPairShapes(ScTickContext* c, uint32_t* pairs2, uint32_t capacity, 
   static_assert(sizeof(ScTickPairShapeInfo) == 6u * sizeof(uint32_t) && kPsInfoWords >= 6u, "the device writes the report word by word");
   static_assert(kPairShapesSatEps == SC_TICK_PAIR_SHAPES_SAT_EPS, "the separating-axis epsilon differs from the header's");
   if (!c || !info) return c ? fail(c, "null argument") : 0;
-  const PairShapeState& e = c->pairShapes;
-  if (!bind(c) || !lastRunResult(c, SC_TICK_PAIR_SHAPES, "the last scTickRun did not request SC_TICK_PAIR_SHAPES", true, nullptr,
-                                 "touching pairs are ready after scTickRunPairs", e.ctl != nullptr, "touching pairs were switched off since the last scTickRun")) return 0;
+  const PairShapeState& e = c->narrow.list;
+  if (!narrowResult(c, kStageList)) return 0;
   return readReportAndRecords(c, info, e.info, &ScTickPairShapeInfo::touching, e.maxTouching, e.list, sizeof(uint2), pairs2, capacity) ? 1 : 0;
 }
 

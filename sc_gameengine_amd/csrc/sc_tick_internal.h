@@ -826,16 +826,19 @@ __device__ __forceinline__ bool boxBoxApart(const Member& ma, const Member& mb)
 #endif
 // ---- touch events (include/sc_tick.h "touch events"): the pair events' difference taken over the TOUCHING set.  A second PairEventState;
 // the narrow-phase kernel enters what it decides "not apart" into that state's current table (its <.., Events> instances), the pair
-// events' sweep and finish do the rest.  One narrow-phase launch per tick: `list` (SC_TICK_PAIR_SHAPES) and `touch`
-// (SC_TICK_TOUCH_EVENTS) may each be null, or not enabled (no ctl): then that half is not written.
-// `contacts` (scTickSetPairContacts; null or not enabled: nothing more is launched) adds k_pair_contacts between the pass and the list's report.
-// `manifolds` (scTickSetPairManifolds; the same) adds k_pair_manifolds behind the contacts' report.
-// `islands` (scTickSetPairIslands; null: this tick computes none) adds the island pass behind all of them, still ahead of the list's report.
-// `persist` (scTickSetPairPersistence; null: this tick matches nothing) adds the persistence pass behind the manifolds', ahead of the list's report.
-// `sleep` (scTickSetPairSleep; null: this tick keeps no rest state) adds the sleep pass behind the islands', ahead of the list's report.
-void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, const PairSleepState* sleep,
-                      hipStream_t s);
+// events' sweep and finish do the rest.
+// The narrow phase's states in one host-side struct (ScTickContext owns it; the device-argument structs inside keep their layout), and
+// the stages one run of it executes as a bit set.  planTick is the set's only writer and applies the dependency rules there: contacts
+// and islands need the list, manifolds the contacts, persistence the manifolds, sleep the islands.
+struct NarrowPhase {
+  PairEventState touch;           // scTickSetTouchEvents
+  PairShapeState list; PairContactState contacts; PairManifoldState manifolds; PairIslandState islands; PairPersistState persist; PairSleepState sleep;
+};
+enum NarrowStage : uint32_t { kStageList = 1, kStageTouch = 2, kStageContacts = 4, kStageManifolds = 8, kStageIslands = 16, kStagePersist = 32, kStageSleep = 64 };
+// One narrow-phase launch per tick for the list (SC_TICK_PAIR_SHAPES) and / or the touch state (SC_TICK_TOUCH_EVENTS), then the stages of
+// `stages` in this order, all ahead of the list's report: contacts and their report, manifolds, persistence, islands, sleep.  It goes by
+// `stages` alone: a stage named there is enabled and has what it needs (planTick).
+void launchPairShapes(const DeviceState& d, const TickParams& p, const NarrowPhase& np, uint32_t stages, hipStream_t s);
 // the sleep pass and its report (sc_tick_pair_sleep.hip), launched by launchPairShapes behind launchPairIslands; launchPairSleepWake is
 // scTickWakeEntities' one launch over `n` dense indices on the device
 void launchPairSleep(const DeviceState& d, const TickParams& p, const PairShapeState& list, const PairIslandState& islands, const PairSleepState& sleep,

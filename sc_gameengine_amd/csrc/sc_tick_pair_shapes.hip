@@ -228,30 +228,27 @@ __global__ __launch_bounds__(64) void k_pair_contacts_finish(const PairShapeStat
 
 // One narrow-phase launch per tick, whatever mix of SC_TICK_PAIR_SHAPES (list) and SC_TICK_TOUCH_EVENTS (touch) the run carries: each
 // pair is decided once.  Behind it the list's report and / or the touch state's sweep and finish (k_pair_events_sweep / _finish, unchanged).
-void launchPairShapes(const DeviceState& d, const TickParams& p, const PairShapeState* list, const PairEventState* touch, const PairContactState* contacts,
-                      const PairManifoldState* manifolds, const PairIslandState* islands, const PairPersistState* persist, const PairSleepState* sleep,
-                      hipStream_t s)
+void launchPairShapes(const DeviceState& d, const TickParams& p, const NarrowPhase& np, uint32_t stages, hipStream_t s)
 {
-  if (list && !list->ctl) list = nullptr;
-  if (touch && !touch->ctl) touch = nullptr;
+  const bool list = (stages & kStageList) != 0u, touch = (stages & kStageTouch) != 0u;
   if (!list && !touch) return;
   // the grid by the pair list's capacity alone: a thread per pair it can hold (grid-stride beyond that)
   const uint32_t blocks = std::min(std::max((p.maxPairs + kTile - 1u) / kTile, 1u), 2048u);
-  const PairShapeState e = list ? *list : PairShapeState{};
-  const PairEventState t = touch ? *touch : PairEventState{};
+  const PairShapeState e = list ? np.list : PairShapeState{};
+  const PairEventState t = touch ? np.touch : PairEventState{};
   if (list && touch) hipLaunchKernelGGL((k_pair_shapes<true, true>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
   else if (list) hipLaunchKernelGGL((k_pair_shapes<true, false>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
   else hipLaunchKernelGGL((k_pair_shapes<false, true>), dim3(blocks), dim3(kTile), 0, s, d, e, t, p.parity, p.maxPairs, p.n, p.rankBits);
-  if (list && contacts && contacts->ctl) {
+  if (stages & kStageContacts) {
     // a thread per entry the list can hold (grid-stride beyond the cap), between the pass and its report, which zeroes the count
-    const uint32_t cblocks = std::min(std::max((list->maxTouching + kTile - 1u) / kTile, 1u), 2048u);
-    hipLaunchKernelGGL(k_pair_contacts, dim3(cblocks), dim3(kTile), 0, s, d, e, *contacts, p.n, p.rankBits);
-    hipLaunchKernelGGL(k_pair_contacts_finish, dim3(1), dim3(64), 0, s, e, *contacts);
+    const uint32_t cblocks = std::min(std::max((e.maxTouching + kTile - 1u) / kTile, 1u), 2048u);
+    hipLaunchKernelGGL(k_pair_contacts, dim3(cblocks), dim3(kTile), 0, s, d, e, np.contacts, p.n, p.rankBits);
+    hipLaunchKernelGGL(k_pair_contacts_finish, dim3(1), dim3(64), 0, s, e, np.contacts);
   }
-  if (list && manifolds && manifolds->ctl) launchPairManifolds(d, p, e, *manifolds, s);      // behind the contacts' report, before the list's
-  if (list && manifolds && manifolds->ctl && persist && persist->ctl) launchPairPersist(d, p, e, *manifolds, *persist, s);      // behind the manifolds' records
-  if (list && islands && islands->ctl) launchPairIslands(d, p, e, *islands, s);      // needs the list, not the contacts; before the list's report
-  if (list && islands && islands->ctl && sleep && sleep->ctl) launchPairSleep(d, p, e, *islands, *sleep, s);      // labels and edge islands are final
+  if (stages & kStageManifolds) launchPairManifolds(d, p, e, np.manifolds, s);      // behind the contacts' report, before the list's
+  if (stages & kStagePersist) launchPairPersist(d, p, e, np.manifolds, np.persist, s);      // behind the manifolds' records
+  if (stages & kStageIslands) launchPairIslands(d, p, e, np.islands, s);      // needs the list, not the contacts; before the list's report
+  if (stages & kStageSleep) launchPairSleep(d, p, e, np.islands, np.sleep, s);      // labels and edge islands are final
   if (list) hipLaunchKernelGGL(k_pair_shapes_finish, dim3(1), dim3(64), 0, s, e);
   if (touch) launchPairEventsTail(t, s);
 }

@@ -937,16 +937,21 @@ class WorldTick:
         self._ok(self.lib.scTickSetPairShapes(self.ctx, int(max_touching)), "scTickSetPairShapes")
         self._max_touching = int(max_touching)
 
+    def _read_listed(self, name, info_type, count, dtype, shape=(), pointer=capi.U32P):
+        """What the readers of the touching list and of the records per entry of it share: room for max_touching records of `dtype`, the
+        call `name`, the report as a dict, and the first min(report[count], max_touching) records."""
+        cap = getattr(self, "_max_touching", 0)
+        rec = np.zeros((max(cap, 1),) + shape, dtype)
+        info = info_type()
+        self._ok(getattr(self.lib, name)(self.ctx, rec.ctypes.data_as(pointer), cap, C.byref(info)), name)
+        out = {k: int(getattr(info, k)) for k, _ in info_type._fields_}
+        return rec[:min(out[count], cap)].copy(), out
+
     def read_pair_shapes(self):
         """(touching[n, 2], info) of the last run with capi.PAIR_SHAPES: uint32 ids a < b in unspecified order; info is a dict (tested,
         touching, refined, kept_as_boxes, truncated, pairs_truncated) whose touching is the true total -- the list holds at most
         max_touching."""
-        cap = getattr(self, "_max_touching", 0)
-        pairs = np.zeros((max(cap, 1), 2), np.uint32)
-        info = capi.PairShapeInfo()
-        self._ok(self.lib.scTickReadPairShapes(self.ctx, _u(pairs), cap, C.byref(info)), "scTickReadPairShapes")
-        out = {k: int(getattr(info, k)) for k, _ in capi.PairShapeInfo._fields_}
-        return pairs[:min(out["touching"], cap)].copy(), out
+        return self._read_listed("scTickReadPairShapes", capi.PairShapeInfo, "touching", np.uint32, (2,))
 
     # ---- pair contacts: point, depth, normal and kind of every entry of the touching list ----
     CONTACT_DTYPE = np.dtype([("point", np.float32, 3), ("depth", np.float32), ("normal", np.float32, 3), ("kind", np.uint32)])
@@ -965,12 +970,7 @@ class WorldTick:
         """(records[n], info) of the last run with capi.PAIR_SHAPES while contacts were enabled: a structured array (point[3], depth,
         normal[3], kind), record i for entry i of read_pair_shapes()'s list; info is a dict (written, round_round, round_box, box_box,
         unrefined, deep, degenerate, reserved) over the records written."""
-        cap = getattr(self, "_max_touching", 0)
-        rec = np.zeros(max(cap, 1), self.CONTACT_DTYPE)
-        info = capi.PairContactInfo()
-        self._ok(self.lib.scTickReadPairContacts(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairContact)), cap, C.byref(info)), "scTickReadPairContacts")
-        out = {k: int(getattr(info, k)) for k, _ in capi.PairContactInfo._fields_}
-        return rec[:min(out["written"], cap)].copy(), out
+        return self._read_listed("scTickReadPairContacts", capi.PairContactInfo, "written", self.CONTACT_DTYPE, pointer=C.POINTER(capi.PairContact))
 
     # ---- pair manifolds: up to four points and depths of every entry of the touching list ----
     MANIFOLD_DTYPE = np.dtype([("point", np.float32, (4, 3)), ("depth", np.float32, 4), ("count", np.uint32), ("kind", np.uint32),
@@ -990,12 +990,7 @@ class WorldTick:
         """(records[n], info) of the last run with capi.PAIR_SHAPES while manifolds were enabled: a structured array (point[4][3],
         depth[4], count, kind, reserved[2]), record i for entry i of read_pair_shapes()'s list and record i of read_pair_contacts(); info
         is a dict (written, points, with_one, with_two, with_three, with_four, face, reduced) over the records written."""
-        cap = getattr(self, "_max_touching", 0)
-        rec = np.zeros(max(cap, 1), self.MANIFOLD_DTYPE)
-        info = capi.PairManifoldInfo()
-        self._ok(self.lib.scTickReadPairManifolds(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairManifold)), cap, C.byref(info)), "scTickReadPairManifolds")
-        out = {k: int(getattr(info, k)) for k, _ in capi.PairManifoldInfo._fields_}
-        return rec[:min(out["written"], cap)].copy(), out
+        return self._read_listed("scTickReadPairManifolds", capi.PairManifoldInfo, "written", self.MANIFOLD_DTYPE, pointer=C.POINTER(capi.PairManifold))
 
     # ---- pair islands: the connected components of the movable entities under the touching list ----
     def pair_islands(self, on, fixed_groups=2):
@@ -1068,12 +1063,7 @@ class WorldTick:
         """(records[n], info) of the last run with capi.PAIR_SHAPES while persistence was enabled: a structured array (prev_entry,
         prev_slot[4], age[4], reserved), record i for entry i of read_pair_shapes()'s list and record i of read_pair_manifolds(); info is a
         dict (written, kept_pairs, new_pairs, kept_points, new_points, resync, list_truncated, gave_up)."""
-        cap = getattr(self, "_max_touching", 0)
-        rec = np.zeros(max(cap, 1), self.PERSIST_DTYPE)
-        info = capi.PairPersistInfo()
-        self._ok(self.lib.scTickReadPairPersistence(self.ctx, rec.ctypes.data_as(C.POINTER(capi.PairPersist)), cap, C.byref(info)), "scTickReadPairPersistence")
-        out = {k: int(getattr(info, k)) for k, _ in capi.PairPersistInfo._fields_}
-        return rec[:min(out["written"], cap)].copy(), out
+        return self._read_listed("scTickReadPairPersistence", capi.PairPersistInfo, "written", self.PERSIST_DTYPE, pointer=C.POINTER(capi.PairPersist))
 
     # ---- pair sleep: which islands are at rest, who fell asleep, who woke ----
     def pair_sleep(self, on, lin_tol=0.005, ang_tol=0.005, rest_runs=120, max_events=4096):
